@@ -7,9 +7,12 @@ G16V frames per GPU, inputs resident in HBM.  N GPUs = N independent frame shard
 (one process per GPU, no data-path collective; torch.distributed is used only for the
 barrier and the max-over-ranks of the elapsed time) -> "scaling": "weak".
 
-Prints ONE JSON line (rank 0) with the driver's contract plus
+Prints ONE JSON line (rank 0) with the driver's contract (metric, value, unit, higher_is_better,
+dtype, ms_per_step = milliseconds of one of the --steps timed steps).  A plain run does nothing
+else: set-up, --warmup steps, the timed steps, then --dump-outputs DIR if given (what the last
+timed step returned, as DIR/<name>.npy).  With --full the line also carries
   "roofline":     the dominant kernel's achieved TFLOP/s (algorithmic conv FLOPs of its
-                  launches / their HIP-event durations measured in the timed region)
+                  launches / their HIP-event durations, in a second pass of the K steps)
                   against the gfx950 bf16-MFMA (or fp32-MFMA) peak;
   "cpu_baseline": the CPU oracle (torch-CPU restatement of the reference path) timed on this
                   host's cores on a bounded sample (rank 0, N == 1 only), whole path + per stage;
@@ -40,6 +43,8 @@ DTYPE = {"f32": "f32", "bf16x3": "bf16x3 (split-bf16 MFMA operands, f32 accumula
 PEAK_HBM_GBS = 8000.0
 EXTRA_CONFIGS = (("G16VV", 32), ("E8", 64), ("4cam-32", 16), ("E16-48-96", 32))      # (tag, frames per part (= per stream) at which the configuration runs best on MI355X: tools/config_batch_probe.py)
 LIB = os.path.join(ROOT, "mvs_gi_amd", "libmvsgi_hip.so")
+DUMP_BYTES = 60_000_000      # --dump-outputs writes at most this much array data (G16V: 8 of a step's 256 frames, 7 MB each)
+OUTPUT_NAMES = ("inv_dist", "norm_costs")      # what one part of a step returns (DistanceRegressorWithFixedCandidates.forward)
 
 
 def parse_args(argv=None):
@@ -58,8 +63,14 @@ def parse_args(argv=None):
     ap.add_argument("--mode", default="f16x3", choices=["bf16x3", "f16x3", "f32"],
                     help="conv arithmetic: split-fp16 MFMA (the library's default: 3 fp16 MFMAs per product, 11 + 11 bits per operand, "
                          "fp32 accumulate; level-0 convs in Winograd form), the same in the bf16 split (8 + 8 bits, fp32's range) or exact fp32 MFMA")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline as well: CPU baseline, parity against the CPU oracle, per-kernel attribution "
+                         "and roofline, extras and the other configurations.  Off: set up, warm up, time the K steps, print the line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last one returned (inv_dist, norm_costs of every part, float32) as "
+                         "DIR/<name>.npy: whole frames, a seeded sample of them when the step holds more than DUMP_BYTES")
     ap.add_argument("--no-extras", action="store_true",
-                    help="skip the extras / configs blocks (rig cache off, hipGraph, B=1 latency, images -> inverse "
+                    help="with --full: skip the extras / configs blocks (rig cache off, hipGraph, B=1 latency, images -> inverse "
                          "distance, host feed, other BASELINE configs); they never touch the headline's timed region")
     ap.add_argument("--extra-steps", type=int, default=20, help="timed steps of each extras / configs measurement")
     ap.add_argument("--graph", action="store_true", help=argparse.SUPPRESS)         # kept: the default since round 3
@@ -656,10 +667,46 @@ def make_feats(B, shape, rng, dev, torch, np, nchw=False):
     """[B, N, C, Hi, Wi] synthetic feature maps.  Default: channels-last storage ([B, N, Hi, Wi, C] presented with the
     reference's shape), which is what the HIP feature extractor in front of this path emits; nchw=True is the reference
     extractor's contiguous layout, which the sweep transposes once per step (extras.feats_nchw)."""
+    return upload_feats(draw_feats(B, shape, rng, np, nchw), dev, torch, nchw)
+
+
+def draw_feats(B, shape, rng, np, nchw=False):
+    """The host array behind make_feats.  numpy releases the GIL while it draws (G16V's 256 frames: 3.2 GB, seconds of one core),
+    so main() draws the timed step's frames on a thread beside the GPU set-up."""
     _, N, C, Hi, Wi = shape
-    if nchw:
-        return torch.from_numpy(rng.standard_normal((B, N, C, Hi, Wi), dtype=np.float32)).to(dev)
-    return torch.from_numpy(rng.standard_normal((B, N, Hi, Wi, C), dtype=np.float32)).to(dev).permute(0, 1, 4, 2, 3)
+    return rng.standard_normal((B, N, C, Hi, Wi) if nchw else (B, N, Hi, Wi, C), dtype=np.float32)
+
+
+def upload_feats(x, dev, torch, nchw=False):
+    t = torch.from_numpy(x).to(dev)
+    return t if nchw else t.permute(0, 1, 4, 2, 3)
+
+
+def dump_frames(n_frames: int, bytes_per_frame: int, budget: int = DUMP_BYTES):
+    """The frames --dump-outputs writes: all of them when they fit in `budget`, else the first, the last and a sample of the
+    others drawn with a fixed seed (the same frames for the same batch, run after run)."""
+    import numpy as np
+    n = max(1, min(n_frames, budget // bytes_per_frame))
+    if n == n_frames:
+        return list(range(n_frames))
+    inner = np.random.default_rng(0).permutation(np.arange(1, n_frames - 1))[:max(0, n - 2)]
+    return sorted({0, n_frames - 1}.union(int(f) for f in inner)) if n >= 2 else [0]
+
+
+def dump_outputs(out_dir: str, parts, torch, np):
+    """parts: what one step returned, one (inv_dist, norm_costs) pair per part in frame order -> <out_dir>/<name>.npy, float32,
+    frames dump_frames() picks.  Returns {name: shape written} and the frame indices."""
+    arrays = {name: [p[i] for p in parts] for i, name in enumerate(OUTPUT_NAMES) if parts[0][i] is not None}
+    per_part = parts[0][0].shape[0]
+    n_frames = per_part * len(parts)
+    frames = dump_frames(n_frames, sum(a[0][0].numel() * 4 for a in arrays.values()))
+    os.makedirs(out_dir, exist_ok=True)
+    shapes = {}
+    for name, per in arrays.items():
+        x = torch.stack([per[f // per_part][f % per_part] for f in frames]).to(torch.float32).cpu().numpy()
+        np.save(os.path.join(out_dir, name + ".npy"), x)
+        shapes[name] = list(x.shape)
+    return shapes, frames
 
 
 def measure_path(cfg, B, mode, steps, warmup, dev, H, HotPath, synth, torch, np, rng, graph=False, kernels=False, streams=1, ref_dump=None):
@@ -753,19 +800,25 @@ def main(argv=None):
             raise SystemExit(self_launch(args, sys.argv[1:] if argv is None else argv))
         raise SystemExit(f"WORLD_SIZE={world} does not match --gpus {args.gpus}")
     cpu_res, ref_dump = None, None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         ref_dump = os.path.join(tempfile.mkdtemp(prefix="mvsgi_bench_"), "oracle_inv_dist.npy")
         cpu_res = cpu_baseline_subprocess(args, ref_dump)      # before any GPU initialisation
-    elif rank == 0 and world > 1:
+    elif args.full and rank == 0 and world > 1:
         # a multi-rank line carries no CPU baseline, but it does carry an error figure: one oracle frame, before any GPU call
         ref_dump = os.path.join(tempfile.mkdtemp(prefix="mvsgi_bench_"), "oracle_inv_dist.npy")
         oracle_dump_subprocess(args, ref_dump)
-    ensure_library(local_rank)
     import numpy as np
+    from concurrent.futures import ThreadPoolExecutor
+    from mvs_gi_amd.configs import CONFIGS, path_gflop
+    cfg = CONFIGS[args.config]
+    B = args.batch
+    rng = np.random.default_rng(1000 + rank)     # every rank owns different frames
+    drawer = ThreadPoolExecutor(max_workers=1)
+    feats_drawn = drawer.submit(draw_feats, B, (1, cfg.num_cams, cfg.feat_chs, *cfg.feat_hw), rng, np)
+    ensure_library(local_rank)
     import torch
     import torch.distributed as dist
     from mvs_gi_amd import hip_ops as H, synth
-    from mvs_gi_amd.configs import CONFIGS, path_gflop
     from mvs_gi_amd.pipeline import HotPath, StreamedHotPath
 
     assert torch.cuda.is_available(), "bench.py needs a GPU (the HIP path has no CPU fallback)"
@@ -785,8 +838,6 @@ def main(argv=None):
         backend_ready = True
     devices = gather_device_ordinals(local_rank, world, dev) if backend_ready else [local_rank]
 
-    cfg = CONFIGS[args.config]
-    B = args.batch
     H.set_conv_mode(args.mode)
     # the fp16 split's range report: a measurement run REPORTS it (parity.saturation_flags, the configs' parity blocks) instead of
     # stopping on it; the library's default for a deployment is MVSGI_RANGE_CHECK=raise
@@ -800,17 +851,17 @@ def main(argv=None):
         S -= 1
     shp = StreamedHotPath(cfg, weights, inp, device=dev, n_streams=S)
     hp = shp.parts[0]                            # one part: what the per-kernel attribution, the parity frame and the extras run on
-    rng = np.random.default_rng(1000 + rank)     # every rank owns different frames
-    feats = make_feats(B, inp["feats"].shape, rng, dev, torch, np)
+    feats = upload_feats(feats_drawn.result(), dev, torch)
+    drawer.shutdown()
     out = {}
 
     def step():
-        out["inv"], out["pr"] = shp(feats)[-1]
+        out["parts"] = shp(feats)
 
     def step_serial():
         # the same launches, part after part on ONE stream: per-kernel event pairs then time a kernel alone on the chip
         for part, f in zip(shp.parts, feats.split(B // S, dim=0)):
-            out["inv"], out["pr"] = part(f)
+            part(f)
 
     def sync():
         torch.cuda.synchronize(dev)
@@ -833,7 +884,7 @@ def main(argv=None):
             torch.cuda.synchronize(dev)
     if use_graph:
         def timed_step():
-            out["inv"], out["pr"] = shp.replay()[-1]
+            out["parts"] = shp.replay()
         for _ in range(max(2, args.warmup // 2)):
             timed_step()
         sync()
@@ -850,26 +901,45 @@ def main(argv=None):
     sync()
     # the timed region: K steps, nothing but the path's own launches in it
     el = timed_steps(timed_step, sync, args.steps, 0, world, backend_ready, dev, per_rank)
-    # per-kernel attribution: the same K steps once more with a HIP event pair around every conv launch (on the launch
-    # stream).  Kept out of the region above: ~70 event records per step cost ~3 % of it.
-    with ConvProbe(H) as probe:
-        probe.enabled = True
-        el_ev = timed_steps(step_serial, sync, args.steps, 0, world, backend_ready, dev)
-        probe.enabled = False
-        sync()
-        agg = probe.summary()
-        hbm_agg = probe.hbm_summary()
-
-    assert torch.isfinite(out["inv"]).all()
+    assert all(torch.isfinite(inv).all() for inv, _ in out["parts"])
+    dumped = None
+    if args.dump_outputs and rank == 0:      # before anything else runs on the modules' buffers the last step's outputs live in
+        shapes, dump_idx = dump_outputs(args.dump_outputs, out["parts"], torch, np)
+        dumped = {"dir": args.dump_outputs, "shapes": shapes, "frames": dump_idx}
     frames = B * world * args.steps
     value = frames / el
-    # dominant kernel = largest total time among the conv variants
-    dom = max(agg.items(), key=lambda kv: kv[1][2])
-    dname, (dn, dflops, dms, _) = dom
-    achieved = dflops / (dms * 1e-3) / 1e12
-    conv_ms = sum(v[2] for v in agg.values())
-    attributed_ms = conv_ms + sum(v[2] for v in hbm_agg.values())
-    traffic, traffic_src = read_pmc_traffic(dname, B // S, args.config)
+    attribution = {}
+    if args.full:
+        # per-kernel attribution: the same K steps once more with a HIP event pair around every conv launch (on the launch
+        # stream).  Kept out of the region above: ~70 event records per step cost ~3 % of it.
+        with ConvProbe(H) as probe:
+            probe.enabled = True
+            el_ev = timed_steps(step_serial, sync, args.steps, 0, world, backend_ready, dev)
+            probe.enabled = False
+            sync()
+            agg = probe.summary()
+            hbm_agg = probe.hbm_summary()
+        # dominant kernel = largest total time among the conv variants
+        dom = max(agg.items(), key=lambda kv: kv[1][2])
+        dname, (dn, dflops, dms, _) = dom
+        achieved = dflops / (dms * 1e-3) / 1e12
+        conv_ms = sum(v[2] for v in agg.values())
+        attributed_ms = conv_ms + sum(v[2] for v in hbm_agg.values())
+        traffic, traffic_src = read_pmc_traffic(dname, B // S, args.config)
+        attribution = {
+            "roofline": {"bound": "mfma", "kernel": dname, "achieved": round(achieved, 2), "peak": peak,
+                         "unit": "TFLOP/s", "frac": round(achieved / peak, 4),
+                         "note": ("achieved = ALGORITHMIC conv FLOPs / kernel time; a split kernel issues 3 16-bit "
+                                  "MFMA FLOPs per algorithmic FLOP, so frac tops out at 1/3 (the Winograd-form level-0 kernel of the fp16 split: 3 x 16 / 36)"
+                                  if args.mode in OTHER_SPLIT else "exact fp32 MFMA"),
+                         "traffic": traffic, "traffic_source": traffic_src, "launches": dn,
+                         "avg_launch_us": round(dms / dn * 1e3, 2), "gflop_per_launch": round(dflops / dn / 1e9, 3),
+                         "conv_time_frac_of_step": round(conv_ms / (el_ev * 1e3), 3),
+                         "attributed_time_frac_of_step": round(attributed_ms / (el_ev * 1e3), 3),
+                         "how": "HIP events around every conv launch in a second pass of the same K steps, the parts one after the other on "
+                                f"one stream ({round(el_ev / args.steps * 1e3, 4)} ms per step with the events in): a launch is {B // S} frames"},
+            "kernels": kernels_block(agg, hbm_agg),
+        }
     res = {
         "metric": f"stereo frames/sec/GPU ({cfg.tag}, {cfg.num_cams}-cam, D={cfg.num_cands}) + inv-dist L1 vs reference",
         "value": round(value, 2), "unit": "frames/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -893,21 +963,12 @@ def main(argv=None):
         "per_rank_frames_per_s": {"min": round(B * args.steps / max(per_rank), 2), "max": round(B * args.steps / min(per_rank), 2)}
         if per_rank else None,
         "path_tflops": round(value * path_gflop(cfg) / 1e3, 2),
-        "roofline": {"bound": "mfma", "kernel": dname, "achieved": round(achieved, 2), "peak": peak,
-                     "unit": "TFLOP/s", "frac": round(achieved / peak, 4),
-                     "note": ("achieved = ALGORITHMIC conv FLOPs / kernel time; a split kernel issues 3 16-bit "
-                              "MFMA FLOPs per algorithmic FLOP, so frac tops out at 1/3 (the Winograd-form level-0 kernel of the fp16 split: 3 x 16 / 36)"
-                              if args.mode in OTHER_SPLIT else "exact fp32 MFMA"),
-                     "traffic": traffic, "traffic_source": traffic_src, "launches": dn,
-                     "avg_launch_us": round(dms / dn * 1e3, 2), "gflop_per_launch": round(dflops / dn / 1e9, 3),
-                     "conv_time_frac_of_step": round(conv_ms / (el_ev * 1e3), 3),
-                     "attributed_time_frac_of_step": round(attributed_ms / (el_ev * 1e3), 3),
-                     "how": "HIP events around every conv launch in a second pass of the same K steps, the parts one after the other on "
-                            f"one stream ({round(el_ev / args.steps * 1e3, 4)} ms per step with the events in): a launch is {B // S} frames"},
-        "kernels": kernels_block(agg, hbm_agg),
+        **attribution,
         "n_ranks_seen": dist.get_world_size() if backend_ready else 1,
         "devices": devices,
     }
+    if dumped is not None:
+        res["outputs_dumped"] = dumped
     # ---- parity of the benchmarked weights: the seed-0 frame (B=1) against the CPU oracle's inverse distance
     if ref_dump is not None and os.path.isfile(ref_dump):
         ref = np.load(ref_dump)
@@ -935,7 +996,7 @@ def main(argv=None):
         # stopped the run otherwise)
         res["parity"]["saturation_flags"] = H.saturation_flags(clear=True) | H.range_flags_seen()
     # ---- extras: single GPU only, outside the timed region above
-    if world == 1 and rank == 0 and not args.no_extras:
+    if args.full and world == 1 and rank == 0 and not args.no_extras:
         args.ref_dump = ref_dump
         res["extras"] = run_extras(args, cfg, B // S, hp, feats[:B // S], weights, dev, H, synth, torch, np, rng, value, shp, feats)
         # round-to-round comparable figure beside `value` (rounds 1-3 ran one part on one stream): one part of the step, one stream

@@ -99,18 +99,61 @@ def test_unpickle_reference_modules_into_dropin_alias_mode():
     assert "OK" in out
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/dsta_mvs"), reason="reference checkout not present")
-def test_patch_mode_rebinds_reference_classes():
+# The classes install()'s patch mode re-binds, at the reference's import paths (dropin/install.py, _patch_reference)
+REFERENCE_CLASSES = {
+    "dsta_mvs/model/cost_volume_builder/__init__.py": ["SphericalSweepStdMasked", "SphericalSweep"],
+    "dsta_mvs/model/cost_volume_regulator/unet_regulator.py": ["UNetCostVolumeRegulatorBase", "UNetCostVolumeRegulator",
+                                                                "UNetDownBlk"],
+    "dsta_mvs/model/distance_regressor/distance_regressor.py": ["DistanceRegressorWithFixedCandidates"],
+    "dsta_mvs/model/common/common_modules.py": ["BaseConvBlk3d", "ResConvBlk3d", "ResizeConv3d", "BaseConvBlk2d", "ResConvBlk2d",
+                                                "SphereConvEquirect2d", "SphereConvBlk"],
+    "dsta_mvs/model/feature_extractor/simple_feature_extractor.py": ["SimpleFeatExtraction"],
+    "dsta_mvs/model/feature_extractor/sphere_feature_extractor.py": ["SphereEquirectFeatExtraction"],
+    "dsta_mvs/model/mvs_model/torch_only.py": ["SphericalSweepStereoBase"],
+}
+
+
+def _write_reference_stand_in(root):
+    """A stand-in for a user's mvs_gi checkout: the reference's package layout and class names, each class with a forward of its
+    own that runs on the CPU (the regulator's: a 3-D conv to one channel, the shape of the reference's output)."""
+    for rel, names in REFERENCE_CLASSES.items():
+        path = root.joinpath(*rel.split("/"))
+        for pkg in [path.parent, *path.parent.parents]:
+            if pkg == root:
+                break
+            pkg.mkdir(parents=True, exist_ok=True)
+            pkg.joinpath("__init__.py").touch()
+        src = ["import torch", ""]
+        for n in names:
+            if n == "UNetCostVolumeRegulatorBase":
+                src += [f"class {n}(torch.nn.Module):",
+                        "    def __init__(self, in_chs=16, f_int_chs=32):",
+                        "        super().__init__()",
+                        "        self.out = torch.nn.Conv3d(in_chs, 1, 3, padding=1)",
+                        "",
+                        "    def forward(self, x):",
+                        "        return self.out(x)", ""]
+            else:
+                src += [f"class {n}(torch.nn.Module):",
+                        "    def forward(self, *args, **kwargs):",
+                        f"        return {n!r}", ""]
+        with open(path, "a") as f:
+            f.write("\n".join(src) + "\n")
+
+
+def test_patch_mode_rebinds_reference_classes(tmp_path):
+    _write_reference_stand_in(tmp_path)
     out = _run("""
-        import sys, types
-        tv, ops = types.ModuleType("torchvision"), types.ModuleType("torchvision.ops")
-        ops.deform_conv2d = lambda *a, **k: None; tv.ops = ops
-        sys.modules["torchvision"], sys.modules["torchvision.ops"] = tv, ops
+        import importlib
         import torch, mvs_gi_amd
+        classes = [getattr(importlib.import_module(rel[:-3].replace("/", ".").replace(".__init__", "")), n)
+                   for rel, names in %r.items() for n in names]
+        original = {c: c.forward for c in classes}
         assert mvs_gi_amd.install() == "patch"
         from dsta_mvs.model.cost_volume_regulator.unet_regulator import UNetCostVolumeRegulatorBase
-        from dsta_mvs.model.cost_volume_builder import SphericalSweepStdMasked
         assert UNetCostVolumeRegulatorBase.__module__.startswith("dsta_mvs.")
+        unpatched = [c.__name__ for c in classes if c.forward is original[c]]
+        assert not unpatched, unpatched
         reg = UNetCostVolumeRegulatorBase(16, 32).eval()
         try:
             reg(torch.zeros(1, 16, 4, 4, 8))
@@ -120,10 +163,12 @@ def test_patch_mode_rebinds_reference_classes():
             raise SystemExit("reference forward still runs on CPU")
         from mvs_gi_amd.dropin.install import uninstall
         uninstall()
+        not_restored = [c.__name__ for c in classes if c.forward is not original[c]]
+        assert not not_restored, not_restored
         y = reg(torch.zeros(1, 16, 8, 8, 8))  # original forward restored
         assert tuple(y.shape) == (1, 1, 8, 8, 8)
         print("OK")
-    """, extra_path=["/root/reference"])
+    """ % (REFERENCE_CLASSES,), extra_path=[str(tmp_path)])
     assert "OK" in out
 
 

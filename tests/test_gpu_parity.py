@@ -976,7 +976,7 @@ def test_cold_compile_and_load_on_this_box(tmp_path):
 
 
 def test_bench_default_submission_line():
-    """`python bench.py` as the driver calls it at N = 1 (here with a small batch): the step is two parts on two HIP streams inside one
+    """`python bench.py --full` at N = 1 (here with a small batch): the step is two parts on two HIP streams inside one
     hipGraph behind a settle phase; one JSON line with metric / value / roofline (+ traffic from profiles/pmc_traffic.json) / every
     launch attributed / parity against the oracle frame / cpu_baseline."""
     import json
@@ -984,7 +984,7 @@ def test_bench_default_submission_line():
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--batch", "8", "--steps", "3", "--warmup", "2", "--no-extras",
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--batch", "8", "--steps", "3", "--warmup", "2", "--full", "--no-extras",
                         "--settle-seconds", "0.2", "--cpu-seconds", "1"], capture_output=True, text=True, env=env, timeout=900, cwd=root)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -998,6 +998,45 @@ def test_bench_default_submission_line():
     assert any(k.startswith("sweep_std") for k in d["kernels"]) and any(k.startswith("softargmin") for k in d["kernels"])
 
 
+def test_bench_plain_line_and_dumped_outputs(tmp_path):
+    """`python bench.py` without --full: the headline only (exactly --steps timed steps, ms_per_step), and --dump-outputs writes what
+    the last timed step returned -- the same numbers this process computes from the same seeded frames through the same path."""
+    import json
+    import subprocess
+    import sys
+    import bench
+    from mvs_gi_amd.configs import CONFIGS
+    from mvs_gi_amd.pipeline import StreamedHotPath
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    out_dir = str(tmp_path / "outputs")
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--batch", "8", "--steps", "4", "--warmup", "2",
+                        "--settle-seconds", "0.2", "--dump-outputs", out_dir], capture_output=True, text=True, env=env, timeout=600, cwd=root)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    assert d["steps"] == 4 and d["value"] > 0 and d["higher_is_better"] and d["unit"] == "frames/s" and d["dtype"].startswith("f16x3")
+    assert abs(d["value"] - 8 * 4 / (d["ms_per_step"] * 4e-3)) / d["value"] < 0.01
+    assert not {"roofline", "kernels", "parity", "cpu_baseline", "extras", "configs"} & set(d)
+    assert d["outputs_dumped"]["frames"] == list(range(8))          # 8 G16V frames fit in bench.DUMP_BYTES
+    files = sorted(os.listdir(out_dir))
+    assert files == ["inv_dist.npy", "norm_costs.npy"]
+    assert sum(os.path.getsize(os.path.join(out_dir, f)) for f in files) <= 64e6
+    got = {f[:-4]: np.load(os.path.join(out_dir, f)) for f in files}
+    assert got["inv_dist"].dtype == np.float32 and got["inv_dist"].shape == (8, 1, 160, 640)
+    assert got["norm_costs"].dtype == np.float32 and got["norm_costs"].shape == (8, 16, 160, 640)
+    H.set_conv_mode("f16x3")      # bench.py's default --mode (this file's autouse fixture restores its own)
+    cfg = CONFIGS["G16V"]
+    x = bench.draw_feats(8,(1, cfg.num_cams, cfg.feat_chs, *cfg.feat_hw), np.random.default_rng(1000), np)
+    shp = StreamedHotPath(cfg, synth.make_weights(cfg, seed=0), synth.make_inputs(cfg, seed=0, batch=1), device=DEV, n_streams=2)
+    parts = shp(bench.upload_feats(x, torch.device(DEV), torch))
+    torch.cuda.synchronize()
+    for i, name in enumerate(bench.OUTPUT_NAMES):
+        ref = torch.cat([p[i] for p in parts]).cpu().numpy()
+        assert np.abs(got[name] - ref).max() <= 1e-6 * np.abs(ref).max(), name
+
+
 def test_bench_two_ranks_frame_sharded_on_one_gpu():
     """bench.py's N>1 path end to end (rendezvous, per-rank frames, barrier, max-over-ranks, one JSON
     line from rank 0): two ranks share this box's single GPU, control plane over gloo."""
@@ -1008,7 +1047,7 @@ def test_bench_two_ranks_frame_sharded_on_one_gpu():
     env = dict(os.environ, MVSGI_BENCH_SHARE_GPU="1", MASTER_ADDR="127.0.0.1", MASTER_PORT="29655")
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
                         "--master-addr", "127.0.0.1", "--master-port", "29655", os.path.join(root, "bench.py"),
-                        "--gpus", "2", "--steps", "3", "--warmup", "1", "--batch", "2", "--backend", "gloo", "--settle-seconds", "0"],
+                        "--gpus", "2", "--steps", "3", "--warmup", "1", "--batch", "2", "--backend", "gloo", "--settle-seconds", "0", "--full"],
                        capture_output=True, text=True, env=env, timeout=600, cwd=root)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -1033,7 +1072,7 @@ def test_bench_self_launches_its_ranks():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env["MVSGI_BENCH_SHARE_GPU"] = "1"
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "4", "--steps", "3", "--warmup", "1",
-                        "--batch", "1", "--backend", "gloo", "--settle-seconds", "0"], capture_output=True, text=True, env=env, timeout=900, cwd=root)
+                        "--batch", "1", "--backend", "gloo", "--settle-seconds", "0", "--full"], capture_output=True, text=True, env=env, timeout=900, cwd=root)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, "exactly one JSON line (rank 0)"

@@ -13,7 +13,7 @@ for r in range(rounds):
         for kv in a.split(","):
             k, v = kv.split("=")
             env[k] = v
-        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--no-extras", "--no-cpu-baseline"] + extra,
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--no-extras", "--no-cpu-baseline"] + extra,
                              capture_output=True, text=True, env=env).stdout
         d = json.loads([l for l in out.splitlines() if l.startswith("{")][-1])
         res[a].append(d)

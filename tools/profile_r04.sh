@@ -30,7 +30,7 @@ rm -rf $R/$OUT/sq1 $R/$OUT/sq2
 for T in G16VV E8 4cam-32; do
   PB=32; [ $T = E8 ] && PB=64; [ $T = 4cam-32 ] && PB=16
   C="$B --config $T --streams 1 --batch $PB"
-  timeout -k 10 280 python3 $R/bench.py --config $T --batch $((2 * PB)) --steps 10 --warmup 3 --no-cpu-baseline --no-extras > $R/$OUT/bench_$T.json 2> $R/$OUT/bench_$T.err || exit 1
+  timeout -k 10 280 python3 $R/bench.py --config $T --batch $((2 * PB)) --steps 10 --warmup 3 --full --no-cpu-baseline --no-extras > $R/$OUT/bench_$T.json 2> $R/$OUT/bench_$T.err || exit 1
   timeout -k 10 280 rocprofv3 --kernel-trace --stats --output-format csv -d $R/$OUT/stats_$T -- $C --steps 4 --warmup 2 > $R/$OUT/stats_$T.log 2>&1 || exit 1
   $S stats $R/$OUT/stats_$T $R/$OUT/${T}_kernel_stats.txt > /dev/null || exit 1
   rm -rf $R/$OUT/stats_$T

@@ -29,14 +29,14 @@ python3 $R/tools/summarize_sq.py $R/$OUT/pmc_step_kernels.txt "B=64 step, one st
 rm -rf $R/$OUT/sq1 $R/$OUT/sq2
 # the bf16 split of the same step (MVSGI_CONV_MODE=bf16x3, the default of rounds 1-4): line, kernel-trace stats alone on the chip
 BF="$B --mode bf16x3"
-timeout -k 10 280 python3 $R/bench.py --mode bf16x3 --steps 20 --warmup 5 --no-cpu-baseline --no-extras > $R/$OUT/bench_G16V_bf16x3.json 2> $R/$OUT/bench_G16V_bf16x3.err || exit 1
+timeout -k 10 280 python3 $R/bench.py --mode bf16x3 --steps 20 --warmup 5 --full --no-cpu-baseline --no-extras > $R/$OUT/bench_G16V_bf16x3.json 2> $R/$OUT/bench_G16V_bf16x3.err || exit 1
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $R/$OUT/stats_bf16 -- $BF --streams 1 --batch 64 --steps 5 --warmup 2 > $R/$OUT/stats_bf16.log 2>&1 || exit 1
 $S stats $R/$OUT/stats_bf16 $R/$OUT/bench_streams1_b64_bf16x3_kernel_stats.txt > /dev/null || exit 1
 rm -rf $R/$OUT/stats_bf16
 for T in G16VV E8 4cam-32; do
   PB=32; [ $T = E8 ] && PB=64; [ $T = 4cam-32 ] && PB=16
   C="$B --config $T --streams 1 --batch $PB"
-  timeout -k 10 280 python3 $R/bench.py --config $T --batch $((2 * PB)) --steps 10 --warmup 3 --no-cpu-baseline --no-extras > $R/$OUT/bench_$T.json 2> $R/$OUT/bench_$T.err || exit 1
+  timeout -k 10 280 python3 $R/bench.py --config $T --batch $((2 * PB)) --steps 10 --warmup 3 --full --no-cpu-baseline --no-extras > $R/$OUT/bench_$T.json 2> $R/$OUT/bench_$T.err || exit 1
   timeout -k 10 280 rocprofv3 --kernel-trace --stats --output-format csv -d $R/$OUT/stats_$T -- $C --steps 4 --warmup 2 > $R/$OUT/stats_$T.log 2>&1 || exit 1
   $S stats $R/$OUT/stats_$T $R/$OUT/${T}_kernel_stats.txt > /dev/null || exit 1
   rm -rf $R/$OUT/stats_$T

@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define MVSGI_ABI_VERSION 3   /* 3: mvsgi_conv3d_d32_applies, mvsgi_conv3d_up2_d32_applies + MVSGI_CONV_BF16X3_D32; 2: mvsgi_saturation_flags; the symbol set of round 5 */
+#define MVSGI_ABI_VERSION 4   /* 4: mvsgi_instance_norm_f32, mvsgi_instance_norm_ws_bytes (norm_type 'instance'); 3: mvsgi_conv3d_d32_applies, mvsgi_conv3d_up2_d32_applies + MVSGI_CONV_BF16X3_D32; 2: mvsgi_saturation_flags; the symbol set of round 5 */
 
 typedef void* mvsgi_stream_t;
 
@@ -453,6 +453,19 @@ int mvsgi_conv3d_wino32_pack_weights(const float* w_oidhw, void* w_packed, float
  * voxel, zero border): the hand-over between Winograd layers, which split their operands behind the transform anyway. */
 int mvsgi_conv3d_wino32_f16(const void* x_split, const void* w_packed, const float* scale, const float* shift, const void* res_split,
                             void* y, int y_is_f32, int act_f32p, int B, int D, int H, int W, float neg_slope, mvsgi_stream_t stream);
+
+/* ---- instance norm (csrc/instnorm.hip) ------------------------------------------------------------------------------
+ * nn.InstanceNorm3d / nn.InstanceNorm2d with input statistics (track_running_stats=False, train or eval: F.instance_norm's
+ * use_input_stats) in a conv block, common/common_modules.py:107-115, applied after the conv:
+ *   y[b][s][c] = act( (x[b][s][c] - mean[b][c]) / sqrt(var[b][c] + eps) * gamma[c] + beta[c] (+ res[b][s][c]) )
+ * mean / var (biased) over the S spatial positions of frame b, channel c; act(v) = v > 0 ? v : v * neg_slope (0 = ReLU,
+ * 1 = none).  x / res / y are channels-last [B][S][C] (NDHWC with S = D*H*W, or NHWC with S = H*W), 16-byte aligned;
+ * res, gamma and beta may be NULL (no residual, gamma = 1, beta = 0); y may alias x (in place).  C % 4 == 0, C <= 1024, S >= 2.
+ * Two launches (statistics partials into `ws`, then merge + apply); no atomics: frame b's result depends on frame b alone.
+ * ws: caller-owned device scratch of mvsgi_instance_norm_ws_bytes(B, S, C) bytes (0 = invalid arguments). */
+size_t mvsgi_instance_norm_ws_bytes(int B, int S, int C);
+int mvsgi_instance_norm_f32(const float* x, const float* res, const float* gamma, const float* beta, float* y, float* ws,
+                            int B, int S, int C, float eps, float neg_slope, mvsgi_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -13,7 +13,7 @@ from ctypes import c_char_p, c_float, c_int, c_longlong, c_size_t, c_void_p
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MVSGI_LIB", os.path.join(_HERE, "libmvsgi_hip.so"))   # MVSGI_LIB: diagnostic builds
 
-ABI_VERSION = 3
+ABI_VERSION = 4
 
 
 class MvsgiLibraryMissing(RuntimeError):
@@ -118,6 +118,8 @@ SIGNATURES = {
     "mvsgi_conv3d_up2_poly_wino_pays": (c_int, [c_int] * 4),
     "mvsgi_ncv_to_nvc_f32": (c_int, [_P, _P, c_int, c_int, c_longlong, _P]),
     "mvsgi_nvc_to_ncv_f32": (c_int, [_P, _P, c_int, c_int, c_longlong, _P]),
+    "mvsgi_instance_norm_ws_bytes": (c_size_t, [c_int] * 3),
+    "mvsgi_instance_norm_f32": (c_int, [_P] * 6 + [c_int] * 3 + [c_float, c_float, _P]),
 }
 
 _lib = None

@@ -49,6 +49,10 @@ class PathConfig:
     bf: float = BF
     interp_scale_factor: int = 2
     pre_interp: bool = True
+    # norm layer of every conv block with one (NORM3D_TYPE of dsta_mvs/model/common/__init__.py:13-23): "batch" | "instance" | "none";
+    # norm_affine: the instance norms carry gamma / beta (nn.InstanceNorm3d(c, affine=True))
+    norm_type: str = "batch"
+    norm_affine: bool = False
 
     @property
     def num_cands(self) -> int:

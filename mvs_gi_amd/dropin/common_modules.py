@@ -56,9 +56,14 @@ class ConvLaunch:
     """Device-resident launch arguments of one BaseConvBlk3d: PyTorch-layout weight, packed
     MFMA weight (or None), per-channel scale/shift (eval BatchNorm3d or bias), stride, slope."""
     __slots__ = ("w", "wp", "wp_b3", "wp_c16", "wp_v32", "wp_d32", "wp_rs", "wp_s2", "wp_poly", "wp_head", "head_sc", "scale", "shift", "stride",
-                 "neg_slope", "cin", "cout", "key", "f16")
+                 "neg_slope", "cin", "cout", "key", "f16", "inorm")
 
     def run(self, x_ndhwc: Tensor, res: Optional[Tensor] = None, impl: Optional[int] = None) -> Tensor:
+        if self.inorm is not None:          # conv (+ bias) -> instance norm (+ res) -> act: two more launches
+            return self.inorm.apply(self._run_conv(x_ndhwc, None, impl), res)
+        return self._run_conv(x_ndhwc, res, impl)
+
+    def _run_conv(self, x_ndhwc: Tensor, res: Optional[Tensor] = None, impl: Optional[int] = None) -> Tensor:
         wp = self.wp
         if impl is None and H.get_conv_mode() == "f16x3" and self.cin % 16 == 0 and self.cout % 16 == 0:
             B, D, Hh, W, _ = x_ndhwc.shape
@@ -127,7 +132,7 @@ class ConvLaunch:
 
     def rs_ok(self) -> bool:
         """The register-stationary kernel (csrc/conv3d_rs.hip) serves this layer."""
-        return H.conv3d_rs_applies(self.cin, self.cout, self.stride, self.neg_slope)
+        return self.inorm is None and H.conv3d_rs_applies(self.cin, self.cout, self.stride, self.neg_slope)
 
     def _wp_rs(self):
         if self.wp_rs is None:
@@ -147,7 +152,7 @@ class ConvLaunch:
 
     def wino_ok(self, D: int, Hh: int, W: int) -> bool:
         """The Winograd-form kernel (csrc/conv3d_wino.hip) serves this layer on a [D, Hh, W] volume (fp16 split only)."""
-        return H.conv3d_wino_applies(self.cin, self.cout, D, Hh, W, self.stride, self.neg_slope)
+        return self.inorm is None and H.conv3d_wino_applies(self.cin, self.cout, D, Hh, W, self.stride, self.neg_slope)
 
     def _wino(self):
         """(packed weights, per-channel scale) of the Winograd-form kernel."""
@@ -164,7 +169,7 @@ class ConvLaunch:
 
     def s2rs_ok(self) -> bool:
         """The stride-2 16 -> 32 kernel on split-padded activations (csrc/conv3d_s2rs.hip) serves this layer."""
-        return H.split_mode() and H.conv3d_s2rs_applies(self.cin, self.cout, self.stride, self.neg_slope)
+        return self.inorm is None and H.split_mode() and H.conv3d_s2rs_applies(self.cin, self.cout, self.stride, self.neg_slope)
 
     def _wp_s2(self):
         if self.wp_s2 is None:
@@ -189,7 +194,7 @@ class ConvLaunch:
 
     def poly_ok(self) -> bool:
         """ResizeConv3d in polyphase form on the register-stationary kernel (csrc/conv3d_up2poly.hip)."""
-        return H.split_mode() and self.stride == 1 and H.conv3d_up2_poly_applies(self.cin, self.cout, self.neg_slope)
+        return self.inorm is None and H.split_mode() and self.stride == 1 and H.conv3d_up2_poly_applies(self.cin, self.cout, self.neg_slope)
 
     def _poly_plan(self, D: int, Hh: int, W: int, fmt: str = "bf16"):
         """(folded phase weights + face tables for a low-resolution input of D x Hh x W in the split `fmt`, the layer's scale):
@@ -207,7 +212,7 @@ class ConvLaunch:
 
     def head_split_ok(self) -> bool:
         """The split cost head on a split-padded input (csrc/conv3d_headsplit.hip), in either 16-bit split."""
-        return H.split_mode() and self.cout == 1 and self.cin % 16 == 0 and self.stride == 1
+        return self.inorm is None and H.split_mode() and self.cout == 1 and self.cin % 16 == 0 and self.stride == 1
 
     def run_head_split(self, x_split) -> Tensor:
         if x_split.fmt == "f16":
@@ -233,6 +238,7 @@ class ConvLaunch:
 
     def run_up2_split(self, x_lowres_ndhwc: Tensor, res: Optional[Tensor], out) -> "H.SplitAct":
         """conv(trilinear_x2(x)) (+ res) written split-padded into `out` (the polyphase layer's input, the split head's input)."""
+        _no_inorm(self, "run_up2_split")
         if H.get_conv_mode() == "f16x3":
             layout = H.CONV_BF16X3_C16 if self._c16() else H.CONV_BF16X3
             wp16, sc16 = self._f16(layout)
@@ -244,10 +250,16 @@ class ConvLaunch:
         return H.conv3d_up2_out_split(x_lowres_ndhwc, self._wp_b3(), self.scale, self.shift, out=out, res=res, neg_slope=self.neg_slope)
 
     def can_fuse_up2(self) -> bool:
+        """conv(trilinear_x2(x)) in one launch writing fp32 (run_up2): an instance norm follows it like any other conv."""
         return H.split_mode() and self.stride == 1 and self.cin % 16 == 0 and self.cout % 16 == 0
 
     def run_up2(self, x_lowres_ndhwc: Tensor, res: Optional[Tensor] = None) -> Tensor:
         """conv(trilinear_x2(x)) in one launch (mvsgi_conv3d_up2_f32)."""
+        if self.inorm is not None:
+            return self.inorm.apply(self._run_up2(x_lowres_ndhwc, None), res)
+        return self._run_up2(x_lowres_ndhwc, res)
+
+    def _run_up2(self, x_lowres_ndhwc: Tensor, res: Optional[Tensor] = None) -> Tensor:
         B, Dl, Hl, Wl, _ = x_lowres_ndhwc.shape
         d32 = False
         if _USE_D32 and not _NO_D32U and not self._c16() and self.cin % 32 == 0:
@@ -286,16 +298,86 @@ def _fingerprint(blk) -> tuple:
     parts = [conv.weight.data_ptr(), conv.weight._version, tuple(conv.stride)]
     if conv.bias is not None:
         parts += [conv.bias.data_ptr(), conv.bias._version]
-    norm = blk.norm_layer
-    parts.append(type(norm).__name__)
-    if isinstance(norm, (nn.BatchNorm3d, nn.BatchNorm2d)):
-        parts += [bool(norm.training), float(norm.eps)]
-        for t in (norm.weight, norm.bias, norm.running_mean, norm.running_var):
-            if t is not None:
-                parts += [t.data_ptr(), t._version]
+    parts += norm_key(blk.norm_layer)
     act = blk.activation
     parts += [type(act).__name__, float(getattr(act, "negative_slope", 0.0))]
     return tuple(parts)
+
+
+_BN = (nn.BatchNorm3d, nn.BatchNorm2d)
+_IN = (nn.InstanceNorm3d, nn.InstanceNorm2d)
+
+
+def norm_key(norm) -> list:
+    """The part of a launch record's key that the norm layer decides: type, mode, eps, affine / running-statistics tensors."""
+    parts = [type(norm).__name__]
+    if isinstance(norm, _BN + _IN):
+        parts += [bool(norm.training), float(norm.eps), bool(getattr(norm, "track_running_stats", True))]
+        for t in (norm.weight, norm.bias, norm.running_mean, norm.running_var):
+            parts += [None, None] if t is None else [t.data_ptr(), t._version]
+    return parts
+
+
+class InstanceNormLaunch:
+    """Instance norm with input statistics after a conv (F.instance_norm, use_input_stats): the conv writes conv + bias with no
+    activation, then mvsgi_instance_norm_f32 normalises per (frame, channel) and adds the residual and the activation in place."""
+    __slots__ = ("gamma", "beta", "eps", "neg_slope")
+
+    def apply(self, y: Tensor, res: Optional[Tensor] = None) -> Tensor:
+        return H.instance_norm(y, res=res, gamma=self.gamma, beta=self.beta, eps=self.eps, neg_slope=self.neg_slope, out=y)
+
+
+def _no_inorm(L, what: str) -> None:
+    if L.inorm is not None:
+        raise RuntimeError(f"{what}: this layer has an instance norm (its epilogue does not fold); use the plain fp32 path")
+
+
+def lower_norm(norm, conv_bias: Optional[Tensor], cout: int, device, slope: float, dims: int = 3):
+    """-> (scale, shift, InstanceNormLaunch | None) of the conv epilogue for the block's norm layer (common_modules.py:107-115:
+    conv -> norm -> (+ res) -> act).  Eval BatchNorm, and InstanceNorm with running statistics in eval mode (then the same
+    formula), fold into scale / shift; InstanceNorm with input statistics leaves scale = 1, shift = bias and returns the record
+    of the norm launch that follows the conv."""
+    bias = conv_bias.detach().float() if conv_bias is not None else None
+    name = type(norm).__name__
+    use_running = isinstance(norm, _BN) or (isinstance(norm, _IN) and norm.track_running_stats)
+    if use_running:
+        if norm.training:
+            raise RuntimeError(f"HIP path implements eval-mode {name} only: call model.eval()")
+        if norm.running_mean is None or norm.running_var is None:
+            raise NotImplementedError(f"{name} without running statistics")
+        gamma = norm.weight.detach().float() if norm.weight is not None else torch.ones(cout, device=device)
+        beta = norm.bias.detach().float() if norm.bias is not None else torch.zeros(cout, device=device)
+        # ATen eval batch_norm: alpha = gamma / sqrt(var + eps); y = x * alpha + (beta - mean * alpha)
+        alpha = gamma / torch.sqrt(norm.running_var.detach().float() + norm.eps)
+        scale = alpha
+        shift = beta - norm.running_mean.detach().float() * alpha
+        if bias is not None:
+            shift = shift + bias * alpha
+        return scale, shift, None
+    scale = torch.ones(cout, device=device, dtype=torch.float32)
+    shift = bias.clone() if bias is not None else torch.zeros(cout, device=device, dtype=torch.float32)
+    if _is_identity(norm):
+        return scale, shift, None
+    if isinstance(norm, _IN):
+        if norm.affine and norm.num_features != cout:          # (as _InstanceNorm.forward: without affine tensors torch only warns)
+            raise ValueError(f"{name}({norm.num_features}) after a conv with {cout} output channels")
+        rec = InstanceNormLaunch()
+        rec.gamma = norm.weight.detach().float().contiguous() if norm.affine and norm.weight is not None else None
+        rec.beta = norm.bias.detach().float().contiguous() if norm.affine and norm.bias is not None else None
+        rec.eps, rec.neg_slope = float(norm.eps), float(slope)
+        return scale, shift, rec
+    raise NotImplementedError(f"norm layer {name} has no HIP implementation "
+                              f"(only BatchNorm{dims}d in eval mode, InstanceNorm{dims}d and NoOp)")
+
+
+def act_slope(act) -> float:
+    if isinstance(act, nn.LeakyReLU):
+        return float(act.negative_slope)
+    if isinstance(act, nn.ReLU):
+        return 0.0
+    if _is_identity(act):
+        return 1.0
+    raise NotImplementedError(f"activation {type(act).__name__} has no HIP implementation")
 
 
 def lower_conv_block(blk) -> ConvLaunch:
@@ -320,36 +402,12 @@ def lower_conv_block(blk) -> ConvLaunch:
                            "(there is no CPU fallback)")
     w = w.to(torch.float32).contiguous()
     cout = w.shape[0]
-    norm = blk.norm_layer
-    if isinstance(norm, nn.BatchNorm3d):
-        if norm.training:
-            raise RuntimeError("HIP path implements eval-mode BatchNorm3d only: call model.eval()")
-        if norm.running_mean is None or norm.running_var is None:
-            raise NotImplementedError("BatchNorm3d without running statistics")
-        gamma = norm.weight.detach().float() if norm.weight is not None else torch.ones(cout, device=w.device)
-        beta = norm.bias.detach().float() if norm.bias is not None else torch.zeros(cout, device=w.device)
-        # ATen eval batch_norm: alpha = gamma / sqrt(var + eps); y = x * alpha + (beta - mean * alpha)
-        alpha = gamma / torch.sqrt(norm.running_var.detach().float() + norm.eps)
-        scale = alpha
-        shift = beta - norm.running_mean.detach().float() * alpha
-        if conv.bias is not None:
-            shift = shift + conv.bias.detach().float() * alpha
-    elif _is_identity(norm):
-        scale = torch.ones(cout, device=w.device, dtype=torch.float32)
-        shift = conv.bias.detach().float().clone() if conv.bias is not None \
-            else torch.zeros(cout, device=w.device, dtype=torch.float32)
-    else:
-        raise NotImplementedError(f"norm layer {type(norm).__name__} has no HIP implementation "
-                                  "(only BatchNorm3d in eval mode and NoOp)")
-    act = blk.activation
-    if isinstance(act, nn.LeakyReLU):
-        slope = float(act.negative_slope)
-    elif isinstance(act, nn.ReLU):
-        slope = 0.0
-    elif _is_identity(act):
-        slope = 1.0
-    else:
-        raise NotImplementedError(f"activation {type(act).__name__} has no HIP implementation")
+    if isinstance(blk.norm_layer, (nn.BatchNorm2d, nn.InstanceNorm2d)):
+        raise NotImplementedError(f"norm layer {type(blk.norm_layer).__name__} after a Conv3d")
+    slope = act_slope(blk.activation)
+    scale, shift, inorm = lower_norm(blk.norm_layer, conv.bias, cout, w.device, slope)
+    if inorm is not None:
+        slope = 1.0                 # the conv writes conv + bias; the activation follows the norm
     L = ConvLaunch()
     L.w = w
     L.wp = H.pack_conv_weights(w)
@@ -367,6 +425,7 @@ def lower_conv_block(blk) -> ConvLaunch:
     L.shift = shift.contiguous()
     L.stride = int(conv.stride[0])
     L.neg_slope = slope
+    L.inorm = inorm
     L.cin, L.cout = int(w.shape[1]), int(cout)
     L.key = key
     blk.__dict__["_mvsgi_launch"] = L

@@ -119,7 +119,7 @@ def _std_front(self, feats: Tensor, grids: Tensor, grid_masks: Tensor, masks: Te
     regulator's stride-2 first layer stages by LDS-DMA (csrc/conv3d_s2rs.hip) -- or None when the layer shapes / mode do not
     put post_vol on that kernel."""
     L = cm.lower_conv_block(self.post_vol)
-    if not (_USE_RS and H.split_mode() and L.cin == 16 and L.cout == 16 and L.stride == 1
+    if not (_USE_RS and H.split_mode() and L.cin == 16 and L.cout == 16 and L.stride == 1 and L.inorm is None
             and 0.0 <= L.neg_slope <= 1.0 and feats.dim() == 5 and feats.shape[2] == 16 and grids.dim() == 6):
         return None
     B, D, Ho, Wo = feats.shape[0], grids.shape[2], grids.shape[3], grids.shape[4]

@@ -48,7 +48,7 @@ def _rs_chain(blk, x: Tensor):
     if not (_USE_RS and H.split_mode() and len(blk.blks) > 0):
         return None
     L0 = cm.lower_conv_block(blk.first)
-    if L0.cin % 16 or L0.cout != 32:
+    if L0.cin % 16 or L0.cout != 32 or L0.inorm is not None:      # (the first conv writes split-padded: no norm pass after it)
         return None
     B, D, Hh, W, _ = x.shape
     s = L0.stride
@@ -187,7 +187,7 @@ def _poly_tail(self, x: Tensor, skip: Tensor):
         return None
     up, oc = self.upBlks[len(self.upBlks) - 1], self.out_costs[0]
     Lu, Lo = cm.lower_conv_block(up.conv), cm.lower_conv_block(oc.conv)
-    if not (Lo.poly_ok() and Lu.can_fuse_up2() and Lu.cout == 32 and oc.scale == 2 and oc.out_pad == 0 and up.scale == 2 and up.out_pad == 0):
+    if not (Lo.poly_ok() and Lu.can_fuse_up2() and Lu.inorm is None and Lu.cout == 32 and oc.scale == 2 and oc.out_pad == 0 and up.scale == 2 and up.out_pad == 0):
         return None
     B, Dl, Hl, Wl, _ = x.shape
     if tuple(skip.shape[1:4]) != (2 * Dl, 2 * Hl, 2 * Wl):
@@ -239,7 +239,7 @@ def _split_head_tail(self, x: Tensor):
     exact-fp32 head's 8 x 64 per 32 voxels, which is bound by the fp32 matrix rate.  Returns costs [B, D, H, W, 1] or None."""
     oc = self.out_costs[0]
     Lo, Lh = cm.lower_conv_block(oc.conv), cm.lower_conv_block(self.out_costs[1])
-    if not (_HEAD_SPLIT and Lh.head_split_ok() and Lo.can_fuse_up2() and oc.scale == 2 and oc.out_pad == 0 and Lh.cin == Lo.cout):
+    if not (_HEAD_SPLIT and Lh.head_split_ok() and Lo.can_fuse_up2() and Lo.inorm is None and oc.scale == 2 and oc.out_pad == 0 and Lh.cin == Lo.cout):
         return None
     B, Dl, Hl, Wl, _ = x.shape
     if (2 * Dl + 2) * (2 * Hl + 4) * (2 * Wl + 4) * Lo.cout * 4 >= 2 ** 31:        # the launcher's bound for a split-padded output frame (32-bit offsets)

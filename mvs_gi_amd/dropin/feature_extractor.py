@@ -29,11 +29,21 @@ _STEM_MFMA = H.exp_env("MVSGI_STEM_MFMA", "1") != "0"      # 0: the LDS-tiled VA
 # feature maps, is the INPUT of the path whose 1e-3 bar the modes are about (the sweep consumes them bit-exactly); MVSGI_CONV_MODE=f32
 # runs it on the exact-fp32 kernels.
 class Conv2dLaunch:
-    __slots__ = ("w", "wp_b3", "wp_f32", "wp_stem", "wp_rs", "scale", "shift", "stride", "neg_slope", "k", "cin", "cout", "key")
+    __slots__ = ("w", "wp_b3", "wp_f32", "wp_stem", "wp_rs", "scale", "shift", "stride", "neg_slope", "k", "cin", "cout", "key",
+                 "inorm")
 
     def run(self, x: Tensor, res: Optional[Tensor] = None, in_nchw: bool = False, out_split: Optional[Tensor] = None) -> Tensor:
+        if self.inorm is not None:           # conv (+ bias) -> instance norm (+ res) -> act (cm.InstanceNormLaunch)
+            if out_split is not None:
+                cm._no_inorm(self, "Conv2dLaunch.run(out_split=...)")
+            return self.inorm.apply(self._run_conv(x, None, in_nchw), res)
+        return self._run_conv(x, res, in_nchw, out_split)
+
+    def _run_conv(self, x: Tensor, res: Optional[Tensor] = None, in_nchw: bool = False, out_split: Optional[Tensor] = None) -> Tensor:
         impl, wp = H.CONV_AUTO, None
-        if H.split_mode() and self.k == 3 and self.cin % 16 == 0 and self.cout % 16 == 0 and not in_nchw:
+        # instance-norm layers stay on the exact-fp32 kernels in every mode: the norm divides each channel by its own spread, so
+        # the bf16 split's rounding (relative to the conv output's level) is amplified by 1 / std and compounds over the chain
+        if H.split_mode() and self.inorm is None and self.k == 3 and self.cin % 16 == 0 and self.cout % 16 == 0 and not in_nchw:
             if self.wp_b3 is None:
                 self.wp_b3 = H.pack_conv2d_weights_bf16x3(self.w)
             impl, wp = H.CONV_BF16X3, self.wp_b3
@@ -49,6 +59,7 @@ class Conv2dLaunch:
                         neg_slope=self.neg_slope, impl=impl, in_nchw=in_nchw, out_split=out_split)
 
     def rs_weights(self) -> Tensor:
+        cm._no_inorm(self, "Conv2dLaunch.rs_weights")
         if self.wp_rs is None:
             self.wp_rs = H.pack_resblock2d_split_weights(self.w, self.scale)
         return self.wp_rs
@@ -74,34 +85,18 @@ def lower_conv2d_block(blk) -> Conv2dLaunch:
                            "(there is no CPU fallback)")
     w = w.float().contiguous()
     cout = w.shape[0]
-    if isinstance(norm, nn.BatchNorm2d):
-        if norm.training:
-            raise RuntimeError("HIP path implements eval-mode BatchNorm2d only: call model.eval()")
-        gamma = norm.weight.detach().float() if norm.weight is not None else torch.ones(cout, device=w.device)
-        beta = norm.bias.detach().float() if norm.bias is not None else torch.zeros(cout, device=w.device)
-        alpha = gamma / torch.sqrt(norm.running_var.detach().float() + norm.eps)
-        scale, shift = alpha, beta - norm.running_mean.detach().float() * alpha
-        if conv.bias is not None:
-            shift = shift + conv.bias.detach().float() * alpha
-    elif _is_identity(norm):
-        scale = torch.ones(cout, device=w.device)
-        shift = conv.bias.detach().float().clone() if conv.bias is not None else torch.zeros(cout, device=w.device)
-    else:
-        raise NotImplementedError(f"norm layer {type(norm).__name__} has no HIP implementation")
-    act = blk.activation
-    if isinstance(act, nn.LeakyReLU):
-        slope = float(act.negative_slope)
-    elif isinstance(act, nn.ReLU):
-        slope = 0.0
-    elif _is_identity(act):
-        slope = 1.0
-    else:
-        raise NotImplementedError(f"activation {type(act).__name__} has no HIP implementation")
+    if isinstance(norm, (nn.BatchNorm3d, nn.InstanceNorm3d)):
+        raise NotImplementedError(f"norm layer {type(norm).__name__} after a Conv2d")
+    slope = cm.act_slope(blk.activation)
+    scale, shift, inorm = cm.lower_norm(norm, conv.bias, cout, w.device, slope, dims=2)
+    if inorm is not None:
+        slope = 1.0                  # the conv writes conv + bias; the activation follows the norm
     L = Conv2dLaunch()
     L.w, L.wp_b3, L.wp_f32, L.wp_stem, L.wp_rs = w, None, None, None, None
     L.scale, L.shift = scale.contiguous(), shift.contiguous()
     L.stride, L.neg_slope, L.k = int(conv.stride[0]), slope, int(k)
     L.cin, L.cout, L.key = int(w.shape[1]), int(cout), key
+    L.inorm = inorm
     blk.__dict__["_mvsgi_launch"] = L
     return L
 
@@ -158,7 +153,7 @@ def res_block2d_nhwc(blk, x: Tensor) -> Tensor:
     if not _is_identity(blk.one_by_one) or getattr(blk, "out_pad", 0) != 0:
         raise NotImplementedError("ResConvBlk2d with projection / out_pad is not on the extractor path")
     L1, L2 = lower_conv2d_block(blk.blk1), lower_conv2d_block(blk.blk2)
-    if _FUSE_RESBLOCK and H.split_mode() and L1.k == 3 and L2.k == 3 and L1.stride == 1 and L2.stride == 1 \
+    if _FUSE_RESBLOCK and H.split_mode() and L1.inorm is None and L2.inorm is None and L1.k == 3 and L2.k == 3 and L1.stride == 1 and L2.stride == 1 \
             and (L1.cin, L1.cout, L2.cin, L2.cout) == (16, 16, 16, 16) and L1.neg_slope == L2.neg_slope:
         # both convs in one launch, the intermediate stays in LDS (mvsgi_resblock2d_f32)
         for L in (L1, L2):
@@ -201,7 +196,7 @@ def _fusable_resblock(blk) -> bool:
     if not hasattr(blk, "blk1") or not _is_identity(blk.one_by_one) or getattr(blk, "out_pad", 0) != 0:
         return False
     L1, L2 = lower_conv2d_block(blk.blk1), lower_conv2d_block(blk.blk2)
-    return L1.k == 3 and L2.k == 3 and L1.stride == 1 and L2.stride == 1 and \
+    return L1.inorm is None and L2.inorm is None and L1.k == 3 and L2.k == 3 and L1.stride == 1 and L2.stride == 1 and \
         (L1.cin, L1.cout, L2.cin, L2.cout) == (16, 16, 16, 16) and L1.neg_slope == L2.neg_slope and 0.0 <= L1.neg_slope <= 1.0
 
 
@@ -217,7 +212,7 @@ def _split2d_pair(self, N: int, Hh: int, W: int, device):
 
 
 def _s2_split_ok(L) -> bool:
-    return L.k == 3 and L.stride == 2 and (L.cin, L.cout) == (16, 16) and 0.0 <= L.neg_slope <= 1.0
+    return L.inorm is None and L.k == 3 and L.stride == 2 and (L.cin, L.cout) == (16, 16) and 0.0 <= L.neg_slope <= 1.0
 
 
 def _split_chain_forward(self, xin: Tensor, with_final: bool = True) -> Optional[Tensor]:
@@ -253,7 +248,7 @@ def _split_chain_forward(self, xin: Tensor, with_final: bool = True) -> Optional
         else:
             N, Hin, Win = y.shape[0], y.shape[1], y.shape[2]
             can = L.k == 3 and L.cin % 16 == 0 and L.cout == 16
-        if j > idx + 1 and can:
+        if j > idx + 1 and can and L.inorm is None:
             Ho, Wo = _calc((Hin, Win), L.k, L.stride, L.k // 2)
             cur, other = _split2d_pair(self, N, Ho, Wo, y.device)
             if y_is_split:
@@ -413,11 +408,8 @@ def _lower_sphere(conv, norm=None, act=None):
              float(getattr(act, "negative_slope", 0.0))]
     if conv.bias is not None:
         parts += [conv.bias.data_ptr(), conv.bias._version]
-    if isinstance(norm, nn.BatchNorm2d):
-        parts += [bool(norm.training), float(norm.eps)]
-        for t in (norm.weight, norm.bias, norm.running_mean, norm.running_var):
-            if t is not None:
-                parts += [t.data_ptr(), t._version]
+    if norm is not None:
+        parts += cm.norm_key(norm)
     key = tuple(parts)
     cached = conv.__dict__.get("_mvsgi_launch")
     if cached is not None and cached[0] == key:
@@ -429,30 +421,13 @@ def _lower_sphere(conv, norm=None, act=None):
         raise RuntimeError("mvs_gi_amd modules run on the GPU only: call .cuda() on the model (there is no CPU fallback)")
     w = w.float().contiguous()
     cout = w.shape[0]
-    bias = conv.bias.detach().float() if conv.bias is not None else None
-    if isinstance(norm, nn.BatchNorm2d):
-        if norm.training:
-            raise RuntimeError("HIP path implements eval-mode BatchNorm2d only: call model.eval()")
-        gamma = norm.weight.detach().float() if norm.weight is not None else torch.ones(cout, device=w.device)
-        beta = norm.bias.detach().float() if norm.bias is not None else torch.zeros(cout, device=w.device)
-        alpha = gamma / torch.sqrt(norm.running_var.detach().float() + norm.eps)
-        scale, shift = alpha, beta - norm.running_mean.detach().float() * alpha
-        if bias is not None:
-            shift = shift + bias * alpha
-    elif _is_identity(norm) or norm is None:
-        scale = torch.ones(cout, device=w.device)
-        shift = bias.clone() if bias is not None else torch.zeros(cout, device=w.device)
-    else:
-        raise NotImplementedError(f"norm layer {type(norm).__name__} has no HIP implementation")
-    if isinstance(act, nn.LeakyReLU):
-        slope = float(act.negative_slope)
-    elif isinstance(act, nn.ReLU):
-        slope = 0.0
-    elif _is_identity(act) or act is None:
-        slope = 1.0
-    else:
-        raise NotImplementedError(f"activation {type(act).__name__} has no HIP implementation")
-    rec = dict(wp=H.pack_deform_conv2d_weights(w), scale=scale.contiguous(), shift=shift.contiguous(), slope=slope)
+    if isinstance(norm, (nn.BatchNorm3d, nn.InstanceNorm3d)):
+        raise NotImplementedError(f"norm layer {type(norm).__name__} after a SphereConvEquirect2d")
+    slope = cm.act_slope(act)
+    scale, shift, inorm = cm.lower_norm(norm, conv.bias, cout, w.device, slope, dims=2)
+    if inorm is not None:
+        slope = 1.0                  # the conv writes conv + bias; the activation follows the norm
+    rec = dict(wp=H.pack_deform_conv2d_weights(w), scale=scale.contiguous(), shift=shift.contiguous(), slope=slope, inorm=inorm)
     conv.__dict__["_mvsgi_launch"] = (key, rec)
     return rec
 
@@ -461,9 +436,11 @@ def sphere_conv_nhwc(conv, x: Tensor, norm=None, act=None, res: Optional[Tensor]
     if mask is not None:
         raise NotImplementedError("modulated deform_conv2d (mask) is not on the extractor path")
     rec = _lower_sphere(conv, norm, act)
-    return H.deform_conv2d(x, conv.offset.float(), rec["wp"], rec["scale"], rec["shift"], _pair(conv.kernel_size),
-                           _pair(conv.stride), _pair(conv.padding), _pair(conv.dilation), res=res,
-                           neg_slope=rec["slope"])
+    inorm = rec["inorm"]
+    y = H.deform_conv2d(x, conv.offset.float(), rec["wp"], rec["scale"], rec["shift"], _pair(conv.kernel_size),
+                        _pair(conv.stride), _pair(conv.padding), _pair(conv.dilation), res=None if inorm else res,
+                        neg_slope=rec["slope"])
+    return y if inorm is None else inorm.apply(y, res)
 
 
 def sphere_blk_nhwc(blk, x: Tensor, res: Optional[Tensor] = None) -> Tensor:

@@ -996,6 +996,39 @@ def resize_trilinear(x, size) -> torch.Tensor:
     return y
 
 
+def instance_norm(x, res=None, gamma=None, beta=None, eps: float = 1e-5, neg_slope: float = 1.0, out=None) -> torch.Tensor:
+    """Instance norm with input statistics on channels-last x [B, ..., C] (NDHWC or NHWC), per frame and channel over all spatial
+    positions (F.instance_norm, biased variance): y = act((x - mean) / sqrt(var + eps) * gamma + beta (+ res)), act(v) = v if
+    v > 0 else v * neg_slope.  gamma / beta [C] or None; `out` may be x itself (in place).  Two launches on x's stream; the
+    workspace comes from torch's allocator, so the call can be captured into a hipGraph."""
+    lib = _lib.load()
+    x = _dev(x, "x")
+    B, C = int(x.shape[0]), int(x.shape[-1])
+    S = x.numel() // max(B * C, 1)
+    if S < 2:
+        # F.instance_norm -> _verify_spatial_size
+        raise ValueError(f"Expected more than 1 spatial element when training, got input size "
+                         f"{[B, C] + list(x.shape[1:-1])}")
+    if res is not None:
+        res = _dev(res, "res")
+        if tuple(res.shape) != tuple(x.shape):
+            raise AssertionError(f"residual {tuple(res.shape)} does not match {tuple(x.shape)}")
+    for t, name in ((gamma, "gamma"), (beta, "beta")):
+        if t is not None and (t.numel() != C or not t.is_cuda or t.dtype != torch.float32 or not t.is_contiguous()):
+            raise AssertionError(f"{name} must be a contiguous fp32 [{C}] device tensor")
+    if out is None:
+        out = torch.empty_like(x)
+    elif out.data_ptr() != x.data_ptr():
+        out = _dev(out, "out")
+        if tuple(out.shape) != tuple(x.shape) or out.data_ptr() % 16:
+            raise AssertionError(f"out {tuple(out.shape)} does not match {tuple(x.shape)}")
+    nbytes = lib.mvsgi_instance_norm_ws_bytes(B, S, C)
+    ws = torch.empty(max(int(nbytes), 16), device=x.device, dtype=torch.uint8)
+    _lib.check(lib.mvsgi_instance_norm_f32(x.data_ptr(), _ptr(res), _ptr(gamma), _ptr(beta), out.data_ptr(), ws.data_ptr(),
+                                           B, S, C, float(eps), float(neg_slope), _stream_ptr(x)), "mvsgi_instance_norm_f32")
+    return out
+
+
 def softargmin(costs_bdhw, inv_idx, scale: int, want_norm_costs: bool, post_div: float = 1.0):
     """costs [B, D, H, W], inv_idx [D] -> inv_dist [B, 1, sH, sW] (divided by post_div), norm_costs
     [B, D, sH, sW] | None."""

@@ -20,8 +20,11 @@ def build_modules(cfg: PathConfig, weights: Optional[Dict[str, Dict[str, np.ndar
     """Instantiate the three drop-in modules for a config and (optionally) load state dicts
     keyed with the reference's names."""
     Builder = dropin.SphericalSweepStdMasked if cfg.builder == "std" else dropin.SphericalSweep
-    cvb = Builder(num_cams=cfg.num_cams, feat_chs=cfg.vol_chs, post_k_sz=3)
-    reg = dropin.UNetCostVolumeRegulatorBase(in_chs=cfg.reg_in_chs, f_int_chs=cfg.reg_f_int_chs)
+    cvb = Builder(num_cams=cfg.num_cams, feat_chs=cfg.vol_chs, post_k_sz=3, norm_type=cfg.norm_type)
+    reg = dropin.UNetCostVolumeRegulatorBase(in_chs=cfg.reg_in_chs, f_int_chs=cfg.reg_f_int_chs, norm_type=cfg.norm_type)
+    if cfg.norm_type == "instance" and cfg.norm_affine:
+        for m in (cvb, reg):
+            affine_instance_norms(m)
     dr = dropin.DistanceRegressorWithFixedCandidates(bf=cfg.bf, dist_cands=list(cfg.dist_cands),
                                                      interp_scale_factor=cfg.interp_scale_factor,
                                                      pre_interp=cfg.pre_interp)
@@ -32,6 +35,17 @@ def build_modules(cfg: PathConfig, weights: Optional[Dict[str, Dict[str, np.ndar
                             strict=True)
     mods = [m.eval().to(device) for m in (cvb, reg, dr)]
     return tuple(mods)
+
+
+def affine_instance_norms(module: torch.nn.Module) -> torch.nn.Module:
+    """Replace every nn.InstanceNorm3d / 2d under `module` by the same norm with affine=True (gamma = 1, beta = 0 until a state
+    dict is loaded): the `norm_affine` variant of PathConfig, which the reference's tables do not name."""
+    for name, child in list(module.named_children()):
+        if isinstance(child, (torch.nn.InstanceNorm3d, torch.nn.InstanceNorm2d)) and not child.affine:
+            setattr(module, name, type(child)(child.num_features, eps=child.eps, affine=True))
+        else:
+            affine_instance_norms(child)
+    return module
 
 
 class HotPath:
@@ -271,7 +285,7 @@ class InferencePipeline:
         self.hot = HotPath(cfg, weights, consts, device)
         Hi, Wi = cfg.feat_hw
         Extractor = {"simple": dropin.SimpleFeatExtraction, "sphere": dropin.SphereEquirectFeatExtraction}[extractor]
-        fe = Extractor(in_size=(4 * Hi, 4 * Wi), in_chs=3, chs=cfg.feat_chs, k_sz=3, layers=[5, 10])
+        fe = Extractor(in_size=(4 * Hi, 4 * Wi), in_chs=3, chs=cfg.feat_chs, k_sz=3, layers=[5, 10], norm_type=cfg.norm_type)
         sd = {k: torch.from_numpy(np.asarray(v)) for k, v in weights["feature_extractor"].items()}
         if extractor == "sphere":          # the offset field is a constructor-made buffer unless the checkpoint brings one
             sd.setdefault("final_layer.blk.0.offset", fe.final_layer.blk[0].offset)

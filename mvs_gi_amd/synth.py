@@ -100,18 +100,29 @@ def make_inputs(cfg: PathConfig, seed: int = 0, batch: int = 1, grid_kind: str =
 # ----------------------------------------------------------------------------
 # weights
 # ----------------------------------------------------------------------------
-def _conv_block(rng, prefix, cin, cout, has_norm, has_bias, out):
+def _conv_block(rng, prefix, cin, cout, has_norm, has_bias, out, norm_type: str = "batch", norm_affine: bool = False):
     fan_in = cin * 27
     bound = float(np.sqrt(6.0 / fan_in))
     out[f"{prefix}.conv_layer.weight"] = rng.uniform(-bound, bound, (cout, cin, 3, 3, 3)).astype(np.float32)
     if has_bias:
         out[f"{prefix}.conv_layer.bias"] = rng.normal(0, 0.1, (cout,)).astype(np.float32)
     if has_norm:
-        out[f"{prefix}.norm_layer.weight"] = rng.uniform(0.5, 1.5, (cout,)).astype(np.float32)
-        out[f"{prefix}.norm_layer.bias"] = rng.normal(0, 0.1, (cout,)).astype(np.float32)
-        out[f"{prefix}.norm_layer.running_mean"] = rng.normal(0, 0.1, (cout,)).astype(np.float32)
-        out[f"{prefix}.norm_layer.running_var"] = rng.uniform(0.5, 1.5, (cout,)).astype(np.float32)
-        out[f"{prefix}.norm_layer.num_batches_tracked"] = np.asarray(1, np.int64)
+        # drawn whatever the norm type, so that the conv weights of every norm type come from the same generator stream
+        norm = dict(weight=rng.uniform(0.5, 1.5, (cout,)).astype(np.float32),
+                    bias=rng.normal(0, 0.1, (cout,)).astype(np.float32),
+                    running_mean=rng.normal(0, 0.1, (cout,)).astype(np.float32),
+                    running_var=rng.uniform(0.5, 1.5, (cout,)).astype(np.float32),
+                    num_batches_tracked=np.asarray(1, np.int64))
+        if norm_type == "batch":
+            keep = tuple(norm)
+        elif norm_type == "instance":          # nn.InstanceNorm3d defaults: no running statistics; gamma / beta only when affine
+            keep = ("weight", "bias") if norm_affine else ()
+        elif norm_type == "none":
+            keep = ()
+        else:
+            raise ValueError(f"norm_type {norm_type!r}")
+        for k in keep:
+            out[f"{prefix}.norm_layer.{k}"] = norm[k]
 
 
 def make_weights(cfg: PathConfig, seed: int = 0, gain: float = 1.0) -> Dict[str, Dict[str, np.ndarray]]:
@@ -120,45 +131,52 @@ def make_weights(cfg: PathConfig, seed: int = 0, gain: float = 1.0) -> Dict[str,
     peaky like a trained network's (SURVEY.md §7 'Precision vs the 1e-3 bar')."""
     rng = np.random.default_rng(10_000 + seed)
     builder: Dict[str, np.ndarray] = {}
-    _conv_block(rng, "post_vol", cfg.vol_chs, cfg.vol_chs, True, False, builder)
+    nt = dict(norm_type=cfg.norm_type, norm_affine=cfg.norm_affine)
+    _conv_block(rng, "post_vol", cfg.vol_chs, cfg.vol_chs, True, False, builder, **nt)
     reg: Dict[str, np.ndarray] = {}
     for prefix, cin, cout, has_norm, has_bias in regulator_conv_specs(cfg.reg_in_chs, cfg.reg_f_int_chs):
-        _conv_block(rng, prefix, cin, cout, has_norm, has_bias, reg)
+        _conv_block(rng, prefix, cin, cout, has_norm, has_bias, reg, **nt)
     reg["out_costs.1.conv_layer.weight"] = (reg["out_costs.1.conv_layer.weight"] * np.float32(gain)).astype(np.float32)
     return dict(cv_builder=builder, cv_regulator=reg)
 
 
-def _conv_block2d(rng, prefix, cin, cout, k, out):
+def _conv_block2d(rng, prefix, cin, cout, k, out, norm_type: str = "batch"):
     bound = float(np.sqrt(6.0 / (cin * k * k)))
     out[f"{prefix}.conv_layer.weight"] = rng.uniform(-bound, bound, (cout, cin, k, k)).astype(np.float32)
-    out[f"{prefix}.norm_layer.weight"] = rng.uniform(0.5, 1.5, (cout,)).astype(np.float32)
-    out[f"{prefix}.norm_layer.bias"] = rng.normal(0, 0.1, (cout,)).astype(np.float32)
-    out[f"{prefix}.norm_layer.running_mean"] = rng.normal(0, 0.1, (cout,)).astype(np.float32)
-    out[f"{prefix}.norm_layer.running_var"] = rng.uniform(0.5, 1.5, (cout,)).astype(np.float32)
-    out[f"{prefix}.norm_layer.num_batches_tracked"] = np.asarray(1, np.int64)
+    norm = dict(weight=rng.uniform(0.5, 1.5, (cout,)).astype(np.float32),
+                bias=rng.normal(0, 0.1, (cout,)).astype(np.float32),
+                running_mean=rng.normal(0, 0.1, (cout,)).astype(np.float32),
+                running_var=rng.uniform(0.5, 1.5, (cout,)).astype(np.float32),
+                num_batches_tracked=np.asarray(1, np.int64))
+    if norm_type == "batch":
+        for k_, v in norm.items():
+            out[f"{prefix}.norm_layer.{k_}"] = v
+    elif norm_type not in ("instance", "none"):        # nn.InstanceNorm2d defaults: no parameters, no buffers
+        raise ValueError(f"norm_type {norm_type!r}")
 
 
 def make_extractor_weights(seed: int = 0, in_chs: int = 3, chs: int = 16, layers=(5, 10),
-                           out_gain: float = 0.06) -> Dict[str, np.ndarray]:
+                           out_gain: float = 0.06, norm_type: str = "batch") -> Dict[str, np.ndarray]:
     """State dict of SimpleFeatExtraction (reference key names: first, blks.{i}[.blk1|.blk2], final_layer).
     `out_gain` scales the last BatchNorm so that the features come out O(1) like the N(0,1) features
     the hot-path cases use (31 He-initialised layers with residual adds otherwise grow them ~18x, which
     turns the downstream softmax into an arg-max and the end-to-end test into a tie-breaking test)."""
     rng = np.random.default_rng(20_000 + seed)
     sd: Dict[str, np.ndarray] = {}
-    _conv_block2d(rng, "first", in_chs, chs, 5, sd)
+    _conv_block2d(rng, "first", in_chs, chs, 5, sd, norm_type)
     i = 0
     for step, n in enumerate(layers):
         for _ in range(n):
-            _conv_block2d(rng, f"blks.{i}.blk1", chs, chs, 3, sd)
-            _conv_block2d(rng, f"blks.{i}.blk2", chs, chs, 3, sd)
+            _conv_block2d(rng, f"blks.{i}.blk1", chs, chs, 3, sd, norm_type)
+            _conv_block2d(rng, f"blks.{i}.blk2", chs, chs, 3, sd, norm_type)
             i += 1
         if step != len(layers) - 1:
-            _conv_block2d(rng, f"blks.{i}", chs, chs, 3, sd)
+            _conv_block2d(rng, f"blks.{i}", chs, chs, 3, sd, norm_type)
             i += 1
-    _conv_block2d(rng, "final_layer", chs, chs, 3, sd)
-    sd["final_layer.norm_layer.weight"] = (sd["final_layer.norm_layer.weight"] * np.float32(out_gain)).astype(np.float32)
-    sd["final_layer.norm_layer.bias"] = (sd["final_layer.norm_layer.bias"] * np.float32(out_gain)).astype(np.float32)
+    _conv_block2d(rng, "final_layer", chs, chs, 3, sd, norm_type)
+    if norm_type == "batch":
+        sd["final_layer.norm_layer.weight"] = (sd["final_layer.norm_layer.weight"] * np.float32(out_gain)).astype(np.float32)
+        sd["final_layer.norm_layer.bias"] = (sd["final_layer.norm_layer.bias"] * np.float32(out_gain)).astype(np.float32)
     return sd
 
 

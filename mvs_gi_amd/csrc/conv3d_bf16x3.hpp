@@ -1473,26 +1473,22 @@ int launch_bf16x3(ConvArgs a, hipStream_t st) {
     a.tiles_h = (int)mvsgi::cdiv(a.Ho, TH);
     a.tiles_w = (int)mvsgi::cdiv(a.Wo, TW);
     const int CT = a.Cout / (V32 ? 32 : 16);
-    // The border-plane skip (conv3d_x3_body, BRD): the bricks at the bottom and at the top of the volume as launches of their own on
-    // kernels that leave out the taps meeting the padding, the bricks between on this one -- where a layer of bricks is rounds of
-    // the chip by itself (a few-round launch would pay three prologues and three tails for it)
+    // The border-plane skip (conv3d_x3_body, BRD): in a volume four planes deep the bricks at the bottom and at the top as launches of
+    // their own on kernels that leave out the taps meeting the padding -- where a layer of bricks is rounds of the chip by itself (a
+    // few-round launch would pay two prologues and two tails for it)
     constexpr bool kBorderSplit = D32 && !DSK && BRD == 0 && TD == 2 && WM == 2 && MW == 4 && TH == 4 && TW == 16 && S == 1;
     if constexpr (kBorderSplit) {
         const long long layer = (long long)a.B * a.tiles_h * a.tiles_w * mvsgi::cdiv(CT, WN * NW);
         // (measured, tools/d32_probe.py: at D = 4 -- two launches, every brick a border brick -- 64 -> 64 [4,20,80] x 128 0.94 -> 0.90 of
-        // the tap-pair kernel; at D = 8, 16 the third launch and the shorter walks cost what the skipped sixth of 2 of 4 / 2 of 8
-        // bricks saves: 96 -> 96 [16,80,320] x 8 0.931 -> 0.964.  So: volumes four planes deep.)
-        const char* dmax_ = mvsgi::exp_env("MVSGI_BSK_DMAX");
-        if (a.od_cnt == 0 && a.Do >= 4 && a.Do <= (dmax_ ? atoi(dmax_) : 4) && a.Do % 2 == 0 && layer >= 4ll * geo.cus && !mvsgi::exp_env("MVSGI_NO_BSK")) {
+        // the tap-pair kernel; at D = 8, 16 a third launch for the bricks between and the shorter walks cost what the skipped sixth of
+        // 2 of 4 / 2 of 8 bricks saves: 96 -> 96 [16,80,320] x 8 0.931 -> 0.964.  So: volumes four planes deep.)
+        if (a.od_cnt == 0 && a.Do == 4 && layer >= 4ll * geo.cus) {
             ConvArgs b = a;
             b.od_cnt = 1;
             b.od_off = 0;
             if (launch_bf16x3<NW, MW, WM, WN, TD, TH, TW, S, KD, UPS, PLANE, V32, WLDS, F16, D32, DSK, 1>(b, st)) return 1;
-            b.od_off = a.Do - 2;
-            if (launch_bf16x3<NW, MW, WM, WN, TD, TH, TW, S, KD, UPS, PLANE, V32, WLDS, F16, D32, DSK, 2>(b, st)) return 1;
-            if (a.Do == 4) return 0;
-            a.od_off = 2;
-            a.od_cnt = a.Do / 2 - 2;
+            b.od_off = 2;
+            return launch_bf16x3<NW, MW, WM, WN, TD, TH, TW, S, KD, UPS, PLANE, V32, WLDS, F16, D32, DSK, 2>(b, st);
         }
     }
     a.tiles_d = a.od_cnt > 0 ? a.od_cnt : (int)mvsgi::cdiv(a.Do, TD);

@@ -359,12 +359,6 @@ extern "C" int mvsgi_conv3d_s2rs_out_fmt(const void* x_split, const void* w_pack
     hipStream_t st = mvsgi::as_stream(stream);
     if (fmt && y_f32p) return s2_launch<4, 2, true, true>(a, st);
     if (fmt) return s2_launch<4, 2, true>(a, st);
-#ifdef MVSGI_EXPERIMENTAL      // measured equal or slower (DESIGN_HISTORY.md): 2-row bricks with two workgroups per CU, single-window workgroups
-    const char* th_e = mvsgi::exp_env("MVSGI_S2RS_TH");          // brick height: 4 output rows (one workgroup per CU) or 2 (two)
-    const char* nb_e = mvsgi::exp_env("MVSGI_S2RS_NBUF");        // windows per workgroup: 1 (two workgroups per CU) or 2 (TH = 4: one)
-    if (th_e && atoi(th_e) == 2) return s2_launch<2, 2>(a, st);
-    if (nb_e && atoi(nb_e) == 1) return s2_launch<4, 1>(a, st);
-#endif
     return s2_launch<4, 2>(a, st);
 }
 extern "C" int mvsgi_conv3d_s2rs_fmt(const void* x_split, const void* w_packed, const float* shift, void* y_split, int B, int D, int H,

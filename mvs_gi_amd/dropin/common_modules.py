@@ -43,19 +43,16 @@ NORM3D_TYPE: Dict[str, Type[nn.Module]] = {"batch": nn.BatchNorm3d, "instance": 
 # ------------------------------------------------------------------------------------------
 # lowering of one conv block to the arguments of mvsgi_conv3d_f32
 # ------------------------------------------------------------------------------------------
-# MVSGI_V32=1: 32x32x16-MFMA kernels for the Cout % 32 == 0 layers (measured on par with the 16x16x32 kernels, so off by default)
-_USE_V32 = H.exp_env("MVSGI_V32", "0") != "0"
 # MVSGI_D32=0: keep the Cin % 32 == 0 stride-1 layers of large launches on the tap-pair layout (default: 32-channel slices,
 # csrc/conv3d_bf16x3.hpp D32 -- 27 k-steps per 32 channels instead of 28 and half the slices per unit: 6-9 % of those layers)
 _USE_D32 = os.environ.get("MVSGI_D32", "1") != "0"
-_NO_D32U = H.exp_env("MVSGI_NO_D32U", "0") != "0"      # (tools: the fused-upsample layers alone back on tap pairs)
 _D32_OK: Dict[tuple, bool] = {}       # (cin, cout, B, D, H, W) -> mvsgi_conv3d_d32_applies; ("up2", ...) -> mvsgi_conv3d_up2_d32_applies
 
 
 class ConvLaunch:
     """Device-resident launch arguments of one BaseConvBlk3d: PyTorch-layout weight, packed
     MFMA weight (or None), per-channel scale/shift (eval BatchNorm3d or bias), stride, slope."""
-    __slots__ = ("w", "wp", "wp_b3", "wp_c16", "wp_v32", "wp_d32", "wp_rs", "wp_s2", "wp_poly", "wp_head", "head_sc", "scale", "shift", "stride",
+    __slots__ = ("w", "wp", "wp_b3", "wp_c16", "wp_d32", "wp_rs", "wp_s2", "wp_poly", "wp_head", "head_sc", "scale", "shift", "stride",
                  "neg_slope", "cin", "cout", "key", "f16", "inorm")
 
     def run(self, x_ndhwc: Tensor, res: Optional[Tensor] = None, impl: Optional[int] = None) -> Tensor:
@@ -67,9 +64,7 @@ class ConvLaunch:
         wp = self.wp
         if impl is None and H.get_conv_mode() == "f16x3" and self.cin % 16 == 0 and self.cout % 16 == 0:
             B, D, Hh, W, _ = x_ndhwc.shape
-            layout = H.CONV_BF16X3_C16 if self._c16() else \
-                (H.CONV_BF16X3_V32 if _USE_V32 and self.cout % 32 == 0 and H.conv3d_v32_applies(B, self.cin, D, Hh, W, self.cout, self.stride)
-                 else (H.CONV_BF16X3_D32 if self._d32(B, D, Hh, W) else H.CONV_BF16X3))
+            layout = H.CONV_BF16X3_C16 if self._c16() else (H.CONV_BF16X3_D32 if self._d32(B, D, Hh, W) else H.CONV_BF16X3)
             wp16, sc16 = self._f16(layout)
             return H.conv3d(x_ndhwc, self.w, wp16, sc16, self.shift, res=res, stride=self.stride, neg_slope=self.neg_slope,
                             impl=layout | H.CONV_F16)
@@ -79,8 +74,6 @@ class ConvLaunch:
                 B, D, Hh, W, _ = x_ndhwc.shape
                 if self._c16():
                     impl, wp = H.CONV_BF16X3_C16, self._wp_c16()
-                elif _USE_V32 and self.cout % 32 == 0 and H.conv3d_v32_applies(B, self.cin, D, Hh, W, self.cout, self.stride):
-                    impl, wp = H.CONV_BF16X3_V32, self._wp_v32()
                 elif self._d32(B, D, Hh, W):
                     if getattr(self, "wp_d32", None) is None:
                         self.wp_d32 = H.pack_conv_weights_bf16x3_d32(self.w)
@@ -187,11 +180,6 @@ class ConvLaunch:
             self.f16["s2"] = (wp, (self.shift * up).contiguous(), un)
         return self.f16["s2"]
 
-    def _wp_v32(self):
-        if self.wp_v32 is None:
-            self.wp_v32 = H.pack_conv_weights_bf16x3_v32(self.w)
-        return self.wp_v32
-
     def poly_ok(self) -> bool:
         """ResizeConv3d in polyphase form on the register-stationary kernel (csrc/conv3d_up2poly.hip)."""
         return self.inorm is None and H.split_mode() and self.stride == 1 and H.conv3d_up2_poly_applies(self.cin, self.cout, self.neg_slope)
@@ -262,7 +250,7 @@ class ConvLaunch:
     def _run_up2(self, x_lowres_ndhwc: Tensor, res: Optional[Tensor] = None) -> Tensor:
         B, Dl, Hl, Wl, _ = x_lowres_ndhwc.shape
         d32 = False
-        if _USE_D32 and not _NO_D32U and not self._c16() and self.cin % 32 == 0:
+        if _USE_D32 and not self._c16() and self.cin % 32 == 0:
             key = ("up2", self.cin, self.cout, B, Dl, Hl, Wl)
             d32 = _D32_OK.get(key)
             if d32 is None:
@@ -278,9 +266,6 @@ class ConvLaunch:
             if getattr(self, "wp_d32", None) is None:
                 self.wp_d32 = H.pack_conv_weights_bf16x3_d32(self.w)
             return H.conv3d_up2(x_lowres_ndhwc, self.wp_d32, self.scale, self.shift, res=res, neg_slope=self.neg_slope, w_layout=H.CONV_BF16X3_D32)
-        if _USE_V32 and self.cout % 32 == 0 and H.conv3d_v32_applies(B, self.cin, 2 * Dl, 2 * Hl, 2 * Wl, self.cout, 1):
-            return H.conv3d_up2(x_lowres_ndhwc, self._wp_v32(), self.scale, self.shift, res=res,
-                                neg_slope=self.neg_slope, w_layout=H.CONV_BF16X3_V32)
         if self.wp_b3 is None:
             self.wp_b3 = H.pack_conv_weights_bf16x3(self.w)
         return H.conv3d_up2(x_lowres_ndhwc, self.wp_b3, self.scale, self.shift, res=res, neg_slope=self.neg_slope)
@@ -413,7 +398,6 @@ def lower_conv_block(blk) -> ConvLaunch:
     L.wp = H.pack_conv_weights(w)
     L.wp_b3 = None
     L.wp_c16 = None
-    L.wp_v32 = None
     L.wp_d32 = None
     L.wp_rs = None
     L.wp_s2 = None

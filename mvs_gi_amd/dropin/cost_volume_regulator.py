@@ -34,12 +34,11 @@ class UNetDownBlk(nn.Module):
         return cm._to_ncdhw_view(down_block_ndhwc(self, H.as_ndhwc(x)))
 
 
-# MVSGI_RS=0 keeps every layer on the streaming kernels.  MVSGI_RS_MIN_UNITS: minimum
-# 128-voxel bricks per launch (one workgroup per CU, each with a prologue and two drain phases: small launches lose)
-_USE_RS = H.exp_env("MVSGI_RS", "1") != "0"
+# the level-0 residual chain register-stationary (False: every layer on the streaming kernels; the tests' reference path).  Measured
+# faster down to one frame (B=1: 16.9 vs 24.2 us, 23.5 vs 32.2 us)
+_USE_RS = True
 _USE_WINO = os.environ.get("MVSGI_WINO", "1") != "0"        # MVSGI_WINO=0: the level-0 residual convs stay on the direct kernel in the fp16 split too
-_WINO_A32 = H.exp_env("MVSGI_WINO_A32", "1") != "0"          # (experiment switch: 0 = split-padded fp16 pairs between the Winograd layers)
-_RS_MIN_UNITS = int(H.exp_env("MVSGI_RS_MIN_UNITS", "0"))      # measured faster down to one frame (B=1: 16.9 vs 24.2 us, 23.5 vs 32.2 us)
+_WINO_A32 = True          # fp32-padded activations between the Winograd layers (False: split-padded fp16 pairs; the tests' reference path)
 
 
 def _rs_chain(blk, x: Tensor):
@@ -53,8 +52,6 @@ def _rs_chain(blk, x: Tensor):
     B, D, Hh, W, _ = x.shape
     s = L0.stride
     Do, Ho, Wo = (D - 1) // s + 1, (Hh - 1) // s + 1, (W - 1) // s + 1
-    if B * ((Do + 1) // 2) * ((Ho + 3) // 4) * ((Wo + 15) // 16) < _RS_MIN_UNITS:
-        return None
     chain = []
     for rb in blk.blks:
         if not cm._is_identity(rb.one_by_one) or getattr(rb, "out_pad", 0) != 0:
@@ -126,10 +123,8 @@ def _down_block_rs(blk, x: Tensor, L0, chain, dims) -> Tensor:
     return out
 
 
-# MVSGI_S2RS=0: the builder -> regulator hand-over stays an fp32 tensor (the regulator's first layer on the streaming kernel).
-# MVSGI_S2RS_MIN_FRAMES: smallest batch for the split-padded hand-over
+# MVSGI_S2RS=0: the builder -> regulator hand-over stays an fp32 tensor (the regulator's first layer on the streaming kernel)
 _USE_S2RS = os.environ.get("MVSGI_S2RS", "1") != "0"
-_S2RS_MIN_FRAMES = int(H.exp_env("MVSGI_S2RS_MIN_FRAMES", "1"))
 
 
 class _Shape:
@@ -143,8 +138,7 @@ def regulator_takes_split(self, shape) -> bool:
     """True when forward_split_in() can take a split-padded cost volume of geometry `shape` = (B, D, H, W, C): the (16, 32)
     regulator in split-bf16 mode, whose first layer (16 -> 32, stride 2) then stages pre-split voxels by LDS-DMA and whose
     level-0 residual blocks run register-stationary."""
-    if not (_USE_S2RS and H.split_mode() and len(self.down_blks) > 0 and len(shape) == 5 and shape[4] == 16
-            and shape[0] >= _S2RS_MIN_FRAMES):
+    if not (_USE_S2RS and H.split_mode() and len(self.down_blks) > 0 and len(shape) == 5 and shape[4] == 16):
         return False
     blk = self.down_blks[0]
     return cm.lower_conv_block(blk.first).s2rs_ok() and _rs_chain(blk, _Shape(shape)) is not None
@@ -169,14 +163,14 @@ def down_block_ndhwc(blk, x) -> Tensor:
     return x
 
 
-# MVSGI_POLY=0 keeps out_costs.0 on the streaming kernel with the upsample evaluated in its producers.  MVSGI_POLY_MIN_UNITS: minimum
+# MVSGI_POLY=0 keeps out_costs.0 on the streaming kernel with the upsample evaluated in its producers.  _POLY_MIN_UNITS: minimum
 # 128-cell bricks (low resolution) per launch for the polyphase form
 _USE_POLY = os.environ.get("MVSGI_POLY", "1") != "0"
 _HEAD_SPLIT = os.environ.get("MVSGI_HEAD_SPLIT", "1") != "0"      # 0: polyphase out_costs.0 writes fp32 and the exact-fp32 head reads it
 # (measured on MI355X, G16V, 400 bricks per frame and role, one hipGraph replay per step: 1 frame 0.506 vs 0.497 ms with / without,
 # 2 frames 0.779 vs 0.766, 4 frames 1.150 vs 1.167, 64 frames 12.57 vs 13.28 -- three launches and a prologue + two drain phases
 # per workgroup need ~4 frames to pay)
-_POLY_MIN_UNITS = int(H.exp_env("MVSGI_POLY_MIN_UNITS", "1600"))
+_POLY_MIN_UNITS = 1600
 
 
 def _poly_tail(self, x: Tensor, skip: Tensor):

@@ -10,7 +10,6 @@ from __future__ import annotations
 
 import copy
 import math
-import os
 from typing import Optional, Sequence, Tuple
 
 import torch
@@ -20,9 +19,6 @@ from .. import hip_ops as H
 from . import common_modules as cm
 from .common_modules import module_getstate, NoOp, NORM2D_TYPE, RELU_TYPE, _is_identity
 
-
-_SPLIT_CHAIN = H.exp_env("MVSGI_EXTRACTOR_SPLIT", "1") != "0"  # 0: the round-2 chain (fp32 activations between all layers)
-_STEM_MFMA = H.exp_env("MVSGI_STEM_MFMA", "1") != "0"      # 0: the LDS-tiled VALU stem for uint8 images too
 
 
 # The extractor's arithmetic: its split kernels are bf16-split in BOTH split modes of the library (bf16x3, f16x3) -- its output, the
@@ -51,7 +47,7 @@ class Conv2dLaunch:
             if self.wp_f32 is None:                    # exact fp32 mode: fp32 MFMA kernel
                 self.wp_f32 = H.pack_conv2d_weights_f32(self.w)
             impl, wp = H.CONV_MFMA, self.wp_f32
-        elif x.dtype == torch.uint8 and (self.k, self.stride, self.cin, self.cout) == (5, 2, 3, 16) and _STEM_MFMA:
+        elif x.dtype == torch.uint8 and (self.k, self.stride, self.cin, self.cout) == (5, 2, 3, 16):
             if self.wp_stem is None:                   # camera images: the stem on the matrix cores (exact pixels, 24-bit weights)
                 self.wp_stem = H.pack_conv2d_stem_weights(self.w)
             wp = self.wp_stem
@@ -146,14 +142,11 @@ class BaseConvBlk2d(nn.Module):
         return h + 2 * self.out_pad, w + 2 * self.out_pad
 
 
-_FUSE_RESBLOCK = H.exp_env("MVSGI_FUSE_RESBLOCK", "1") != "0"
-
-
 def res_block2d_nhwc(blk, x: Tensor) -> Tensor:
     if not _is_identity(blk.one_by_one) or getattr(blk, "out_pad", 0) != 0:
         raise NotImplementedError("ResConvBlk2d with projection / out_pad is not on the extractor path")
     L1, L2 = lower_conv2d_block(blk.blk1), lower_conv2d_block(blk.blk2)
-    if _FUSE_RESBLOCK and H.split_mode() and L1.inorm is None and L2.inorm is None and L1.k == 3 and L2.k == 3 and L1.stride == 1 and L2.stride == 1 \
+    if H.split_mode() and L1.inorm is None and L2.inorm is None and L1.k == 3 and L2.k == 3 and L1.stride == 1 and L2.stride == 1 \
             and (L1.cin, L1.cout, L2.cin, L2.cout) == (16, 16, 16, 16) and L1.neg_slope == L2.neg_slope:
         # both convs in one launch, the intermediate stays in LDS (mvsgi_resblock2d_f32)
         for L in (L1, L2):
@@ -220,7 +213,7 @@ def _split_chain_forward(self, xin: Tensor, with_final: bool = True) -> Optional
     residual blocks writes the 2-D split-padded format, the blocks hand it on, a stride-2 layer between two runs reads and
     writes it (mvsgi_conv2d_s2_split), the last block in front of any other layer writes fp32.  None when this mode / recipe
     has no such run."""
-    if not (_SPLIT_CHAIN and H.split_mode()):
+    if not H.split_mode():
         return None
     layers = [self.first] + list(self.blks) + ([self.final_layer] if with_final else [])
     fus = [hasattr(m, "blk1") and _fusable_resblock(m) for m in layers]

@@ -32,21 +32,9 @@ if _CONV_MODE not in CONV_MODES:
     raise ValueError(f"MVSGI_CONV_MODE={_CONV_MODE!r} not in {CONV_MODES}")
 
 
-def exp_env(name: str, default: str) -> str:
-    """Experiment switches -- A/B knobs whose measurement is recorded in DESIGN.md / DESIGN_HISTORY.md as neutral or slower -- are
-    read only when MVSGI_EXPERIMENTAL=1; the product configuration surface is MVSGI_CONV_MODE, MVSGI_RIG_CACHE, MVSGI_POLY,
-    MVSGI_S2RS, MVSGI_HEAD_SPLIT, MVSGI_FRONT_CHUNK (each covered by tests/test_gpu_parity.py::test_product_switches_off), MVSGI_WINO
-    (test_full_size_winograd_level0_vs_direct_kernel_and_reference_golden) and MVSGI_LIB."""
-    if os.environ.get("MVSGI_EXPERIMENTAL") == "1":
-        return os.environ.get(name, default)
-    if name in os.environ and name not in _EXP_WARNED:      # a probe / A-B script that forgot the gate would measure the default twice
-        _EXP_WARNED.add(name)
-        import warnings
-        warnings.warn(f"{name} is an experiment switch: it is read only with MVSGI_EXPERIMENTAL=1 (ignored)", RuntimeWarning, stacklevel=2)
-    return default
-
-
-_EXP_WARNED = set()
+# The environment the package reads: MVSGI_CONV_MODE, MVSGI_RANGE_CHECK (below), MVSGI_RIG_CACHE, MVSGI_POLY, MVSGI_S2RS,
+# MVSGI_HEAD_SPLIT, MVSGI_FRONT_CHUNK (each covered by tests/test_gpu_parity.py::test_product_switches_off), MVSGI_WINO
+# (test_full_size_winograd_level0_vs_direct_kernel_and_reference_golden), MVSGI_D32 and MVSGI_LIB.
 
 
 def set_conv_mode(mode: str) -> None:

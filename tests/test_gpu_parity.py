@@ -622,7 +622,7 @@ def test_small_cases_vs_reference_goldens(golden_dir, name, conv_mode):
 
 @pytest.mark.parametrize("switch", ["MVSGI_POLY", "MVSGI_S2RS", "MVSGI_HEAD_SPLIT", "MVSGI_RIG_CACHE", "MVSGI_FRONT_CHUNK", "MVSGI_CONV_MODE"])
 def test_product_switches_off(golden_dir, switch):
-    """The product's configuration surface (hip_ops.exp_env lists it): the std_d16_rand golden (random grids, float grid masks,
+    """The product's configuration surface (hip_ops lists it): the std_d16_rand golden (random grids, float grid masks,
     two frames, a peaky gain) through the whole path with each switch turned away from its default -- every alternative path
     stays within the north-star bar.  (The switches are read at import; the test sets what they set.)"""
     from mvs_gi_amd.dropin import cost_volume_builder as cb, cost_volume_regulator as cr
@@ -1657,14 +1657,14 @@ def test_regulator_register_stationary_chain_matches_streaming_and_goldens(golde
     inp = synth.make_inputs(cfg, seed=case["seed"], batch=case["batch"], grid_kind=case["grid_kind"],
                             grid_mask_dtype=case["grid_mask_dtype"])
     feats = _g(inp["feats"])
-    old_mode, old_min, old_use = H.get_conv_mode(), cr._RS_MIN_UNITS, cr._USE_RS
+    old_mode, old_use = H.get_conv_mode(), cr._USE_RS
     try:
         H.set_conv_mode("bf16x3")
         for gain in case["gains"]:
             w = synth.make_weights(cfg, seed=case["seed"], gain=gain)
             outs = {}
             for use in (False, True):
-                cr._USE_RS, cr._RS_MIN_UNITS = use, 0
+                cr._USE_RS = use
                 hp = HotPath(cfg, w, inp, device=DEV)
                 outs[use] = hp(feats)[0].cpu().numpy()
                 if use:
@@ -1675,7 +1675,7 @@ def test_regulator_register_stationary_chain_matches_streaming_and_goldens(golde
             assert err <= 1e-3 and _rel(outs[True], outs[False]) <= 5e-4      # two 16-bit approximations of the same path
     finally:
         H.set_conv_mode(old_mode)
-        cr._RS_MIN_UNITS, cr._USE_RS = old_min, old_use
+        cr._USE_RS = old_use
 
 
 def test_split_padded_hand_over_between_builder_and_regulator(golden_dir):
@@ -1934,19 +1934,19 @@ def test_builder_register_stationary_post_vol_matches_streaming_and_goldens(gold
                             grid_mask_dtype=case["grid_mask_dtype"])
     w = synth.make_weights(cfg, seed=case["seed"], gain=1.0)
     f, g, gm, m = (_g(inp[k]) for k in ("feats", "grids", "grid_masks", "masks"))
-    old_mode, old_min, old_use = H.get_conv_mode(), cb._RS_MIN_UNITS, cb._USE_RS
+    old_mode, old_use = H.get_conv_mode(), cb._USE_RS
     try:
         H.set_conv_mode("bf16x3")
         outs = {}
         for use in (False, True):
-            cb._USE_RS, cb._RS_MIN_UNITS = use, 0
+            cb._USE_RS = use
             cvb, _, _ = build_modules(cfg, w, DEV)
             outs[use] = cvb(f, g, gm, m).contiguous().cpu().numpy()
             assert ("_mvsgi_rs_vol" in cvb.__dict__) == use
         assert _rel(outs[True], z["vol"]) <= 2e-4 and _rel(outs[True], outs[False]) <= 5e-5
     finally:
         H.set_conv_mode(old_mode)
-        cb._RS_MIN_UNITS, cb._USE_RS = old_min, old_use
+        cb._USE_RS = old_use
 
 
 # ------------------------------------------------------------------------------ round-3 review items

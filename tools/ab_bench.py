@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""A/B of environment toggles through bench.py on one box: python tools/ab_bench.py MVSGI_RS=0 MVSGI_RS=1 [--rounds 2]"""
+"""A/B of environment toggles through bench.py on one box: python tools/ab_bench.py MVSGI_POLY=0 MVSGI_POLY=1 [--rounds 2]"""
 import json, os, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 arms = [a for a in sys.argv[1:] if "=" in a]
@@ -9,7 +9,6 @@ res = {a: [] for a in arms}
 for r in range(rounds):
     for a in arms:
         env = dict(os.environ)
-        env["MVSGI_EXPERIMENTAL"] = "1"      # the arms may name gated experiment switches (mvs_gi_amd/hip_ops.py exp_env)
         for kv in a.split(","):
             k, v = kv.split("=")
             env[k] = v

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """post_vol -> down.0.first timing (G16V level 0, B frames): the fp32 hand-over (rs16 fp32 out + streaming stride-2 kernel) against
-the split-padded hand-over (rs16 split out + csrc/conv3d_s2rs.hip); MVSGI_S2RS_TH selects the brick height of the latter.
+the split-padded hand-over (rs16 split out + csrc/conv3d_s2rs.hip).
 tools/s2rs_probe.py [B]"""
 import os, sys, time
 import numpy as np
@@ -61,4 +61,4 @@ torch.cuda.synchronize()
 a, b = H.act_from_split(out_a), H.act_from_split(out_b)
 print("max |streaming - s2rs| / max:", float((a - b).abs().max() / a.abs().max()))
 print(f"B={B}: post_vol fp32 out {timeit(post_f32):.0f} us, split out {timeit(post_split):.0f} us; "
-      f"down.0.first streaming {timeit(down_stream):.0f} us, s2rs {timeit(down_s2rs):.0f} us (TH={os.environ.get('MVSGI_S2RS_TH', '4')})")
+      f"down.0.first streaming {timeit(down_stream):.0f} us, s2rs {timeit(down_s2rs):.0f} us")

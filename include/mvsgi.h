@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define MVSGI_ABI_VERSION 4   /* 4: mvsgi_instance_norm_f32, mvsgi_instance_norm_ws_bytes (norm_type 'instance'); 3: mvsgi_conv3d_d32_applies, mvsgi_conv3d_up2_d32_applies + MVSGI_CONV_BF16X3_D32; 2: mvsgi_saturation_flags; the symbol set of round 5 */
+#define MVSGI_ABI_VERSION 5   /* 5: mvsgi_softargmin_scaled_f32 (soft-argmin at any interp_scale_factor); 4: mvsgi_instance_norm_f32, mvsgi_instance_norm_ws_bytes (norm_type 'instance'); 3: mvsgi_conv3d_d32_applies, mvsgi_conv3d_up2_d32_applies + MVSGI_CONV_BF16X3_D32; 2: mvsgi_saturation_flags; the symbol set of round 5 */
 
 typedef void* mvsgi_stream_t;
 
@@ -232,7 +232,7 @@ int mvsgi_resize_trilinear_f32(const float* x, float* y, int B, int C,
 
 /* ---- K4: fused upsample + soft-argmin ------------------------------------------------
  * Replaces DistanceRegressorWithFixedCandidates.forward (distance_regressor/
- * distance_regressor.py:51-79): bilinear x`scale` (scale in {1,2}; 1 = no interpolation),
+ * distance_regressor.py:51-79): bilinear x`scale` (scale in {1,2}; 1 = no interpolation; other factors: mvsgi_softargmin_scaled_f32),
  * softmax over D, expectation of inv_idx[d] = bf / dist[d].
  *   costs [B][D][H][W] (the C==1 volume), inv_idx [D],
  *   inv_dist [B][1][sH][sW], norm_costs [B][D][sH][sW] or NULL (inference discards it). */
@@ -245,6 +245,20 @@ int mvsgi_softargmin_f32(const float* costs, const float* inv_idx, float* inv_di
 int mvsgi_softargmin_div_f32(const float* costs, const float* inv_idx, float* inv_dist,
                              float* norm_costs, int B, int D, int H, int W, int scale,
                              float post_div, mvsgi_stream_t stream);
+
+/* The same at any factor F.interpolate(scale_factor = scale, mode = 'bilinear', align_corners = False) accepts (scale finite
+ * and > 0; fractional and down-scaling factors included).  OH, OW are the output sizes the caller allocated; they must equal
+ * floor(H * scale), floor(W * scale) as computed here in double, anything else is rejected (never an overrun).
+ *   inv_dist [B][1][OH][OW], norm_costs [B][D][OH][OW] or NULL.
+ * scale 1 and 2 forward to mvsgi_softargmin_div_f32 (identical results); integer factors 3 .. 64 take a row-band kernel that
+ * stages each low-resolution row pair in LDS once; every other factor takes a thread-per-pixel kernel (correct, not tuned).
+ * variant: MVSGI_SA_AUTO, or MVSGI_SA_PIXEL / MVSGI_SA_BAND to force one kernel (BAND: integer factors 3 .. 64 only). */
+#define MVSGI_SA_AUTO  0
+#define MVSGI_SA_PIXEL 1
+#define MVSGI_SA_BAND  2
+int mvsgi_softargmin_scaled_f32(const float* costs, const float* inv_idx, float* inv_dist,
+                                float* norm_costs, int B, int D, int H, int W, double scale,
+                                int OH, int OW, float post_div, int variant, mvsgi_stream_t stream);
 
 /* ---- layout helpers for the module boundary ------------------------------------------
  * [B][C][D*H*W] <-> [B][D*H*W][C]; V = D*H*W.  Used when a caller hands the regulator a

@@ -8,12 +8,12 @@ from __future__ import annotations
 
 import ctypes
 import os
-from ctypes import c_char_p, c_float, c_int, c_longlong, c_size_t, c_void_p
+from ctypes import c_char_p, c_double, c_float, c_int, c_longlong, c_size_t, c_void_p
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MVSGI_LIB", os.path.join(_HERE, "libmvsgi_hip.so"))   # MVSGI_LIB: diagnostic builds
 
-ABI_VERSION = 4
+ABI_VERSION = 5
 
 
 class MvsgiLibraryMissing(RuntimeError):
@@ -71,6 +71,7 @@ SIGNATURES = {
     "mvsgi_resize_trilinear_f32": (c_int, [_P, _P] + [c_int] * 8 + [_P]),
     "mvsgi_softargmin_f32": (c_int, [_P, _P, _P, _P] + [c_int] * 5 + [_P]),
     "mvsgi_softargmin_div_f32": (c_int, [_P, _P, _P, _P] + [c_int] * 5 + [c_float, _P]),
+    "mvsgi_softargmin_scaled_f32": (c_int, [_P, _P, _P, _P] + [c_int] * 4 + [c_double, c_int, c_int, c_float, c_int, _P]),
     "mvsgi_rays_panorama_f32": (c_int, [_P, _P, c_int, c_int, c_int] + [c_float] * 4 + [_P]),
     "mvsgi_transform_points_f32": (c_int, [_P, _P, _P, c_int, c_longlong, _P]),
     "mvsgi_grid_double_sphere_f32": (c_int, [_P, _P, _P, c_int, c_longlong] + [c_float] * 6 + [c_int, c_int, c_float, _P]),

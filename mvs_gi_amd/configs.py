@@ -47,7 +47,7 @@ class PathConfig:
     mask_hw: Tuple[int, int] = (512, 2048)
     cv_hw: Tuple[int, int] = (80, 320)
     bf: float = BF
-    interp_scale_factor: int = 2
+    interp_scale_factor: float = 2      # any factor F.interpolate accepts; 4 = full image resolution with the stock extractor
     pre_interp: bool = True
     # norm layer of every conv block with one (NORM3D_TYPE of dsta_mvs/model/common/__init__.py:13-23): "batch" | "instance" | "none";
     # norm_affine: the instance norms carry gamma / beta (nn.InstanceNorm3d(c, affine=True))

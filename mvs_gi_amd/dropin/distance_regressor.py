@@ -2,7 +2,8 @@
 (dsta_mvs/model/distance_regressor/distance_regressor.py:7-79) with the same constructor,
 buffer name (`inv_dist_idx` [1, D, 1, 1], persistent), attributes (bf, inv_dist_idx_min/max,
 interp_scale_factor, pre_interp) and `update_dist_cands`; forward is the fused HIP
-upsample + softmax + expectation kernel (mvsgi_softargmin_f32).
+upsample + softmax + expectation kernel (mvsgi_softargmin_div_f32 at x1 / x2, mvsgi_softargmin_scaled_f32 at any other
+factor).
 """
 from __future__ import annotations
 
@@ -15,14 +16,11 @@ from .. import hip_ops as H
 
 
 def regressor_forward(self, costs: Tensor):
-    """costs [B, 1(+), D, H, W] -> (inv_dist [B,1,sH,sW], norm_costs [B,D,sH,sW])."""
+    """costs [B, 1(+), D, H, W] -> (inv_dist [B,1,OH,OW], norm_costs [B,D,OH,OW]), OH = floor(s * H), OW = floor(s * W)."""
     c = costs[:, 0]
     scale = 1
-    if self.pre_interp and self.interp_scale_factor > 0:
-        if float(self.interp_scale_factor) not in (1.0, 2.0):
-            raise NotImplementedError(
-                f"interp_scale_factor={self.interp_scale_factor}: the HIP soft-argmin fuses x1 and x2 only")
-        scale = int(self.interp_scale_factor)
+    if self.pre_interp and self.interp_scale_factor > 0:       # any factor F.interpolate(scale_factor=...) accepts
+        scale = self.interp_scale_factor
     want = getattr(self, "return_norm_costs", True)
     return H.softargmin(c, self.inv_dist_idx, scale, want, getattr(self, "post_div", 1.0))
 

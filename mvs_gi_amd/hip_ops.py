@@ -11,6 +11,7 @@ import torch
 
 from . import _lib
 
+import math
 import os
 
 CONV_AUTO, CONV_DIRECT, CONV_MFMA, CONV_BF16X3, CONV_BF16X3_C16, CONV_BF16X3_V32, CONV_BF16X3_D32 = 0, 1, 2, 3, 4, 5, 6
@@ -1017,19 +1018,35 @@ def instance_norm(x, res=None, gamma=None, beta=None, eps: float = 1e-5, neg_slo
     return out
 
 
-def softargmin(costs_bdhw, inv_idx, scale: int, want_norm_costs: bool, post_div: float = 1.0):
-    """costs [B, D, H, W], inv_idx [D] -> inv_dist [B, 1, sH, sW] (divided by post_div), norm_costs
-    [B, D, sH, sW] | None."""
+SA_AUTO, SA_PIXEL, SA_BAND = 0, 1, 2        # MVSGI_SA_* of include/mvsgi.h
+
+
+def softargmin(costs_bdhw, inv_idx, scale: float, want_norm_costs: bool, post_div: float = 1.0, variant: int = SA_AUTO):
+    """costs [B, D, H, W], inv_idx [D] -> inv_dist [B, 1, OH, OW] (divided by post_div), norm_costs
+    [B, D, OH, OW] | None, with OH = floor(H * scale), OW = floor(W * scale) as F.interpolate(scale_factor=scale) sizes them.
+    scale 1 | 2: the fused x1 / x2 launches; integer factors >= 3: the row-band kernel; any other factor > 0: the
+    thread-per-pixel kernel.  variant: SA_PIXEL | SA_BAND force one of the latter two (tests, A/B timing)."""
     lib = _lib.load()
     c = _dev(costs_bdhw, "costs")
     inv_idx = _dev(inv_idx.reshape(-1), "inv_dist_idx")
     B, D, H, W = c.shape
     if inv_idx.numel() != D:
         raise AssertionError(f"{D} cost planes but {inv_idx.numel()} distance candidates")
-    inv = torch.empty((B, 1, H * scale, W * scale), device=c.device, dtype=torch.float32)
-    pr = torch.empty((B, D, H * scale, W * scale), device=c.device, dtype=torch.float32) if want_norm_costs else None
-    _lib.check(lib.mvsgi_softargmin_div_f32(c.data_ptr(), inv_idx.data_ptr(), inv.data_ptr(), _ptr(pr), B, D, H, W,
-                                            scale, float(post_div), _stream_ptr(c)), "mvsgi_softargmin_div_f32")
+    scale = float(scale)
+    if not (math.isfinite(scale) and scale > 0):
+        raise ValueError(f"softargmin: scale {scale} is not a finite positive factor")
+    OH, OW = math.floor(H * scale), math.floor(W * scale)
+    if OH < 1 or OW < 1:
+        raise ValueError(f"softargmin: scale {scale} gives an empty {OH} x {OW} output for {H} x {W}")
+    inv = torch.empty((B, 1, OH, OW), device=c.device, dtype=torch.float32)
+    pr = torch.empty((B, D, OH, OW), device=c.device, dtype=torch.float32) if want_norm_costs else None
+    if variant == SA_AUTO and scale in (1.0, 2.0):
+        _lib.check(lib.mvsgi_softargmin_div_f32(c.data_ptr(), inv_idx.data_ptr(), inv.data_ptr(), _ptr(pr), B, D, H, W,
+                                                int(scale), float(post_div), _stream_ptr(c)), "mvsgi_softargmin_div_f32")
+    else:
+        _lib.check(lib.mvsgi_softargmin_scaled_f32(c.data_ptr(), inv_idx.data_ptr(), inv.data_ptr(), _ptr(pr), B, D, H, W,
+                                                   scale, OH, OW, float(post_div), int(variant), _stream_ptr(c)),
+                   "mvsgi_softargmin_scaled_f32")
     return inv, pr
 
 

@@ -59,7 +59,7 @@ typedef void* mvsgi_stream_t;
                                    half empty) and a unit has half as many slices to synchronise on.  Cin % 32 == 0, stride 1, launches
                                    large enough for a 128- / 160-voxel brick: where mvsgi_conv3d_d32_applies(); weights from
                                    mvsgi_conv3d_pack_weights_split(layout = MVSGI_CONV_BF16X3_D32 [| MVSGI_CONV_F16]), sized by
-                                   mvsgi_conv3d_packed_weight_bytes_bf16x3.  Same products, another summation order.          */
+                                   mvsgi_conv3d_packed_weight_bytes_bf16x3 (the packer zeroes the 28th k-step's share).  Same products, another order. */
 
 #define MVSGI_CONV_F16 0x100   /* FLAG, OR-ed into MVSGI_CONV_BF16X3 / _C16 / _V32 (impl of mvsgi_conv3d_f32, w_layout of
                                   mvsgi_conv3d_up2_f32, layout of mvsgi_conv3d_pack_weights_split): the same kernels and packed

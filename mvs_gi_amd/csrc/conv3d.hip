@@ -639,6 +639,11 @@ extern "C" int mvsgi_conv3d_pack_weights_split(const float* w_oidhw, void* w_pac
     } else if (layout == MVSGI_CONV_BF16X3_D32) {
         MVSGI_REQUIRE(Cin % 32 == 0, "mvsgi_conv3d_pack_weights_split: the 32-channel-slice layout needs Cin %% 32 == 0 (got %d)", Cin);
         const long long total = (long long)(Cin / 32) * (Cout / 16) * 27 * 64;
+        // the layout fills 27 of the 28 k-steps the buffer is sized for (mvsgi_conv3d_packed_weight_bytes_bf16x3): the rest is zeroed,
+        // so that every byte of the caller's buffer is defined by the weights alone
+        const size_t used = (size_t)total * 2 * sizeof(bf16x8), all = mvsgi_conv3d_packed_weight_bytes_bf16x3(Cout, Cin);
+        MVSGI_REQUIRE(used <= all && hipMemsetAsync(reinterpret_cast<char*>(w_packed) + used, 0, all - used, mvsgi::as_stream(stream)) == hipSuccess,
+                      "mvsgi_conv3d_pack_weights_split: clearing the unused tail of the 32-channel-slice layout failed");
         hipLaunchKernelGGL(pack_weights_bf16x3_d32_kernel, dim3((unsigned)mvsgi::cdiv(total, 256)), dim3(256), 0, mvsgi::as_stream(stream),
                            w_oidhw, wp, Cout, Cin, f16);
     } else {

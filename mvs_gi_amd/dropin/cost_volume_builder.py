@@ -87,6 +87,13 @@ def std_sweep_ndhwc(feats, grids, grid_masks, masks, owner=None, split_out: bool
             g1, gm1, m1 = grids, grid_masks, masks
         cached = (tensors, tuple(t._version for t in tensors), H.sweep_validity(g1, gm1, m1), g1 if g1 is not grids else None)
         _RIG_VALIDITY[owner] = cached            # weak on the module: dies with it, never pickled with it
+    if torch.cuda.is_current_stream_capturing():
+        # a hipGraph being captured records the addresses of the validity byte (and of the one-rig copy of the grids): like the
+        # module-owned split-padded buffers they must then never be freed while the module lives -- another rig or batch size
+        # replaces the cache entry above, and a replay would read freed memory
+        pins = owner.__dict__.setdefault("_mvsgi_graph_pins", [])
+        if not any(p is cached for p in pins):
+            pins.append(cached)
     g_use = cached[3] if cached[3] is not None else grids
     if split_out:
         # vol_raw straight into a module-owned split-padded buffer (zero border, allocated once per shape) for the

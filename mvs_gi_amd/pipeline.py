@@ -78,6 +78,12 @@ class HotPath:
                 # std builder with the rig cache: ONE set presented with the batch's shape (stride-0 views; the sweep reads
                 # frame 0's constants for every frame).  Otherwise replicated once.
                 self._rig_views = ((B, shared), *(exp if shared else [t.contiguous() for t in exp]))
+            if torch.cuda.is_current_stream_capturing():
+                # the hipGraph being captured records the addresses of the replicated copies: an eager call at another batch size
+                # replaces _rig_views, and must not free what a replay still reads
+                pins = self.__dict__.setdefault("_graph_pins", [])
+                if not any(p is self._rig_views for p in pins):
+                    pins.append(self._rig_views)
             _, g, gm, m = self._rig_views          # the same objects every call: the rig cache hits by identity
         return self.dist_regressor(build_and_regulate(self.cv_builder, self.cv_regulator, feats, g, gm, m))
 

@@ -8,9 +8,17 @@ import os
 import pytest
 import torch
 
+import guard_arena
 from mvs_gi_amd import _lib, hip_ops as H
 
 pytestmark = pytest.mark.gpu
+
+
+@pytest.fixture(autouse=True)
+def _guarded_allocations(request):
+    """Every device tensor the library allocates during a test of this module sits between NaN-sentinel guards, and unwritten
+    fp32 outputs read as NaN (tests/guard_arena.py: what is guarded, guard sizes, exemptions)."""
+    yield from guard_arena.fixture_body(request)
 
 PIN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "conv3d_dispatch_pin.json")
 LAYOUTS = {"auto": H.CONV_AUTO, "generic": H.CONV_BF16X3, "c16": H.CONV_BF16X3_C16, "v32": H.CONV_BF16X3_V32,

@@ -11,11 +11,19 @@ import torch.nn.functional as F
 from torch import nn
 
 from instnorm_cases import EXTRACTOR_CASE, FULL_CASES, SMALL_CASES
+import guard_arena
 from mvs_gi_amd import dropin, hip_ops as H, synth
 from mvs_gi_amd.pipeline import HotPath
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
+
+
+@pytest.fixture(autouse=True)
+def _guarded_allocations(request):
+    """Every device tensor the library allocates during a test of this module sits between NaN-sentinel guards, and unwritten
+    fp32 outputs read as NaN (tests/guard_arena.py: what is guarded, guard sizes, exemptions)."""
+    yield from guard_arena.fixture_body(request)
 MODES = ["f16x3", "bf16x3", "f32"]
 
 

@@ -14,12 +14,20 @@ import torch
 import torch.nn.functional as F
 
 from golden_cases import FULL_CASES, SMALL_CASES
+import guard_arena
 from mvs_gi_amd import dropin, hip_ops as H, synth
 from mvs_gi_amd.pipeline import HotPath, build_modules
 from oracle import mvsgi_oracle as O
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
+
+
+@pytest.fixture(autouse=True)
+def _guarded_allocations(request):
+    """Every device tensor the library allocates during a test of this module sits between NaN-sentinel guards, and unwritten
+    fp32 outputs read as NaN (tests/guard_arena.py: what is guarded, guard sizes, exemptions)."""
+    yield from guard_arena.fixture_body(request)
 
 
 @pytest.fixture(autouse=True)

@@ -11,11 +11,19 @@ import pytest
 import torch
 
 from golden_cases import SMALL_CASES
+import guard_arena
 from mvs_gi_amd import hip_ops as H, synth
 from mvs_gi_amd.pipeline import HotPath
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
+
+
+@pytest.fixture(autouse=True)
+def _guarded_allocations(request):
+    """Every device tensor the library allocates during a test of this module sits between NaN-sentinel guards, and unwritten
+    fp32 outputs read as NaN (tests/guard_arena.py: what is guarded, guard sizes, exemptions)."""
+    yield from guard_arena.fixture_body(request)
 
 
 @pytest.fixture(autouse=True)

@@ -13,7 +13,7 @@ from __future__ import annotations
 import os
 
 import copy
-from typing import Dict, Optional, Type
+from typing import Dict, NamedTuple, Optional, Type
 
 import torch
 from torch import nn, Tensor
@@ -27,6 +27,40 @@ def module_getstate(self):
     -- they are rebuilt on the next forward and must not travel with a pickled module or a whole-module checkpoint
     (Lightning's save_hyperparameters() pickles module OBJECTS, spherical_sweep_stereo.py:74)."""
     return {k: v for k, v in self.__dict__.items() if not k.startswith("_mvsgi_")}
+
+
+# ------------------------------------------------------------------------------------------
+# module-owned activation buffers (DESIGN.md section 1): a captured hipGraph holds their addresses
+# ------------------------------------------------------------------------------------------
+def _owned_split_buffer(owner, attr: str, key: tuple, make):
+    """Module-owned split-padded buffers (owner.__dict__[attr], an `_mvsgi_*` name: module_getstate), one per shape key, NEVER
+    replaced or freed while the module lives: a captured hipGraph holds their addresses, and their zero borders are written
+    exactly once (at allocation) -- the kernels write interiors only.  `make` allocates the entry of a new key."""
+    bufs = owner.__dict__.setdefault(attr, {})
+    if key not in bufs:
+        bufs[key] = make()
+    return bufs[key]
+
+
+def _owned_head_buffer(self, B, D, Hh, W, C, device):
+    """The module-owned split-padded buffer between out_costs.0 and the split head: ONE allocation per frame geometry, sized for the
+    largest batch seen, handed out as a view of its first B frames (the format is per frame: a prefix of the batch is a valid
+    buffer).  A caller that varies its batch (batch sweeps, dataset tails) therefore holds one buffer, not one per batch size; a
+    larger batch replaces it -- unless a captured hipGraph may hold its address (`_mvsgi_pinned`, set while capturing), in which
+    case the old one stays alive beside the new."""
+    bufs = self.__dict__.setdefault("_mvsgi_head_bufs", {})
+    key = (D, Hh, W, C, device)
+    ent = bufs.get(key)
+    if ent is None or ent[0].B < B:
+        big = H.SplitAct(B, D, Hh, W, C, device)
+        keep = ent[1] + [ent[0]] if ent is not None and (ent[2] or ent[1]) else []      # graphs may hold the old buffers
+        ent = bufs[key] = [big, keep, False]
+    if torch.cuda.is_current_stream_capturing():
+        ent[2] = True
+    big = ent[0]
+    if big.B == B:
+        return big
+    return H.SplitAct(B, D, Hh, W, C, device, buf=big.buf[:B])
 
 
 class NoOp(nn.Identity):
@@ -46,14 +80,44 @@ NORM3D_TYPE: Dict[str, Type[nn.Module]] = {"batch": nn.BatchNorm3d, "instance": 
 # MVSGI_D32=0: keep the Cin % 32 == 0 stride-1 layers of large launches on the tap-pair layout (default: 32-channel slices,
 # csrc/conv3d_bf16x3.hpp D32 -- 27 k-steps per 32 channels instead of 28 and half the slices per unit: 6-9 % of those layers)
 _USE_D32 = os.environ.get("MVSGI_D32", "1") != "0"
-_D32_OK: Dict[tuple, bool] = {}       # (cin, cout, B, D, H, W) -> mvsgi_conv3d_d32_applies; ("up2", ...) -> mvsgi_conv3d_up2_d32_applies
+_D32_OK: Dict[tuple, bool] = {}       # (up2, cin, cout, B, D, H, W) -> mvsgi_conv3d_up2_d32_applies / mvsgi_conv3d_d32_applies
+
+
+class Packed(NamedTuple):
+    """What one kernel's launch needs of a layer: its packed weights and the epilogue constants that go with THAT packing (an fp16
+    packing's power-of-two pre-scale is undone in `scale`, or, where the kernel has no per-channel multiplier, in `unscale`)."""
+    wp: Tensor
+    scale: object           # Tensor [Cout]; a float for the cost head; None where the scale is folded into the weights
+    shift: object           # Tensor [Cout]; a float for the cost head
+    unscale: float = 1.0
 
 
 class ConvLaunch:
-    """Device-resident launch arguments of one BaseConvBlk3d: PyTorch-layout weight, packed
-    MFMA weight (or None), per-channel scale/shift (eval BatchNorm3d or bias), stride, slope."""
-    __slots__ = ("w", "wp", "wp_b3", "wp_c16", "wp_d32", "wp_rs", "wp_s2", "wp_poly", "wp_head", "head_sc", "scale", "shift", "stride",
-                 "neg_slope", "cin", "cout", "key", "f16", "inorm")
+    """Device-resident launch arguments of one BaseConvBlk3d: PyTorch-layout weight, exact-fp32 packed MFMA weight (or None),
+    per-channel scale/shift (eval BatchNorm3d or bias), stride, slope -- and, in ONE cache, every other packing of the weights
+    a kernel has asked for, keyed ("stream", layout, fmt) | ("rs", fmt) | ("s2", fmt) | ("wino",) | ("head", fmt) |
+    ("poly", D, H, W, fmt) with fmt the 16-bit split ('bf16' | 'f16').  The library's mode picks the key, so a mode switch can
+    never meet another mode's weights; a changed parameter makes a new ConvLaunch (lower_conv_block)."""
+    __slots__ = ("w", "wp", "scale", "shift", "stride", "neg_slope", "cin", "cout", "key", "inorm", "_cache")
+
+    def __init__(self, w: Tensor, scale: Tensor, shift: Tensor, stride: int, neg_slope: float, inorm=None, key=None):
+        self.w = w
+        self.wp = H.pack_conv_weights(w)      # eager: a pack launch in the first forward could fall into a stream capture
+        self.scale, self.shift = scale.contiguous(), shift.contiguous()
+        self.stride, self.neg_slope, self.inorm, self.key = int(stride), neg_slope, inorm, key
+        self.cout, self.cin = int(w.shape[0]), int(w.shape[1])
+        self._cache: Dict[tuple, Packed] = {}
+
+    def _cached(self, key: tuple, make) -> Packed:
+        ent = self._cache.get(key)
+        if ent is None:
+            ent = self._cache[key] = make()
+        return ent
+
+    def _entry(self, packed) -> Packed:
+        """Packed of a packer's result: the weights alone (bf16 split), or (weights, unscale [Cout]) (fp16 split)."""
+        wp, unscale = packed if isinstance(packed, tuple) else (packed, None)
+        return Packed(wp, self.scale if unscale is None else (self.scale * unscale).contiguous(), self.shift)
 
     def run(self, x_ndhwc: Tensor, res: Optional[Tensor] = None, impl: Optional[int] = None) -> Tensor:
         if self.inorm is not None:          # conv (+ bias) -> instance norm (+ res) -> act: two more launches
@@ -61,181 +125,110 @@ class ConvLaunch:
         return self._run_conv(x_ndhwc, res, impl)
 
     def _run_conv(self, x_ndhwc: Tensor, res: Optional[Tensor] = None, impl: Optional[int] = None) -> Tensor:
-        wp = self.wp
-        if impl is None and H.get_conv_mode() == "f16x3" and self.cin % 16 == 0 and self.cout % 16 == 0:
-            B, D, Hh, W, _ = x_ndhwc.shape
-            layout = H.CONV_BF16X3_C16 if self._c16() else (H.CONV_BF16X3_D32 if self._d32(B, D, Hh, W) else H.CONV_BF16X3)
-            wp16, sc16 = self._f16(layout)
-            return H.conv3d(x_ndhwc, self.w, wp16, sc16, self.shift, res=res, stride=self.stride, neg_slope=self.neg_slope,
-                            impl=layout | H.CONV_F16)
+        wp, scale = self.wp, self.scale      # CONV_AUTO (and any explicit impl but CONV_BF16X3): the exact-fp32 weights
         if impl is None:
             impl = H.CONV_AUTO
-            if H.get_conv_mode() == "bf16x3" and self.cin % 16 == 0 and self.cout % 16 == 0:
-                B, D, Hh, W, _ = x_ndhwc.shape
-                if self._c16():
-                    impl, wp = H.CONV_BF16X3_C16, self._wp_c16()
-                elif self._d32(B, D, Hh, W):
-                    if getattr(self, "wp_d32", None) is None:
-                        self.wp_d32 = H.pack_conv_weights_bf16x3_d32(self.w)
-                    impl, wp = H.CONV_BF16X3_D32, self.wp_d32
-                else:
-                    if self.wp_b3 is None:
-                        self.wp_b3 = H.pack_conv_weights_bf16x3(self.w)
-                    impl, wp = H.CONV_BF16X3, self.wp_b3
+            if H.split_mode() and self.cin % 16 == 0 and self.cout % 16 == 0:
+                impl, wp, scale = self._stream(self._stream_layout(x_ndhwc.shape[:4]), H.mode_fmt())
         elif impl == H.CONV_BF16X3:
-            if self.wp_b3 is None:
-                self.wp_b3 = H.pack_conv_weights_bf16x3(self.w)
-            wp = self.wp_b3
-        return H.conv3d(x_ndhwc, self.w, wp, self.scale, self.shift, res=res, stride=self.stride,
-                        neg_slope=self.neg_slope, impl=impl)
+            wp = self._stream_packed(H.CONV_BF16X3, "bf16").wp
+        return H.conv3d(x_ndhwc, self.w, wp, scale, self.shift, res=res, stride=self.stride, neg_slope=self.neg_slope, impl=impl)
 
-    def _f16(self, layout: int):
-        """(packed weights, per-channel scale) of the fp16 split in `layout`: the weights pre-scaled per output channel by a power
-        of two, the epilogue's scale carrying the inverse (H.pack_conv_weights_f16x3)."""
-        if self.f16 is None:
-            self.f16 = {}
-        if layout not in self.f16:
-            wp, unscale = H.pack_conv_weights_f16x3(self.w, layout)
-            self.f16[layout] = (wp, (self.scale * unscale).contiguous())
-        return self.f16[layout]
+    def _stream_layout(self, dims=None, up2: bool = False) -> int:
+        """THE layout rule of the streaming split kernel: the plane schedule for Cout == 16, else 32-channel slices where the
+        library says they serve a launch of dims = (B, D, H, W) (`up2`: the fused upsample + conv, low-resolution sizes; dims
+        None: a kernel with no such form), else tap pairs.  One library query per launch shape, not per launch.  The plain
+        conv asks only for stride-1 layers; in 'f32' mode (a direct run_up2 call: the bf16 split) the slices are never taken."""
+        if self._c16():
+            return H.CONV_BF16X3_C16
+        if dims is not None and _USE_D32 and H.split_mode() and self.cin % 32 == 0 and (up2 or (self.stride == 1 and self.cout % 16 == 0)):
+            key = (up2, self.cin, self.cout) + tuple(dims)
+            ok = _D32_OK.get(key)
+            if ok is None:
+                ok = _D32_OK[key] = H.conv3d_up2_d32_applies(dims[0], self.cin, *dims[1:], self.cout) if up2 else \
+                    H.conv3d_d32_applies(dims[0], self.cin, *dims[1:], self.cout, self.stride)
+            if ok:
+                return H.CONV_BF16X3_D32
+        return H.CONV_BF16X3
 
-    def _d32(self, B: int, D: int, Hh: int, W: int) -> bool:
-        """32-channel slices (MVSGI_CONV_BF16X3_D32) serve this launch: Cin % 32 == 0, stride 1, a large launch."""
-        if not (_USE_D32 and self.stride == 1 and self.cin % 32 == 0 and self.cout % 16 == 0):
-            return False
-        key = (B, D, Hh, W)                      # (one library query per launch shape, not per launch)
-        ok = _D32_OK.get((self.cin, self.cout) + key)
-        if ok is None:
-            ok = _D32_OK[(self.cin, self.cout) + key] = H.conv3d_d32_applies(B, self.cin, D, Hh, W, self.cout, self.stride)
-        return ok
+    def _stream_packed(self, layout: int, fmt: str) -> Packed:
+        """The streaming split kernel's weights in `layout` and the split `fmt`, with the scale that goes with them."""
+        return self._cached(("stream", layout, fmt), lambda: self._entry(H._pack_conv3d_split(self.w, layout, fmt)))
+
+    def _stream(self, layout: int, fmt: str):
+        """(impl / w_layout, packed weights, scale) of the streaming split kernel in `layout` and the split `fmt`."""
+        p = self._stream_packed(layout, fmt)
+        return layout | (H.CONV_F16 if fmt == "f16" else 0), p.wp, p.scale
 
     def _c16(self) -> bool:
         """Cout == 16, stride 1: the plane-schedule kernel (MVSGI_CONV_BF16X3_C16)."""
         return self.cout == 16 and self.stride == 1 and self.cin % 16 == 0
 
-    def _wp_c16(self):
-        if getattr(self, "wp_c16", None) is None:
-            self.wp_c16 = H.pack_conv_weights_bf16x3_c16(self.w)
-        return self.wp_c16
-
-    def _wp_b3(self):
-        if self.wp_b3 is None:
-            self.wp_b3 = H.pack_conv_weights_bf16x3(self.w)
-        return self.wp_b3
-
     def rs_ok(self) -> bool:
         """The register-stationary kernel (csrc/conv3d_rs.hip) serves this layer."""
         return self.inorm is None and H.conv3d_rs_applies(self.cin, self.cout, self.stride, self.neg_slope)
 
-    def _wp_rs(self):
-        if self.wp_rs is None:
-            self.wp_rs = H.pack_conv_weights_rs(self.w)
-        return self.wp_rs
-
-    def _rs(self, fmt: str):
-        """(packed weights, per-channel scale) of the register-stationary kernels in the split `fmt` of the activations."""
-        if fmt == "bf16":
-            return self._wp_rs(), self.scale
-        if self.f16 is None:
-            self.f16 = {}
-        if "rs" not in self.f16:
-            wp, unscale = H.pack_conv_weights_rs(self.w, "f16")
-            self.f16["rs"] = (wp, (self.scale * unscale).contiguous())
-        return self.f16["rs"]
+    def _rs(self, fmt: str) -> Packed:
+        """The register-stationary kernels' weights in the split `fmt` of the activations."""
+        return self._cached(("rs", fmt), lambda: self._entry(H.pack_conv_weights_rs(self.w, fmt)))
 
     def wino_ok(self, D: int, Hh: int, W: int) -> bool:
         """The Winograd-form kernel (csrc/conv3d_wino.hip) serves this layer on a [D, Hh, W] volume (fp16 split only)."""
         return self.inorm is None and H.conv3d_wino_applies(self.cin, self.cout, D, Hh, W, self.stride, self.neg_slope)
 
-    def _wino(self):
-        """(packed weights, per-channel scale) of the Winograd-form kernel."""
-        if self.f16 is None:
-            self.f16 = {}
-        if "wino" not in self.f16:
-            wp, unscale = H.pack_conv_weights_wino(self.w)
-            self.f16["wino"] = (wp, (self.scale * unscale).contiguous())
-        return self.f16["wino"]
-
-    def _b3(self, fmt: str):
-        """(packed weights, per-channel scale) of the streaming split kernel (generic layout) in the split `fmt`."""
-        return (self._wp_b3(), self.scale) if fmt == "bf16" else self._f16(H.CONV_BF16X3)
+    def _wino(self) -> Packed:
+        return self._cached(("wino",), lambda: self._entry(H.pack_conv_weights_wino(self.w)))
 
     def s2rs_ok(self) -> bool:
         """The stride-2 16 -> 32 kernel on split-padded activations (csrc/conv3d_s2rs.hip) serves this layer."""
         return self.inorm is None and H.split_mode() and H.conv3d_s2rs_applies(self.cin, self.cout, self.stride, self.neg_slope)
 
-    def _wp_s2(self):
-        if self.wp_s2 is None:
-            self.wp_s2 = H.pack_conv_weights_s2rs(self.w, self.scale)
-        return self.wp_s2
-
-    def _s2(self, fmt: str):
-        """(packed weights with the scale folded in, shift, unscale) of the stride-2 kernel on split-padded activations."""
-        if fmt == "bf16":
-            return self._wp_s2(), self.shift, 1.0
-        if self.f16 is None:
-            self.f16 = {}
-        if "s2" not in self.f16:
+    def _s2(self, fmt: str) -> Packed:
+        """The stride-2 kernel on split-padded activations: the scale is folded into its weights; in the fp16 split one power of
+        two `up` with them, carried by the shift and undone by `unscale` (H.pack_conv_weights_s2rs)."""
+        def make():
+            if fmt == "bf16":
+                return Packed(H.pack_conv_weights_s2rs(self.w, self.scale), None, self.shift)
             wp, up, un = H.pack_conv_weights_s2rs(self.w, self.scale, "f16")
-            self.f16["s2"] = (wp, (self.shift * up).contiguous(), un)
-        return self.f16["s2"]
+            return Packed(wp, None, (self.shift * up).contiguous(), un)
+        return self._cached(("s2", fmt), make)
 
     def poly_ok(self) -> bool:
         """ResizeConv3d in polyphase form on the register-stationary kernel (csrc/conv3d_up2poly.hip)."""
         return self.inorm is None and H.split_mode() and self.stride == 1 and H.conv3d_up2_poly_applies(self.cin, self.cout, self.neg_slope)
 
-    def _poly_plan(self, D: int, Hh: int, W: int, fmt: str = "bf16"):
-        """(folded phase weights + face tables for a low-resolution input of D x Hh x W in the split `fmt`, the layer's scale):
-        built once per size and split, kept."""
-        if self.wp_poly is None:
-            self.wp_poly = {}
-        k = (int(D), int(Hh), int(W), fmt)
-        if k not in self.wp_poly:
-            if fmt == "f16":
-                plan, unscale = H.conv3d_up2_poly_plan(self.w, *k[:3], fmt="f16")
-                self.wp_poly[k] = (plan, (self.scale * unscale).contiguous())
-            else:
-                self.wp_poly[k] = (H.conv3d_up2_poly_plan(self.w, *k[:3]), self.scale)
-        return self.wp_poly[k]
+    def _poly_plan(self, x_split) -> Packed:
+        """Folded phase weights + face tables for the low-resolution split-padded input: built once per size and split, kept."""
+        D, Hh, W, fmt = x_split.D, x_split.H, x_split.W, x_split.fmt
+        return self._cached(("poly", D, Hh, W, fmt), lambda: self._entry(H.conv3d_up2_poly_plan(self.w, D, Hh, W, fmt=fmt)))
 
     def head_split_ok(self) -> bool:
         """The split cost head on a split-padded input (csrc/conv3d_headsplit.hip), in either 16-bit split."""
         return self.inorm is None and H.split_mode() and self.cout == 1 and self.cin % 16 == 0 and self.stride == 1
 
     def run_head_split(self, x_split) -> Tensor:
-        if x_split.fmt == "f16":
-            if self.f16 is None:
-                self.f16 = {}
-            if "head" not in self.f16:
+        def make():       # scale / shift as host floats: one host read at lowering time
+            if x_split.fmt == "f16":
                 wp, unscale = H.pack_head_split_weights_f16(self.w)
-                self.f16["head"] = (wp, float(self.scale[0]) * unscale, float(self.shift[0]))      # one host read at lowering time
-            wp, sc, sh = self.f16["head"]
-            return H.conv3d_head_split(x_split, wp, sc, sh, neg_slope=self.neg_slope, f16=True)
-        if self.wp_head is None:
-            self.wp_head = H.pack_head_split_weights(self.w)
-            self.head_sc = (float(self.scale[0]), float(self.shift[0]))       # one host read at lowering time
-        return H.conv3d_head_split(x_split, self.wp_head, self.head_sc[0], self.head_sc[1], neg_slope=self.neg_slope)
+                return Packed(wp, float(self.scale[0]) * unscale, float(self.shift[0]))
+            return Packed(H.pack_head_split_weights(self.w), float(self.scale[0]), float(self.shift[0]))
+        p = self._cached(("head", x_split.fmt), make)
+        return H.conv3d_head_split(x_split, p.wp, p.scale, p.shift, neg_slope=self.neg_slope, f16=x_split.fmt == "f16")
 
     def run_up2_poly_split(self, x_split, out) -> "H.SplitAct":
-        plan, sc = self._poly_plan(x_split.D, x_split.H, x_split.W, x_split.fmt)
-        return H.conv3d_up2_poly_split(x_split, plan, sc, self.shift, out=out, neg_slope=self.neg_slope)
+        p = self._poly_plan(x_split)
+        return H.conv3d_up2_poly_split(x_split, p.wp, p.scale, self.shift, out=out, neg_slope=self.neg_slope)
 
     def run_up2_poly(self, x_split, out=None) -> Tensor:
-        plan, sc = self._poly_plan(x_split.D, x_split.H, x_split.W, x_split.fmt)
-        return H.conv3d_up2_poly(x_split, plan, sc, self.shift, neg_slope=self.neg_slope, out=out)
+        p = self._poly_plan(x_split)
+        return H.conv3d_up2_poly(x_split, p.wp, p.scale, self.shift, neg_slope=self.neg_slope, out=out)
 
     def run_up2_split(self, x_lowres_ndhwc: Tensor, res: Optional[Tensor], out) -> "H.SplitAct":
-        """conv(trilinear_x2(x)) (+ res) written split-padded into `out` (the polyphase layer's input, the split head's input)."""
+        """conv(trilinear_x2(x)) (+ res) written split-padded into `out` (the polyphase layer's input, the split head's input);
+        this kernel has no 32-channel-slice form."""
         _no_inorm(self, "run_up2_split")
-        if H.get_conv_mode() == "f16x3":
-            layout = H.CONV_BF16X3_C16 if self._c16() else H.CONV_BF16X3
-            wp16, sc16 = self._f16(layout)
-            return H.conv3d_up2_out_split(x_lowres_ndhwc, wp16, sc16, self.shift, out=out, res=res, neg_slope=self.neg_slope,
-                                          w_layout=layout | H.CONV_F16)
-        if self._c16():       # Cout == 16: the plane schedule (one cout tile)
-            return H.conv3d_up2_out_split(x_lowres_ndhwc, self._wp_c16(), self.scale, self.shift, out=out, res=res,
-                                          neg_slope=self.neg_slope, w_layout=H.CONV_BF16X3_C16)
-        return H.conv3d_up2_out_split(x_lowres_ndhwc, self._wp_b3(), self.scale, self.shift, out=out, res=res, neg_slope=self.neg_slope)
+        w_layout, wp, scale = self._stream(self._stream_layout(), H.mode_fmt())
+        return H.conv3d_up2_out_split(x_lowres_ndhwc, wp, scale, self.shift, out=out, res=res, neg_slope=self.neg_slope, w_layout=w_layout)
 
     def can_fuse_up2(self) -> bool:
         """conv(trilinear_x2(x)) in one launch writing fp32 (run_up2): an instance norm follows it like any other conv."""
@@ -248,27 +241,8 @@ class ConvLaunch:
         return self._run_up2(x_lowres_ndhwc, res)
 
     def _run_up2(self, x_lowres_ndhwc: Tensor, res: Optional[Tensor] = None) -> Tensor:
-        B, Dl, Hl, Wl, _ = x_lowres_ndhwc.shape
-        d32 = False
-        if _USE_D32 and not self._c16() and self.cin % 32 == 0:
-            key = ("up2", self.cin, self.cout, B, Dl, Hl, Wl)
-            d32 = _D32_OK.get(key)
-            if d32 is None:
-                d32 = _D32_OK[key] = H.conv3d_up2_d32_applies(B, self.cin, Dl, Hl, Wl, self.cout)
-        if H.get_conv_mode() == "f16x3":
-            layout = H.CONV_BF16X3_C16 if self._c16() else (H.CONV_BF16X3_D32 if d32 else H.CONV_BF16X3)
-            wp16, sc16 = self._f16(layout)
-            return H.conv3d_up2(x_lowres_ndhwc, wp16, sc16, self.shift, res=res, neg_slope=self.neg_slope, w_layout=layout | H.CONV_F16)
-        if self._c16():
-            return H.conv3d_up2(x_lowres_ndhwc, self._wp_c16(), self.scale, self.shift, res=res,
-                                neg_slope=self.neg_slope, w_layout=H.CONV_BF16X3_C16)
-        if d32 and H.get_conv_mode() == "bf16x3":
-            if getattr(self, "wp_d32", None) is None:
-                self.wp_d32 = H.pack_conv_weights_bf16x3_d32(self.w)
-            return H.conv3d_up2(x_lowres_ndhwc, self.wp_d32, self.scale, self.shift, res=res, neg_slope=self.neg_slope, w_layout=H.CONV_BF16X3_D32)
-        if self.wp_b3 is None:
-            self.wp_b3 = H.pack_conv_weights_bf16x3(self.w)
-        return H.conv3d_up2(x_lowres_ndhwc, self.wp_b3, self.scale, self.shift, res=res, neg_slope=self.neg_slope)
+        w_layout, wp, scale = self._stream(self._stream_layout(x_lowres_ndhwc.shape[:4], up2=True), H.mode_fmt())
+        return H.conv3d_up2(x_lowres_ndhwc, wp, scale, self.shift, res=res, neg_slope=self.neg_slope, w_layout=w_layout)
 
 
 def _is_identity(m) -> bool:
@@ -393,25 +367,7 @@ def lower_conv_block(blk) -> ConvLaunch:
     scale, shift, inorm = lower_norm(blk.norm_layer, conv.bias, cout, w.device, slope)
     if inorm is not None:
         slope = 1.0                 # the conv writes conv + bias; the activation follows the norm
-    L = ConvLaunch()
-    L.w = w
-    L.wp = H.pack_conv_weights(w)
-    L.wp_b3 = None
-    L.wp_c16 = None
-    L.wp_d32 = None
-    L.wp_rs = None
-    L.wp_s2 = None
-    L.wp_poly = None
-    L.wp_head = None
-    L.head_sc = None
-    L.f16 = None
-    L.scale = scale.contiguous()
-    L.shift = shift.contiguous()
-    L.stride = int(conv.stride[0])
-    L.neg_slope = slope
-    L.inorm = inorm
-    L.cin, L.cout = int(w.shape[1]), int(cout)
-    L.key = key
+    L = ConvLaunch(w, scale, shift, conv.stride[0], slope, inorm, key)
     blk.__dict__["_mvsgi_launch"] = L
     return L
 

@@ -57,15 +57,6 @@ def _rig_cache_usable(owner, feats, grids) -> bool:
         and H.nhwc_sweep_ok(feats) and grids.is_cuda
 
 
-def _owned_split_buffer(owner, attr: str, key: tuple, make):
-    """Module-owned split-padded buffers, one per shape key, NEVER replaced or freed while the module lives: a captured
-    hipGraph holds their addresses, and their zero borders are written exactly once (at allocation)."""
-    bufs = owner.__dict__.setdefault(attr, {})
-    if key not in bufs:
-        bufs[key] = make()
-    return bufs[key]
-
-
 def std_sweep_ndhwc(feats, grids, grid_masks, masks, owner=None, split_out: bool = False, buf_frames: int = 0):
     """Masked-variance sweep.  grids / grid_masks / masks are constants of the camera rig (the
     reference builds them once, api/inference_class.py:40-45), so the mask half of the sweep
@@ -101,8 +92,8 @@ def std_sweep_ndhwc(feats, grids, grid_masks, masks, owner=None, split_out: bool
         # (`buf_frames` > B: the buffer is sized for a whole chunk and a shorter tail chunk uses a leading slice of it)
         B, D, Ho, Wo = feats.shape[0], grids.shape[2], grids.shape[3], grids.shape[4]
         nb = max(B, int(buf_frames))
-        full = _owned_split_buffer(owner, "_mvsgi_rs_vol", (nb, D, Ho, Wo, feats.device),
-                                   lambda: H.SplitAct(nb, D, Ho, Wo, 16, feats.device))
+        full = cm._owned_split_buffer(owner, "_mvsgi_rs_vol", (nb, D, Ho, Wo, feats.device),
+                                      lambda: H.SplitAct(nb, D, Ho, Wo, 16, feats.device))
         out = full if nb == B else H.SplitAct(B, D, Ho, Wo, 16, feats.device, buf=full.buf[:B])
         return H.sweep_std_valid_split(feats, g_use, cached[2], out=out, fmt=H.mode_fmt())
     return H.sweep_std_valid(feats, g_use, cached[2])
@@ -133,10 +124,10 @@ def _std_front(self, feats: Tensor, grids: Tensor, grid_masks: Tensor, masks: Te
     B, D, Ho, Wo = feats.shape[0], grids.shape[2], grids.shape[3], grids.shape[4]
     if not _rig_cache_usable(self, feats, grids):
         return None
-    wp_rs, sc_rs = L._rs(H.mode_fmt())      # post_vol's weights / scale in the split the sweep writes
+    wp_rs, sc_rs = L._rs(H.mode_fmt())[:2]      # post_vol's weights / scale in the split the sweep writes
     xs = None
-    if hand_over_split:      # one buffer per shape, never replaced while the module lives (a captured hipGraph holds the address)
-        xs = _owned_split_buffer(self, "_mvsgi_rs_x0", (B, D, Ho, Wo, feats.device), lambda: H.SplitAct(B, D, Ho, Wo, 16, feats.device))
+    if hand_over_split:
+        xs = cm._owned_split_buffer(self, "_mvsgi_rs_x0", (B, D, Ho, Wo, feats.device), lambda: H.SplitAct(B, D, Ho, Wo, 16, feats.device))
     k = _FRONT_CHUNK
     shared = all(t.dim() > 0 and t.shape[0] > 1 and t.stride(0) == 0 for t in (grids, grid_masks, masks))
     if k > 0 and B > k and shared:

@@ -88,13 +88,8 @@ def _down_block_rs(blk, x: Tensor, L0, chain, dims) -> Tensor:
     """first conv (streaming kernel, output written split-padded) -> residual blocks on the register-stationary kernel, three
     rotating split-padded buffers owned by the module (zero borders, allocated once) -> last conv writes plain fp32."""
     B, Do, Ho, Wo = dims
-    # one buffer set per shape, never replaced while the module lives (a captured hipGraph holds the addresses; the zero
-    # borders are written once, at allocation)
-    sets = blk.__dict__.setdefault("_mvsgi_rs_bufs", {})
-    key = (B, Do, Ho, Wo, x.device)
-    if key not in sets:
-        sets[key] = [H.SplitAct(B, Do, Ho, Wo, 32, x.device) for _ in range(3)]
-    b = sets[key]
+    b = cm._owned_split_buffer(blk, "_mvsgi_rs_bufs", (B, Do, Ho, Wo, x.device),
+                               lambda: [H.SplitAct(B, Do, Ho, Wo, 32, x.device) for _ in range(3)])
     fmt = H.mode_fmt()              # the split of this chain's activations and weights (the library's mode)
     # fp16 split on a [8 | 16, even, 32 k] volume: the Winograd form (2.25 x fewer matrix instructions, csrc/conv3d_wino.hip) when its
     # units fill the chip; behind the split-padded hand-over its layers pass fp32-padded activations to each other
@@ -103,22 +98,22 @@ def _down_block_rs(blk, x: Tensor, L0, chain, dims) -> Tensor:
     if isinstance(x, H.SplitAct):      # the builder handed post_vol's output over split-padded: staged by LDS-DMA (csrc/conv3d_s2rs.hip)
         if x.fmt != fmt:
             raise RuntimeError(f"split-padded cost volume holds {x.fmt} pieces, the library's mode writes {fmt}")
-        wp0, sh0, un0 = L0._s2(fmt)
-        H.conv3d_s2rs(x, wp0, sh0, out=b[0], neg_slope=L0.neg_slope, unscale=un0, out_f32p=wino and _WINO_A32)
+        p0 = L0._s2(fmt)
+        H.conv3d_s2rs(x, p0.wp, p0.shift, out=b[0], neg_slope=L0.neg_slope, unscale=p0.unscale, out_f32p=wino and _WINO_A32)
     else:
-        wp0, sc0 = L0._b3(fmt)
-        H.conv3d_out_split(x, wp0, sc0, L0.shift, out=b[0], stride=L0.stride, neg_slope=L0.neg_slope, fmt=fmt)
+        p0 = L0._stream_packed(H.CONV_BF16X3, fmt)
+        H.conv3d_out_split(x, p0.wp, p0.scale, L0.shift, out=b[0], stride=L0.stride, neg_slope=L0.neg_slope, fmt=fmt)
     conv = H.conv3d_wino if wino else H.conv3d_rs
     cur, out = 0, None
     for i, (L1, L2) in enumerate(chain):
         r, y = (cur + 1) % 3, (cur + 2) % 3
-        (wp1, sc1) = L1._wino() if wino else L1._rs(fmt)
-        (wp2, sc2) = L2._wino() if wino else L2._rs(fmt)
-        conv(b[cur], wp1, sc1, L1.shift, neg_slope=L1.neg_slope, out=b[r])
+        p1 = L1._wino() if wino else L1._rs(fmt)
+        p2 = L2._wino() if wino else L2._rs(fmt)
+        conv(b[cur], p1.wp, p1.scale, L1.shift, neg_slope=L1.neg_slope, out=b[r])
         if i == len(chain) - 1:
-            out = conv(b[r], wp2, sc2, L2.shift, res=b[cur], neg_slope=L2.neg_slope, out_f32=True)
+            out = conv(b[r], p2.wp, p2.scale, L2.shift, res=b[cur], neg_slope=L2.neg_slope, out_f32=True)
         else:
-            conv(b[r], wp2, sc2, L2.shift, res=b[cur], neg_slope=L2.neg_slope, out=b[y])
+            conv(b[r], p2.wp, p2.scale, L2.shift, res=b[cur], neg_slope=L2.neg_slope, out=b[y])
             cur = y
     return out
 
@@ -188,18 +183,14 @@ def _poly_tail(self, x: Tensor, skip: Tensor):
         return None                                      # odd pyramid: the second trilinear resize of common_modules.py:343-350
     if B * ((2 * Dl + 1) // 2) * ((2 * Hl + 3) // 4) * ((2 * Wl + 15) // 16) < _POLY_MIN_UNITS:
         return None
-    bufs = self.__dict__.setdefault("_mvsgi_poly_bufs", {})          # one split-padded buffer per shape, never replaced
-    key = (B, 2 * Dl, 2 * Hl, 2 * Wl, x.device)
-    if key not in bufs:
-        bufs[key] = H.SplitAct(B, 2 * Dl, 2 * Hl, 2 * Wl, 32, x.device)
-    xs = Lu.run_up2_split(x, skip, bufs[key])
+    xs = Lu.run_up2_split(x, skip, cm._owned_split_buffer(self, "_mvsgi_poly_bufs", (B, 2 * Dl, 2 * Hl, 2 * Wl, x.device),
+                                                          lambda: H.SplitAct(B, 2 * Dl, 2 * Hl, 2 * Wl, 32, x.device)))
     # the cost head reads split-padded fragments straight into the matrix cores: out_costs.0 then writes that format
     Lh = cm.lower_conv_block(self.out_costs[1])
     if _HEAD_SPLIT and Lh.head_split_ok() and Lh.cin == 16:
-        hkey = (B, 4 * Dl, 4 * Hl, 4 * Wl, "hi", x.device)
-        if hkey not in bufs:
-            bufs[hkey] = H.SplitAct(B, 4 * Dl, 4 * Hl, 4 * Wl, 16, x.device)
-        return Lh.run_head_split(Lo.run_up2_poly_split(xs, bufs[hkey]))
+        hi = cm._owned_split_buffer(self, "_mvsgi_poly_bufs", (B, 4 * Dl, 4 * Hl, 4 * Wl, "hi", x.device),
+                                    lambda: H.SplitAct(B, 4 * Dl, 4 * Hl, 4 * Wl, 16, x.device))
+        return Lh.run_head_split(Lo.run_up2_poly_split(xs, hi))
     return Lh.run(Lo.run_up2_poly(xs))
 
 
@@ -238,29 +229,7 @@ def _split_head_tail(self, x: Tensor):
     B, Dl, Hl, Wl, _ = x.shape
     if (2 * Dl + 2) * (2 * Hl + 4) * (2 * Wl + 4) * Lo.cout * 4 >= 2 ** 31:        # the launcher's bound for a split-padded output frame (32-bit offsets)
         return None
-    return Lh.run_head_split(Lo.run_up2_split(x, None, _owned_head_buffer(self, B, 2 * Dl, 2 * Hl, 2 * Wl, Lo.cout, x.device)))
-
-
-def _owned_head_buffer(self, B, D, Hh, W, C, device):
-    """The module-owned split-padded buffer between out_costs.0 and the split head: ONE allocation per frame geometry, sized for the
-    largest batch seen, handed out as a view of its first B frames (the format is per frame: a prefix of the batch is a valid
-    buffer).  A caller that varies its batch (batch sweeps, dataset tails) therefore holds one buffer, not one per batch size; a
-    larger batch replaces it -- unless a captured hipGraph may hold its address (`_mvsgi_pinned`, set while capturing), in which
-    case the old one stays alive beside the new."""
-    import torch
-    bufs = self.__dict__.setdefault("_mvsgi_head_bufs", {})
-    key = (D, Hh, W, C, device)
-    ent = bufs.get(key)
-    if ent is None or ent[0].B < B:
-        big = H.SplitAct(B, D, Hh, W, C, device)
-        keep = ent[1] + [ent[0]] if ent is not None and (ent[2] or ent[1]) else []      # graphs may hold the old buffers
-        ent = bufs[key] = [big, keep, False]
-    if torch.cuda.is_current_stream_capturing():
-        ent[2] = True
-    big = ent[0]
-    if big.B == B:
-        return big
-    return H.SplitAct(B, D, Hh, W, C, device, buf=big.buf[:B])
+    return Lh.run_head_split(Lo.run_up2_split(x, None, cm._owned_head_buffer(self, B, 2 * Dl, 2 * Hl, 2 * Wl, Lo.cout, x.device)))
 
 
 def regulator_forward(self, x: Tensor) -> Tensor:

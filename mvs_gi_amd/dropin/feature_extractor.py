@@ -25,8 +25,17 @@ from .common_modules import module_getstate, NoOp, NORM2D_TYPE, RELU_TYPE, _is_i
 # feature maps, is the INPUT of the path whose 1e-3 bar the modes are about (the sweep consumes them bit-exactly); MVSGI_CONV_MODE=f32
 # runs it on the exact-fp32 kernels.
 class Conv2dLaunch:
-    __slots__ = ("w", "wp_b3", "wp_f32", "wp_stem", "wp_rs", "scale", "shift", "stride", "neg_slope", "k", "cin", "cout", "key",
-                 "inorm")
+    """Launch arguments of one BaseConvBlk2d, as cm.ConvLaunch: every packing of the weights a kernel has asked for lives in one
+    cache, keyed ("b3",) | ("f32",) | ("stem",) | ("rs",) (the entries are the packed weights: none of them rescales)."""
+    __slots__ = ("w", "scale", "shift", "stride", "neg_slope", "k", "cin", "cout", "key", "inorm", "_cache")
+
+    def __init__(self, w: Tensor, scale: Tensor, shift: Tensor, stride: int, neg_slope: float, inorm=None, key=None):
+        self.w, self.scale, self.shift = w, scale.contiguous(), shift.contiguous()
+        self.stride, self.neg_slope, self.inorm, self.key = int(stride), neg_slope, inorm, key
+        self.cout, self.cin, self.k = int(w.shape[0]), int(w.shape[1]), int(w.shape[-1])
+        self._cache = {}
+
+    _cached = cm.ConvLaunch._cached
 
     def run(self, x: Tensor, res: Optional[Tensor] = None, in_nchw: bool = False, out_split: Optional[Tensor] = None) -> Tensor:
         if self.inorm is not None:           # conv (+ bias) -> instance norm (+ res) -> act (cm.InstanceNormLaunch)
@@ -40,25 +49,21 @@ class Conv2dLaunch:
         # instance-norm layers stay on the exact-fp32 kernels in every mode: the norm divides each channel by its own spread, so
         # the bf16 split's rounding (relative to the conv output's level) is amplified by 1 / std and compounds over the chain
         if H.split_mode() and self.inorm is None and self.k == 3 and self.cin % 16 == 0 and self.cout % 16 == 0 and not in_nchw:
-            if self.wp_b3 is None:
-                self.wp_b3 = H.pack_conv2d_weights_bf16x3(self.w)
-            impl, wp = H.CONV_BF16X3, self.wp_b3
+            impl, wp = H.CONV_BF16X3, self.b3_weights()
         elif self.k == 3 and self.cin % 16 == 0 and self.cout in (16, 32) and not in_nchw:
-            if self.wp_f32 is None:                    # exact fp32 mode: fp32 MFMA kernel
-                self.wp_f32 = H.pack_conv2d_weights_f32(self.w)
-            impl, wp = H.CONV_MFMA, self.wp_f32
+            impl, wp = H.CONV_MFMA, self._cached(("f32",), lambda: H.pack_conv2d_weights_f32(self.w))      # exact fp32 mode: fp32 MFMA kernel
         elif x.dtype == torch.uint8 and (self.k, self.stride, self.cin, self.cout) == (5, 2, 3, 16):
-            if self.wp_stem is None:                   # camera images: the stem on the matrix cores (exact pixels, 24-bit weights)
-                self.wp_stem = H.pack_conv2d_stem_weights(self.w)
-            wp = self.wp_stem
+            # camera images: the stem on the matrix cores (exact pixels, 24-bit weights)
+            wp = self._cached(("stem",), lambda: H.pack_conv2d_stem_weights(self.w))
         return H.conv2d(x, self.w, wp, self.scale, self.shift, res=res, stride=self.stride,
                         neg_slope=self.neg_slope, impl=impl, in_nchw=in_nchw, out_split=out_split)
 
+    def b3_weights(self) -> Tensor:
+        return self._cached(("b3",), lambda: H.pack_conv2d_weights_bf16x3(self.w))
+
     def rs_weights(self) -> Tensor:
         cm._no_inorm(self, "Conv2dLaunch.rs_weights")
-        if self.wp_rs is None:
-            self.wp_rs = H.pack_resblock2d_split_weights(self.w, self.scale)
-        return self.wp_rs
+        return self._cached(("rs",), lambda: H.pack_resblock2d_split_weights(self.w, self.scale))
 
 
 def lower_conv2d_block(blk) -> Conv2dLaunch:
@@ -87,12 +92,7 @@ def lower_conv2d_block(blk) -> Conv2dLaunch:
     scale, shift, inorm = cm.lower_norm(norm, conv.bias, cout, w.device, slope, dims=2)
     if inorm is not None:
         slope = 1.0                  # the conv writes conv + bias; the activation follows the norm
-    L = Conv2dLaunch()
-    L.w, L.wp_b3, L.wp_f32, L.wp_stem, L.wp_rs = w, None, None, None, None
-    L.scale, L.shift = scale.contiguous(), shift.contiguous()
-    L.stride, L.neg_slope, L.k = int(conv.stride[0]), slope, int(k)
-    L.cin, L.cout, L.key = int(w.shape[1]), int(cout), key
-    L.inorm = inorm
+    L = Conv2dLaunch(w, scale, shift, conv.stride[0], slope, inorm, key)
     blk.__dict__["_mvsgi_launch"] = L
     return L
 
@@ -104,10 +104,8 @@ def _nhwc(x: Tensor) -> Tensor:
         return v
     lib_x = H._dev(x, "x")
     B, C, Hh, W = lib_x.shape
-    from .. import _lib
     y = torch.empty((B, Hh, W, C), device=lib_x.device, dtype=torch.float32)
-    _lib.check(_lib.load().mvsgi_ncv_to_nvc_f32(lib_x.data_ptr(), y.data_ptr(), B, C, Hh * W, H._stream_ptr(lib_x)),
-               "mvsgi_ncv_to_nvc_f32")
+    H._call("mvsgi_ncv_to_nvc_f32", lib_x.data_ptr(), y.data_ptr(), B, C, Hh * W, H._stream_ptr(lib_x))
     return y
 
 
@@ -149,10 +147,7 @@ def res_block2d_nhwc(blk, x: Tensor) -> Tensor:
     if H.split_mode() and L1.inorm is None and L2.inorm is None and L1.k == 3 and L2.k == 3 and L1.stride == 1 and L2.stride == 1 \
             and (L1.cin, L1.cout, L2.cin, L2.cout) == (16, 16, 16, 16) and L1.neg_slope == L2.neg_slope:
         # both convs in one launch, the intermediate stays in LDS (mvsgi_resblock2d_f32)
-        for L in (L1, L2):
-            if L.wp_b3 is None:
-                L.wp_b3 = H.pack_conv2d_weights_bf16x3(L.w)
-        return H.resblock2d(x, L1.wp_b3, L1.scale, L1.shift, L2.wp_b3, L2.scale, L2.shift, L1.neg_slope)
+        return H.resblock2d(x, L1.b3_weights(), L1.scale, L1.shift, L2.b3_weights(), L2.scale, L2.shift, L1.neg_slope)
     r = L1.run(x)
     return L2.run(r, res=x)
 
@@ -194,14 +189,9 @@ def _fusable_resblock(blk) -> bool:
 
 
 def _split2d_pair(self, N: int, Hh: int, W: int, device):
-    """Two zero-bordered 2-D split-padded buffers per (image count, resolution), owned by the module and NEVER replaced or freed
-    while it lives: the kernels write interiors only, so the borders stay zero from one forward to the next, and a captured
-    hipGraph (InferencePipeline.capture) holds their addresses."""
-    cache = self.__dict__.setdefault("_mvsgi_split2d", {})
-    key = (N, Hh, W, str(device))
-    if key not in cache:
-        cache[key] = (H.split2d_buffer(N, Hh, W, device), H.split2d_buffer(N, Hh, W, device))
-    return cache[key]
+    """Two zero-bordered 2-D split-padded buffers per (image count, resolution), module-owned (cm._owned_split_buffer)."""
+    return cm._owned_split_buffer(self, "_mvsgi_split2d", (N, Hh, W, str(device)),
+                                  lambda: (H.split2d_buffer(N, Hh, W, device), H.split2d_buffer(N, Hh, W, device)))
 
 
 def _s2_split_ok(L) -> bool:

@@ -16,8 +16,7 @@ from typing import Sequence
 import numpy as np
 import torch
 
-from .. import _lib
-from ..hip_ops import _dev, _stream_ptr
+from ..hip_ops import _call, _dev, _stream_ptr
 
 
 def _as_f32_cuda(t, device) -> torch.Tensor:
@@ -38,19 +37,16 @@ class RayMaker_UEPanorama:
 
     def make_rays_for_candidates(self, grid_shape: Sequence[int]) -> torch.Tensor:
         """-> rays [3, N, H, W] in the panorama frame (z backward, x left, y down); :76-132."""
-        lib = _lib.load()
         H, W = int(grid_shape[0]), int(grid_shape[1])
         N = self.dist.numel()
         rays = torch.empty((3, N, H, W), device=self.device, dtype=torch.float32)
-        _lib.check(lib.mvsgi_rays_panorama_f32(self.dist.data_ptr(), rays.data_ptr(), N, H, W, self.lat_range[0],
-                                               self.lat_range[1], self.long_range[0], self.long_range[1],
-                                               _stream_ptr(rays)), "mvsgi_rays_panorama_f32")
+        _call("mvsgi_rays_panorama_f32", self.dist.data_ptr(), rays.data_ptr(), N, H, W, self.lat_range[0], self.lat_range[1], self.long_range[0],
+              self.long_range[1], _stream_ptr(rays))
         return rays
 
 
 def transform_3D_points_torch(T: torch.Tensor, points: torch.Tensor) -> torch.Tensor:
     """T [B, 4, 4], points [B, 3, N, H, W] -> R p + t, same shape (torch_cuda_sweep.py:385-408)."""
-    lib = _lib.load()
     points = _dev(points, "points")
     T = _dev(T.to(torch.float32), "T")
     B = points.shape[0]
@@ -58,8 +54,7 @@ def transform_3D_points_torch(T: torch.Tensor, points: torch.Tensor) -> torch.Te
         raise AssertionError(f"expected T [B,4,4] and points [B,3,N,H,W], got {tuple(T.shape)}, {tuple(points.shape)}")
     out = torch.empty_like(points)
     M = points[0, 0].numel()
-    _lib.check(lib.mvsgi_transform_points_f32(T.data_ptr(), points.data_ptr(), out.data_ptr(), B, M, _stream_ptr(points)),
-               "mvsgi_transform_points_f32")
+    _call("mvsgi_transform_points_f32", T.data_ptr(), points.data_ptr(), out.data_ptr(), B, M, _stream_ptr(points))
     return out
 
 
@@ -74,15 +69,12 @@ class DoubleSphereSampleGridMaker:
 
     def make_grid(self, points: torch.Tensor):
         """points [B, 3, N, H, W] -> (grid [B, N, H, W, 2] in [-1, 1], mask [B, N, H, W] bool); :262-298."""
-        lib = _lib.load()
         points = _dev(points, "points")
         B, _, N, H, W = points.shape
         grid = torch.empty((B, N, H, W, 2), device=points.device, dtype=torch.float32)
         mask = torch.empty((B, N, H, W), device=points.device, dtype=torch.uint8)
-        _lib.check(lib.mvsgi_grid_double_sphere_f32(points.data_ptr(), grid.data_ptr(), mask.data_ptr(), B, N * H * W,
-                                                    self.xi, self.alpha, self.fx, self.fy, self.cx, self.cy,
-                                                    self.calib_shape[0], self.calib_shape[1], self.w2,
-                                                    _stream_ptr(points)), "mvsgi_grid_double_sphere_f32")
+        _call("mvsgi_grid_double_sphere_f32", points.data_ptr(), grid.data_ptr(), mask.data_ptr(), B, N * H * W, self.xi, self.alpha, self.fx,
+              self.fy, self.cx, self.cy, self.calib_shape[0], self.calib_shape[1], self.w2, _stream_ptr(points))
         return grid, mask.bool()
 
 
@@ -90,12 +82,10 @@ class EquirectangularSampleGridMaker:
     """torch_cuda_sweep.py:300-335: longitude / latitude of 3-D points as grid_sample coordinates."""
 
     def make_grid(self, points: torch.Tensor) -> torch.Tensor:
-        lib = _lib.load()
         points = _dev(points, "points")
         B, _, N, H, W = points.shape
         grid = torch.empty((B, N, H, W, 2), device=points.device, dtype=torch.float32)
-        _lib.check(lib.mvsgi_grid_equirect_f32(points.data_ptr(), grid.data_ptr(), B, N * H * W, _stream_ptr(points)),
-                   "mvsgi_grid_equirect_f32")
+        _call("mvsgi_grid_equirect_f32", points.data_ptr(), grid.data_ptr(), B, N * H * W, _stream_ptr(points))
         return grid
 
 

@@ -182,6 +182,11 @@ def _ptr(t: Optional[torch.Tensor]) -> Optional[int]:
     return None if t is None else t.data_ptr()
 
 
+def _call(name: str, *args) -> None:
+    """One launch through the C ABI: lib.<name>(*args); a failure raises with the name of the symbol that failed."""
+    _lib.check(getattr(_lib.load(), name)(*args), name)
+
+
 # --------------------------------------------------------------------------------------
 def _feats_nhwc(feats):
     """[B, N, C, Hi, Wi] -> channels-last storage [B, N, Hi, Wi, C] (no copy if it already is)."""
@@ -190,12 +195,10 @@ def _feats_nhwc(feats):
     v = feats.permute(0, 1, 3, 4, 2)
     if v.is_contiguous() and v.data_ptr() % 16 == 0 and v.is_cuda and v.dtype == torch.float32:
         return v
-    lib = _lib.load()
     f = _dev(feats, "feats")
     B, N, C, Hi, Wi = f.shape
     y = torch.empty((B, N, Hi, Wi, C), device=f.device, dtype=torch.float32)
-    _lib.check(lib.mvsgi_ncv_to_nvc_f32(f.data_ptr(), y.data_ptr(), B * N, C, Hi * Wi, _stream_ptr(f)),
-               "mvsgi_ncv_to_nvc_f32")
+    _call("mvsgi_ncv_to_nvc_f32", f.data_ptr(), y.data_ptr(), B * N, C, Hi * Wi, _stream_ptr(f))
     return y
 
 
@@ -203,31 +206,42 @@ def nhwc_sweep_ok(feats) -> bool:
     return feats.dim() == 5 and feats.shape[2] % 4 == 0 and feats.shape[1] <= 4
 
 
-def sweep_validity(grids, grid_masks, masks) -> torch.Tensor:
-    """Rig-constant validity byte per voxel, [B, D, Ho, Wo] uint8 (bit cam = camera cam valid):
-    (bilinear_grid_sample(masks) > 0) & grid_masks of spherical_sweep_avg.py:92-102."""
-    lib = _lib.load()
+def _rig_args(grids, grid_masks, masks, B: int, N: int):
+    """The rig tensors of a masked sweep, checked against B frames of N cameras -> (grids, grid_masks, gm_f32, masks, sizes):
+    gm_f32 = 1 when the grid masks are fp32 (any dtype but bool / uint8 is converted), 0 for one byte per sample;
+    sizes = (D, Ho, Wo, Hm, Wm)."""
     grids = _dev(grids, "grids")
     masks = _dev(masks, "masks")
-    gm, gm_f32 = _gm_arg(grid_masks)
-    B, N, D, Ho, Wo, two = grids.shape
-    if two != 2 or N > 8:
-        raise AssertionError(f"grids must be [B, N<=8, D, Ho, Wo, 2], got {tuple(grids.shape)}")
+    if grid_masks.dtype in (torch.bool, torch.uint8):
+        gm, gm_f32 = _dev(grid_masks, "grid_masks", grid_masks.dtype), 0
+    else:
+        gm, gm_f32 = _dev(grid_masks.to(torch.float32) if grid_masks.dtype != torch.float32 else grid_masks, "grid_masks"), 1
+    Bg, Ng, D, Ho, Wo, two = grids.shape
+    if (Bg, Ng, two) != (B, N, 2):
+        raise AssertionError(f"grids {tuple(grids.shape)} must be [{B}, {N}, D, Ho, Wo, 2]")
     if tuple(gm.shape[:5]) != (B, N, D, Ho, Wo) or gm.numel() != B * N * D * Ho * Wo:
         raise AssertionError(f"grid_masks {tuple(gm.shape)} do not match grids {tuple(grids.shape)}")
     if masks.shape[0] != B or masks.shape[1] != N or masks.numel() != B * N * masks.shape[-2] * masks.shape[-1]:
         raise AssertionError(f"masks {tuple(masks.shape)} do not match grids {tuple(grids.shape)}")
-    Hm, Wm = masks.shape[-2:]
+    return grids, gm, gm_f32, masks, (D, Ho, Wo) + tuple(masks.shape[-2:])
+
+
+def sweep_validity(grids, grid_masks, masks) -> torch.Tensor:
+    """Rig-constant validity byte per voxel, [B, D, Ho, Wo] uint8 (bit cam = camera cam valid):
+    (bilinear_grid_sample(masks) > 0) & grid_masks of spherical_sweep_avg.py:92-102."""
+    B, N = grids.shape[:2]
+    if N > 8:
+        raise AssertionError(f"grids must be [B, N<=8, D, Ho, Wo, 2], got {tuple(grids.shape)}")
+    grids, gm, gm_f32, masks, (D, Ho, Wo, Hm, Wm) = _rig_args(grids, grid_masks, masks, B, N)
     vmask = torch.empty((B, D, Ho, Wo), device=grids.device, dtype=torch.uint8)
-    _lib.check(lib.mvsgi_sweep_validity_u8(grids.data_ptr(), gm.data_ptr(), gm_f32, masks.data_ptr(), vmask.data_ptr(),
-                                           B, N, Hm, Wm, D, Ho, Wo, _stream_ptr(grids)), "mvsgi_sweep_validity_u8")
+    _call("mvsgi_sweep_validity_u8", grids.data_ptr(), gm.data_ptr(), gm_f32, masks.data_ptr(), vmask.data_ptr(),
+          B, N, Hm, Wm, D, Ho, Wo, _stream_ptr(grids))
     return vmask
 
 
 def sweep_std_valid(feats, grids, vmask) -> torch.Tensor:
     """sweep_std with the cached validity byte (channels-last kernel only) -> vol_raw [B, D, Ho, Wo, C].
     grids / vmask with batch 1 against feats with batch B > 1 = one rig shared by the whole batch."""
-    lib = _lib.load()
     if not nhwc_sweep_ok(feats):
         raise AssertionError(f"sweep_std_valid needs C % 4 == 0 and N <= 4, got feats {tuple(feats.shape)}")
     B, N, C, Hi, Wi = feats.shape
@@ -240,15 +254,13 @@ def sweep_std_valid(feats, grids, vmask) -> torch.Tensor:
     if tuple(vmask.shape) != (Bg, D, Ho, Wo):
         raise AssertionError(f"vmask {tuple(vmask.shape)} does not match grids {tuple(grids.shape)}")
     vol = torch.empty((B, D, Ho, Wo, C), device=f.device, dtype=torch.float32)
-    fn = lib.mvsgi_sweep_std_nhwc_valid_rig_f32 if (Bg == 1 and B > 1) else lib.mvsgi_sweep_std_nhwc_valid_f32
-    _lib.check(fn(f.data_ptr(), grids.data_ptr(), vmask.data_ptr(), vol.data_ptr(), B, N, C, Hi, Wi, D, Ho, Wo, _stream_ptr(f)),
-               "mvsgi_sweep_std_nhwc_valid_f32")
+    _call("mvsgi_sweep_std_nhwc_valid_rig_f32" if (Bg == 1 and B > 1) else "mvsgi_sweep_std_nhwc_valid_f32",
+          f.data_ptr(), grids.data_ptr(), vmask.data_ptr(), vol.data_ptr(), B, N, C, Hi, Wi, D, Ho, Wo, _stream_ptr(f))
     return vol
 
 
 def sweep_std_valid_split(feats, grids, vmask, out: "SplitAct", fmt: str = "bf16") -> "SplitAct":
     """sweep_std_valid with vol_raw written split-padded (C == 16) into `out` (B, D, Ho, Wo, 16), its pieces in the split `fmt`."""
-    lib = _lib.load()
     B, N, C, Hi, Wi = feats.shape
     f = _feats_nhwc(feats)
     grids = _dev(grids, "grids")
@@ -258,8 +270,8 @@ def sweep_std_valid_split(feats, grids, vmask, out: "SplitAct", fmt: str = "bf16
         raise AssertionError(f"grids {tuple(grids.shape)} / vmask {tuple(vmask.shape)} do not match feats {tuple(feats.shape)}")
     if out.shape != (B, D, Ho, Wo, C):
         raise AssertionError(f"split output {out.shape} does not match {(B, D, Ho, Wo, C)}")
-    _lib.check(lib.mvsgi_sweep_std_nhwc_valid_split_fmt(f.data_ptr(), grids.data_ptr(), vmask.data_ptr(), out.buf.data_ptr(), B, N, C, Hi,
-                                                        Wi, D, Ho, Wo, Bg, _fmt_code(fmt), _stream_ptr(f)), "mvsgi_sweep_std_nhwc_valid_split")
+    _call("mvsgi_sweep_std_nhwc_valid_split_fmt", f.data_ptr(), grids.data_ptr(), vmask.data_ptr(), out.buf.data_ptr(), B, N, C, Hi, Wi, D, Ho, Wo,
+          Bg, _fmt_code(fmt), _stream_ptr(f))
     out.fmt = fmt
     return out
 
@@ -268,90 +280,28 @@ def sweep_std(feats, grids, grid_masks, masks, layout: str = "auto") -> torch.Te
     """-> vol_raw [B, D, Ho, Wo, C] (masked variance over cameras).  layout: 'auto' uses the
     channels-last kernel when C % 4 == 0 and N <= 4 (transposing NCHW feats once), 'nchw'
     forces the plane-gather kernel."""
-    lib = _lib.load()
-    if layout == "auto" and nhwc_sweep_ok(feats):
-        return _sweep_std_nhwc(feats, grids, grid_masks, masks)
-    feats = _dev(feats, "feats")
-    grids = _dev(grids, "grids")
-    masks = _dev(masks, "masks")
-    if grid_masks.dtype == torch.bool:
-        gm = _dev(grid_masks, "grid_masks", torch.bool)
-        gm_f32 = 0
-    elif grid_masks.dtype == torch.uint8:
-        gm = _dev(grid_masks, "grid_masks", torch.uint8)
-        gm_f32 = 0
-    else:
-        gm = _dev(grid_masks.to(torch.float32) if grid_masks.dtype != torch.float32 else grid_masks, "grid_masks")
-        gm_f32 = 1
+    nhwc = layout == "auto" and nhwc_sweep_ok(feats)
     B, N, C, Hi, Wi = feats.shape
-    Bg, Ng, D, Ho, Wo, two = grids.shape
-    if (Bg, Ng, two) != (B, N, 2):
-        raise AssertionError(f"grids {tuple(grids.shape)} do not match feats {tuple(feats.shape)}")
-    if tuple(gm.shape[:5]) != (B, N, D, Ho, Wo) or gm.numel() != B * N * D * Ho * Wo:
-        raise AssertionError(f"grid_masks {tuple(gm.shape)} do not match grids {tuple(grids.shape)}")
-    if masks.shape[0] != B or masks.shape[1] != N or masks.numel() != B * N * masks.shape[-2] * masks.shape[-1]:
-        raise AssertionError(f"masks {tuple(masks.shape)} do not match feats {tuple(feats.shape)}")
-    Hm, Wm = masks.shape[-2:]
-    vol = torch.empty((B, D, Ho, Wo, C), device=feats.device, dtype=torch.float32)
-    _lib.check(lib.mvsgi_sweep_std_f32(feats.data_ptr(), grids.data_ptr(), gm.data_ptr(), gm_f32, masks.data_ptr(),
-                                       vol.data_ptr(), B, N, C, Hi, Wi, Hm, Wm, D, Ho, Wo, _stream_ptr(feats)),
-               "mvsgi_sweep_std_f32")
-    return vol
-
-
-def _gm_arg(grid_masks):
-    if grid_masks.dtype == torch.bool:
-        return _dev(grid_masks, "grid_masks", torch.bool), 0
-    if grid_masks.dtype == torch.uint8:
-        return _dev(grid_masks, "grid_masks", torch.uint8), 0
-    return _dev(grid_masks.to(torch.float32) if grid_masks.dtype != torch.float32 else grid_masks, "grid_masks"), 1
-
-
-def _sweep_std_nhwc(feats, grids, grid_masks, masks) -> torch.Tensor:
-    lib = _lib.load()
-    B, N, C, Hi, Wi = feats.shape
-    f = _feats_nhwc(feats)
-    grids = _dev(grids, "grids")
-    masks = _dev(masks, "masks")
-    gm, gm_f32 = _gm_arg(grid_masks)
-    Bg, Ng, D, Ho, Wo, two = grids.shape
-    if (Bg, Ng, two) != (B, N, 2):
-        raise AssertionError(f"grids {tuple(grids.shape)} do not match feats {tuple(feats.shape)}")
-    if tuple(gm.shape[:5]) != (B, N, D, Ho, Wo) or gm.numel() != B * N * D * Ho * Wo:
-        raise AssertionError(f"grid_masks {tuple(gm.shape)} do not match grids {tuple(grids.shape)}")
-    if masks.shape[0] != B or masks.shape[1] != N or masks.numel() != B * N * masks.shape[-2] * masks.shape[-1]:
-        raise AssertionError(f"masks {tuple(masks.shape)} do not match feats {tuple(feats.shape)}")
-    Hm, Wm = masks.shape[-2:]
+    f = _feats_nhwc(feats) if nhwc else _dev(feats, "feats")
+    grids, gm, gm_f32, masks, (D, Ho, Wo, Hm, Wm) = _rig_args(grids, grid_masks, masks, B, N)
     vol = torch.empty((B, D, Ho, Wo, C), device=f.device, dtype=torch.float32)
-    _lib.check(lib.mvsgi_sweep_std_nhwc_f32(f.data_ptr(), grids.data_ptr(), gm.data_ptr(), gm_f32, masks.data_ptr(),
-                                            vol.data_ptr(), B, N, C, Hi, Wi, Hm, Wm, D, Ho, Wo, _stream_ptr(f)),
-               "mvsgi_sweep_std_nhwc_f32")
+    _call("mvsgi_sweep_std_nhwc_f32" if nhwc else "mvsgi_sweep_std_f32", f.data_ptr(), grids.data_ptr(), gm.data_ptr(), gm_f32,
+          masks.data_ptr(), vol.data_ptr(), B, N, C, Hi, Wi, Hm, Wm, D, Ho, Wo, _stream_ptr(f))
     return vol
 
 
 def sweep_cat(feats, grids, layout: str = "auto") -> torch.Tensor:
     """-> vol_raw [B, D, Ho, Wo, N*C] (channel = cam*C + c)."""
-    lib = _lib.load()
-    if layout == "auto" and feats.dim() == 5 and feats.shape[2] % 4 == 0:
-        B, N, C, Hi, Wi = feats.shape
-        f = _feats_nhwc(feats)
-        grids = _dev(grids, "grids")
-        Bg, Ng, D, Ho, Wo, two = grids.shape
-        if (Bg, Ng, two) != (B, N, 2):
-            raise AssertionError(f"grids {tuple(grids.shape)} do not match feats {tuple(feats.shape)}")
-        vol = torch.empty((B, D, Ho, Wo, N * C), device=f.device, dtype=torch.float32)
-        _lib.check(lib.mvsgi_sweep_cat_nhwc_f32(f.data_ptr(), grids.data_ptr(), vol.data_ptr(), B, N, C, Hi, Wi, D,
-                                                Ho, Wo, _stream_ptr(f)), "mvsgi_sweep_cat_nhwc_f32")
-        return vol
-    feats = _dev(feats, "feats")
-    grids = _dev(grids, "grids")
+    nhwc = layout == "auto" and feats.dim() == 5 and feats.shape[2] % 4 == 0
+    f = _feats_nhwc(feats) if nhwc else _dev(feats, "feats")
     B, N, C, Hi, Wi = feats.shape
+    grids = _dev(grids, "grids")
     Bg, Ng, D, Ho, Wo, two = grids.shape
     if (Bg, Ng, two) != (B, N, 2):
         raise AssertionError(f"grids {tuple(grids.shape)} do not match feats {tuple(feats.shape)}")
-    vol = torch.empty((B, D, Ho, Wo, N * C), device=feats.device, dtype=torch.float32)
-    _lib.check(lib.mvsgi_sweep_cat_f32(feats.data_ptr(), grids.data_ptr(), vol.data_ptr(), B, N, C, Hi, Wi, D, Ho, Wo,
-                                       _stream_ptr(feats)), "mvsgi_sweep_cat_f32")
+    vol = torch.empty((B, D, Ho, Wo, N * C), device=f.device, dtype=torch.float32)
+    _call("mvsgi_sweep_cat_nhwc_f32" if nhwc else "mvsgi_sweep_cat_f32", f.data_ptr(), grids.data_ptr(), vol.data_ptr(), B, N, C, Hi, Wi,
+          D, Ho, Wo, _stream_ptr(f))
     return vol
 
 
@@ -366,46 +316,67 @@ def pack_conv_weights(w_oidhw: torch.Tensor) -> Optional[torch.Tensor]:
     if Cin % 16 or not (Cout % 16 == 0 or Cout == 1):
         return None
     wp = torch.empty(lib.mvsgi_conv3d_packed_weight_floats(Cout, Cin), device=w.device, dtype=torch.float32)
-    _lib.check(lib.mvsgi_conv3d_pack_weights_f32(w.data_ptr(), wp.data_ptr(), Cout, Cin, _stream_ptr(w)),
-               "mvsgi_conv3d_pack_weights_f32")
+    _call("mvsgi_conv3d_pack_weights_f32", w.data_ptr(), wp.data_ptr(), Cout, Cin, _stream_ptr(w))
     return wp
 
 
-def pack_conv_weights_bf16x3(w_oidhw: torch.Tensor) -> Optional[torch.Tensor]:
-    """[Cout, Cin, 3, 3, 3] -> split-bf16 (hi | lo) MFMA layout, or None when unsupported."""
-    lib = _lib.load()
-    w = _dev(w_oidhw, "conv weight")
-    Cout, Cin = w.shape[:2]
-    if tuple(w.shape[2:]) != (3, 3, 3) or Cin % 16 or Cout % 16:
-        return None
-    wp = torch.empty(lib.mvsgi_conv3d_packed_weight_bytes_bf16x3(Cout, Cin), device=w.device, dtype=torch.uint8)
-    _lib.check(lib.mvsgi_conv3d_pack_weights_bf16x3(w.data_ptr(), wp.data_ptr(), Cout, Cin, _stream_ptr(w)),
-               "mvsgi_conv3d_pack_weights_bf16x3")
-    return wp
-
-
-def pack_conv_weights_f16x3(w_oidhw: torch.Tensor, layout: int = CONV_BF16X3):
-    """[Cout, Cin, 3, 3, 3] -> (packed weights of the fp16 split in `layout` (CONV_BF16X3 | _C16 | _V32), unscale [Cout]) or None.
-    Every output channel's weights are pre-scaled by a power of two so that its largest weight lies in (512, 1024] -- the lo parts
-    (2^-11 of the weight) are then normal fp16 numbers instead of subnormals with an absolute quantum of 2^-24; `unscale` = 2^-k
-    per channel goes into the epilogue's per-channel scale (exact: powers of two)."""
+def _pack_conv3d_split(w_oidhw: torch.Tensor, layout: int, fmt: str = "bf16"):
+    """[Cout, Cin, 3, 3, 3] -> (weights of the streaming split kernel in `layout` (CONV_BF16X3 | _C16 | _V32 | _D32) and the split
+    `fmt`, unscale [Cout] | None), or None when the layout does not take these channel counts.  fmt = 'f16': every output channel's
+    weights are pre-scaled by a power of two so that its largest weight lies in (512, 1024] -- the lo parts (2^-11 of the weight)
+    are then normal fp16 numbers instead of subnormals with an absolute quantum of 2^-24; `unscale` = 2^-k per channel goes into
+    the epilogue's per-channel scale (exact: powers of two).  The bf16 split has fp32's range: no scaling, unscale None."""
     lib = _lib.load()
     w = _dev(w_oidhw, "conv weight")
     Cout, Cin = w.shape[:2]
     if tuple(w.shape[2:]) != (3, 3, 3) or Cin % 16 or Cout % 16 or (layout == CONV_BF16X3_C16 and Cout != 16) or \
             (layout == CONV_BF16X3_V32 and Cout % 32) or (layout == CONV_BF16X3_D32 and Cin % 32):
         return None
-    amax = w.abs().amax(dim=(1, 2, 3, 4))
-    k = torch.where(amax > 0, torch.floor(torch.log2(1024.0 / amax.clamp_min(1e-37))), torch.zeros_like(amax)).clamp(-100.0, 100.0)
-    ws = (w * torch.exp2(k).view(-1, 1, 1, 1, 1)).contiguous()
+    unscale = None
+    if fmt == "f16":
+        up, unscale = _pow2_unscale(w.abs().amax(dim=(1, 2, 3, 4)))
+        w = (w * up.view(-1, 1, 1, 1, 1)).contiguous()
     n = {CONV_BF16X3: lambda: lib.mvsgi_conv3d_packed_weight_bytes_bf16x3(Cout, Cin),
          CONV_BF16X3_C16: lambda: lib.mvsgi_conv3d_packed_weight_bytes_bf16x3_c16(Cin),
          CONV_BF16X3_D32: lambda: lib.mvsgi_conv3d_packed_weight_bytes_bf16x3(Cout, Cin),
          CONV_BF16X3_V32: lambda: lib.mvsgi_conv3d_packed_weight_bytes_bf16x3_v32(Cout, Cin)}[layout]()
     wp = torch.empty(n, device=w.device, dtype=torch.uint8)
-    _lib.check(lib.mvsgi_conv3d_pack_weights_split(ws.data_ptr(), wp.data_ptr(), Cout, Cin, layout | CONV_F16, _stream_ptr(w)),
-               "mvsgi_conv3d_pack_weights_split")
-    return wp, torch.exp2(-k).contiguous()
+    _call("mvsgi_conv3d_pack_weights_split", w.data_ptr(), wp.data_ptr(), Cout, Cin, layout | (CONV_F16 if _fmt_code(fmt) else 0),
+          _stream_ptr(w))
+    return wp, (None if unscale is None else unscale.contiguous())
+
+
+# The public packers: (bf16) -> packed weights | None; (fp16) -> (packed weights, unscale [Cout]) | None.  The library's per-layout
+# bf16 entry points (mvsgi_conv3d_pack_weights_bf16x3 / _c16 / _v32) launch the same kernels with the same arguments as
+# mvsgi_conv3d_pack_weights_split (csrc/conv3d.hip); tests/test_gpu_pack_split.py compares the bytes.
+def _pack_bf16(w_oidhw: torch.Tensor, layout: int) -> Optional[torch.Tensor]:
+    p = _pack_conv3d_split(w_oidhw, layout)
+    return None if p is None else p[0]
+
+
+def pack_conv_weights_bf16x3(w_oidhw: torch.Tensor) -> Optional[torch.Tensor]:
+    """[Cout, Cin, 3, 3, 3] -> split-bf16 (hi | lo) MFMA layout, or None when unsupported."""
+    return _pack_bf16(w_oidhw, CONV_BF16X3)
+
+
+def pack_conv_weights_f16x3(w_oidhw: torch.Tensor, layout: int = CONV_BF16X3):
+    """-> (packed weights of the fp16 split in `layout`, unscale [Cout]) or None (_pack_conv3d_split)."""
+    return _pack_conv3d_split(w_oidhw, layout, "f16")
+
+
+def pack_conv_weights_bf16x3_d32(w_oidhw: torch.Tensor) -> Optional[torch.Tensor]:
+    """-> the bf16 split's weights in the 32-channel-slice layout (CONV_BF16X3_D32), or None (Cin % 32, Cout % 16)."""
+    return _pack_bf16(w_oidhw, CONV_BF16X3_D32)
+
+
+def pack_conv_weights_bf16x3_v32(w_oidhw: torch.Tensor) -> Optional[torch.Tensor]:
+    """[Cout % 32 == 0, Cin % 16 == 0, 3, 3, 3] -> 32x32x16-MFMA split-bf16 layout, or None when unsupported."""
+    return _pack_bf16(w_oidhw, CONV_BF16X3_V32)
+
+
+def pack_conv_weights_bf16x3_c16(w_oidhw: torch.Tensor) -> Optional[torch.Tensor]:
+    """[16, Cin, 3, 3, 3] -> plane-schedule split-bf16 layout (impl CONV_BF16X3_C16), or None when unsupported."""
+    return _pack_bf16(w_oidhw, CONV_BF16X3_C16)
 
 
 def conv3d_d32_applies(B, Cin, Din, Hin, Win, Cout, stride=1) -> bool:
@@ -419,55 +390,15 @@ def conv3d_up2_d32_applies(B, Cin, Dl, Hl, Wl, Cout) -> bool:
     return bool(_lib.load().mvsgi_conv3d_up2_d32_applies(B, Cin, Dl, Hl, Wl, Cout))
 
 
-def pack_conv_weights_bf16x3_d32(w_oidhw: torch.Tensor) -> Optional[torch.Tensor]:
-    """[Cout, Cin, 3, 3, 3] -> the bf16 split's weights in the 32-channel-slice layout (CONV_BF16X3_D32), or None (Cin % 32, Cout % 16)."""
-    lib = _lib.load()
-    w = _dev(w_oidhw, "conv weight")
-    Cout, Cin = w.shape[:2]
-    if tuple(w.shape[2:]) != (3, 3, 3) or Cin % 32 or Cout % 16:
-        return None
-    wp = torch.empty(lib.mvsgi_conv3d_packed_weight_bytes_bf16x3(Cout, Cin), device=w.device, dtype=torch.uint8)
-    _lib.check(lib.mvsgi_conv3d_pack_weights_split(w.data_ptr(), wp.data_ptr(), Cout, Cin, CONV_BF16X3_D32, _stream_ptr(w)),
-               "mvsgi_conv3d_pack_weights_split")
-    return wp
-
-
 def conv3d_v32_applies(B, Cin, Din, Hin, Win, Cout, stride=1) -> bool:
     """Whether the 32x32x16-MFMA kernel (impl / w_layout CONV_BF16X3_V32) serves this problem
     (for conv3d_up2 pass the upsampled input size)."""
     return bool(_lib.load().mvsgi_conv3d_v32_applies(B, Cin, Din, Hin, Win, Cout, stride))
 
 
-def pack_conv_weights_bf16x3_v32(w_oidhw: torch.Tensor) -> Optional[torch.Tensor]:
-    """[Cout % 32 == 0, Cin % 16 == 0, 3, 3, 3] -> 32x32x16-MFMA split-bf16 layout, or None when unsupported."""
-    lib = _lib.load()
-    w = _dev(w_oidhw, "conv weight")
-    Cout, Cin = w.shape[:2]
-    if tuple(w.shape[2:]) != (3, 3, 3) or Cin % 16 or Cout % 32:
-        return None
-    wp = torch.empty(lib.mvsgi_conv3d_packed_weight_bytes_bf16x3_v32(Cout, Cin), device=w.device, dtype=torch.uint8)
-    _lib.check(lib.mvsgi_conv3d_pack_weights_bf16x3_v32(w.data_ptr(), wp.data_ptr(), Cout, Cin, _stream_ptr(w)),
-               "mvsgi_conv3d_pack_weights_bf16x3_v32")
-    return wp
-
-
-def pack_conv_weights_bf16x3_c16(w_oidhw: torch.Tensor) -> Optional[torch.Tensor]:
-    """[16, Cin, 3, 3, 3] -> plane-schedule split-bf16 layout (impl CONV_BF16X3_C16), or None when unsupported."""
-    lib = _lib.load()
-    w = _dev(w_oidhw, "conv weight")
-    Cout, Cin = w.shape[:2]
-    if tuple(w.shape[2:]) != (3, 3, 3) or Cin % 16 or Cout != 16:
-        return None
-    wp = torch.empty(lib.mvsgi_conv3d_packed_weight_bytes_bf16x3_c16(Cin), device=w.device, dtype=torch.uint8)
-    _lib.check(lib.mvsgi_conv3d_pack_weights_bf16x3_c16(w.data_ptr(), wp.data_ptr(), Cin, _stream_ptr(w)),
-               "mvsgi_conv3d_pack_weights_bf16x3_c16")
-    return wp
-
-
 def conv3d(x, w_oidhw, w_packed, scale, shift, res=None, stride=1, neg_slope=0.01, impl=CONV_AUTO, out=None):
     """x [B, D, H, W, Cin] -> y [B, Do, Ho, Wo, Cout] = act(conv(x) * scale + shift (+ res));
     act(v) = v if v > 0 else v * neg_slope (1.0 = no activation)."""
-    lib = _lib.load()
     x = _dev(x, "x")
     B, Din, Hin, Win, Cin = x.shape
     Cout = scale.numel()
@@ -477,16 +408,14 @@ def conv3d(x, w_oidhw, w_packed, scale, shift, res=None, stride=1, neg_slope=0.0
         if tuple(res.shape) != (B, Do, Ho, Wo, Cout):
             raise AssertionError(f"residual {tuple(res.shape)} does not match output {(B, Do, Ho, Wo, Cout)}")
     y = out if out is not None else torch.empty((B, Do, Ho, Wo, Cout), device=x.device, dtype=torch.float32)
-    _lib.check(lib.mvsgi_conv3d_f32(x.data_ptr(), _ptr(w_oidhw), _ptr(w_packed), scale.data_ptr(), shift.data_ptr(),
-                                    _ptr(res), y.data_ptr(), B, Cin, Din, Hin, Win, Cout, stride, float(neg_slope),
-                                    impl, _stream_ptr(x)), "mvsgi_conv3d_f32")
+    _call("mvsgi_conv3d_f32", x.data_ptr(), _ptr(w_oidhw), _ptr(w_packed), scale.data_ptr(), shift.data_ptr(), _ptr(res), y.data_ptr(), B, Cin, Din,
+          Hin, Win, Cout, stride, float(neg_slope), impl, _stream_ptr(x))
     return y
 
 
 def conv3d_up2(x, w_packed_b3, scale, shift, res=None, neg_slope=0.01, out=None, w_layout=CONV_BF16X3):
     """Fused trilinear x2 upsample + conv3d (split-bf16): x [B, Dl, Hl, Wl, Cin] -> y [B, 2Dl, 2Hl, 2Wl, Cout].
     w_layout: CONV_BF16X3 (pack_conv_weights_bf16x3) or CONV_BF16X3_C16 (pack_conv_weights_bf16x3_c16, Cout == 16)."""
-    lib = _lib.load()
     x = _dev(x, "x")
     B, Dl, Hl, Wl, Cin = x.shape
     Cout = scale.numel()
@@ -496,15 +425,13 @@ def conv3d_up2(x, w_packed_b3, scale, shift, res=None, neg_slope=0.01, out=None,
         if tuple(res.shape) != shp:
             raise AssertionError(f"residual {tuple(res.shape)} does not match output {shp}")
     y = out if out is not None else torch.empty(shp, device=x.device, dtype=torch.float32)
-    _lib.check(lib.mvsgi_conv3d_up2_f32(x.data_ptr(), _ptr(w_packed_b3), w_layout, scale.data_ptr(), shift.data_ptr(), _ptr(res),
-                                        y.data_ptr(), B, Cin, Dl, Hl, Wl, Cout, float(neg_slope), _stream_ptr(x)),
-               "mvsgi_conv3d_up2_f32")
+    _call("mvsgi_conv3d_up2_f32", x.data_ptr(), _ptr(w_packed_b3), w_layout, scale.data_ptr(), shift.data_ptr(), _ptr(res), y.data_ptr(), B, Cin, Dl,
+          Hl, Wl, Cout, float(neg_slope), _stream_ptr(x))
     return y
 
 
 def conv3d_up2_out_split(x, w_packed_b3, scale, shift, out: "SplitAct", res=None, neg_slope=0.01, w_layout=CONV_BF16X3) -> "SplitAct":
     """conv3d_up2 with the result written split-padded into `out` (B, 2Dl, 2Hl, 2Wl, Cout)."""
-    lib = _lib.load()
     x = _dev(x, "x")
     B, Dl, Hl, Wl, Cin = x.shape
     Cout = scale.numel()
@@ -514,9 +441,8 @@ def conv3d_up2_out_split(x, w_packed_b3, scale, shift, out: "SplitAct", res=None
         res = _dev(res, "res")
         if tuple(res.shape) != out.shape:
             raise AssertionError(f"residual {tuple(res.shape)} does not match output {out.shape}")
-    _lib.check(lib.mvsgi_conv3d_up2_f32_out_split(x.data_ptr(), _ptr(w_packed_b3), w_layout, scale.data_ptr(), shift.data_ptr(), _ptr(res),
-                                                  out.buf.data_ptr(), B, Cin, Dl, Hl, Wl, Cout, float(neg_slope), _stream_ptr(x)),
-               "mvsgi_conv3d_up2_f32_out_split")
+    _call("mvsgi_conv3d_up2_f32_out_split", x.data_ptr(), _ptr(w_packed_b3), w_layout, scale.data_ptr(), shift.data_ptr(), _ptr(res),
+          out.buf.data_ptr(), B, Cin, Dl, Hl, Wl, Cout, float(neg_slope), _stream_ptr(x))
     out.fmt = "f16" if w_layout & CONV_F16 else "bf16"
     return out
 
@@ -544,7 +470,7 @@ def conv3d_up2_poly_plan(w_oidhw: torch.Tensor, D: int, H: int, W: int, fmt: str
         wh = (wh * up.view(-1, 1, 1, 1, 1)).contiguous()
         unscale = un.to(w_oidhw.device)
     plan = torch.empty(n, dtype=torch.uint8)
-    _lib.check(lib.mvsgi_conv3d_up2_poly_plan_fmt(wh.data_ptr(), plan.data_ptr(), D, H, W, _fmt_code(fmt)), "mvsgi_conv3d_up2_poly_plan")
+    _call("mvsgi_conv3d_up2_poly_plan_fmt", wh.data_ptr(), plan.data_ptr(), D, H, W, _fmt_code(fmt))
     plan = plan.to(w_oidhw.device)
     return (plan, unscale) if fmt == "f16" else plan
 
@@ -552,16 +478,14 @@ def conv3d_up2_poly_plan(w_oidhw: torch.Tensor, D: int, H: int, W: int, fmt: str
 def conv3d_up2_poly(x: "SplitAct", plan: torch.Tensor, scale, shift, neg_slope=0.01, out=None) -> torch.Tensor:
     """act(conv(trilinear_x2(x)) * scale + shift) for Cin = 32, Cout = 16 in polyphase form: x split-padded (low resolution)
     -> fp32 [B, 2D, 2H, 2W, 16]."""
-    lib = _lib.load()
     if x.C != 32 or scale.numel() != 16:
         raise AssertionError("conv3d_up2_poly is the 32 -> 16 kernel")
     shp = (x.B, 2 * x.D, 2 * x.H, 2 * x.W, 16)
     y = out if out is not None else torch.empty(shp, device=x.buf.device, dtype=torch.float32)
     if tuple(y.shape) != shp or not y.is_contiguous():
         raise AssertionError(f"output {tuple(y.shape)} does not match {shp}")
-    _lib.check(lib.mvsgi_conv3d_up2_poly_fmt(x.buf.data_ptr(), plan.data_ptr(), scale.data_ptr(), shift.data_ptr(), y.data_ptr(), 0,
-                                             x.B, x.D, x.H, x.W, float(neg_slope), _fmt_code(x.fmt), _stream_ptr(x.buf)),
-               "mvsgi_conv3d_up2_poly_f32")
+    _call("mvsgi_conv3d_up2_poly_fmt", x.buf.data_ptr(), plan.data_ptr(), scale.data_ptr(), shift.data_ptr(), y.data_ptr(), 0, x.B, x.D, x.H, x.W,
+          float(neg_slope), _fmt_code(x.fmt), _stream_ptr(x.buf))
     return y
 
 
@@ -579,13 +503,10 @@ def conv3d_up2_poly_split(x: "SplitAct", plan: torch.Tensor, scale, shift, out: 
     """conv3d_up2_poly with the result written split-padded into `out` (B, 2D, 2H, 2W, 16).  In the fp16 split the library picks
     the main kernel: the Winograd form where conv3d_up2_poly_wino_pays(), else the direct kernel; `direct` (or MVSGI_POLY_WINO=0)
     keeps the direct kernel, `wino` forces the Winograd form (an error where it does not apply)."""
-    lib = _lib.load()
     if x.C != 32 or scale.numel() != 16 or out.shape != (x.B, 2 * x.D, 2 * x.H, 2 * x.W, 16):
         raise AssertionError(f"conv3d_up2_poly_split: input {x.shape}, output {out.shape}")
-    _lib.check(lib.mvsgi_conv3d_up2_poly_fmt(x.buf.data_ptr(), plan.data_ptr(), scale.data_ptr(), shift.data_ptr(), out.buf.data_ptr(),
-                                             5 if wino else (3 if (direct or not POLY_WINO) else 1),
-                                             x.B, x.D, x.H, x.W, float(neg_slope), _fmt_code(x.fmt), _stream_ptr(x.buf)),
-               "mvsgi_conv3d_up2_poly_split")
+    _call("mvsgi_conv3d_up2_poly_fmt", x.buf.data_ptr(), plan.data_ptr(), scale.data_ptr(), shift.data_ptr(), out.buf.data_ptr(),
+          5 if wino else (3 if (direct or not POLY_WINO) else 1), x.B, x.D, x.H, x.W, float(neg_slope), _fmt_code(x.fmt), _stream_ptr(x.buf))
     out.fmt = x.fmt
     return out
 
@@ -597,8 +518,7 @@ def pack_head_split_weights(w_oidhw: torch.Tensor) -> Optional[torch.Tensor]:
     if w.shape[0] != 1 or tuple(w.shape[2:]) != (3, 3, 3) or w.shape[1] % 16:
         return None
     wp = torch.empty(lib.mvsgi_conv3d_head_split_packed_weight_bytes(int(w.shape[1])), device=w.device, dtype=torch.uint8)
-    _lib.check(lib.mvsgi_conv3d_head_split_pack_weights(w.data_ptr(), wp.data_ptr(), int(w.shape[1]), _stream_ptr(w)),
-               "mvsgi_conv3d_head_split_pack_weights")
+    _call("mvsgi_conv3d_head_split_pack_weights", w.data_ptr(), wp.data_ptr(), int(w.shape[1]), _stream_ptr(w))
     return wp
 
 
@@ -609,27 +529,26 @@ def pack_head_split_weights_f16(w_oidhw: torch.Tensor):
     w = _dev(w_oidhw, "conv weight")
     if w.shape[0] != 1 or tuple(w.shape[2:]) != (3, 3, 3) or w.shape[1] % 16:
         return None
+    # NOT _pow2_unscale: here 1024 / amax is a double quotient rounded to fp32 afterwards (two roundings, no clamps), there one fp32
+    # division of a clamped amax -- not shown to floor to the same k for every amax (either k is exact, but the output bits differ)
     amax = float(w.abs().max())
     k = 0.0 if amax == 0.0 else float(torch.floor(torch.log2(torch.tensor(1024.0 / amax))))
     ws = (w * (2.0 ** k)).contiguous()
     wp = torch.empty(lib.mvsgi_conv3d_head_split_packed_weight_bytes(int(w.shape[1])), device=w.device, dtype=torch.uint8)
-    _lib.check(lib.mvsgi_conv3d_head_split_pack_weights_f16(ws.data_ptr(), wp.data_ptr(), int(w.shape[1]), _stream_ptr(w)),
-               "mvsgi_conv3d_head_split_pack_weights_f16")
+    _call("mvsgi_conv3d_head_split_pack_weights_f16", ws.data_ptr(), wp.data_ptr(), int(w.shape[1]), _stream_ptr(w))
     return wp, 2.0 ** -k
 
 
 def conv3d_head_split(x: "SplitAct", w_packed, scale: float, shift: float, neg_slope=1.0, out=None, f16: bool = False) -> torch.Tensor:
     """Cost head (Cout = 1) on a split-padded input -> fp32 [B, D, H, W, 1] = act(conv(x) * scale + shift).  f16: input and weights
     in the fp16 split."""
-    lib = _lib.load()
     if x.fmt != ("f16" if f16 else "bf16"):
         raise AssertionError(f"conv3d_head_split(f16={f16}) on a split-padded buffer holding {x.fmt} pieces")
     y = out if out is not None else torch.empty((x.B, x.D, x.H, x.W, 1), device=x.buf.device, dtype=torch.float32)
     if tuple(y.shape) != (x.B, x.D, x.H, x.W, 1) or not y.is_contiguous():
         raise AssertionError(f"head output {tuple(y.shape)} does not match {(x.B, x.D, x.H, x.W, 1)}")
-    fn = lib.mvsgi_conv3d_head_split_f16 if f16 else lib.mvsgi_conv3d_head_split
-    _lib.check(fn(x.buf.data_ptr(), w_packed.data_ptr(), float(scale), float(shift), y.data_ptr(), x.B, x.C,
-                  x.D, x.H, x.W, float(neg_slope), _stream_ptr(x.buf)), "mvsgi_conv3d_head_split")
+    _call("mvsgi_conv3d_head_split_f16" if f16 else "mvsgi_conv3d_head_split", x.buf.data_ptr(), w_packed.data_ptr(), float(scale),
+          float(shift), y.data_ptr(), x.B, x.C, x.D, x.H, x.W, float(neg_slope), _stream_ptr(x.buf))
     return y
 
 
@@ -675,23 +594,19 @@ class SplitAct:
 
 
 def act_to_split(x_ndhwc: torch.Tensor, out: Optional[SplitAct] = None, fmt: str = "bf16") -> SplitAct:
-    lib = _lib.load()
     x = _dev(x_ndhwc, "x")
     B, D, Hh, W, C = x.shape
     y = out if out is not None else SplitAct(B, D, Hh, W, C, x.device)
     if y.shape != (B, D, Hh, W, C):
         raise AssertionError(f"split buffer {y.shape} does not match {tuple(x.shape)}")
-    _lib.check(lib.mvsgi_act_f32_to_split_fmt(x.data_ptr(), y.buf.data_ptr(), B, C, D, Hh, W, _fmt_code(fmt), _stream_ptr(x)),
-               "mvsgi_act_f32_to_split")
+    _call("mvsgi_act_f32_to_split_fmt", x.data_ptr(), y.buf.data_ptr(), B, C, D, Hh, W, _fmt_code(fmt), _stream_ptr(x))
     y.fmt = fmt
     return y
 
 
 def act_from_split(x: SplitAct, out: Optional[torch.Tensor] = None) -> torch.Tensor:
-    lib = _lib.load()
     y = out if out is not None else torch.empty(x.shape, device=x.buf.device, dtype=torch.float32)
-    _lib.check(lib.mvsgi_act_split_to_f32_fmt(x.buf.data_ptr(), y.data_ptr(), x.B, x.C, x.D, x.H, x.W, _fmt_code(x.fmt), _stream_ptr(x.buf)),
-               "mvsgi_act_split_to_f32")
+    _call("mvsgi_act_split_to_f32_fmt", x.buf.data_ptr(), y.data_ptr(), x.B, x.C, x.D, x.H, x.W, _fmt_code(x.fmt), _stream_ptr(x.buf))
     return y
 
 
@@ -710,8 +625,7 @@ def pack_conv_weights_rs(w_oidhw: torch.Tensor, fmt: str = "bf16"):
     if not nbytes:
         return None
     wp = torch.empty(nbytes, device=w.device, dtype=torch.uint8)
-    _lib.check(lib.mvsgi_conv3d_rs_pack_weights_fmt(w.data_ptr(), wp.data_ptr(), Cout, Cin, _fmt_code(fmt), _stream_ptr(w)),
-               "mvsgi_conv3d_rs_pack_weights")
+    _call("mvsgi_conv3d_rs_pack_weights_fmt", w.data_ptr(), wp.data_ptr(), Cout, Cin, _fmt_code(fmt), _stream_ptr(w))
     return (wp, unscale.contiguous()) if fmt == "f16" else wp
 
 
@@ -719,7 +633,6 @@ def conv3d_rs(x: SplitAct, w_packed_rs, scale, shift, res: Optional[SplitAct] = 
               out=None, out_f32: bool = False):
     """Register-stationary split-bf16 conv (Cin = Cout = 32, stride 1) on split-padded activations.  `out_f32`: the
     result is a plain fp32 [B, D, H, W, 32] tensor instead of a SplitAct (hand-over to an fp32-reading kernel)."""
-    lib = _lib.load()
     Cout = scale.numel()
     if out_f32:
         y = out if out is not None else torch.empty((x.B, x.D, x.H, x.W, Cout), device=x.buf.device, dtype=torch.float32)
@@ -733,9 +646,9 @@ def conv3d_rs(x: SplitAct, w_packed_rs, scale, shift, res: Optional[SplitAct] = 
             raise AssertionError(f"split output {y.shape} does not match {(x.B, x.D, x.H, x.W, Cout)}")
     if res is not None and (res.shape != (x.B, x.D, x.H, x.W, Cout) or res.fmt != x.fmt):
         raise AssertionError(f"residual {res.shape} ({res.fmt}) does not match the output ({x.fmt})")
-    _lib.check(lib.mvsgi_conv3d_rs_split_fmt(x.buf.data_ptr(), w_packed_rs.data_ptr(), scale.data_ptr(), shift.data_ptr(),
-                                             None if res is None else res.buf.data_ptr(), yp, int(out_f32), x.B, x.C, x.D, x.H,
-                                             x.W, Cout, float(neg_slope), _fmt_code(x.fmt), _stream_ptr(x.buf)), "mvsgi_conv3d_rs_split")
+    _call("mvsgi_conv3d_rs_split_fmt", x.buf.data_ptr(), w_packed_rs.data_ptr(), scale.data_ptr(), shift.data_ptr(),
+          None if res is None else res.buf.data_ptr(), yp, int(out_f32), x.B, x.C, x.D, x.H, x.W, Cout, float(neg_slope), _fmt_code(x.fmt),
+          _stream_ptr(x.buf))
     if not out_f32:
         y.fmt = x.fmt
     return y
@@ -756,8 +669,7 @@ def pack_conv_weights_wino(w_oidhw: torch.Tensor):
         return None
     wp = torch.empty(lib.mvsgi_conv3d_wino32_packed_weight_bytes(), device=w.device, dtype=torch.uint8)
     unscale = torch.empty(32, device=w.device, dtype=torch.float32)
-    _lib.check(lib.mvsgi_conv3d_wino32_pack_weights(w.data_ptr(), wp.data_ptr(), unscale.data_ptr(), _stream_ptr(w)),
-               "mvsgi_conv3d_wino32_pack_weights")
+    _call("mvsgi_conv3d_wino32_pack_weights", w.data_ptr(), wp.data_ptr(), unscale.data_ptr(), _stream_ptr(w))
     return wp, unscale
 
 
@@ -803,9 +715,9 @@ def conv3d_wino(x: SplitAct, w_packed, scale, shift, res: Optional[SplitAct] = N
         raise AssertionError(f"residual {res.shape} ({res.fmt}) does not match the input ({x.fmt})")
     if w_packed.numel() != lib.mvsgi_conv3d_wino32_packed_weight_bytes():
         raise AssertionError("conv3d_wino: packed weights of the wrong size")
-    _lib.check(lib.mvsgi_conv3d_wino32_f16(x.buf.data_ptr(), w_packed.data_ptr(), scale.data_ptr(), shift.data_ptr(),
-                                           None if res is None else res.buf.data_ptr(), yp, int(out_f32), int(x.fmt == "f32p"),
-                                           x.B, x.D, x.H, x.W, float(neg_slope), _stream_ptr(x.buf)), "mvsgi_conv3d_wino32_f16")
+    _call("mvsgi_conv3d_wino32_f16", x.buf.data_ptr(), w_packed.data_ptr(), scale.data_ptr(), shift.data_ptr(),
+          None if res is None else res.buf.data_ptr(), yp, int(out_f32), int(x.fmt == "f32p"), x.B, x.D, x.H, x.W, float(neg_slope),
+          _stream_ptr(x.buf))
     if not out_f32:
         y.fmt = x.fmt
     return y
@@ -814,7 +726,6 @@ def conv3d_wino(x: SplitAct, w_packed, scale, shift, res: Optional[SplitAct] = N
 def conv3d_out_split(x, w_packed_b3, scale, shift, out: "SplitAct", res=None, stride=1, neg_slope=0.01, fmt: str = "bf16") -> "SplitAct":
     """mvsgi_conv3d_f32 (streaming split kernel) with the output written split-padded into `out`; fmt = 'f16': weights packed by
     pack_conv_weights_f16x3 (scale carrying the unscale) and the output in the fp16 split."""
-    lib = _lib.load()
     x = _dev(x, "x")
     B, Din, Hin, Win, Cin = x.shape
     Cout = scale.numel()
@@ -823,9 +734,8 @@ def conv3d_out_split(x, w_packed_b3, scale, shift, out: "SplitAct", res=None, st
         raise AssertionError(f"split output {out.shape} does not match {(B, Do, Ho, Wo, Cout)}")
     if res is not None:
         res = _dev(res, "res")
-    _lib.check(lib.mvsgi_conv3d_f32_out_split_fmt(x.data_ptr(), w_packed_b3.data_ptr(), scale.data_ptr(), shift.data_ptr(), _ptr(res),
-                                                  out.buf.data_ptr(), B, Cin, Din, Hin, Win, Cout, stride, float(neg_slope),
-                                                  _fmt_code(fmt), _stream_ptr(x)), "mvsgi_conv3d_f32_out_split")
+    _call("mvsgi_conv3d_f32_out_split_fmt", x.data_ptr(), w_packed_b3.data_ptr(), scale.data_ptr(), shift.data_ptr(), _ptr(res), out.buf.data_ptr(),
+          B, Cin, Din, Hin, Win, Cout, stride, float(neg_slope), _fmt_code(fmt), _stream_ptr(x))
     out.fmt = fmt
     return out
 
@@ -833,21 +743,18 @@ def conv3d_out_split(x, w_packed_b3, scale, shift, out: "SplitAct", res=None, st
 def conv3d_rs16(x: "SplitAct", w_packed_rs, scale, shift, neg_slope=0.01, out=None, out_split: Optional["SplitAct"] = None):
     """Register-stationary 16 -> 16 conv (post_vol) on a split-padded volume -> fp32 [B, D, H, W, 16], or (out_split) a
     split-padded volume of the same geometry (the hand-over to conv3d_s2rs)."""
-    lib = _lib.load()
     if x.C != 16 or scale.numel() != 16:
         raise AssertionError("conv3d_rs16 is the 16 -> 16 kernel")
     if out_split is not None:
         if out_split.shape != x.shape or out_split.buf.data_ptr() == x.buf.data_ptr():
             raise AssertionError(f"split output {out_split.shape} must match the input {x.shape} and be another buffer")
-        _lib.check(lib.mvsgi_conv3d_rs16_split_fmt(x.buf.data_ptr(), w_packed_rs.data_ptr(), scale.data_ptr(), shift.data_ptr(),
-                                                   out_split.buf.data_ptr(), 1, x.B, x.D, x.H, x.W, float(neg_slope), _fmt_code(x.fmt),
-                                                   _stream_ptr(x.buf)), "mvsgi_conv3d_rs16_split_out_split")
+        _call("mvsgi_conv3d_rs16_split_fmt", x.buf.data_ptr(), w_packed_rs.data_ptr(), scale.data_ptr(), shift.data_ptr(), out_split.buf.data_ptr(),
+              1, x.B, x.D, x.H, x.W, float(neg_slope), _fmt_code(x.fmt), _stream_ptr(x.buf))
         out_split.fmt = x.fmt
         return out_split
     y = out if out is not None else torch.empty((x.B, x.D, x.H, x.W, 16), device=x.buf.device, dtype=torch.float32)
-    _lib.check(lib.mvsgi_conv3d_rs16_split_fmt(x.buf.data_ptr(), w_packed_rs.data_ptr(), scale.data_ptr(), shift.data_ptr(), y.data_ptr(), 0,
-                                               x.B, x.D, x.H, x.W, float(neg_slope), _fmt_code(x.fmt), _stream_ptr(x.buf)),
-               "mvsgi_conv3d_rs16_split")
+    _call("mvsgi_conv3d_rs16_split_fmt", x.buf.data_ptr(), w_packed_rs.data_ptr(), scale.data_ptr(), shift.data_ptr(), y.data_ptr(), 0, x.B, x.D,
+          x.H, x.W, float(neg_slope), _fmt_code(x.fmt), _stream_ptr(x.buf))
     return y
 
 
@@ -871,21 +778,18 @@ def pack_conv_weights_s2rs(w_oidhw: torch.Tensor, scale: torch.Tensor, fmt: str 
         up, un = float(up_t[0]), float(un_t[0])
         scale = (scale * up).contiguous()
     wp = torch.empty(lib.mvsgi_conv3d_s2rs_packed_weight_bytes(), device=w.device, dtype=torch.uint8)
-    _lib.check(lib.mvsgi_conv3d_s2rs_pack_weights_fmt(w.data_ptr(), scale.data_ptr(), wp.data_ptr(), _fmt_code(fmt), _stream_ptr(w)),
-               "mvsgi_conv3d_s2rs_pack_weights")
+    _call("mvsgi_conv3d_s2rs_pack_weights_fmt", w.data_ptr(), scale.data_ptr(), wp.data_ptr(), _fmt_code(fmt), _stream_ptr(w))
     return (wp, up, un) if fmt == "f16" else wp
 
 
 def conv3d_s2rs(x: "SplitAct", w_packed, shift, out: "SplitAct", neg_slope=0.01, unscale: float = 1.0, out_f32p: bool = False) -> "SplitAct":
     """16 -> 32 channel 3x3x3 stride-2 conv + scale / shift + LeakyReLU, split-padded in and out (LDS-DMA staging).
     `out_f32p` (fp16 split): the output is fp32-padded (plain fp32 records, fmt 'f32p') for a Winograd-form level 0 behind it."""
-    lib = _lib.load()
     Do, Ho, Wo = (x.D - 1) // 2 + 1, (x.H - 1) // 2 + 1, (x.W - 1) // 2 + 1
     if x.C != 16 or out.shape != (x.B, Do, Ho, Wo, 32) or shift.numel() != 32:
         raise AssertionError(f"conv3d_s2rs: input {x.shape} -> output {out.shape}, expected {(x.B, Do, Ho, Wo, 32)}")
-    _lib.check(lib.mvsgi_conv3d_s2rs_out_fmt(x.buf.data_ptr(), w_packed.data_ptr(), shift.data_ptr(), out.buf.data_ptr(), x.B, x.D, x.H, x.W,
-                                             float(neg_slope), float(unscale), _fmt_code(x.fmt), int(out_f32p), _stream_ptr(x.buf)),
-               "mvsgi_conv3d_s2rs")
+    _call("mvsgi_conv3d_s2rs_out_fmt", x.buf.data_ptr(), w_packed.data_ptr(), shift.data_ptr(), out.buf.data_ptr(), x.B, x.D, x.H, x.W,
+          float(neg_slope), float(unscale), _fmt_code(x.fmt), int(out_f32p), _stream_ptr(x.buf))
     out.fmt = "f32p" if out_f32p else x.fmt
     return out
 
@@ -902,8 +806,7 @@ def pack_conv2d_weights_bf16x3(w_oihw: torch.Tensor) -> Optional[torch.Tensor]:
     if tuple(w.shape[2:]) != (3, 3) or Cin % 16 or Cout % 16:
         return None
     wp = torch.empty(lib.mvsgi_conv2d_packed_weight_bytes_bf16x3(Cout, Cin), device=w.device, dtype=torch.uint8)
-    _lib.check(lib.mvsgi_conv2d_pack_weights_bf16x3(w.data_ptr(), wp.data_ptr(), Cout, Cin, _stream_ptr(w)),
-               "mvsgi_conv2d_pack_weights_bf16x3")
+    _call("mvsgi_conv2d_pack_weights_bf16x3", w.data_ptr(), wp.data_ptr(), Cout, Cin, _stream_ptr(w))
     return wp
 
 
@@ -914,7 +817,7 @@ def pack_conv2d_stem_weights(w_oihw: torch.Tensor) -> Optional[torch.Tensor]:
     if tuple(w.shape) != (16, 3, 5, 5):
         return None
     wp = torch.empty(lib.mvsgi_conv2d_stem_packed_weight_bytes(), device=w.device, dtype=torch.uint8)
-    _lib.check(lib.mvsgi_conv2d_stem_pack_weights(w.data_ptr(), wp.data_ptr(), _stream_ptr(w)), "mvsgi_conv2d_stem_pack_weights")
+    _call("mvsgi_conv2d_stem_pack_weights", w.data_ptr(), wp.data_ptr(), _stream_ptr(w))
     return wp
 
 
@@ -926,15 +829,13 @@ def pack_conv2d_weights_f32(w_oihw: torch.Tensor) -> Optional[torch.Tensor]:
     if tuple(w.shape[2:]) != (3, 3) or Cin % 16 or Cout not in (16, 32):
         return None
     wp = torch.empty(lib.mvsgi_conv2d_packed_weight_floats(Cout, Cin), device=w.device, dtype=torch.float32)
-    _lib.check(lib.mvsgi_conv2d_pack_weights_f32(w.data_ptr(), wp.data_ptr(), Cout, Cin, _stream_ptr(w)),
-               "mvsgi_conv2d_pack_weights_f32")
+    _call("mvsgi_conv2d_pack_weights_f32", w.data_ptr(), wp.data_ptr(), Cout, Cin, _stream_ptr(w))
     return wp
 
 
 def conv2d(x, w_oihw, w_packed, scale, shift, res=None, stride=1, neg_slope=0.01, impl=CONV_AUTO, in_nchw=False, out_split=None):
     """x [B, H, W, Cin] (or [B, Cin, H, W] with in_nchw) -> y [B, Ho, Wo, Cout] = act(conv(x)*scale + shift (+res)).
     out_split: a zero-bordered 2-D split-padded buffer (split2d_buffer) that receives the output instead (Cout == 16)."""
-    lib = _lib.load()
     layout = int(bool(in_nchw))
     if x.dtype == torch.uint8:                 # camera images [B, H, W, 3]: converted (/255) inside the stem kernel
         x = _dev(x, "imgs", torch.uint8)
@@ -955,14 +856,12 @@ def conv2d(x, w_oihw, w_packed, scale, shift, res=None, stride=1, neg_slope=0.01
             raise AssertionError(f"residual {tuple(res.shape)} does not match output {(B, Ho, Wo, Cout)}")
     if out_split is not None:
         _check_split2d(out_split, B, Ho, Wo, x.device)
-        _lib.check(lib.mvsgi_conv2d_f32_out_split2d(x.data_ptr(), _ptr(w_oihw), _ptr(w_packed), scale.data_ptr(), shift.data_ptr(),
-                                                    _ptr(res), out_split.data_ptr(), B, Cin, Hin, Win, Cout, k, stride,
-                                                    float(neg_slope), impl, layout, _stream_ptr(x)), "mvsgi_conv2d_f32_out_split2d")
+        _call("mvsgi_conv2d_f32_out_split2d", x.data_ptr(), _ptr(w_oihw), _ptr(w_packed), scale.data_ptr(), shift.data_ptr(), _ptr(res),
+              out_split.data_ptr(), B, Cin, Hin, Win, Cout, k, stride, float(neg_slope), impl, layout, _stream_ptr(x))
         return out_split
     y = torch.empty((B, Ho, Wo, Cout), device=x.device, dtype=torch.float32)
-    _lib.check(lib.mvsgi_conv2d_f32(x.data_ptr(), _ptr(w_oihw), _ptr(w_packed), scale.data_ptr(), shift.data_ptr(),
-                                    _ptr(res), y.data_ptr(), B, Cin, Hin, Win, Cout, k, stride, float(neg_slope), impl,
-                                    layout, _stream_ptr(x)), "mvsgi_conv2d_f32")
+    _call("mvsgi_conv2d_f32", x.data_ptr(), _ptr(w_oihw), _ptr(w_packed), scale.data_ptr(), shift.data_ptr(), _ptr(res), y.data_ptr(), B, Cin, Hin,
+          Win, Cout, k, stride, float(neg_slope), impl, layout, _stream_ptr(x))
     return y
 
 
@@ -975,13 +874,11 @@ def conv2d_variant(Cin, Cout, k=3, stride=1, impl=CONV_AUTO, in_nchw=False) -> s
 
 
 def resize_trilinear(x, size) -> torch.Tensor:
-    lib = _lib.load()
     x = _dev(x, "x")
     B, Di, Hi, Wi, C = x.shape
     Do, Ho, Wo = (int(s) for s in size)
     y = torch.empty((B, Do, Ho, Wo, C), device=x.device, dtype=torch.float32)
-    _lib.check(lib.mvsgi_resize_trilinear_f32(x.data_ptr(), y.data_ptr(), B, C, Di, Hi, Wi, Do, Ho, Wo,
-                                              _stream_ptr(x)), "mvsgi_resize_trilinear_f32")
+    _call("mvsgi_resize_trilinear_f32", x.data_ptr(), y.data_ptr(), B, C, Di, Hi, Wi, Do, Ho, Wo, _stream_ptr(x))
     return y
 
 
@@ -1013,8 +910,8 @@ def instance_norm(x, res=None, gamma=None, beta=None, eps: float = 1e-5, neg_slo
             raise AssertionError(f"out {tuple(out.shape)} does not match {tuple(x.shape)}")
     nbytes = lib.mvsgi_instance_norm_ws_bytes(B, S, C)
     ws = torch.empty(max(int(nbytes), 16), device=x.device, dtype=torch.uint8)
-    _lib.check(lib.mvsgi_instance_norm_f32(x.data_ptr(), _ptr(res), _ptr(gamma), _ptr(beta), out.data_ptr(), ws.data_ptr(),
-                                           B, S, C, float(eps), float(neg_slope), _stream_ptr(x)), "mvsgi_instance_norm_f32")
+    _call("mvsgi_instance_norm_f32", x.data_ptr(), _ptr(res), _ptr(gamma), _ptr(beta), out.data_ptr(), ws.data_ptr(), B, S, C, float(eps),
+          float(neg_slope), _stream_ptr(x))
     return out
 
 
@@ -1026,7 +923,6 @@ def softargmin(costs_bdhw, inv_idx, scale: float, want_norm_costs: bool, post_di
     [B, D, OH, OW] | None, with OH = floor(H * scale), OW = floor(W * scale) as F.interpolate(scale_factor=scale) sizes them.
     scale 1 | 2: the fused x1 / x2 launches; integer factors >= 3: the row-band kernel; any other factor > 0: the
     thread-per-pixel kernel.  variant: SA_PIXEL | SA_BAND force one of the latter two (tests, A/B timing)."""
-    lib = _lib.load()
     c = _dev(costs_bdhw, "costs")
     inv_idx = _dev(inv_idx.reshape(-1), "inv_dist_idx")
     B, D, H, W = c.shape
@@ -1041,33 +937,28 @@ def softargmin(costs_bdhw, inv_idx, scale: float, want_norm_costs: bool, post_di
     inv = torch.empty((B, 1, OH, OW), device=c.device, dtype=torch.float32)
     pr = torch.empty((B, D, OH, OW), device=c.device, dtype=torch.float32) if want_norm_costs else None
     if variant == SA_AUTO and scale in (1.0, 2.0):
-        _lib.check(lib.mvsgi_softargmin_div_f32(c.data_ptr(), inv_idx.data_ptr(), inv.data_ptr(), _ptr(pr), B, D, H, W,
-                                                int(scale), float(post_div), _stream_ptr(c)), "mvsgi_softargmin_div_f32")
+        _call("mvsgi_softargmin_div_f32", c.data_ptr(), inv_idx.data_ptr(), inv.data_ptr(), _ptr(pr), B, D, H, W, int(scale), float(post_div),
+              _stream_ptr(c))
     else:
-        _lib.check(lib.mvsgi_softargmin_scaled_f32(c.data_ptr(), inv_idx.data_ptr(), inv.data_ptr(), _ptr(pr), B, D, H, W,
-                                                   scale, OH, OW, float(post_div), int(variant), _stream_ptr(c)),
-                   "mvsgi_softargmin_scaled_f32")
+        _call("mvsgi_softargmin_scaled_f32", c.data_ptr(), inv_idx.data_ptr(), inv.data_ptr(), _ptr(pr), B, D, H, W, scale, OH, OW, float(post_div),
+              int(variant), _stream_ptr(c))
     return inv, pr
 
 
 def ncdhw_to_ndhwc(x) -> torch.Tensor:
     """contiguous [B, C, D, H, W] -> [B, D, H, W, C]."""
-    lib = _lib.load()
     x = _dev(x, "x")
     B, C, D, H, W = x.shape
     y = torch.empty((B, D, H, W, C), device=x.device, dtype=torch.float32)
-    _lib.check(lib.mvsgi_ncv_to_nvc_f32(x.data_ptr(), y.data_ptr(), B, C, D * H * W, _stream_ptr(x)),
-               "mvsgi_ncv_to_nvc_f32")
+    _call("mvsgi_ncv_to_nvc_f32", x.data_ptr(), y.data_ptr(), B, C, D * H * W, _stream_ptr(x))
     return y
 
 
 def ndhwc_to_ncdhw(x) -> torch.Tensor:
-    lib = _lib.load()
     x = _dev(x, "x")
     B, D, H, W, C = x.shape
     y = torch.empty((B, C, D, H, W), device=x.device, dtype=torch.float32)
-    _lib.check(lib.mvsgi_nvc_to_ncv_f32(x.data_ptr(), y.data_ptr(), B, C, D * H * W, _stream_ptr(x)),
-               "mvsgi_nvc_to_ncv_f32")
+    _call("mvsgi_nvc_to_ncv_f32", x.data_ptr(), y.data_ptr(), B, C, D * H * W, _stream_ptr(x))
     return y
 
 
@@ -1086,12 +977,10 @@ def as_ndhwc(vol: torch.Tensor) -> torch.Tensor:
 # --------------------------------------------------------------------------------------
 def pack_deform_conv2d_weights(w_oihw: torch.Tensor) -> torch.Tensor:
     """[Cout, Cin, Kh, Kw] -> [Kh*Kw, Cin, Cout] for mvsgi_deform_conv2d_f32."""
-    lib = _lib.load()
     w = _dev(w_oihw, "deform conv weight")
     Cout, Cin, Kh, Kw = w.shape
     wp = torch.empty((Kh * Kw, Cin, Cout), device=w.device, dtype=torch.float32)
-    _lib.check(lib.mvsgi_deform_conv2d_pack_weights_f32(w.data_ptr(), wp.data_ptr(), Cout, Cin, Kh, Kw, _stream_ptr(w)),
-               "mvsgi_deform_conv2d_pack_weights_f32")
+    _call("mvsgi_deform_conv2d_pack_weights_f32", w.data_ptr(), wp.data_ptr(), Cout, Cin, Kh, Kw, _stream_ptr(w))
     return wp
 
 
@@ -1099,7 +988,6 @@ def deform_conv2d(x_nhwc, offset, w_packed, scale, shift, kernel_size, stride=(1
                   res=None, neg_slope=1.0) -> torch.Tensor:
     """x [N, H, W, Cin], offset [1 | N, 2*Kh*Kw, Ho, Wo] -> y [N, Ho, Wo, Cout] (torchvision.ops.deform_conv2d
     semantics + per-channel scale / shift, residual, LeakyReLU)."""
-    lib = _lib.load()
     x = _dev(x_nhwc, "x")
     offset = _dev(offset, "offset")
     N, Hh, W, Cin = x.shape
@@ -1116,11 +1004,9 @@ def deform_conv2d(x_nhwc, offset, w_packed, scale, shift, kernel_size, stride=(1
         if tuple(res.shape) != (N, Ho, Wo, Cout):
             raise AssertionError(f"residual {tuple(res.shape)} does not match output {(N, Ho, Wo, Cout)}")
     y = torch.empty((N, Ho, Wo, Cout), device=x.device, dtype=torch.float32)
-    _lib.check(lib.mvsgi_deform_conv2d_f32(x.data_ptr(), offset.data_ptr(), int(offset.shape[0] == N and N > 1),
-                                           w_packed.data_ptr(), scale.data_ptr(), shift.data_ptr(), _ptr(res),
-                                           y.data_ptr(), N, Cin, Hh, W, Cout, Kh, Kw, stride[0], stride[1], padding[0],
-                                           padding[1], dilation[0], dilation[1], float(neg_slope), _stream_ptr(x)),
-               "mvsgi_deform_conv2d_f32")
+    _call("mvsgi_deform_conv2d_f32", x.data_ptr(), offset.data_ptr(), int(offset.shape[0] == N and N > 1), w_packed.data_ptr(), scale.data_ptr(),
+          shift.data_ptr(), _ptr(res), y.data_ptr(), N, Cin, Hh, W, Cout, Kh, Kw, stride[0], stride[1], padding[0], padding[1], dilation[0],
+          dilation[1], float(neg_slope), _stream_ptr(x))
     return y
 
 
@@ -1137,7 +1023,6 @@ def _check_split2d(t: torch.Tensor, N: int, H: int, W: int, device) -> None:
 
 
 def f32_to_split2d(x_nhwc: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
-    lib = _lib.load()
     x = _dev(x_nhwc, "x")
     N, Hh, W, C = x.shape
     if C != 16:
@@ -1145,16 +1030,15 @@ def f32_to_split2d(x_nhwc: torch.Tensor, out: Optional[torch.Tensor] = None) -> 
     if out is None:
         out = split2d_buffer(N, Hh, W, x.device)
     _check_split2d(out, N, Hh, W, x.device)
-    _lib.check(lib.mvsgi_f32_to_split2d(x.data_ptr(), out.data_ptr(), N, Hh, W, _stream_ptr(x)), "mvsgi_f32_to_split2d")
+    _call("mvsgi_f32_to_split2d", x.data_ptr(), out.data_ptr(), N, Hh, W, _stream_ptr(x))
     return out
 
 
 def split2d_to_f32(x_split: torch.Tensor) -> torch.Tensor:
-    lib = _lib.load()
     N, Hp, Wp, _ = x_split.shape
     _check_split2d(x_split, N, Hp - 4, Wp - 4, x_split.device)
     y = torch.empty((N, Hp - 4, Wp - 4, 16), device=x_split.device, dtype=torch.float32)
-    _lib.check(lib.mvsgi_split2d_to_f32(x_split.data_ptr(), y.data_ptr(), N, Hp - 4, Wp - 4, _stream_ptr(x_split)), "mvsgi_split2d_to_f32")
+    _call("mvsgi_split2d_to_f32", x_split.data_ptr(), y.data_ptr(), N, Hp - 4, Wp - 4, _stream_ptr(x_split))
     return y
 
 
@@ -1166,8 +1050,7 @@ def pack_resblock2d_split_weights(w_oihw: torch.Tensor, scale: torch.Tensor) -> 
     if tuple(w.shape) != (16, 16, 3, 3) or scale.numel() != 16:
         raise AssertionError(f"resblock2d_split is the 16 -> 16 channel 3x3 block, got weights {tuple(w.shape)}")
     wp = torch.empty(lib.mvsgi_resblock2d_split_packed_weight_bytes(), device=w.device, dtype=torch.uint8)
-    _lib.check(lib.mvsgi_resblock2d_split_pack_weights(w.data_ptr(), scale.data_ptr(), wp.data_ptr(), _stream_ptr(w)),
-               "mvsgi_resblock2d_split_pack_weights")
+    _call("mvsgi_resblock2d_split_pack_weights", w.data_ptr(), scale.data_ptr(), wp.data_ptr(), _stream_ptr(w))
     return wp
 
 
@@ -1175,7 +1058,6 @@ def resblock2d_split(x_split, wp1, shift1, wp2, shift2, neg_slope=0.01, out_spli
     """Fused 16 -> 16 residual block on a 2-D split-padded input [N, H + 4, W + 4, 64] uint8 (wp1 / wp2 carry the scales).
     out_split: the split-padded buffer that receives the output (returned); None: the output is a plain fp32 [N, H, W, 16]
     tensor."""
-    lib = _lib.load()
     N, Hp, Wp, _ = x_split.shape
     Hh, W = Hp - 4, Wp - 4
     _check_split2d(x_split, N, Hh, W, x_split.device)
@@ -1186,35 +1068,31 @@ def resblock2d_split(x_split, wp1, shift1, wp2, shift2, neg_slope=0.01, out_spli
         y = out_split
     else:
         y = torch.empty((N, Hh, W, 16), device=x_split.device, dtype=torch.float32)
-    _lib.check(lib.mvsgi_resblock2d_split(x_split.data_ptr(), wp1.data_ptr(), shift1.data_ptr(), wp2.data_ptr(), shift2.data_ptr(),
-                                          y.data_ptr(), int(out_split is not None), N, Hh, W, float(neg_slope),
-                                          _stream_ptr(x_split)), "mvsgi_resblock2d_split")
+    _call("mvsgi_resblock2d_split", x_split.data_ptr(), wp1.data_ptr(), shift1.data_ptr(), wp2.data_ptr(), shift2.data_ptr(), y.data_ptr(),
+          int(out_split is not None), N, Hh, W, float(neg_slope), _stream_ptr(x_split))
     return y
 
 
 def conv2d_s2_split(x_split, w_packed, shift, out_split, neg_slope=0.01) -> torch.Tensor:
     """16 -> 16 channel 3x3 stride-2 layer on 2-D split-padded activations (weights from pack_resblock2d_split_weights)."""
-    lib = _lib.load()
     N, Hp, Wp, _ = x_split.shape
     Hh, W = Hp - 4, Wp - 4
     _check_split2d(x_split, N, Hh, W, x_split.device)
     _check_split2d(out_split, N, (Hh - 1) // 2 + 1, (W - 1) // 2 + 1, x_split.device)
     if shift.numel() != 16:
         raise AssertionError("conv2d_s2_split is the 16-channel layer")
-    _lib.check(lib.mvsgi_conv2d_s2_split(x_split.data_ptr(), w_packed.data_ptr(), shift.data_ptr(), out_split.data_ptr(), N, Hh, W,
-                                         float(neg_slope), _stream_ptr(x_split)), "mvsgi_conv2d_s2_split")
+    _call("mvsgi_conv2d_s2_split", x_split.data_ptr(), w_packed.data_ptr(), shift.data_ptr(), out_split.data_ptr(), N, Hh, W, float(neg_slope),
+          _stream_ptr(x_split))
     return out_split
 
 
 def resblock2d(x_nhwc, wp1, scale1, shift1, wp2, scale2, shift2, neg_slope=0.01) -> torch.Tensor:
     """Fused 16 -> 16 residual block (two 3x3 convs + BN + LeakyReLU + skip): x [N, H, W, 16] -> y, same shape."""
-    lib = _lib.load()
     x = _dev(x_nhwc, "x")
     N, Hh, W, C = x.shape
     if C != 16 or scale1.numel() != 16 or scale2.numel() != 16:
         raise AssertionError(f"resblock2d is the 16-channel block, got x {tuple(x.shape)}")
     y = torch.empty_like(x)
-    _lib.check(lib.mvsgi_resblock2d_f32(x.data_ptr(), wp1.data_ptr(), scale1.data_ptr(), shift1.data_ptr(),
-                                        wp2.data_ptr(), scale2.data_ptr(), shift2.data_ptr(), y.data_ptr(), N, Hh, W,
-                                        float(neg_slope), _stream_ptr(x)), "mvsgi_resblock2d_f32")
+    _call("mvsgi_resblock2d_f32", x.data_ptr(), wp1.data_ptr(), scale1.data_ptr(), shift1.data_ptr(), wp2.data_ptr(), scale2.data_ptr(),
+          shift2.data_ptr(), y.data_ptr(), N, Hh, W, float(neg_slope), _stream_ptr(x))
     return y

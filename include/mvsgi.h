@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define MVSGI_ABI_VERSION 5   /* 5: mvsgi_softargmin_scaled_f32 (soft-argmin at any interp_scale_factor); 4: mvsgi_instance_norm_f32, mvsgi_instance_norm_ws_bytes (norm_type 'instance'); 3: mvsgi_conv3d_d32_applies, mvsgi_conv3d_up2_d32_applies + MVSGI_CONV_BF16X3_D32; 2: mvsgi_saturation_flags; the symbol set of round 5 */
+#define MVSGI_ABI_VERSION 6   /* 6: mvsgi_sweep_max_cams (masked-variance sweep for rigs of up to 8 cameras); 5: mvsgi_softargmin_scaled_f32 (soft-argmin at any interp_scale_factor); 4: mvsgi_instance_norm_f32, mvsgi_instance_norm_ws_bytes (norm_type 'instance'); 3: mvsgi_conv3d_d32_applies, mvsgi_conv3d_up2_d32_applies + MVSGI_CONV_BF16X3_D32; 2: mvsgi_saturation_flags; the symbol set of round 5 */
 
 typedef void* mvsgi_stream_t;
 
@@ -100,7 +100,9 @@ int mvsgi_saturation_words(unsigned* words8);      /* diagnostics: the 8 raw wor
  *   masks      [B][N][1][Hm][Wm]      fp32
  *   vol        [B][D][Ho][Wo][C]      fp32 out: population variance over the valid cameras,
  *                                     0 where fewer than two cameras are valid
+ * N <= mvsgi_sweep_max_cams() (8: one validity bit per camera in a byte); the cameras are added in order, camera 0 first.
  */
+int mvsgi_sweep_max_cams(void);
 int mvsgi_sweep_std_f32(const float* feats, const float* grids, const void* grid_masks,
                         int grid_mask_is_f32, const float* masks, float* vol,
                         int B, int N, int C, int Hi, int Wi, int Hm, int Wm,
@@ -112,7 +114,8 @@ int mvsgi_sweep_cat_f32(const float* feats, const float* grids, float* vol,
                         int B, int N, int C, int Hi, int Wi,
                         int D, int Ho, int Wo, mvsgi_stream_t stream);
 
-/* The same two sweeps on channels-last feature maps, feats [B][N][Hi][Wi][C] (C % 4 == 0; std: N <= 4):
+/* The same two sweeps on channels-last feature maps, feats [B][N][Hi][Wi][C] (C % 4 == 0; mvsgi_sweep_std_nhwc_f32: N <= 4,
+ * the kernels that read the validity byte below: N <= 8):
  * one 64-byte texel per tap instead of C strided planes.  The Python layer transposes the
  * feature extractor's NCHW output once (mvsgi_ncv_to_nvc_f32) unless it already is channels-last. */
 int mvsgi_sweep_std_nhwc_f32(const float* feats, const float* grids, const void* grid_masks,
@@ -128,7 +131,8 @@ int mvsgi_sweep_cat_nhwc_f32(const float* feats, const float* grids, float* vol,
  * masks, which the reference builds once per camera rig (api/inference_class.py:40-45).
  * mvsgi_sweep_validity_u8 evaluates it once into vmask [B][D][Ho][Wo] (bit cam set = camera cam is
  * valid; N <= 8); mvsgi_sweep_std_nhwc_valid_f32 is mvsgi_sweep_std_nhwc_f32 reading that byte
- * instead of re-sampling the masks every frame.  Bit-identical output. */
+ * instead of re-sampling the masks every frame, for N <= 8 (five cameras and more: two groups of four per lane quad).
+ * Bit-identical output. */
 int mvsgi_sweep_validity_u8(const float* grids, const void* grid_masks, int grid_mask_is_f32,
                             const float* masks, unsigned char* vmask,
                             int B, int N, int Hm, int Wm, int D, int Ho, int Wo, mvsgi_stream_t stream);

@@ -13,7 +13,7 @@ from ctypes import c_char_p, c_double, c_float, c_int, c_longlong, c_size_t, c_v
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MVSGI_LIB", os.path.join(_HERE, "libmvsgi_hip.so"))   # MVSGI_LIB: diagnostic builds
 
-ABI_VERSION = 5
+ABI_VERSION = 6
 
 
 class MvsgiLibraryMissing(RuntimeError):
@@ -27,6 +27,7 @@ SIGNATURES = {
     "mvsgi_last_error": (c_char_p, []),
     "mvsgi_saturation_flags": (c_int, [c_int, _P]),
     "mvsgi_saturation_words": (c_int, [_P]),
+    "mvsgi_sweep_max_cams": (c_int, []),
     "mvsgi_sweep_std_f32": (c_int, [_P, _P, _P, c_int, _P, _P] + [c_int] * 10 + [_P]),
     "mvsgi_sweep_cat_f32": (c_int, [_P, _P, _P] + [c_int] * 8 + [_P]),
     "mvsgi_sweep_std_nhwc_f32": (c_int, [_P, _P, _P, c_int, _P, _P] + [c_int] * 10 + [_P]),

@@ -10,14 +10,17 @@
 //
 // Kernels, slowest to fastest (all the same bits):
 //   sweep_std_kernel / sweep_cat_kernel      feats in the extractor's NCHW planes, one thread per voxel
-//                                            (any C, up to 6 cameras);
+//                                            (any C, up to 8 cameras);
 //   sweep_std_nhwc_kernel / sweep_cat_nhwc_kernel   channels-last feats: 4 lanes share a voxel, one 64-byte
 //                                            texel per tap through buffer descriptors (zero padding = the
 //                                            hardware range check), XCD-contiguous block order;
 //   sweep_validity_kernel + sweep_std_nhwc_v_kernel   the default: the rig-constant mask half evaluated once
 //                                            per rig, the per-frame kernel walks the candidates of a row
-//                                            with the next candidate's grid point prefetched.
+//                                            with the next candidate's grid point prefetched
+//                                            (sweep_std_nhwc_v_wide_kernel for rigs of 5 to 8 cameras).
 #include "common.hpp"
+
+#include <type_traits>
 
 namespace {
 
@@ -669,6 +672,237 @@ __global__ __launch_bounds__(256, MVSGI_SWEEP_WAVES) void sweep_std_nhwc_v_kerne
     if constexpr (F16) sf_sat_report(sat, kSatSweep, satm, kF16Max);
 }
 
+// The same kernel for rigs of 5 to 8 cameras (same arguments, block shape, block order and output formats).  A quad has four lanes,
+// so lane q sets up TWO cameras, q and q + 4: two grid points per candidate, both prefetched with the validity byte.  The cameras
+// are gathered in two groups of (up to) four -- 16 texel quads in flight, as in the 4-camera kernel, never 32 -- and only a group's
+// blended samples (four registers per camera) outlive it; the masked variance runs once both groups are in.  Arithmetic as above:
+// the cameras are added in order, camera 0 first (sweep_std_kernel's order), and the two divisions by the camera count are the
+// reciprocal-fma sequence, which is the correctly rounded quotient for 1e-30 <= |x| <= 1e30 (Markstein: y = RN(1 / d), q within an
+// ulp of x / d).  Below that range a quotient x / 6 can be an exact tie between two subnormals, which the sequence rounds the
+// wrong way, so tiny non-zero operands take the hardware division like the huge ones do.  Same bits as sweep_std_kernel<NCAM>.
+#ifndef MVSGI_SWEEP_WIDE_WAVES
+#define MVSGI_SWEEP_WIDE_WAVES 4      // waves per SIMD the register allocation of the 5..8-camera kernel aims at (<= 128 registers)
+#endif
+template <int NCAM, bool C16, bool F16 = false>
+__global__ __launch_bounds__(256, MVSGI_SWEEP_WIDE_WAVES) void sweep_std_nhwc_v_wide_kernel(const float* __restrict__ feats,
+                                                               const float* __restrict__ grids,
+                                                               const unsigned char* __restrict__ vmask,
+                                                               float* __restrict__ vol, SweepDims s, int dchunk,
+                                                               int nd, int rig_shared, unsigned char* __restrict__ vol_split,
+                                                               unsigned* __restrict__ sat) {
+#pragma clang fp contract(off)
+    static_assert(NCAM > 4 && NCAM <= 8, "two cameras per lane of a quad, one validity bit per camera in a byte");
+    typedef float f32x2_t __attribute__((ext_vector_type(2)));
+    float satm = 0.f;          // fp16 split output: running maximum |value written| (range report, csrc/split_fmt.hpp)
+    const int q = threadIdx.x & 3;
+    const int WT = (s.Wo + 63) >> 6;
+    int L = sweep_xcd_remap((int)blockIdx.x, (int)gridDim.x);
+    const int wt = L % WT;
+    L /= WT;
+    const int dc = L % nd;
+    L /= nd;
+    const int ho = L % s.Ho;
+    const int b = L / s.Ho;
+    int wo = wt * 64 + (threadIdx.x >> 2);
+    const bool live = wo < s.Wo;
+    if (!live) wo = s.Wo - 1;            // keep whole quads alive for the DPP broadcasts
+    const int d0 = dc * dchunk;
+    const int d1 = d0 + dchunk < s.D ? d0 + dchunk : s.D;
+    const int HWi = s.Hi * s.Wi;
+    const long long HW = (long long)s.Ho * s.Wo;
+
+    __amdgpu_buffer_rsrc_t img[NCAM];                  // one descriptor per camera image (wave-uniform)
+#pragma unroll
+    for (int cam = 0; cam < NCAM; ++cam)
+        img[cam] = __builtin_amdgcn_make_buffer_rsrc(
+            const_cast<float*>(feats + (long long)(b * NCAM + cam) * HWi * s.C), 0, HWi * s.C * 4, 0x00020000);
+    // lane q walks the grids of cameras q and q + 4 (lanes beyond the rig re-read the last camera; unused)
+    const int cam1 = q + 4 < NCAM ? q + 4 : NCAM - 1;
+    const int br = rig_shared ? 0 : b;                 // one grid / validity set for the whole batch (see above)
+    const long long grow = (long long)d0 * HW + (long long)ho * s.Wo + wo;
+    const float2* gp0 = reinterpret_cast<const float2*>(grids) + (long long)(br * NCAM + q) * s.D * HW + grow;
+    const float2* gp1 = reinterpret_cast<const float2*>(grids) + (long long)(br * NCAM + cam1) * s.D * HW + grow;
+    const unsigned char* vp = vmask + (long long)br * s.D * HW + grow;
+    float* out = vol + ((((long long)b * s.D + d0) * s.Ho + ho) * s.Wo + wo) * s.C;
+    const long long vstep = HW * s.C;
+    // vol_split (C == 16): split-padded records, every lane stores one whole 16 B piece (see the kernel above)
+    unsigned char* outs = vol_split ? vol_split + ((((long long)b * (s.D + 2) + d0 + 1) * (s.Ho + 2) + ho + 1) * (s.Wo + 2) + wo + 1) * 64 +
+                                          ((q & 1) * 2 + (q >> 1)) * 16
+                                    : nullptr;
+    const long long sstep = (long long)(s.Ho + 2) * (s.Wo + 2) * 64;
+    const int C4 = C16 ? 64 : s.C * 4, rowB = s.Wi * C4;
+    auto candidate = [&](const float2 g0, const float2 g1, const unsigned vm, float* __restrict__ o, unsigned char* __restrict__ os) {
+        // taps as BYTE offsets, worked out once by the cameras' lane and broadcast through the quad group by group
+        const Bilin mine0 = bilin_setup_bytes(g0.x, g0.y, s.Wi, s.Hi, C4, rowB);
+        const Bilin mine1 = bilin_setup_bytes(g1.x, g1.y, s.Wi, s.Hi, C4, rowB);
+        bool val[NCAM];
+        f32x2_t VF[NCAM];
+        float n = 0.0f;
+#pragma unroll
+        for (int cam = 0; cam < NCAM; ++cam) {
+            val[cam] = ((vm >> cam) & 1u) != 0;
+            const float vf = val[cam] ? 1.0f : 0.0f;
+            VF[cam] = f32x2_t{vf, vf};
+            n = n + vf;
+        }
+        const bool ok = n > 1.0f;
+        const float cnt = ok ? n : 1.0f;
+        // RN(1 / cnt) for the camera counts there are: exactly what the division 1.0f / cnt returns
+        const float inv = cnt == 2.0f ? 0.5f : cnt == 3.0f ? 0x1.555556p-2f : cnt == 4.0f ? 0.25f : cnt == 5.0f ? 0x1.99999ap-3f :
+                          cnt == 6.0f ? 0x1.555556p-3f : cnt == 7.0f ? 0x1.24924ap-3f : cnt == 8.0f ? 0.125f : 1.0f;
+        const f32x2_t INV = {inv, inv}, NCNT = {-cnt, -cnt};
+#pragma unroll 1
+        // (every lane of a quad makes every trip -- the taps travel by DPP INSIDE the loop, and a lane that had left it would
+        // broadcast nothing: with C = 8 lanes 2 and 3 have no channels, yet they set up cameras 2, 3, 6, 7.  A lane beyond the
+        // channels gathers out of range and stores nothing.)
+        for (int cb0 = 0; cb0 < (C16 ? 64 : C4); cb0 += 64) {
+            const int cb = cb0 + q * 16;
+            const bool mych = C16 || cb < C4;
+            f32x2_t sv[NCAM][2];
+            // one group of cameras: taps through the quad, 4 gathers per camera, blend; only sv leaves it
+            auto group = [&](auto G_) {
+                constexpr int G = decltype(G_)::value, base = 4 * G, NG = NCAM - base < 4 ? NCAM - base : 4;
+                const Bilin& mine = G ? mine1 : mine0;
+                Bilin ft[NG];
+                ft[0] = quad_bcast<0>(mine);
+                if constexpr (NG > 1) ft[1] = quad_bcast<1>(mine);
+                if constexpr (NG > 2) ft[2] = quad_bcast<2>(mine);
+                if constexpr (NG > 3) ft[3] = quad_bcast<3>(mine);
+                f32x4_t tx[NG][4];
+#pragma unroll
+                for (int c = 0; c < NG; ++c) {
+                    const bool need = val[base + c] & ok;
+#if MVSGI_SWEEP_SKIP_CAM
+                    // a camera no voxel of this wave needs is not gathered at all (the texture addresser's instruction rate bounds
+                    // the kernel; see above)
+                    if (__builtin_amdgcn_ballot_w64(need) == 0) {
+                        tx[c][0] = tx[c][1] = tx[c][2] = tx[c][3] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+                        continue;
+                    }
+#endif
+                    // texels nobody needs (camera invalid here, or fewer than two cameras): offsets out of the descriptor's range.
+                    // (the sign bit OR-ed into the final offset, not a select: image byte offsets are below 2^31, and a select between two addresses
+                    // becomes two loads under complementary exec masks with a wait between them)
+                    const int far = (need & mych) ? 0 : (int)0x80000000;
+                    tx[c][0] = __builtin_bit_cast(f32x4_t, __builtin_amdgcn_raw_buffer_load_b128(img[base + c], (ft[c].o00 + cb) | far, 0, 0));
+                    tx[c][1] = __builtin_bit_cast(f32x4_t, __builtin_amdgcn_raw_buffer_load_b128(img[base + c], (ft[c].o01 + cb) | far, 0, 0));
+                    tx[c][2] = __builtin_bit_cast(f32x4_t, __builtin_amdgcn_raw_buffer_load_b128(img[base + c], (ft[c].o10 + cb) | far, 0, 0));
+                    tx[c][3] = __builtin_bit_cast(f32x4_t, __builtin_amdgcn_raw_buffer_load_b128(img[base + c], (ft[c].o11 + cb) | far, 0, 0));
+                }
+#pragma unroll
+                for (int c = 0; c < NG; ++c) {
+                    const f32x2_t W00 = {ft[c].w00, ft[c].w00}, W01 = {ft[c].w01, ft[c].w01};
+                    const f32x2_t W10 = {ft[c].w10, ft[c].w10}, W11 = {ft[c].w11, ft[c].w11};
+#pragma unroll
+                    for (int p = 0; p < 2; ++p) {
+                        const f32x2_t i00 = {tx[c][0][2 * p], tx[c][0][2 * p + 1]}, i01 = {tx[c][1][2 * p], tx[c][1][2 * p + 1]};
+                        const f32x2_t i10 = {tx[c][2][2 * p], tx[c][2][2 * p + 1]}, i11 = {tx[c][3][2 * p], tx[c][3][2 * p + 1]};
+                        sv[base + c][p] = ((i00 * W00 + i01 * W01) + i10 * W10) + i11 * W11;          // backports.py:86, left to right
+                        // (opaque: the blend happens HERE, and the texels die here -- the compiler otherwise sinks it to the
+                        // reduction, behind the other group's gathers, and holds both groups' texels at once)
+                        asm volatile("" : "+v"(sv[base + c][p]));
+                    }
+                }
+            };
+            group(std::integral_constant<int, 0>{});
+            group(std::integral_constant<int, 1>{});
+            // spherical_sweep_avg.py:106-125 on channel pairs, the cameras in order
+            f32x2_t sum[2], var[2];
+            f32x4_t r;
+            bool rare = false;
+#pragma unroll
+            for (int p = 0; p < 2; ++p) {
+                sum[p] = sv[0][p] * VF[0];
+#pragma unroll
+                for (int cam = 1; cam < NCAM; ++cam) sum[p] = sum[p] + sv[cam][p] * VF[cam];
+                const f32x2_t qa = sum[p] * INV;
+                const f32x2_t avg = __builtin_elementwise_fma(__builtin_elementwise_fma(NCNT, qa, sum[p]), INV, qa);
+#pragma unroll
+                for (int cam = 0; cam < NCAM; ++cam) {
+                    const f32x2_t t = {val[cam] ? sv[cam][p].x : avg.x, val[cam] ? sv[cam][p].y : avg.y};   // :119
+                    const f32x2_t df = t - avg;
+                    var[p] = cam == 0 ? df * df : var[p] + df * df;                                           // :122
+                }
+                const f32x2_t qv = var[p] * INV;
+                const f32x2_t v = __builtin_elementwise_fma(__builtin_elementwise_fma(NCNT, qv, var[p]), INV, qv);
+                r[2 * p] = ok ? v.x : 0.0f;                                                                   // :125
+                r[2 * p + 1] = ok ? v.y : 0.0f;
+#pragma unroll
+                for (int k = 0; k < 2; ++k) {        // outside [1e-30, 1e30] (and not 0): not what the sequence is proven for
+                    const float as = __builtin_fabsf(sum[p][k]), av = var[p][k];
+                    rare |= (as != 0.0f && !(as >= 1e-30f && as <= 1e30f)) | (av != 0.0f && !(av >= 1e-30f && av <= 1e30f));
+                }
+            }
+            if (__builtin_amdgcn_ballot_w64(rare) != 0) {                 // wave-uniform, never taken on real features
+                float dv = cnt;
+                asm volatile("; exact-division path" : "+v"(dv));          // (opaque: keeps the divisions inside the branch)
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    const float sm = sum[k >> 1][k & 1];
+                    const float avg = sm / dv;
+                    float vr = 0.0f;
+#pragma unroll
+                    for (int cam = 0; cam < NCAM; ++cam) {
+                        const float t = val[cam] ? sv[cam][k >> 1][k & 1] : avg;
+                        const float df = t - avg;
+                        vr = vr + df * df;
+                    }
+                    vr = vr / dv;
+                    r[k] = ok ? vr : 0.0f;
+                }
+            }
+            if (os) {
+                // x = hi + lo, hi = bf16(x) (RNE), lo = bf16(x - hi): the same split as the conv kernels' staging
+                unsigned hi[2], lo[2];
+#pragma unroll
+                for (int p = 0; p < 2; ++p) {
+                    if constexpr (F16) {
+                        const float a_ = sf_clamp<true>(r[2 * p]), b_ = sf_clamp<true>(r[2 * p + 1]);
+                        satm = sf_sat_acc(satm, a_, b_);
+                        const unsigned hb = sf_cvt_pk<true>(a_, b_);
+                        hi[p] = hb;
+                        lo[p] = sf_cvt_pk<true>(a_ - sf_widen_lo<true>(hb), b_ - sf_widen_hi<true>(hb));
+                    } else {
+                        typedef __bf16 b2_t __attribute__((ext_vector_type(2)));
+                        const f32x2_t v = {r[2 * p], r[2 * p + 1]};
+                        const unsigned hb = __builtin_bit_cast(unsigned, __builtin_convertvector(v, b2_t));
+                        const f32x2_t hf = {__builtin_bit_cast(float, hb << 16), __builtin_bit_cast(float, hb & 0xffff0000u)};
+                        hi[p] = hb;
+                        lo[p] = __builtin_bit_cast(unsigned, __builtin_convertvector(v - hf, b2_t));
+                    }
+                }
+                // even lanes keep their hi and take the odd neighbour's hi; odd lanes take the even neighbour's lo
+                const bool odd = (q & 1) != 0;
+                const unsigned r0 = (unsigned)__builtin_amdgcn_mov_dpp((int)(odd ? hi[0] : lo[0]), 0xB1, 0xf, 0xf, true);   // quad_perm [1,0,3,2]
+                const unsigned r1 = (unsigned)__builtin_amdgcn_mov_dpp((int)(odd ? hi[1] : lo[1]), 0xB1, 0xf, 0xf, true);
+                const uint4 piece = odd ? make_uint4(r0, r1, lo[0], lo[1]) : make_uint4(hi[0], hi[1], r0, r1);
+                if (live) *reinterpret_cast<uint4*>(os) = piece;
+            } else if (live & mych) *reinterpret_cast<f32x4_t*>(reinterpret_cast<char*>(o) + cb) = r;
+        }
+    };
+    // two candidates per trip with ping-pong registers (A, B), as above, with two grid points per candidate
+    float2 g0A = *gp0, g1A = *gp1;
+    unsigned vA = *vp;
+    for (int d = d0; d < d1; d += 2) {
+        const bool hasB = d + 1 < d1;
+        const long long sB = hasB ? HW : 0;
+        const float2 g0B = gp0[sB], g1B = gp1[sB];
+        const unsigned vB = vp[sB];
+        candidate(g0A, g1A, vA, out, outs);
+        const long long sA = d + 2 < d1 ? 2 * HW : sB;
+        g0A = gp0[sA];
+        g1A = gp1[sA];
+        vA = vp[sA];
+        if (hasB) candidate(g0B, g1B, vB, out + vstep, outs ? outs + sstep : nullptr);
+        gp0 += 2 * HW;
+        gp1 += 2 * HW;
+        vp += 2 * HW;
+        out += 2 * vstep;
+        if (outs) outs += 2 * sstep;
+    }
+    if constexpr (F16) sf_sat_report(sat, kSatSweep, satm, kF16Max);
+}
+
 // grid = ceil(Wo / 64) * N * D * Ho * B blocks (flat), logical order (b, ho, d, cam, w-tile)
 __global__ __launch_bounds__(256) void sweep_cat_nhwc_kernel(const float* __restrict__ feats,
                                                              const float* __restrict__ grids,
@@ -724,7 +958,7 @@ extern "C" int mvsgi_sweep_std_f32(const float* feats, const float* grids, const
     if (check_dims(s, "mvsgi_sweep_std_f32")) return 1;
     MVSGI_REQUIRE(Hm > 0 && Wm > 0, "mvsgi_sweep_std_f32: non-positive mask size");
     MVSGI_REQUIRE(feats && grids && grid_masks && masks && vol, "mvsgi_sweep_std_f32: null pointer");
-    MVSGI_REQUIRE(N >= 1 && N <= 6, "mvsgi_sweep_std_f32: num_cams %d not in [1, 6]", N);
+    MVSGI_REQUIRE(N >= 1 && N <= 8, "mvsgi_sweep_std_f32: num_cams %d not in [1, 8]", N);
     const long long total = (long long)B * D * Ho * Wo;
     const dim3 grid((unsigned)mvsgi::cdiv(total, 256)), block(256);
     const unsigned char* g8 = grid_mask_is_f32 ? nullptr : static_cast<const unsigned char*>(grid_masks);
@@ -746,6 +980,8 @@ extern "C" int mvsgi_sweep_std_f32(const float* feats, const float* grids, const
         LAUNCH_STD(4)
         LAUNCH_STD(5)
         LAUNCH_STD(6)
+        LAUNCH_STD(7)
+        LAUNCH_STD(8)
     }
 #undef LAUNCH_STD
     return mvsgi::check_launch("mvsgi_sweep_std_f32");
@@ -836,7 +1072,7 @@ int sweep_std_nhwc_valid_impl(const float* feats, const float* grids, const unsi
     if (check_dims(s, "mvsgi_sweep_std_nhwc_valid_f32")) return 1;
     MVSGI_REQUIRE(feats && grids && vmask && (vol || vol_split), "mvsgi_sweep_std_nhwc_valid_f32: null pointer");
     MVSGI_REQUIRE(!vol_split || C == 16, "mvsgi_sweep_std_nhwc_valid_split: the split-padded output needs C == 16 (got %d)", C);
-    MVSGI_REQUIRE(N >= 1 && N <= 4, "mvsgi_sweep_std_nhwc_valid_f32: num_cams %d not in [1, 4]", N);
+    MVSGI_REQUIRE(N >= 1 && N <= 8, "mvsgi_sweep_std_nhwc_valid_f32: num_cams %d not in [1, 8]", N);
     MVSGI_REQUIRE(C % 4 == 0, "mvsgi_sweep_std_nhwc_valid_f32: C=%d must be a multiple of 4", C);
     // candidates per block: as many as keeps >= ~8k blocks in the launch (latency hiding across d
     // needs a few; filling 256 CUs x 4 resident blocks needs the rest)
@@ -859,6 +1095,10 @@ int sweep_std_nhwc_valid_impl(const float* feats, const float* grids, const unsi
             case 2: hipLaunchKernelGGL((sweep_std_nhwc_v_kernel<2, true, true>), grid, block, 0, st, feats, grids, vmask, vol, s, dchunk, (int)nd, rig_shared, vol_split, sat); break;
             case 3: hipLaunchKernelGGL((sweep_std_nhwc_v_kernel<3, true, true>), grid, block, 0, st, feats, grids, vmask, vol, s, dchunk, (int)nd, rig_shared, vol_split, sat); break;
             case 4: hipLaunchKernelGGL((sweep_std_nhwc_v_kernel<4, true, true>), grid, block, 0, st, feats, grids, vmask, vol, s, dchunk, (int)nd, rig_shared, vol_split, sat); break;
+            case 5: hipLaunchKernelGGL((sweep_std_nhwc_v_wide_kernel<5, true, true>), grid, block, 0, st, feats, grids, vmask, vol, s, dchunk, (int)nd, rig_shared, vol_split, sat); break;
+            case 6: hipLaunchKernelGGL((sweep_std_nhwc_v_wide_kernel<6, true, true>), grid, block, 0, st, feats, grids, vmask, vol, s, dchunk, (int)nd, rig_shared, vol_split, sat); break;
+            case 7: hipLaunchKernelGGL((sweep_std_nhwc_v_wide_kernel<7, true, true>), grid, block, 0, st, feats, grids, vmask, vol, s, dchunk, (int)nd, rig_shared, vol_split, sat); break;
+            case 8: hipLaunchKernelGGL((sweep_std_nhwc_v_wide_kernel<8, true, true>), grid, block, 0, st, feats, grids, vmask, vol, s, dchunk, (int)nd, rig_shared, vol_split, sat); break;
         }
         return mvsgi::check_launch("mvsgi_sweep_std_nhwc_valid_split");
     }
@@ -874,6 +1114,18 @@ int sweep_std_nhwc_valid_impl(const float* feats, const float* grids, const unsi
                 break;
         case 4: if (C == 16) hipLaunchKernelGGL((sweep_std_nhwc_v_kernel<4, true>), grid, block, 0, st, feats, grids, vmask, vol, s, dchunk, (int)nd, rig_shared, vol_split, sat);
                 else hipLaunchKernelGGL((sweep_std_nhwc_v_kernel<4, false>), grid, block, 0, st, feats, grids, vmask, vol, s, dchunk, (int)nd, rig_shared, vol_split, sat);
+                break;
+        case 5: if (C == 16) hipLaunchKernelGGL((sweep_std_nhwc_v_wide_kernel<5, true>), grid, block, 0, st, feats, grids, vmask, vol, s, dchunk, (int)nd, rig_shared, vol_split, sat);
+                else hipLaunchKernelGGL((sweep_std_nhwc_v_wide_kernel<5, false>), grid, block, 0, st, feats, grids, vmask, vol, s, dchunk, (int)nd, rig_shared, vol_split, sat);
+                break;
+        case 6: if (C == 16) hipLaunchKernelGGL((sweep_std_nhwc_v_wide_kernel<6, true>), grid, block, 0, st, feats, grids, vmask, vol, s, dchunk, (int)nd, rig_shared, vol_split, sat);
+                else hipLaunchKernelGGL((sweep_std_nhwc_v_wide_kernel<6, false>), grid, block, 0, st, feats, grids, vmask, vol, s, dchunk, (int)nd, rig_shared, vol_split, sat);
+                break;
+        case 7: if (C == 16) hipLaunchKernelGGL((sweep_std_nhwc_v_wide_kernel<7, true>), grid, block, 0, st, feats, grids, vmask, vol, s, dchunk, (int)nd, rig_shared, vol_split, sat);
+                else hipLaunchKernelGGL((sweep_std_nhwc_v_wide_kernel<7, false>), grid, block, 0, st, feats, grids, vmask, vol, s, dchunk, (int)nd, rig_shared, vol_split, sat);
+                break;
+        case 8: if (C == 16) hipLaunchKernelGGL((sweep_std_nhwc_v_wide_kernel<8, true>), grid, block, 0, st, feats, grids, vmask, vol, s, dchunk, (int)nd, rig_shared, vol_split, sat);
+                else hipLaunchKernelGGL((sweep_std_nhwc_v_wide_kernel<8, false>), grid, block, 0, st, feats, grids, vmask, vol, s, dchunk, (int)nd, rig_shared, vol_split, sat);
                 break;
     }
     return mvsgi::check_launch("mvsgi_sweep_std_nhwc_valid_f32");

@@ -54,7 +54,7 @@ def _rig_hit(entry, tensors) -> bool:
 def _rig_cache_usable(owner, feats, grids) -> bool:
     """Whether the validity-byte kernels serve this call (decided ONCE per forward, before a code path is chosen)."""
     return owner is not None and getattr(owner, "cache_rig_constants", True) and _RIG_CACHE_ENV \
-        and H.nhwc_sweep_ok(feats) and grids.is_cuda
+        and grids.is_cuda and H.valid_sweep_ok(feats)
 
 
 def std_sweep_ndhwc(feats, grids, grid_masks, masks, owner=None, split_out: bool = False, buf_frames: int = 0):

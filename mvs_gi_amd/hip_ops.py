@@ -203,7 +203,19 @@ def _feats_nhwc(feats):
 
 
 def nhwc_sweep_ok(feats) -> bool:
+    """The channels-last kernel that samples the masks itself (mvsgi_sweep_std_nhwc_f32) takes these feats: C % 4 == 0, N <= 4."""
     return feats.dim() == 5 and feats.shape[2] % 4 == 0 and feats.shape[1] <= 4
+
+
+def sweep_max_cams() -> int:
+    """Cameras the masked-variance sweep takes (one validity bit per camera in a byte); the library's own bound."""
+    return int(_lib.load().mvsgi_sweep_max_cams())
+
+
+def valid_sweep_ok(feats) -> bool:
+    """The kernels that read the rig's validity byte (sweep_std_valid, sweep_std_valid_split) take these feats:
+    C % 4 == 0 and N <= sweep_max_cams()."""
+    return feats.dim() == 5 and feats.shape[2] % 4 == 0 and 1 <= feats.shape[1] <= sweep_max_cams()
 
 
 def _rig_args(grids, grid_masks, masks, B: int, N: int):
@@ -230,8 +242,8 @@ def sweep_validity(grids, grid_masks, masks) -> torch.Tensor:
     """Rig-constant validity byte per voxel, [B, D, Ho, Wo] uint8 (bit cam = camera cam valid):
     (bilinear_grid_sample(masks) > 0) & grid_masks of spherical_sweep_avg.py:92-102."""
     B, N = grids.shape[:2]
-    if N > 8:
-        raise AssertionError(f"grids must be [B, N<=8, D, Ho, Wo, 2], got {tuple(grids.shape)}")
+    if N > sweep_max_cams():
+        raise AssertionError(f"grids must be [B, N<={sweep_max_cams()}, D, Ho, Wo, 2], got {tuple(grids.shape)}")
     grids, gm, gm_f32, masks, (D, Ho, Wo, Hm, Wm) = _rig_args(grids, grid_masks, masks, B, N)
     vmask = torch.empty((B, D, Ho, Wo), device=grids.device, dtype=torch.uint8)
     _call("mvsgi_sweep_validity_u8", grids.data_ptr(), gm.data_ptr(), gm_f32, masks.data_ptr(), vmask.data_ptr(),
@@ -242,8 +254,8 @@ def sweep_validity(grids, grid_masks, masks) -> torch.Tensor:
 def sweep_std_valid(feats, grids, vmask) -> torch.Tensor:
     """sweep_std with the cached validity byte (channels-last kernel only) -> vol_raw [B, D, Ho, Wo, C].
     grids / vmask with batch 1 against feats with batch B > 1 = one rig shared by the whole batch."""
-    if not nhwc_sweep_ok(feats):
-        raise AssertionError(f"sweep_std_valid needs C % 4 == 0 and N <= 4, got feats {tuple(feats.shape)}")
+    if not valid_sweep_ok(feats):
+        raise AssertionError(f"sweep_std_valid needs C % 4 == 0 and num_cams in [1, {sweep_max_cams()}], got feats {tuple(feats.shape)}")
     B, N, C, Hi, Wi = feats.shape
     f = _feats_nhwc(feats)
     grids = _dev(grids, "grids")
@@ -261,6 +273,8 @@ def sweep_std_valid(feats, grids, vmask) -> torch.Tensor:
 
 def sweep_std_valid_split(feats, grids, vmask, out: "SplitAct", fmt: str = "bf16") -> "SplitAct":
     """sweep_std_valid with vol_raw written split-padded (C == 16) into `out` (B, D, Ho, Wo, 16), its pieces in the split `fmt`."""
+    if not valid_sweep_ok(feats):
+        raise AssertionError(f"sweep_std_valid_split needs C == 16 and num_cams in [1, {sweep_max_cams()}], got feats {tuple(feats.shape)}")
     B, N, C, Hi, Wi = feats.shape
     f = _feats_nhwc(feats)
     grids = _dev(grids, "grids")
@@ -278,9 +292,18 @@ def sweep_std_valid_split(feats, grids, vmask, out: "SplitAct", fmt: str = "bf16
 
 def sweep_std(feats, grids, grid_masks, masks, layout: str = "auto") -> torch.Tensor:
     """-> vol_raw [B, D, Ho, Wo, C] (masked variance over cameras).  layout: 'auto' uses the
-    channels-last kernel when C % 4 == 0 and N <= 4 (transposing NCHW feats once), 'nchw'
+    channels-last kernel when C % 4 == 0 and N <= 4 (transposing NCHW feats once) and, for rigs of 5 to
+    sweep_max_cams() cameras with C % 4 == 0, the validity byte and the kernel that reads it (same bits); 'nchw'
     forces the plane-gather kernel."""
+    if feats.dim() != 5:
+        raise AssertionError(f"feats must be [B, N, C, Hi, Wi], got {tuple(feats.shape)}")
+    if not 1 <= feats.shape[1] <= sweep_max_cams():
+        raise AssertionError(f"sweep_std: num_cams {feats.shape[1]} not in [1, {sweep_max_cams()}]")
     nhwc = layout == "auto" and nhwc_sweep_ok(feats)
+    if layout == "auto" and not nhwc and valid_sweep_ok(feats):
+        if tuple(grids.shape[:2]) != tuple(feats.shape[:2]):
+            raise AssertionError(f"grids {tuple(grids.shape)} must be [{feats.shape[0]}, {feats.shape[1]}, D, Ho, Wo, 2]")
+        return sweep_std_valid(feats, grids, sweep_validity(grids, grid_masks, masks))
     B, N, C, Hi, Wi = feats.shape
     f = _feats_nhwc(feats) if nhwc else _dev(feats, "feats")
     grids, gm, gm_f32, masks, (D, Ho, Wo, Hm, Wm) = _rig_args(grids, grid_masks, masks, B, N)

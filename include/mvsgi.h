@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define MVSGI_ABI_VERSION 6   /* 6: mvsgi_sweep_max_cams (masked-variance sweep for rigs of up to 8 cameras); 5: mvsgi_softargmin_scaled_f32 (soft-argmin at any interp_scale_factor); 4: mvsgi_instance_norm_f32, mvsgi_instance_norm_ws_bytes (norm_type 'instance'); 3: mvsgi_conv3d_d32_applies, mvsgi_conv3d_up2_d32_applies + MVSGI_CONV_BF16X3_D32; 2: mvsgi_saturation_flags; the symbol set of round 5 */
+#define MVSGI_ABI_VERSION 7   /* 7: mvsgi_resample_bilinear_u8_f32, mvsgi_resample_bilinear_f32, mvsgi_resample_validity_u8, mvsgi_resample_u8_table_f32, mvsgi_rays_equirect_surrogate_f32 (fisheye -> surrogate-view resampler); 6: mvsgi_sweep_max_cams (masked-variance sweep for rigs of up to 8 cameras); 5: mvsgi_softargmin_scaled_f32 (soft-argmin at any interp_scale_factor); 4: mvsgi_instance_norm_f32, mvsgi_instance_norm_ws_bytes (norm_type 'instance'); 3: mvsgi_conv3d_d32_applies, mvsgi_conv3d_up2_d32_applies + MVSGI_CONV_BF16X3_D32; 2: mvsgi_saturation_flags; the symbol set of round 5 */
 
 typedef void* mvsgi_stream_t;
 
@@ -321,6 +321,34 @@ int mvsgi_grid_double_sphere_f32(const float* points, float* grid, unsigned char
                                  float xi, float alpha, float fx, float fy, float cx, float cy,
                                  int calib_h, int calib_w, float w2, mvsgi_stream_t stream);
 int mvsgi_grid_equirect_f32(const float* points, float* grid, int B, long long M, mvsgi_stream_t stream);
+/* rays [3][H][W] of the pixel centres of an H x W equirectangular surrogate view (align_corners=False): u = (2j+1)/W - 1,
+ * v = (2i+1)/H - 1, lon = pi u, lat = pi v / 2, p = (cos lat cos lon, sin lat, -cos lat sin lon); mvsgi_grid_equirect_f32
+ * of these rays returns (u, v). */
+int mvsgi_rays_equirect_surrogate_f32(float* rays, int H, int W, mvsgi_stream_t stream);
+
+/* ---- raw camera image -> surrogate view -------------------------------
+ * The reference's sample_input=True step (api/inference_pytorch.py:61-74) for double-sphere cameras, DEFINED as the
+ * composition of the reference's own closed forms (its image_sampler package is an empty submodule, so parity with that
+ * package is unpinned): per output pixel
+ *     out = valid ? bilinear_grid_sample(img, grid, align_corners=False) : invalid_value
+ * (model/backports/backports.py:11-86: zero padding, weights from the unclamped coordinates, Ia*wa + Ib*wb + Ic*wc + Id*wd
+ * left to right, no contraction).  The taps of an invalid pixel are not fetched; its grid may hold anything.
+ *   grid  [T][H][W][2] fp32, grid_sample coordinates of the raw image (16-byte aligned when W % 4 == 0)
+ *   valid [T][H][W]    uint8, non-zero = sample (4-byte aligned when W % 4 == 0)
+ *   out   [M][C][H][W] fp32 planar (16-byte aligned when W % 4 == 0); every element is written
+ * Image m uses table m % T (T cameras, M = frames x cameras; M % T == 0).
+ * _u8_f32: imgs [M][Hr][Wr][3] uint8, each byte converted as RN(k / 255.0f) (inference_pytorch.py:58-59); C = 3.
+ * _f32:    imgs [M][C][Hr][Wr] fp32, any C >= 1.
+ * Limits: raw row bytes < 2^23 and (Hr + 2) rows within 2^31 bytes; H * W < 2^31; M < 2^31. */
+int mvsgi_resample_bilinear_u8_f32(const unsigned char* imgs, const float* grid, const unsigned char* valid, float* out,
+                                   long long M, int T, int Hr, int Wr, int H, int W, float invalid_value, mvsgi_stream_t stream);
+int mvsgi_resample_bilinear_f32(const float* imgs, const float* grid, const unsigned char* valid, float* out, long long M, int T,
+                                int C, int Hr, int Wr, int H, int W, float invalid_value, mvsgi_stream_t stream);
+/* valid[i] = ds_mask[i] && |grid[i].x| <= 1 && |grid[i].y| <= 1 for n table entries (a NaN coordinate is invalid); once per rig */
+int mvsgi_resample_validity_u8(const float* grid, const unsigned char* ds_mask, unsigned char* valid, long long n,
+                               mvsgi_stream_t stream);
+/* the uint8 conversion table of the resampler, RN(k / 255.0f) for k = 0..255, copied to 256 host floats */
+int mvsgi_resample_u8_table_f32(float* table256);
 
 /* ---- deformable 2-D convolution with a given offset field ------------
  * SphereConvEquirect2d.forward + SphereConvBlk (common/common_modules.py:411-425, :509-547):

@@ -95,6 +95,24 @@ __global__ __launch_bounds__(256) void grid_equirect_kernel(const float* __restr
     grid[idx * 2 + 1] = (2.0f * lat) / pi_f;                            // :332
 }
 
+// Rays of the pixel centres of an H x W equirectangular surrogate view, [3][H][W]: the inverse of grid_equirect_kernel
+// under align_corners=False -- u = (2j+1)/W - 1, v = (2i+1)/H - 1, lon = pi u, lat = pi v / 2,
+// p = (cos lat cos lon, sin lat, -cos lat sin lon), so that grid_equirect(p) = (u, v).
+__global__ __launch_bounds__(256) void rays_equirect_surrogate_kernel(float* __restrict__ rays, int H, int W, float pi_f) {
+#pragma clang fp contract(off)
+    const long long total = (long long)H * W;
+    const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= total) return;
+    const int j = (int)(idx % W), i = (int)(idx / W);
+    const float u = (float)(2 * j + 1) / (float)W - 1.0f;
+    const float v = (float)(2 * i + 1) / (float)H - 1.0f;
+    const float lon = u * pi_f, lat = (v * pi_f) / 2.0f;
+    const float cl = cosf(lat);
+    rays[idx] = cl * cosf(lon);
+    rays[total + idx] = sinf(lat);
+    rays[2 * total + idx] = -(cl * sinf(lon));
+}
+
 inline int blocks_for(long long n, unsigned* out) {
     const long long nb = mvsgi::cdiv(n, 256);
     MVSGI_REQUIRE(n > 0 && nb < (1ll << 31), "grid generator: bad element count %lld", n);
@@ -115,6 +133,16 @@ extern "C" int mvsgi_rays_panorama_f32(const float* dist, float* rays, int N, in
     hipLaunchKernelGGL(rays_panorama_kernel, dim3(nb), dim3(256), 0, mvsgi::as_stream(stream), dist, rays, N, H, W, lat0,
                        lat_span, lon0, lon_span);
     return mvsgi::check_launch("mvsgi_rays_panorama_f32");
+}
+
+extern "C" int mvsgi_rays_equirect_surrogate_f32(float* rays, int H, int W, mvsgi_stream_t stream) {
+    MVSGI_REQUIRE(rays, "mvsgi_rays_equirect_surrogate_f32: null pointer");
+    MVSGI_REQUIRE(H > 0 && W > 0 && H < (1 << 24) && W < (1 << 24), "mvsgi_rays_equirect_surrogate_f32: bad dimension %d x %d", H, W);
+    unsigned nb;
+    if (blocks_for((long long)H * W, &nb)) return 1;
+    hipLaunchKernelGGL(rays_equirect_surrogate_kernel, dim3(nb), dim3(256), 0, mvsgi::as_stream(stream), rays, H, W,
+                       3.14159274101257324f /* float32(np.pi) */);
+    return mvsgi::check_launch("mvsgi_rays_equirect_surrogate_f32");
 }
 
 extern "C" int mvsgi_transform_points_f32(const float* T, const float* points, float* out, int B, long long M,

@@ -1,0 +1,240 @@
+// Fisheye -> surrogate-view resampler: raw camera images sampled through a per-camera table
+// (grid [T][H][W][2] in grid_sample coordinates of the raw image + validity [T][H][W]) into the fp32 planar
+// [M][C][H][W] views the RGB stem reads.  The table is rig-constant (dropin/image_sampler.py builds it once with the
+// kernels of grids.hip); this kernel is the per-frame part:
+//
+//   out = valid ? bilinear_grid_sample(img, grid, align_corners=False) : invalid_value
+//
+// with the arithmetic of the reference's own sampler (dsta_mvs/model/backports/backports.py:34-86), operation by
+// operation and with fp contraction off, exactly as K1 (sweep.hip) evaluates it: weights from the unclamped
+// coordinates, zero padding, Ia*wa + Ib*wb + Ic*wc + Id*wd summed left to right.  A uint8 image is converted as
+// the facade does (api/inference_pytorch.py:58-59: .float() / 255.0) through a 256-entry table of RN(k / 255.0f).
+//
+// One thread owns four consecutive output pixels of a row: 32 B of grid and 4 B of validity read contiguously,
+// one 16-byte store per channel plane.  Rows whose length is no multiple of four take the element-wise form of
+// the same thread shape.  The taps of an invalid pixel are never fetched (its grid may be anything, NaN included).
+// Image m uses table m % T: T cameras, M = frames x cameras.
+#include "common.hpp"
+
+namespace {
+
+struct Bilin {
+    int o00, o01, o10, o11;     // pixel offsets y*W+x, or -1 when the tap is outside
+    float w00, w01, w10, w11;   // weights of (x0,y0), (x0,y1), (x1,y0), (x1,y1)
+};
+
+// K1's bilin_setup (sweep.hip), verbatim
+__device__ __forceinline__ Bilin bilin_setup(float gx, float gy, int W, int H) {
+#pragma clang fp contract(off)
+    Bilin t;
+    // backports.py:41-42 (align_corners=False)
+    const float x = ((gx + 1.0f) * (float)W - 1.0f) / 2.0f;
+    const float y = ((gy + 1.0f) * (float)H - 1.0f) / 2.0f;
+    const float xf = floorf(x), yf = floorf(y);
+    const float x1f = xf + 1.0f, y1f = yf + 1.0f;
+    // backports.py:52-55: weights from the unclamped coordinates
+    t.w00 = (x1f - x) * (y1f - y);
+    t.w01 = (x1f - x) * (y - yf);
+    t.w10 = (x - xf) * (y1f - y);
+    t.w11 = (x - xf) * (y - yf);
+    // anything further out than one texel is outside anyway; clamping first keeps the
+    // float->int conversion defined for huge or NaN coordinates
+    const int x0 = (int)fminf(fmaxf(xf, -2.0f), (float)W + 1.0f);
+    const int y0 = (int)fminf(fmaxf(yf, -2.0f), (float)H + 1.0f);
+    const int x1 = x0 + 1, y1 = y0 + 1;
+    const bool vx0 = (x0 >= 0) & (x0 < W), vx1 = (x1 >= 0) & (x1 < W);
+    const bool vy0 = (y0 >= 0) & (y0 < H), vy1 = (y1 >= 0) & (y1 < H);
+    t.o00 = (vx0 & vy0) ? y0 * W + x0 : -1;
+    t.o01 = (vx0 & vy1) ? y1 * W + x0 : -1;
+    t.o10 = (vx1 & vy0) ? y0 * W + x1 : -1;
+    t.o11 = (vx1 & vy1) ? y1 * W + x1 : -1;
+    return t;
+}
+
+// K1's bilin_fetch for a fp32 plane
+__device__ __forceinline__ float bilin_fetch(const float* __restrict__ plane, const Bilin& t) {
+#pragma clang fp contract(off)
+    // zero padding: a tap outside the image reads 0 (backports.py:58-72)
+    const float i00 = t.o00 >= 0 ? plane[t.o00] : 0.0f;
+    const float i01 = t.o01 >= 0 ? plane[t.o01] : 0.0f;
+    const float i10 = t.o10 >= 0 ? plane[t.o10] : 0.0f;
+    const float i11 = t.o11 >= 0 ? plane[t.o11] : 0.0f;
+    // backports.py:86: Ia*wa + Ib*wb + Ic*wc + Id*wd, left to right
+    return ((i00 * t.w00 + i01 * t.w01) + i10 * t.w10) + i11 * t.w11;
+}
+
+// the same for channel c of an interleaved uint8 RGB image; lut[k] = RN(k / 255.0f)
+__device__ __forceinline__ float bilin_fetch_u8(const unsigned char* __restrict__ img, int c, const float* lut, const Bilin& t) {
+#pragma clang fp contract(off)
+    const float i00 = t.o00 >= 0 ? lut[img[t.o00 * 3 + c]] : 0.0f;
+    const float i01 = t.o01 >= 0 ? lut[img[t.o01 * 3 + c]] : 0.0f;
+    const float i10 = t.o10 >= 0 ? lut[img[t.o10 * 3 + c]] : 0.0f;
+    const float i11 = t.o11 >= 0 ? lut[img[t.o11 * 3 + c]] : 0.0f;
+    return ((i00 * t.w00 + i01 * t.w01) + i10 * t.w10) + i11 * t.w11;
+}
+
+typedef float f32x4_t __attribute__((ext_vector_type(4)));
+
+// RN(k / 255.0f), k = 0..255, evaluated by the host compiler (IEEE single division)
+struct U8Table {
+    float v[256];
+};
+constexpr U8Table make_u8_table() {
+    U8Table t{};
+    for (int k = 0; k < 256; ++k) t.v[k] = (float)k / 255.0f;
+    return t;
+}
+constexpr U8Table kU8Host = make_u8_table();
+__constant__ U8Table kU8Dev = make_u8_table();
+
+enum ResampleIn { U8HWC3 = 0, F32CHW = 1 };
+
+struct ResampleDims {
+    long long M;      // images
+    int T, C, Hr, Wr, H, W;
+    int Wq;           // threads per output row: ceil(W / 4)
+};
+
+// IN: layout of the raw images.  VEC: W % 4 == 0 (16-byte table reads and stores); otherwise element-wise with a row tail.
+template <int IN, bool VEC>
+__global__ __launch_bounds__(256) void resample_bilinear_kernel(const void* __restrict__ imgs, const float* __restrict__ grid,
+                                                                const unsigned char* __restrict__ valid,
+                                                                float* __restrict__ out, ResampleDims s, float invalid_value) {
+#pragma clang fp contract(off)
+    __shared__ float lut[IN == U8HWC3 ? 256 : 1];
+    if (IN == U8HWC3) {
+        lut[threadIdx.x] = kU8Dev.v[threadIdx.x];
+        __syncthreads();
+    }
+    const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= s.M * s.H * s.Wq) return;
+    const int j = (int)(idx % s.Wq) * 4;
+    const long long row = idx / s.Wq;
+    const int i = (int)(row % s.H);
+    const long long m = row / s.H;
+    const int t = (int)(m % s.T);
+    const int n = VEC ? 4 : min(4, s.W - j);                            // pixels of this thread inside the row
+    const long long tab = ((long long)t * s.H + i) * s.W + j;           // first table entry of this thread
+
+    float gx[4], gy[4];
+    bool ok[4];
+    if (VEC) {
+        const f32x4_t g0 = *reinterpret_cast<const f32x4_t*>(grid + tab * 2);
+        const f32x4_t g1 = *reinterpret_cast<const f32x4_t*>(grid + tab * 2 + 4);
+        const unsigned v = *reinterpret_cast<const unsigned*>(valid + tab);
+        gx[0] = g0.x, gy[0] = g0.y, gx[1] = g0.z, gy[1] = g0.w;
+        gx[2] = g1.x, gy[2] = g1.y, gx[3] = g1.z, gy[3] = g1.w;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) ok[k] = ((v >> (8 * k)) & 0xffu) != 0;
+    } else {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            ok[k] = k < n && valid[tab + k] != 0;
+            gx[k] = ok[k] ? grid[(tab + k) * 2] : 0.0f;
+            gy[k] = ok[k] ? grid[(tab + k) * 2 + 1] : 0.0f;
+        }
+    }
+    Bilin bt[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) bt[k] = bilin_setup(gx[k], gy[k], s.Wr, s.Hr);
+
+    const long long HWr = (long long)s.Hr * s.Wr, HW = (long long)s.H * s.W;
+    float* o = out + ((m * s.C) * s.H + i) * s.W + j;                     // channel 0; + c * HW per plane
+    auto channel = [&](int c) {
+        float r[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            r[k] = invalid_value;
+            if (ok[k]) {                                                // an invalid pixel's taps are not fetched
+                if (IN == U8HWC3)
+                    r[k] = bilin_fetch_u8(static_cast<const unsigned char*>(imgs) + m * HWr * 3, c, lut, bt[k]);
+                else
+                    r[k] = bilin_fetch(static_cast<const float*>(imgs) + (m * s.C + c) * HWr, bt[k]);
+            }
+        }
+        if (VEC) {
+            *reinterpret_cast<f32x4_t*>(o + c * HW) = f32x4_t{r[0], r[1], r[2], r[3]};
+        } else {
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+                if (k < n) o[c * HW + k] = r[k];
+        }
+    };
+    if (IN == U8HWC3) {
+        channel(0), channel(1), channel(2);
+    } else {
+#pragma unroll 1
+        for (int c = 0; c < s.C; ++c) channel(c);
+    }
+}
+
+// rig validity of the resampler: ds_mask & |gx| <= 1 & |gy| <= 1 (a NaN coordinate compares false: invalid)
+__global__ __launch_bounds__(256) void resample_validity_kernel(const float* __restrict__ grid, const unsigned char* __restrict__ ds_mask,
+                                                                unsigned char* __restrict__ valid, long long n) {
+    const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= n) return;
+    const float gx = grid[idx * 2], gy = grid[idx * 2 + 1];
+    valid[idx] = (ds_mask[idx] != 0 && fabsf(gx) <= 1.0f && fabsf(gy) <= 1.0f) ? 1 : 0;
+}
+
+int launch_resample(const char* what, int in, const void* imgs, const float* grid, const unsigned char* valid, float* out,
+                    long long M, int T, int C, int Hr, int Wr, int H, int W, float invalid_value, mvsgi_stream_t stream) {
+    MVSGI_REQUIRE(imgs && grid && valid && out, "%s: null pointer", what);
+    MVSGI_REQUIRE(T >= 1, "%s: T = %d tables (need T >= 1)", what, T);
+    MVSGI_REQUIRE(M >= 1 && M % T == 0, "%s: M = %lld images is no multiple of T = %d tables", what, M, T);
+    MVSGI_REQUIRE(C >= 1 && Hr >= 1 && Wr >= 1 && H >= 1 && W >= 1, "%s: non-positive dimension", what);
+    // tap offsets are 32-bit: (y * Wr + x) * 3 + c for the interleaved bytes, y * Wr + x within a fp32 plane, y up to Hr + 1
+    const long long row_bytes = (long long)Wr * (in == U8HWC3 ? 3 : 4);
+    MVSGI_REQUIRE(row_bytes < (1ll << 23) && ((long long)Hr + 2) * row_bytes < (1ll << 31),
+                  "%s: raw image %d x %d: row bytes %lld (limit 2^23) or image bytes beyond the 32-bit tap offsets", what, Hr, Wr,
+                  row_bytes);
+    MVSGI_REQUIRE((long long)H * W < (1ll << 31) && M < (1ll << 31), "%s: view %d x %d or batch %lld too large", what, H, W, M);
+    const bool vec = W % 4 == 0;
+    if (vec)
+        MVSGI_REQUIRE(((uintptr_t)grid % 16 == 0) && ((uintptr_t)out % 16 == 0) && ((uintptr_t)valid % 4 == 0),
+                      "%s: grid and out must be 16-byte aligned, valid 4-byte aligned", what);
+    ResampleDims s{M, T, C, Hr, Wr, H, W, (W + 3) / 4};
+    const long long nb = mvsgi::cdiv(M * H * s.Wq, 256);
+    MVSGI_REQUIRE(nb < (1ll << 31), "%s: %lld blocks (M * H * W too large for one launch)", what, nb);
+    hipStream_t st = mvsgi::as_stream(stream);
+#define MVSGI_RESAMPLE_LAUNCH(IN, VEC)                                                                                      \
+    hipLaunchKernelGGL((resample_bilinear_kernel<IN, VEC>), dim3((unsigned)nb), dim3(256), 0, st, imgs, grid, valid, out, s, \
+                       invalid_value)
+    if (in == U8HWC3) {
+        if (vec) MVSGI_RESAMPLE_LAUNCH(U8HWC3, true); else MVSGI_RESAMPLE_LAUNCH(U8HWC3, false);
+    } else {
+        if (vec) MVSGI_RESAMPLE_LAUNCH(F32CHW, true); else MVSGI_RESAMPLE_LAUNCH(F32CHW, false);
+    }
+#undef MVSGI_RESAMPLE_LAUNCH
+    return mvsgi::check_launch(what);
+}
+
+}  // namespace
+
+extern "C" int mvsgi_resample_bilinear_u8_f32(const unsigned char* imgs, const float* grid, const unsigned char* valid, float* out,
+                                              long long M, int T, int Hr, int Wr, int H, int W, float invalid_value,
+                                              mvsgi_stream_t stream) {
+    return launch_resample("mvsgi_resample_bilinear_u8_f32", U8HWC3, imgs, grid, valid, out, M, T, 3, Hr, Wr, H, W, invalid_value,
+                           stream);
+}
+
+extern "C" int mvsgi_resample_bilinear_f32(const float* imgs, const float* grid, const unsigned char* valid, float* out, long long M,
+                                           int T, int C, int Hr, int Wr, int H, int W, float invalid_value, mvsgi_stream_t stream) {
+    return launch_resample("mvsgi_resample_bilinear_f32", F32CHW, imgs, grid, valid, out, M, T, C, Hr, Wr, H, W, invalid_value,
+                           stream);
+}
+
+extern "C" int mvsgi_resample_validity_u8(const float* grid, const unsigned char* ds_mask, unsigned char* valid, long long n,
+                                          mvsgi_stream_t stream) {
+    MVSGI_REQUIRE(grid && ds_mask && valid, "mvsgi_resample_validity_u8: null pointer");
+    const long long nb = mvsgi::cdiv(n, 256);
+    MVSGI_REQUIRE(n > 0 && nb < (1ll << 31), "mvsgi_resample_validity_u8: bad element count %lld", n);
+    hipLaunchKernelGGL(resample_validity_kernel, dim3((unsigned)nb), dim3(256), 0, mvsgi::as_stream(stream), grid, ds_mask, valid, n);
+    return mvsgi::check_launch("mvsgi_resample_validity_u8");
+}
+
+extern "C" int mvsgi_resample_u8_table_f32(float* table256) {
+    MVSGI_REQUIRE(table256, "mvsgi_resample_u8_table_f32: null pointer");
+    memcpy(table256, kU8Host.v, sizeof(kU8Host.v));
+    return 0;
+}

@@ -5,4 +5,6 @@ from .distance_regressor import DistanceRegressorWithFixedCandidates  # noqa: F4
 from .torch_only import SphericalSweepStereoBase  # noqa: F401
 from .feature_extractor import (BaseConvBlk2d, ResConvBlk2d, SimpleFeatExtraction, SphereConvEquirect2d,  # noqa: F401
                                 SphereConvBlk, SphereEquirectFeatExtraction)
+from .image_sampler import (DoubleSphereToEquirectSampler, NoOpSampler, equirect_surrogate_rays, sample_masks,  # noqa: F401
+                            stack_tables)
 from .install import install, uninstall  # noqa: F401

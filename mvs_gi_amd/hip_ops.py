@@ -905,6 +905,42 @@ def resize_trilinear(x, size) -> torch.Tensor:
     return y
 
 
+def resample_bilinear(imgs, grid, valid, invalid_value: float = 0.0, out=None) -> torch.Tensor:
+    """Raw camera images through a per-camera sampling table -> fp32 planar views [M, C, H, W]:
+    out = valid ? bilinear_grid_sample(img, grid, align_corners=False) : invalid_value (backports.py:11-86 arithmetic).
+    imgs: uint8 [M, Hr, Wr, 3] (each byte / 255 first) or fp32 [M, C, Hr, Wr]; grid [T, H, W, 2] fp32; valid [T, H, W] bool or
+    uint8.  Image m uses table m % T.  One launch on the images' stream; `out`, when given, is written in place."""
+    if not isinstance(imgs, torch.Tensor) or imgs.dtype not in (torch.uint8, torch.float32):
+        raise TypeError(f"imgs: expected a uint8 [M, Hr, Wr, 3] or fp32 [M, C, Hr, Wr] tensor, got {getattr(imgs, 'dtype', type(imgs))}")
+    u8 = imgs.dtype == torch.uint8
+    imgs = _dev(imgs, "imgs", imgs.dtype)
+    grid = _dev(grid, "grid")
+    if not isinstance(valid, torch.Tensor) or valid.dtype not in (torch.bool, torch.uint8):
+        raise TypeError(f"valid: expected a bool or uint8 tensor, got {getattr(valid, 'dtype', type(valid))}")
+    valid = _dev(valid, "valid", valid.dtype)
+    if imgs.dim() != 4 or (u8 and imgs.shape[3] != 3):
+        raise AssertionError(f"imgs must be uint8 [M, Hr, Wr, 3] or fp32 [M, C, Hr, Wr], got {imgs.dtype} {tuple(imgs.shape)}")
+    if grid.dim() != 4 or grid.shape[3] != 2 or tuple(valid.shape) != tuple(grid.shape[:3]):
+        raise AssertionError(f"grid must be [T, H, W, 2] and valid [T, H, W], got {tuple(grid.shape)}, {tuple(valid.shape)}")
+    if u8:
+        M, Hr, Wr, C = imgs.shape
+    else:
+        M, C, Hr, Wr = imgs.shape
+    T, Ho, Wo = valid.shape
+    if out is None:
+        out = torch.empty((M, C, Ho, Wo), device=imgs.device, dtype=torch.float32)
+    elif tuple(out.shape) != (M, C, Ho, Wo) or out.dtype != torch.float32 or out.device != imgs.device or not out.is_contiguous() \
+            or out.data_ptr() % 16:
+        raise AssertionError(f"out must be a contiguous, 16-byte aligned fp32 [{M}, {C}, {Ho}, {Wo}] tensor on {imgs.device}")
+    if u8:
+        _call("mvsgi_resample_bilinear_u8_f32", imgs.data_ptr(), grid.data_ptr(), valid.data_ptr(), out.data_ptr(), M, T, Hr, Wr, Ho, Wo,
+              float(invalid_value), _stream_ptr(imgs))
+    else:
+        _call("mvsgi_resample_bilinear_f32", imgs.data_ptr(), grid.data_ptr(), valid.data_ptr(), out.data_ptr(), M, T, C, Hr, Wr, Ho, Wo,
+              float(invalid_value), _stream_ptr(imgs))
+    return out
+
+
 def instance_norm(x, res=None, gamma=None, beta=None, eps: float = 1e-5, neg_slope: float = 1.0, out=None) -> torch.Tensor:
     """Instance norm with input statistics on channels-last x [B, ..., C] (NDHWC or NHWC), per frame and channel over all spatial
     positions (F.instance_norm, biased variance): y = act((x - mean) / sqrt(var + eps) * gamma + beta (+ res)), act(v) = v if

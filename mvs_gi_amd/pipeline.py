@@ -282,12 +282,33 @@ class InferencePipeline:
     """Build-owned counterpart of InferencePytorch.__call__ (api/inference_class.py:120-127): uint8
     HWC camera images in, metric inverse distance (inv_dist / bf) as a host array out.  The uint8 ->
     float / 255 conversion is folded into the extractor's stem kernel and the division by bf into the
-    soft-argmin kernel, so the only host traffic is the image upload and the result download."""
+    soft-argmin kernel, so the only host traffic is the image upload and the result download.
 
-    def __init__(self, cfg: PathConfig, weights, consts, device="cuda", extractor: str = "simple"):
+    With `samplers` (one dropin.DoubleSphereToEquirectSampler per camera: the facade's sample_input=True,
+    inference_pytorch.py:61-74) the images are the cameras' RAW uint8 frames [N, Hr, Wr, 3]: one resample launch turns them
+    into the fp32 surrogate views [N, 3, H, W] the extractor's fp32 stem reads."""
+
+    def __init__(self, cfg: PathConfig, weights, consts, device="cuda", extractor: str = "simple", samplers=None, raw_masks=None):
         """extractor: 'simple' = SimpleFeatExtraction (G16V, config29), 'sphere' = SphereEquirectFeatExtraction with the
-        sphere-convolution final layer (G16VV, config103; configs/feature_extractor/sphereconv_featext.yaml)."""
+        sphere-convolution final layer (G16VV, config103; configs/feature_extractor/sphereconv_featext.yaml).
+        samplers / raw_masks: per-camera image samplers and raw-resolution masks; with both, consts["masks"] may be omitted
+        (it is dropin.sample_masks(samplers, raw_masks))."""
         self.cfg = cfg
+        self.samplers = None
+        if samplers is not None:
+            if len(samplers) != cfg.num_cams:
+                raise ValueError(f"{len(samplers)} samplers for a rig of {cfg.num_cams} cameras")
+            self.samplers = list(samplers)
+            self._table = dropin.stack_tables(self.samplers)          # rig constants, built before any capture
+            if tuple(self._table[1].shape[1:]) != (4 * cfg.feat_hw[0], 4 * cfg.feat_hw[1]):
+                raise ValueError(f"the samplers' out_shape {tuple(self._table[1].shape[1:])} is not the extractor's input size "
+                                 f"{(4 * cfg.feat_hw[0], 4 * cfg.feat_hw[1])}")
+            if "masks" not in consts:
+                if raw_masks is None:
+                    raise ValueError('consts["masks"] may only be omitted when raw_masks are given')
+                consts = dict(consts, masks=dropin.sample_masks(self.samplers, raw_masks).cpu().numpy())
+        elif raw_masks is not None:
+            raise ValueError("raw_masks need samplers")
         self.hot = HotPath(cfg, weights, consts, device)
         Hi, Wi = cfg.feat_hw
         Extractor = {"simple": dropin.SimpleFeatExtraction, "sphere": dropin.SphereEquirectFeatExtraction}[extractor]
@@ -320,7 +341,12 @@ class InferencePipeline:
 
     @torch.no_grad()
     def forward_device(self, imgs_u8: torch.Tensor) -> torch.Tensor:
-        """uint8 [N, H, W, 3] images of one frame on the device -> inv_dist / bf [1, 1, H, W] on the device."""
+        """uint8 [N, H, W, 3] images of one frame on the device (raw [N, Hr, Wr, 3] with samplers) -> inv_dist / bf
+        [1, 1, H, W] on the device."""
+        if self.samplers is not None:
+            if imgs_u8.dtype != torch.uint8:
+                raise TypeError("InferencePipeline expects uint8 HWC camera images")
+            imgs_u8 = H.resample_bilinear(imgs_u8, *self._table)   # fp32 [N, 3, H, W]: the fp32 RGB stem's input
         f = self.feature_extractor(imgs_u8)                        # [N, C, Hi, Wi], channels-last storage
         inv, _ = self.hot(f.unsqueeze(0))
         return inv

@@ -16,8 +16,8 @@
 //                                            hardware range check), XCD-contiguous block order;
 //   sweep_validity_kernel + sweep_std_nhwc_v_kernel   the default: the rig-constant mask half evaluated once
 //                                            per rig, the per-frame kernel walks the candidates of a row
-//                                            with the next candidate's grid point prefetched
-//                                            (sweep_std_nhwc_v_wide_kernel for rigs of 5 to 8 cameras).
+//                                            with the next candidate's grid point(s) prefetched (one template
+//                                            for 1 to 8 cameras; from 5 on a lane carries two grid points).
 #include "common.hpp"
 
 #include <type_traits>
@@ -99,6 +99,7 @@ __device__ __forceinline__ float bilin_fetch(const float* __restrict__ plane, co
 }
 
 typedef float f32x4_t __attribute__((ext_vector_type(4)));
+typedef float f32x2_t __attribute__((ext_vector_type(2)));
 
 // Correctly rounded x / d for a small positive integer-valued d, given inv = RN(1 / d):
 // q = RN(x * inv); r = x - d*q (exact in an fma); q' = RN(q + r * inv)  (Markstein).  Identical to
@@ -423,28 +424,62 @@ __device__ __forceinline__ Bilin quad_bcast(const Bilin& m) {
     t.w11 = quad_bcast_f<CAM>(m.w11);
     return t;
 }
+template <int NG>
+__device__ __forceinline__ void quad_bcast_group(Bilin (&ft)[NG], const Bilin& mine) {     // cameras 0 .. NG - 1 of a group of four
+    ft[0] = quad_bcast<0>(mine);
+    if constexpr (NG > 1) ft[1] = quad_bcast<1>(mine);
+    if constexpr (NG > 2) ft[2] = quad_bcast<2>(mine);
+    if constexpr (NG > 3) ft[3] = quad_bcast<3>(mine);
+}
 
-// Per-frame kernel with the validity byte.  A block owns 64 consecutive wo of one (b, ho) row and
-// walks `dchunk` candidates, fetching the NEXT candidate's grid point and validity byte before the
-// 12 texel gathers of the current one, so a voxel costs one exposed memory round trip instead of
-// three.  Logical block order (b, ho, d-chunk, w-tile), XCD-contiguous (see sweep_xcd_remap).
-#ifndef MVSGI_SWEEP_NT
-#define MVSGI_SWEEP_NT 0      // nt stores of the split-padded volume: measured neutral (post_vol reads it straight back)
-#endif
+// The four texels of one camera's taps t at channel byte cb (far: 0, or the sign bit, which sends the requests out of the
+// descriptor's range), and their blend on channel pairs (backports.py:86, left to right)
+__device__ __forceinline__ void gather4(f32x4_t (&tx)[4], __amdgpu_buffer_rsrc_t img, const Bilin t, int cb, int far) {
+    tx[0] = __builtin_bit_cast(f32x4_t, __builtin_amdgcn_raw_buffer_load_b128(img, (t.o00 + cb) | far, 0, 0));
+    tx[1] = __builtin_bit_cast(f32x4_t, __builtin_amdgcn_raw_buffer_load_b128(img, (t.o01 + cb) | far, 0, 0));
+    tx[2] = __builtin_bit_cast(f32x4_t, __builtin_amdgcn_raw_buffer_load_b128(img, (t.o10 + cb) | far, 0, 0));
+    tx[3] = __builtin_bit_cast(f32x4_t, __builtin_amdgcn_raw_buffer_load_b128(img, (t.o11 + cb) | far, 0, 0));
+}
+__device__ __forceinline__ f32x2_t blend4(const f32x4_t (&tx)[4], const Bilin t, int p) {
+#pragma clang fp contract(off)
+    const f32x2_t W00 = {t.w00, t.w00}, W01 = {t.w01, t.w01}, W10 = {t.w10, t.w10}, W11 = {t.w11, t.w11};
+    const f32x2_t i00 = {tx[0][2 * p], tx[0][2 * p + 1]}, i01 = {tx[1][2 * p], tx[1][2 * p + 1]};
+    const f32x2_t i10 = {tx[2][2 * p], tx[2][2 * p + 1]}, i11 = {tx[3][2 * p], tx[3][2 * p + 1]};
+    return ((i00 * W00 + i01 * W01) + i10 * W10) + i11 * W11;
+}
+
+// Per-frame kernel with the validity byte, for rigs of 1 to 8 cameras.  A block owns 64 consecutive wo of one (b, ho) row and
+// walks `dchunk` candidates, fetching the NEXT candidate's grid point(s) and validity byte before the texel gathers of the
+// current one, so a voxel costs one exposed memory round trip instead of three.  Logical block order (b, ho, d-chunk, w-tile),
+// XCD-contiguous (see sweep_xcd_remap).
+//
+// Lane q of a quad walks the grid of camera q and, for rigs of 5 to 8 cameras, of camera q + 4 as well (two grid points per
+// candidate), works out their taps as BYTE offsets and broadcasts them through the quad.  What depends on the rig's size:
+//   NCAM <= 4: the taps are broadcast once per candidate, and the taps of texels nobody needs are moved out of range there.
+//   NCAM > 4:  the cameras are gathered in two groups of (up to) four -- 16 texel quads in flight, as with 4 cameras, never 32 --
+//              and only a group's blended samples (four registers per camera) outlive it; the masked variance runs once both
+//              groups are in.  The taps travel per channel trip, so every lane of a quad makes every trip.  The reciprocal
+//              sequence of the two divisions is also left for tiny operands (below).
+// Everything else -- block decode, descriptors, validity decode, masked variance, exact-division branch, output stage, the walk --
+// is the same code for every rig.  Same bits as sweep_std_kernel<NCAM>.
+// (The body is kept in the order the compiler was given before the two kernels became one, down to where `sv` is declared and
+// the two forms of the grid cursors: every instantiation is instruction for instruction what it was, DESIGN.md section 2 K1.  Moving a
+// piece into a function of its own -- the output stage, the decode -- changes the generated code; gather4 / blend4 do not.)
 #ifndef MVSGI_SWEEP_WAVES
 #define MVSGI_SWEEP_WAVES 5      // waves per SIMD the register allocation aims at (experiment knob; 92 registers -> 5)
+#endif
+#ifndef MVSGI_SWEEP_WIDE_WAVES
+#define MVSGI_SWEEP_WIDE_WAVES 4      // waves per SIMD the register allocation of the 5..8-camera kernel aims at (<= 128 registers)
 #endif
 // F16: a split-padded output (vol_split) holds fp16 pairs instead of bf16 pairs (csrc/split_fmt.hpp; the variance is >= 0 and clamped
 // to fp16's range)
 template <int NCAM, bool C16, bool F16 = false>
-__global__ __launch_bounds__(256, MVSGI_SWEEP_WAVES) void sweep_std_nhwc_v_kernel(const float* __restrict__ feats,
-                                                               const float* __restrict__ grids,
-                                                               const unsigned char* __restrict__ vmask,
-                                                               float* __restrict__ vol, SweepDims s, int dchunk,
-                                                               int nd, int rig_shared, unsigned char* __restrict__ vol_split,
-                                                               unsigned* __restrict__ sat) {
+__global__ __launch_bounds__(256, NCAM <= 4 ? MVSGI_SWEEP_WAVES : MVSGI_SWEEP_WIDE_WAVES) void sweep_std_nhwc_v_kernel(
+    const float* __restrict__ feats, const float* __restrict__ grids, const unsigned char* __restrict__ vmask, float* __restrict__ vol,
+    SweepDims s, int dchunk, int nd, int rig_shared, unsigned char* __restrict__ vol_split, unsigned* __restrict__ sat) {
 #pragma clang fp contract(off)
-    static_assert(NCAM <= 4, "one camera per lane of a quad");
+    static_assert(NCAM >= 1 && NCAM <= 8, "one or two cameras per lane of a quad, one validity bit per camera in a byte");
+    constexpr bool WIDE = NCAM > 4;            // two grid points per lane and candidate, two groups of (up to) four cameras
     float satm = 0.f;          // fp16 split output: running maximum |value written| (range report, csrc/split_fmt.hpp)
     const int q = threadIdx.x & 3;
     const int WT = (s.Wo + 63) >> 6;
@@ -468,14 +503,24 @@ __global__ __launch_bounds__(256, MVSGI_SWEEP_WAVES) void sweep_std_nhwc_v_kerne
     for (int cam = 0; cam < NCAM; ++cam)
         img[cam] = __builtin_amdgcn_make_buffer_rsrc(
             const_cast<float*>(feats + (long long)(b * NCAM + cam) * HWi * s.C), 0, HWi * s.C * 4, 0x00020000);
-    // lane q walks camera q's grid (lanes beyond the rig re-read the last camera; unused)
-    const int mycam = q < NCAM ? q : NCAM - 1;
+    // lane q walks the grids of cameras q and q + 4 (lanes beyond the rig re-read the last camera; unused).
     // rig_shared: one grid / validity set for the whole batch (the rig constants of api/inference_class.py:40-45 are the
     // same for every frame): all frames read frame 0's, which then stay in L2 instead of streaming B copies from HBM
-    const int br = rig_shared ? 0 : b;
-    const float2* gp = reinterpret_cast<const float2*>(grids) + ((long long)(br * NCAM + mycam) * s.D + d0) * HW +
-                       (long long)ho * s.Wo + wo;
-    const unsigned char* vp = vmask + ((long long)br * s.D + d0) * HW + (long long)ho * s.Wo + wo;
+    const float2 *gp, *gp1;                            // gp1 (WIDE): the grid of camera q + 4
+    const unsigned char* vp;
+    if constexpr (!WIDE) {
+        const int mycam = q < NCAM ? q : NCAM - 1;
+        const int br = rig_shared ? 0 : b;
+        gp = gp1 = reinterpret_cast<const float2*>(grids) + ((long long)(br * NCAM + mycam) * s.D + d0) * HW + (long long)ho * s.Wo + wo;
+        vp = vmask + ((long long)br * s.D + d0) * HW + (long long)ho * s.Wo + wo;
+    } else {       // (the same cursors for cameras q and q + 4, the offset of candidate d0 added last)
+        const int cam1 = q + 4 < NCAM ? q + 4 : NCAM - 1;
+        const int br = rig_shared ? 0 : b;
+        const long long grow = (long long)d0 * HW + (long long)ho * s.Wo + wo;
+        gp = reinterpret_cast<const float2*>(grids) + (long long)(br * NCAM + q) * s.D * HW + grow;
+        gp1 = reinterpret_cast<const float2*>(grids) + (long long)(br * NCAM + cam1) * s.D * HW + grow;
+        vp = vmask + (long long)br * s.D * HW + grow;
+    }
     float* out = vol + ((((long long)b * s.D + d0) * s.Ho + ho) * s.Wo + wo) * s.C;
     const long long vstep = HW * s.C;
     // vol_split (C == 16): the volume goes out in the split-padded format of conv3d_rs.hip instead -- [B][D+2][Ho+2][Wo+2]
@@ -486,18 +531,15 @@ __global__ __launch_bounds__(256, MVSGI_SWEEP_WAVES) void sweep_std_nhwc_v_kerne
                                           ((q & 1) * 2 + (q >> 1)) * 16
                                     : nullptr;
     const long long sstep = (long long)(s.Ho + 2) * (s.Wo + 2) * 64;
-    // one candidate: grid point -> taps (lane q = camera q, broadcast through the quad) -> 4 x NCAM
-    // texel gathers -> masked variance
+    // one candidate: grid point(s) -> taps (lane q = cameras q, q + 4, broadcast through the quad) -> 4 x NCAM texel gathers ->
+    // masked variance -> store
     const int C4 = C16 ? 64 : s.C * 4, rowB = s.Wi * C4;
-    auto candidate = [&](const float2 gxy, const unsigned vm, float* __restrict__ o, unsigned char* __restrict__ os) {
-        typedef float f32x2_t __attribute__((ext_vector_type(2)));
-        // taps as BYTE offsets, worked out once by the camera's lane and broadcast through the quad
+    auto candidate = [&](const float2 gxy, const float2 gxy1, const unsigned vm, float* __restrict__ o, unsigned char* __restrict__ os) {
+        // taps as BYTE offsets, worked out once by the camera's lane
         const Bilin mine = bilin_setup_bytes(gxy.x, gxy.y, s.Wi, s.Hi, C4, rowB);
-        Bilin ft[NCAM];
-        ft[0] = quad_bcast<0>(mine);
-        if (NCAM > 1) ft[NCAM > 1 ? 1 : 0] = quad_bcast<1>(mine);
-        if (NCAM > 2) ft[NCAM > 2 ? 2 : 0] = quad_bcast<2>(mine);
-        if (NCAM > 3) ft[NCAM > 3 ? 3 : 0] = quad_bcast<3>(mine);
+        Bilin mine1, ft[WIDE ? 1 : NCAM];
+        if constexpr (WIDE) mine1 = bilin_setup_bytes(gxy1.x, gxy1.y, s.Wi, s.Hi, C4, rowB);
+        else quad_bcast_group(ft, mine);
         bool val[NCAM];
         f32x2_t VF[NCAM];
         float n = 0.0f;
@@ -512,303 +554,100 @@ __global__ __launch_bounds__(256, MVSGI_SWEEP_WAVES) void sweep_std_nhwc_v_kerne
         const float cnt = ok ? n : 1.0f;
         // A camera that is not valid at this voxel contributes sv * 0 to the sum and is replaced by the mean in the variance
         // (spherical_sweep_avg.py:114-119), and a voxel seen by fewer than two cameras is 0 whatever was sampled (:125): those
-        // texels are never needed.  Their tap offsets are sent out of the descriptor's range -- the loads return zeros and move no
+        // texels are never needed.  Their requests are sent out of the descriptor's range -- the loads return zeros and move no
         // data (same bits out for finite features: +-0 instead of +-0; a non-finite feature under an invalid camera would have
         // poisoned the reference's sum with NaN, here it is not read).  On the benchmark rig 35 % of the (voxel, camera) pairs.
-#ifndef MVSGI_SWEEP_GATHER_ALL
-#pragma unroll
-        for (int cam = 0; cam < NCAM; ++cam) {
-            const bool need = val[cam] & ok;
-            ft[cam].o00 = need ? ft[cam].o00 : (int)0x80000000;
-            ft[cam].o01 = need ? ft[cam].o01 : (int)0x80000000;
-            ft[cam].o10 = need ? ft[cam].o10 : (int)0x80000000;
-            ft[cam].o11 = need ? ft[cam].o11 : (int)0x80000000;
-        }
-#endif
-        // RN(1 / cnt) for the camera counts there are: exactly what the division 1.0f / cnt returns
-        const float inv = cnt == 2.0f ? 0.5f : cnt == 3.0f ? 0x1.555556p-2f : cnt == 4.0f ? 0.25f : 1.0f;
-        const f32x2_t INV = {inv, inv}, NCNT = {-cnt, -cnt};
-#pragma unroll 1
-        for (int cb = q * 16; cb < (C16 ? 64 : C4); cb += 64) {      // C16: one trip, the tap offsets die with the loads
-            f32x4_t tx[NCAM][4];
-#ifdef MVSGI_SWEEP_ABL_NOGATHER              // diagnostic builds only: every tap reads texel 0 (L1 hits)
-#pragma unroll
-            for (int cam = 0; cam < NCAM; ++cam) { ft[cam].o00 &= 64; ft[cam].o01 &= 64; ft[cam].o10 &= 64; ft[cam].o11 &= 64; }
-#endif
+        if constexpr (!WIDE) {
 #pragma unroll
             for (int cam = 0; cam < NCAM; ++cam) {
-#if MVSGI_SWEEP_SKIP_CAM
-                // a camera no voxel of this wave needs (validity is spatially coherent: whole waves fall outside a camera's image
-                // or mask) is not gathered at all: the kernel is bound by the texture addresser's instruction rate
-                // (profiles/r04_sweep_texture_path_counters.txt), and a range-checked-away gather still costs its instruction
-                if (__builtin_amdgcn_ballot_w64(val[cam] & ok) == 0) {
-                    tx[cam][0] = tx[cam][1] = tx[cam][2] = tx[cam][3] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-                    continue;
-                }
-#endif
-                tx[cam][0] = __builtin_bit_cast(f32x4_t, __builtin_amdgcn_raw_buffer_load_b128(img[cam], ft[cam].o00 + cb, 0, 0));
-                tx[cam][1] = __builtin_bit_cast(f32x4_t, __builtin_amdgcn_raw_buffer_load_b128(img[cam], ft[cam].o01 + cb, 0, 0));
-                tx[cam][2] = __builtin_bit_cast(f32x4_t, __builtin_amdgcn_raw_buffer_load_b128(img[cam], ft[cam].o10 + cb, 0, 0));
-                tx[cam][3] = __builtin_bit_cast(f32x4_t, __builtin_amdgcn_raw_buffer_load_b128(img[cam], ft[cam].o11 + cb, 0, 0));
+                const bool need = val[cam] & ok;
+                ft[cam].o00 = need ? ft[cam].o00 : (int)0x80000000;
+                ft[cam].o01 = need ? ft[cam].o01 : (int)0x80000000;
+                ft[cam].o10 = need ? ft[cam].o10 : (int)0x80000000;
+                ft[cam].o11 = need ? ft[cam].o11 : (int)0x80000000;
             }
-            f32x2_t sv[NCAM][2];
-#pragma unroll
-            for (int cam = 0; cam < NCAM; ++cam) {
-                const f32x2_t W00 = {ft[cam].w00, ft[cam].w00}, W01 = {ft[cam].w01, ft[cam].w01};
-                const f32x2_t W10 = {ft[cam].w10, ft[cam].w10}, W11 = {ft[cam].w11, ft[cam].w11};
-#pragma unroll
-                for (int p = 0; p < 2; ++p) {
-                    const f32x2_t i00 = {tx[cam][0][2 * p], tx[cam][0][2 * p + 1]}, i01 = {tx[cam][1][2 * p], tx[cam][1][2 * p + 1]};
-                    const f32x2_t i10 = {tx[cam][2][2 * p], tx[cam][2][2 * p + 1]}, i11 = {tx[cam][3][2 * p], tx[cam][3][2 * p + 1]};
-                    sv[cam][p] = ((i00 * W00 + i01 * W01) + i10 * W10) + i11 * W11;          // backports.py:86, left to right
-                }
-            }
-            // spherical_sweep_avg.py:106-125 on channel pairs.  The two divisions by cnt in {1, 2, 3, 4} are Markstein's
-            // q = RN(x inv), r = x - cnt q (exact in the fma), RN(q + r inv): the correctly rounded quotient for every finite x
-            // (cnt a power of two: q is already exact or correctly rounded; cnt = 3: r / 3 is a multiple of ulp / 3, never near
-            // a rounding boundary, down to the subnormals).  Sums beyond 1e30 (and infinities) take the hardware division.
-            f32x2_t sum[2], var[2];
-            f32x4_t r;
-            float big = 0.0f;
-#pragma unroll
-            for (int p = 0; p < 2; ++p) {
-                sum[p] = sv[0][p] * VF[0];
-#pragma unroll
-                for (int cam = 1; cam < NCAM; ++cam) sum[p] = sum[p] + sv[cam][p] * VF[cam];
-                const f32x2_t qa = sum[p] * INV;
-                const f32x2_t avg = __builtin_elementwise_fma(__builtin_elementwise_fma(NCNT, qa, sum[p]), INV, qa);
-#pragma unroll
-                for (int cam = 0; cam < NCAM; ++cam) {
-                    const f32x2_t t = {val[cam] ? sv[cam][p].x : avg.x, val[cam] ? sv[cam][p].y : avg.y};   // :119
-                    const f32x2_t df = t - avg;
-                    var[p] = cam == 0 ? df * df : var[p] + df * df;                                           // :122
-                }
-                const f32x2_t qv = var[p] * INV;
-                const f32x2_t v = __builtin_elementwise_fma(__builtin_elementwise_fma(NCNT, qv, var[p]), INV, qv);
-                r[2 * p] = ok ? v.x : 0.0f;                                                                   // :125
-                r[2 * p + 1] = ok ? v.y : 0.0f;
-                big = __builtin_fmaxf(__builtin_fmaxf(big, __builtin_fmaxf(__builtin_fabsf(sum[p].x), __builtin_fabsf(sum[p].y))),
-                                      __builtin_fmaxf(var[p].x, var[p].y));
-            }
-            if (__builtin_amdgcn_ballot_w64(big > 1e30f) != 0) {                 // wave-uniform, never taken on real features
-                float dv = cnt;
-                asm volatile("; exact-division path" : "+v"(dv));          // (opaque: keeps the divisions inside the branch)
-#pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    const float sm = sum[k >> 1][k & 1];
-                    const float avg = sm / dv;
-                    float vr = 0.0f;
-#pragma unroll
-                    for (int cam = 0; cam < NCAM; ++cam) {
-                        const float t = val[cam] ? sv[cam][k >> 1][k & 1] : avg;
-                        const float df = t - avg;
-                        vr = vr + df * df;
-                    }
-                    vr = vr / dv;
-                    r[k] = ok ? vr : 0.0f;
-                }
-            }
-            if (os) {
-                // x = hi + lo, hi = bf16(x) (RNE), lo = bf16(x - hi): the same split as the conv kernels' staging
-                unsigned hi[2], lo[2];
-#pragma unroll
-                for (int p = 0; p < 2; ++p) {
-                    if constexpr (F16) {
-                        const float a_ = sf_clamp<true>(r[2 * p]), b_ = sf_clamp<true>(r[2 * p + 1]);
-                        satm = sf_sat_acc(satm, a_, b_);
-                        const unsigned hb = sf_cvt_pk<true>(a_, b_);
-                        hi[p] = hb;
-                        lo[p] = sf_cvt_pk<true>(a_ - sf_widen_lo<true>(hb), b_ - sf_widen_hi<true>(hb));
-                    } else {
-                        typedef __bf16 b2_t __attribute__((ext_vector_type(2)));
-                        const f32x2_t v = {r[2 * p], r[2 * p + 1]};
-                        const unsigned hb = __builtin_bit_cast(unsigned, __builtin_convertvector(v, b2_t));
-                        const f32x2_t hf = {__builtin_bit_cast(float, hb << 16), __builtin_bit_cast(float, hb & 0xffff0000u)};
-                        hi[p] = hb;
-                        lo[p] = __builtin_bit_cast(unsigned, __builtin_convertvector(v - hf, b2_t));
-                    }
-                }
-                // even lanes keep their hi and take the odd neighbour's hi; odd lanes take the even neighbour's lo
-                const bool odd = (q & 1) != 0;
-                const unsigned r0 = (unsigned)__builtin_amdgcn_mov_dpp((int)(odd ? hi[0] : lo[0]), 0xB1, 0xf, 0xf, true);   // quad_perm [1,0,3,2]
-                const unsigned r1 = (unsigned)__builtin_amdgcn_mov_dpp((int)(odd ? hi[1] : lo[1]), 0xB1, 0xf, 0xf, true);
-                const uint4 piece = odd ? make_uint4(r0, r1, lo[0], lo[1]) : make_uint4(hi[0], hi[1], r0, r1);
-#ifdef MVSGI_SWEEP_ABL_NOSTORE               // diagnostic builds only
-                if (live && hi[0] == 0x12345678u) {
-#else
-                if (live) {
-#endif
-#if MVSGI_SWEEP_NT
-                    {
-                        typedef unsigned nt_u32x4 __attribute__((ext_vector_type(4)));
-                        __builtin_nontemporal_store(nt_u32x4{piece.x, piece.y, piece.z, piece.w}, reinterpret_cast<nt_u32x4*>(os));
-                    }
-#else
-                    *reinterpret_cast<uint4*>(os) = piece;
-#endif
-                }
-            } else if (live) *reinterpret_cast<f32x4_t*>(reinterpret_cast<char*>(o) + cb) = r;
         }
-    };
-    // two candidates per trip with ping-pong registers (A, B): the loads of the next candidate are
-    // issued before the gathers of the current one and nothing waits for them until its turn
-    float2 gA = *gp;
-    unsigned vA = *vp;
-    for (int d = d0; d < d1; d += 2) {
-        const bool hasB = d + 1 < d1;
-        const long long sB = hasB ? HW : 0;
-        const float2 gB = gp[sB];
-        const unsigned vB = vp[sB];
-        candidate(gA, vA, out, outs);
-        const long long sA = d + 2 < d1 ? 2 * HW : sB;
-        gA = gp[sA];
-        vA = vp[sA];
-        if (hasB) candidate(gB, vB, out + vstep, outs ? outs + sstep : nullptr);
-        gp += 2 * HW;
-        vp += 2 * HW;
-        out += 2 * vstep;
-        if (outs) outs += 2 * sstep;
-    }
-    if constexpr (F16) sf_sat_report(sat, kSatSweep, satm, kF16Max);
-}
-
-// The same kernel for rigs of 5 to 8 cameras (same arguments, block shape, block order and output formats).  A quad has four lanes,
-// so lane q sets up TWO cameras, q and q + 4: two grid points per candidate, both prefetched with the validity byte.  The cameras
-// are gathered in two groups of (up to) four -- 16 texel quads in flight, as in the 4-camera kernel, never 32 -- and only a group's
-// blended samples (four registers per camera) outlive it; the masked variance runs once both groups are in.  Arithmetic as above:
-// the cameras are added in order, camera 0 first (sweep_std_kernel's order), and the two divisions by the camera count are the
-// reciprocal-fma sequence, which is the correctly rounded quotient for 1e-30 <= |x| <= 1e30 (Markstein: y = RN(1 / d), q within an
-// ulp of x / d).  Below that range a quotient x / 6 can be an exact tie between two subnormals, which the sequence rounds the
-// wrong way, so tiny non-zero operands take the hardware division like the huge ones do.  Same bits as sweep_std_kernel<NCAM>.
-#ifndef MVSGI_SWEEP_WIDE_WAVES
-#define MVSGI_SWEEP_WIDE_WAVES 4      // waves per SIMD the register allocation of the 5..8-camera kernel aims at (<= 128 registers)
-#endif
-template <int NCAM, bool C16, bool F16 = false>
-__global__ __launch_bounds__(256, MVSGI_SWEEP_WIDE_WAVES) void sweep_std_nhwc_v_wide_kernel(const float* __restrict__ feats,
-                                                               const float* __restrict__ grids,
-                                                               const unsigned char* __restrict__ vmask,
-                                                               float* __restrict__ vol, SweepDims s, int dchunk,
-                                                               int nd, int rig_shared, unsigned char* __restrict__ vol_split,
-                                                               unsigned* __restrict__ sat) {
-#pragma clang fp contract(off)
-    static_assert(NCAM > 4 && NCAM <= 8, "two cameras per lane of a quad, one validity bit per camera in a byte");
-    typedef float f32x2_t __attribute__((ext_vector_type(2)));
-    float satm = 0.f;          // fp16 split output: running maximum |value written| (range report, csrc/split_fmt.hpp)
-    const int q = threadIdx.x & 3;
-    const int WT = (s.Wo + 63) >> 6;
-    int L = sweep_xcd_remap((int)blockIdx.x, (int)gridDim.x);
-    const int wt = L % WT;
-    L /= WT;
-    const int dc = L % nd;
-    L /= nd;
-    const int ho = L % s.Ho;
-    const int b = L / s.Ho;
-    int wo = wt * 64 + (threadIdx.x >> 2);
-    const bool live = wo < s.Wo;
-    if (!live) wo = s.Wo - 1;            // keep whole quads alive for the DPP broadcasts
-    const int d0 = dc * dchunk;
-    const int d1 = d0 + dchunk < s.D ? d0 + dchunk : s.D;
-    const int HWi = s.Hi * s.Wi;
-    const long long HW = (long long)s.Ho * s.Wo;
-
-    __amdgpu_buffer_rsrc_t img[NCAM];                  // one descriptor per camera image (wave-uniform)
-#pragma unroll
-    for (int cam = 0; cam < NCAM; ++cam)
-        img[cam] = __builtin_amdgcn_make_buffer_rsrc(
-            const_cast<float*>(feats + (long long)(b * NCAM + cam) * HWi * s.C), 0, HWi * s.C * 4, 0x00020000);
-    // lane q walks the grids of cameras q and q + 4 (lanes beyond the rig re-read the last camera; unused)
-    const int cam1 = q + 4 < NCAM ? q + 4 : NCAM - 1;
-    const int br = rig_shared ? 0 : b;                 // one grid / validity set for the whole batch (see above)
-    const long long grow = (long long)d0 * HW + (long long)ho * s.Wo + wo;
-    const float2* gp0 = reinterpret_cast<const float2*>(grids) + (long long)(br * NCAM + q) * s.D * HW + grow;
-    const float2* gp1 = reinterpret_cast<const float2*>(grids) + (long long)(br * NCAM + cam1) * s.D * HW + grow;
-    const unsigned char* vp = vmask + (long long)br * s.D * HW + grow;
-    float* out = vol + ((((long long)b * s.D + d0) * s.Ho + ho) * s.Wo + wo) * s.C;
-    const long long vstep = HW * s.C;
-    // vol_split (C == 16): split-padded records, every lane stores one whole 16 B piece (see the kernel above)
-    unsigned char* outs = vol_split ? vol_split + ((((long long)b * (s.D + 2) + d0 + 1) * (s.Ho + 2) + ho + 1) * (s.Wo + 2) + wo + 1) * 64 +
-                                          ((q & 1) * 2 + (q >> 1)) * 16
-                                    : nullptr;
-    const long long sstep = (long long)(s.Ho + 2) * (s.Wo + 2) * 64;
-    const int C4 = C16 ? 64 : s.C * 4, rowB = s.Wi * C4;
-    auto candidate = [&](const float2 g0, const float2 g1, const unsigned vm, float* __restrict__ o, unsigned char* __restrict__ os) {
-        // taps as BYTE offsets, worked out once by the cameras' lane and broadcast through the quad group by group
-        const Bilin mine0 = bilin_setup_bytes(g0.x, g0.y, s.Wi, s.Hi, C4, rowB);
-        const Bilin mine1 = bilin_setup_bytes(g1.x, g1.y, s.Wi, s.Hi, C4, rowB);
-        bool val[NCAM];
-        f32x2_t VF[NCAM];
-        float n = 0.0f;
-#pragma unroll
-        for (int cam = 0; cam < NCAM; ++cam) {
-            val[cam] = ((vm >> cam) & 1u) != 0;
-            const float vf = val[cam] ? 1.0f : 0.0f;
-            VF[cam] = f32x2_t{vf, vf};
-            n = n + vf;
-        }
-        const bool ok = n > 1.0f;
-        const float cnt = ok ? n : 1.0f;
         // RN(1 / cnt) for the camera counts there are: exactly what the division 1.0f / cnt returns
-        const float inv = cnt == 2.0f ? 0.5f : cnt == 3.0f ? 0x1.555556p-2f : cnt == 4.0f ? 0.25f : cnt == 5.0f ? 0x1.99999ap-3f :
+        const float inv = cnt == 2.0f ? 0.5f : cnt == 3.0f ? 0x1.555556p-2f : cnt == 4.0f ? 0.25f : !WIDE ? 1.0f : cnt == 5.0f ? 0x1.99999ap-3f :
                           cnt == 6.0f ? 0x1.555556p-3f : cnt == 7.0f ? 0x1.24924ap-3f : cnt == 8.0f ? 0.125f : 1.0f;
         const f32x2_t INV = {inv, inv}, NCNT = {-cnt, -cnt};
 #pragma unroll 1
-        // (every lane of a quad makes every trip -- the taps travel by DPP INSIDE the loop, and a lane that had left it would
-        // broadcast nothing: with C = 8 lanes 2 and 3 have no channels, yet they set up cameras 2, 3, 6, 7.  A lane beyond the
-        // channels gathers out of range and stores nothing.)
-        for (int cb0 = 0; cb0 < (C16 ? 64 : C4); cb0 += 64) {
-            const int cb = cb0 + q * 16;
-            const bool mych = C16 || cb < C4;
-            f32x2_t sv[NCAM][2];
-            // one group of cameras: taps through the quad, 4 gathers per camera, blend; only sv leaves it
-            auto group = [&](auto G_) {
-                constexpr int G = decltype(G_)::value, base = 4 * G, NG = NCAM - base < 4 ? NCAM - base : 4;
-                const Bilin& mine = G ? mine1 : mine0;
-                Bilin ft[NG];
-                ft[0] = quad_bcast<0>(mine);
-                if constexpr (NG > 1) ft[1] = quad_bcast<1>(mine);
-                if constexpr (NG > 2) ft[2] = quad_bcast<2>(mine);
-                if constexpr (NG > 3) ft[3] = quad_bcast<3>(mine);
-                f32x4_t tx[NG][4];
+        // C16: one trip, the tap offsets die with the loads.  WIDE: every lane of a quad makes every trip -- the taps travel by DPP
+        // INSIDE the loop, and a lane that had left it would broadcast nothing: with C = 8 lanes 2 and 3 have no channels, yet
+        // they set up cameras 2, 3, 6, 7.  A lane beyond the channels (!mych) gathers out of range and stores nothing.
+        for (int cb0 = WIDE ? 0 : q * 16; cb0 < (C16 ? 64 : C4); cb0 += 64) {
+            const int cb = WIDE ? cb0 + q * 16 : cb0;
+            const bool mych = !WIDE || C16 || cb < C4;
+            f32x4_t tx[WIDE ? 1 : NCAM][4];              // !WIDE: the texels of all cameras
+            if constexpr (!WIDE) {
 #pragma unroll
-                for (int c = 0; c < NG; ++c) {
-                    const bool need = val[base + c] & ok;
+                for (int cam = 0; cam < NCAM; ++cam) {
 #if MVSGI_SWEEP_SKIP_CAM
-                    // a camera no voxel of this wave needs is not gathered at all (the texture addresser's instruction rate bounds
-                    // the kernel; see above)
-                    if (__builtin_amdgcn_ballot_w64(need) == 0) {
-                        tx[c][0] = tx[c][1] = tx[c][2] = tx[c][3] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+                    // a camera no voxel of this wave needs (validity is spatially coherent: whole waves fall outside a camera's image
+                    // or mask) is not gathered at all: the kernel is bound by the texture addresser's instruction rate
+                    // (profiles/r04_sweep_texture_path_counters.txt), and a range-checked-away gather still costs its instruction
+                    if (__builtin_amdgcn_ballot_w64(val[cam] & ok) == 0) {
+                        tx[cam][0] = tx[cam][1] = tx[cam][2] = tx[cam][3] = f32x4_t{0.f, 0.f, 0.f, 0.f};
                         continue;
                     }
 #endif
-                    // texels nobody needs (camera invalid here, or fewer than two cameras): offsets out of the descriptor's range.
-                    // (the sign bit OR-ed into the final offset, not a select: image byte offsets are below 2^31, and a select between two addresses
-                    // becomes two loads under complementary exec masks with a wait between them)
-                    const int far = (need & mych) ? 0 : (int)0x80000000;
-                    tx[c][0] = __builtin_bit_cast(f32x4_t, __builtin_amdgcn_raw_buffer_load_b128(img[base + c], (ft[c].o00 + cb) | far, 0, 0));
-                    tx[c][1] = __builtin_bit_cast(f32x4_t, __builtin_amdgcn_raw_buffer_load_b128(img[base + c], (ft[c].o01 + cb) | far, 0, 0));
-                    tx[c][2] = __builtin_bit_cast(f32x4_t, __builtin_amdgcn_raw_buffer_load_b128(img[base + c], (ft[c].o10 + cb) | far, 0, 0));
-                    tx[c][3] = __builtin_bit_cast(f32x4_t, __builtin_amdgcn_raw_buffer_load_b128(img[base + c], (ft[c].o11 + cb) | far, 0, 0));
+                    gather4(tx[cam], img[cam], ft[cam], cb, 0);
                 }
+            }
+            f32x2_t sv[NCAM][2];
+            if constexpr (!WIDE) {
 #pragma unroll
-                for (int c = 0; c < NG; ++c) {
-                    const f32x2_t W00 = {ft[c].w00, ft[c].w00}, W01 = {ft[c].w01, ft[c].w01};
-                    const f32x2_t W10 = {ft[c].w10, ft[c].w10}, W11 = {ft[c].w11, ft[c].w11};
+                for (int cam = 0; cam < NCAM; ++cam) {
 #pragma unroll
-                    for (int p = 0; p < 2; ++p) {
-                        const f32x2_t i00 = {tx[c][0][2 * p], tx[c][0][2 * p + 1]}, i01 = {tx[c][1][2 * p], tx[c][1][2 * p + 1]};
-                        const f32x2_t i10 = {tx[c][2][2 * p], tx[c][2][2 * p + 1]}, i11 = {tx[c][3][2 * p], tx[c][3][2 * p + 1]};
-                        sv[base + c][p] = ((i00 * W00 + i01 * W01) + i10 * W10) + i11 * W11;          // backports.py:86, left to right
-                        // (opaque: the blend happens HERE, and the texels die here -- the compiler otherwise sinks it to the
-                        // reduction, behind the other group's gathers, and holds both groups' texels at once)
-                        asm volatile("" : "+v"(sv[base + c][p]));
+                    for (int p = 0; p < 2; ++p) sv[cam][p] = blend4(tx[cam], ft[cam], p);
+                }
+            } else {
+                // one group of (up to) four cameras: taps through the quad, 4 gathers per camera, blend; only sv leaves it
+                auto group = [&](auto G_) {
+                    constexpr int G = decltype(G_)::value, base = 4 * G, NGC = NCAM - base < 4 ? NCAM - base : 4;
+                    Bilin ft[NGC];
+                    quad_bcast_group(ft, G ? mine1 : mine);
+                    f32x4_t tx[NGC][4];
+#pragma unroll
+                    for (int c = 0; c < NGC; ++c) {
+                        const bool need = val[base + c] & ok;
+#if MVSGI_SWEEP_SKIP_CAM
+                        // a camera no voxel of this wave needs (validity is spatially coherent: whole waves fall outside a camera's image
+                        // or mask) is not gathered at all: the kernel is bound by the texture addresser's instruction rate
+                        // (profiles/r04_sweep_texture_path_counters.txt), and a range-checked-away gather still costs its instruction
+                        if (__builtin_amdgcn_ballot_w64(need) == 0) {
+                            tx[c][0] = tx[c][1] = tx[c][2] = tx[c][3] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+                            continue;
+                        }
+#endif
+                        // the sign bit OR-ed into the final offset, not a select as above: image byte offsets are below 2^31, and a
+                        // select between two addresses becomes two loads under complementary exec masks with a wait between them
+                        const int far = (need & mych) ? 0 : (int)0x80000000;
+                        gather4(tx[c], img[base + c], ft[c], cb, far);
                     }
-                }
-            };
-            group(std::integral_constant<int, 0>{});
-            group(std::integral_constant<int, 1>{});
-            // spherical_sweep_avg.py:106-125 on channel pairs, the cameras in order
+#pragma unroll
+                    for (int c = 0; c < NGC; ++c) {
+#pragma unroll
+                        for (int p = 0; p < 2; ++p) {
+                            sv[base + c][p] = blend4(tx[c], ft[c], p);
+                            // (opaque: the blend happens HERE, and the texels die here -- the compiler otherwise sinks it to the
+                            // reduction, behind the other group's gathers, and holds both groups' texels at once)
+                            asm volatile("" : "+v"(sv[base + c][p]));
+                        }
+                    }
+                };
+                group(std::integral_constant<int, 0>{});
+                group(std::integral_constant<int, 1>{});
+            }
+            // spherical_sweep_avg.py:106-125 on channel pairs, the cameras in order, camera 0 first (sweep_std_kernel's order).  The
+            // two divisions by cnt are Markstein's q = RN(x inv), r = x - cnt q (exact in the fma), RN(q + r inv), inv = RN(1 / cnt):
+            // the correctly rounded quotient for 1e-30 <= |x| <= 1e30 (cnt a power of two: q is already exact or correctly rounded;
+            // cnt = 3: r / 3 is a multiple of ulp / 3, never near a rounding boundary, down to the subnormals).  Sums beyond 1e30 (and
+            // infinities) take the hardware division; from 5 cameras on so do tiny non-zero operands: a quotient x / 6 below 1e-30
+            // can be an exact tie between two subnormals, which the sequence rounds the wrong way.
             f32x2_t sum[2], var[2];
             f32x4_t r;
+            float big = 0.0f;
             bool rare = false;
 #pragma unroll
             for (int p = 0; p < 2; ++p) {
@@ -827,13 +666,18 @@ __global__ __launch_bounds__(256, MVSGI_SWEEP_WIDE_WAVES) void sweep_std_nhwc_v_
                 const f32x2_t v = __builtin_elementwise_fma(__builtin_elementwise_fma(NCNT, qv, var[p]), INV, qv);
                 r[2 * p] = ok ? v.x : 0.0f;                                                                   // :125
                 r[2 * p + 1] = ok ? v.y : 0.0f;
+                if constexpr (!WIDE) {
+                    big = __builtin_fmaxf(__builtin_fmaxf(big, __builtin_fmaxf(__builtin_fabsf(sum[p].x), __builtin_fabsf(sum[p].y))),
+                                          __builtin_fmaxf(var[p].x, var[p].y));
+                } else {
 #pragma unroll
-                for (int k = 0; k < 2; ++k) {        // outside [1e-30, 1e30] (and not 0): not what the sequence is proven for
-                    const float as = __builtin_fabsf(sum[p][k]), av = var[p][k];
-                    rare |= (as != 0.0f && !(as >= 1e-30f && as <= 1e30f)) | (av != 0.0f && !(av >= 1e-30f && av <= 1e30f));
+                    for (int k = 0; k < 2; ++k) {        // outside [1e-30, 1e30] (and not 0): not what the sequence is proven for
+                        const float as = __builtin_fabsf(sum[p][k]), av = var[p][k];
+                        rare |= (as != 0.0f && !(as >= 1e-30f && as <= 1e30f)) | (av != 0.0f && !(av >= 1e-30f && av <= 1e30f));
+                    }
                 }
             }
-            if (__builtin_amdgcn_ballot_w64(rare) != 0) {                 // wave-uniform, never taken on real features
+            if (__builtin_amdgcn_ballot_w64(WIDE ? rare : big > 1e30f) != 0) {   // wave-uniform, never taken on real features
                 float dv = cnt;
                 asm volatile("; exact-division path" : "+v"(dv));          // (opaque: keeps the divisions inside the branch)
 #pragma unroll
@@ -880,22 +724,23 @@ __global__ __launch_bounds__(256, MVSGI_SWEEP_WIDE_WAVES) void sweep_std_nhwc_v_
             } else if (live & mych) *reinterpret_cast<f32x4_t*>(reinterpret_cast<char*>(o) + cb) = r;
         }
     };
-    // two candidates per trip with ping-pong registers (A, B), as above, with two grid points per candidate
-    float2 g0A = *gp0, g1A = *gp1;
+    // two candidates per trip with ping-pong registers (A, B): the loads of the next candidate are
+    // issued before the gathers of the current one and nothing waits for them until its turn
+    float2 gA = *gp, hA = WIDE ? *gp1 : gA;
     unsigned vA = *vp;
     for (int d = d0; d < d1; d += 2) {
         const bool hasB = d + 1 < d1;
         const long long sB = hasB ? HW : 0;
-        const float2 g0B = gp0[sB], g1B = gp1[sB];
+        const float2 gB = gp[sB], hB = WIDE ? gp1[sB] : gB;
         const unsigned vB = vp[sB];
-        candidate(g0A, g1A, vA, out, outs);
+        candidate(gA, hA, vA, out, outs);
         const long long sA = d + 2 < d1 ? 2 * HW : sB;
-        g0A = gp0[sA];
-        g1A = gp1[sA];
+        gA = gp[sA];
+        hA = WIDE ? gp1[sA] : gA;
         vA = vp[sA];
-        if (hasB) candidate(g0B, g1B, vB, out + vstep, outs ? outs + sstep : nullptr);
-        gp0 += 2 * HW;
-        gp1 += 2 * HW;
+        if (hasB) candidate(gB, hB, vB, out + vstep, outs ? outs + sstep : nullptr);
+        gp += 2 * HW;
+        if (WIDE) gp1 += 2 * HW;
         vp += 2 * HW;
         out += 2 * vstep;
         if (outs) outs += 2 * sstep;
@@ -1089,46 +934,14 @@ int sweep_std_nhwc_valid_impl(const float* feats, const float* grids, const unsi
     hipStream_t st = mvsgi::as_stream(stream);
     MVSGI_SAT_WORDS(sat);
     const dim3 grid((unsigned)nblk), block(256);
-    if (fmt) {      // split-padded output in the fp16 split (C == 16 checked above)
-        switch (N) {
-            case 1: hipLaunchKernelGGL((sweep_std_nhwc_v_kernel<1, true, true>), grid, block, 0, st, feats, grids, vmask, vol, s, dchunk, (int)nd, rig_shared, vol_split, sat); break;
-            case 2: hipLaunchKernelGGL((sweep_std_nhwc_v_kernel<2, true, true>), grid, block, 0, st, feats, grids, vmask, vol, s, dchunk, (int)nd, rig_shared, vol_split, sat); break;
-            case 3: hipLaunchKernelGGL((sweep_std_nhwc_v_kernel<3, true, true>), grid, block, 0, st, feats, grids, vmask, vol, s, dchunk, (int)nd, rig_shared, vol_split, sat); break;
-            case 4: hipLaunchKernelGGL((sweep_std_nhwc_v_kernel<4, true, true>), grid, block, 0, st, feats, grids, vmask, vol, s, dchunk, (int)nd, rig_shared, vol_split, sat); break;
-            case 5: hipLaunchKernelGGL((sweep_std_nhwc_v_wide_kernel<5, true, true>), grid, block, 0, st, feats, grids, vmask, vol, s, dchunk, (int)nd, rig_shared, vol_split, sat); break;
-            case 6: hipLaunchKernelGGL((sweep_std_nhwc_v_wide_kernel<6, true, true>), grid, block, 0, st, feats, grids, vmask, vol, s, dchunk, (int)nd, rig_shared, vol_split, sat); break;
-            case 7: hipLaunchKernelGGL((sweep_std_nhwc_v_wide_kernel<7, true, true>), grid, block, 0, st, feats, grids, vmask, vol, s, dchunk, (int)nd, rig_shared, vol_split, sat); break;
-            case 8: hipLaunchKernelGGL((sweep_std_nhwc_v_wide_kernel<8, true, true>), grid, block, 0, st, feats, grids, vmask, vol, s, dchunk, (int)nd, rig_shared, vol_split, sat); break;
-        }
-        return mvsgi::check_launch("mvsgi_sweep_std_nhwc_valid_split");
-    }
-    switch (N) {
-        case 1: if (C == 16) hipLaunchKernelGGL((sweep_std_nhwc_v_kernel<1, true>), grid, block, 0, st, feats, grids, vmask, vol, s, dchunk, (int)nd, rig_shared, vol_split, sat);
-                else hipLaunchKernelGGL((sweep_std_nhwc_v_kernel<1, false>), grid, block, 0, st, feats, grids, vmask, vol, s, dchunk, (int)nd, rig_shared, vol_split, sat);
-                break;
-        case 2: if (C == 16) hipLaunchKernelGGL((sweep_std_nhwc_v_kernel<2, true>), grid, block, 0, st, feats, grids, vmask, vol, s, dchunk, (int)nd, rig_shared, vol_split, sat);
-                else hipLaunchKernelGGL((sweep_std_nhwc_v_kernel<2, false>), grid, block, 0, st, feats, grids, vmask, vol, s, dchunk, (int)nd, rig_shared, vol_split, sat);
-                break;
-        case 3: if (C == 16) hipLaunchKernelGGL((sweep_std_nhwc_v_kernel<3, true>), grid, block, 0, st, feats, grids, vmask, vol, s, dchunk, (int)nd, rig_shared, vol_split, sat);
-                else hipLaunchKernelGGL((sweep_std_nhwc_v_kernel<3, false>), grid, block, 0, st, feats, grids, vmask, vol, s, dchunk, (int)nd, rig_shared, vol_split, sat);
-                break;
-        case 4: if (C == 16) hipLaunchKernelGGL((sweep_std_nhwc_v_kernel<4, true>), grid, block, 0, st, feats, grids, vmask, vol, s, dchunk, (int)nd, rig_shared, vol_split, sat);
-                else hipLaunchKernelGGL((sweep_std_nhwc_v_kernel<4, false>), grid, block, 0, st, feats, grids, vmask, vol, s, dchunk, (int)nd, rig_shared, vol_split, sat);
-                break;
-        case 5: if (C == 16) hipLaunchKernelGGL((sweep_std_nhwc_v_wide_kernel<5, true>), grid, block, 0, st, feats, grids, vmask, vol, s, dchunk, (int)nd, rig_shared, vol_split, sat);
-                else hipLaunchKernelGGL((sweep_std_nhwc_v_wide_kernel<5, false>), grid, block, 0, st, feats, grids, vmask, vol, s, dchunk, (int)nd, rig_shared, vol_split, sat);
-                break;
-        case 6: if (C == 16) hipLaunchKernelGGL((sweep_std_nhwc_v_wide_kernel<6, true>), grid, block, 0, st, feats, grids, vmask, vol, s, dchunk, (int)nd, rig_shared, vol_split, sat);
-                else hipLaunchKernelGGL((sweep_std_nhwc_v_wide_kernel<6, false>), grid, block, 0, st, feats, grids, vmask, vol, s, dchunk, (int)nd, rig_shared, vol_split, sat);
-                break;
-        case 7: if (C == 16) hipLaunchKernelGGL((sweep_std_nhwc_v_wide_kernel<7, true>), grid, block, 0, st, feats, grids, vmask, vol, s, dchunk, (int)nd, rig_shared, vol_split, sat);
-                else hipLaunchKernelGGL((sweep_std_nhwc_v_wide_kernel<7, false>), grid, block, 0, st, feats, grids, vmask, vol, s, dchunk, (int)nd, rig_shared, vol_split, sat);
-                break;
-        case 8: if (C == 16) hipLaunchKernelGGL((sweep_std_nhwc_v_wide_kernel<8, true>), grid, block, 0, st, feats, grids, vmask, vol, s, dchunk, (int)nd, rig_shared, vol_split, sat);
-                else hipLaunchKernelGGL((sweep_std_nhwc_v_wide_kernel<8, false>), grid, block, 0, st, feats, grids, vmask, vol, s, dchunk, (int)nd, rig_shared, vol_split, sat);
-                break;
-    }
-    return mvsgi::check_launch("mvsgi_sweep_std_nhwc_valid_f32");
+    // one kernel per (N, C == 16, split format); fmt != 0: split-padded output in the fp16 split (C == 16 checked above)
+    using Kernel = void (*)(const float*, const float*, const unsigned char*, float*, SweepDims, int, int, int, unsigned char*, unsigned*);
+#define SWEEP_V(NC) {sweep_std_nhwc_v_kernel<NC, false, false>, sweep_std_nhwc_v_kernel<NC, true, false>, sweep_std_nhwc_v_kernel<NC, true, true>}
+    static const Kernel table[8][3] = {SWEEP_V(1), SWEEP_V(2), SWEEP_V(3), SWEEP_V(4), SWEEP_V(5), SWEEP_V(6), SWEEP_V(7), SWEEP_V(8)};
+#undef SWEEP_V
+    hipLaunchKernelGGL(table[N - 1][fmt ? 2 : C == 16], grid, block, 0, st, feats, grids, vmask, vol, s, dchunk, (int)nd, rig_shared,
+                       vol_split, sat);
+    return mvsgi::check_launch(fmt ? "mvsgi_sweep_std_nhwc_valid_split" : "mvsgi_sweep_std_nhwc_valid_f32");
 }
 }  // namespace
 

@@ -1,8 +1,9 @@
 """GPU (MI355X): the masked-variance sweep for rigs of 5 to 8 cameras on the channels-last fast path
-(sweep_std_nhwc_v_wide_kernel, csrc/sweep.hip) -- against the reference's own outputs (tests/golden/wide_rig.npz), bit for bit
+(sweep_std_nhwc_v_kernel<N> with N > 4, csrc/sweep.hip) -- against the reference's own outputs (tests/golden/wide_rig.npz), bit for bit
 against the plane-gather kernel sweep_std_kernel<N> (the same arithmetic in the same order: no tolerance), both output formats,
 the divisions from subnormal to huge variances, several candidates per block, the range report, the whole path against the CPU
-oracle, the drop-in's rig plumbing and the entry checks."""
+oracle, the drop-in's rig plumbing and the entry checks.  The kernel is one template for 1 to 8 cameras: every instantiation its
+launch table can select, and the candidate walk of the rigs up to 4 cameras, are pinned here too."""
 import ctypes
 import os
 
@@ -193,6 +194,53 @@ def test_sweep_wide_walks_several_candidates(arena, N):
     # one rig for both frames (the two frames' rigs are equal here): the same volume
     assert torch.equal(H.sweep_std_valid(c.f_cl, arena.guarded(c.g[:1]), arena.guarded(vm[:1])), c.nchw)
     assert _flags() == 0
+
+
+@pytest.mark.parametrize("N", [1, 3, 4])
+def test_sweep_narrow_walks_several_candidates(arena, N):
+    """The same for rigs of up to 4 cameras (one grid point per lane): at the small shapes every block walks exactly one candidate,
+    so this is the only test of their walk.  B = 2, D = 10, Ho = 32, Wo = 2054 -> rows 2112, nd 4, chunks of 3, 3, 3, 1: the
+    ping-pong pair, its odd tail and a one-candidate chunk; fp32 volume, fp16 split output and one rig for both frames against the
+    plane-gather kernel."""
+    shape = (1, W.HI, W.WI, 10, 32, 2054, W.HM, W.WM)
+    inp = W.small_case(N, 16, shape)
+    f2 = np.random.default_rng(200 + N).standard_normal(inp["feats"].shape).astype(np.float32)
+    inp = dict(inp, feats=np.concatenate([inp["feats"], f2]),
+               **{k: np.concatenate([inp[k]] * 2) for k in ("grids", "grid_masks", "masks")})
+    c = Case(arena, inp)
+    vm = H.sweep_validity(c.g, c.gm, c.m)
+    assert int(vm.max()) < (1 << N) and len(torch.unique(vm)) > N
+    assert N == 1 or bool(c.nchw.any())                              # (one camera: fewer than two valid everywhere, all zeros)
+    assert torch.equal(H.sweep_std_valid(c.f_cl, c.g, vm), c.nchw)
+    want = H.act_to_split(c.nchw, fmt="f16")
+    vs = H.sweep_std_valid_split(c.f_cl, c.g, vm, out=H.SplitAct(2, 10, 32, 2054, 16, DEV), fmt="f16")
+    assert torch.equal(vs.buf, want.buf)
+    assert torch.equal(H.sweep_std_valid(c.f_cl, arena.guarded(c.g[:1]), arena.guarded(vm[:1])), c.nchw)
+    assert _flags() == 0
+
+
+@pytest.mark.parametrize("C", [8, 16, 24])
+@pytest.mark.parametrize("N", [1, 2, 3, 4, 5, 6, 7, 8])
+def test_sweep_every_walking_instantiation(arena, N, C):
+    """Every kernel the launch table of the validity-byte sweep can select, (N, C == 16, split format), at the small shape (Wo 70:
+    a full 64-voxel tile and a 6-voxel tail) against the plane-gather kernel, no tolerance.  C = 8 leaves lanes 2 and 3 of a quad
+    without channels, C = 24 gives lanes 0 and 1 two channel trips and lanes 2 and 3 one, C = 16 is the one-trip template; for
+    C = 16 also both split formats, with per-frame rig and one rig for both frames, and no range flag."""
+    c = Case(arena, W.small_case(N, C))
+    assert c.f.shape[1:3] == (N, C)
+    vm = H.sweep_validity(c.g, c.gm, c.m)
+    assert int(vm.max()) < (1 << N)
+    assert N == 1 or bool(c.nchw.any())
+    for ft in (c.f, c.f_cl):
+        assert torch.equal(H.sweep_std_valid(ft, c.g, vm), c.nchw)
+    if C == 16:
+        g1, rig = c.rig0(arena)
+        for fmt in ("bf16", "f16"):
+            for gg, vv, vol in ((c.g, vm, c.nchw), (g1, arena.guarded(vm[:1]), rig)):
+                want = H.act_to_split(vol, fmt=fmt)
+                vs = H.sweep_std_valid_split(c.f_cl, gg, vv, out=H.SplitAct(W.B, W.D, W.HO, W.WO, C, DEV), fmt=fmt)
+                assert vs.fmt == fmt and torch.equal(vs.buf, want.buf)
+        assert _flags() == 0
 
 
 # ------------------------------------------------------------------------------ 9: range report

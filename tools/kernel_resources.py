@@ -1,6 +1,8 @@
 #!/usr/bin/env python3
 """Registers, scratch (spills) and LDS of every kernel in built objects (default build/obj/*.o), from the code objects' metadata
-notes: `python tools/kernel_resources.py [objects] > file` -- diff two builds to see what a change cost a kernel's register budget."""
+notes: `python tools/kernel_resources.py [objects] > file` -- diff two builds to see what a change cost a kernel's register budget.
+`--disasm DIR` also writes every kernel's disassembly to DIR/<demangled name>.s with the kernel's own symbol (and the address
+column of branch comments) replaced by a placeholder: `diff -r` of two builds' directories shows which kernels a change moved."""
 import glob
 import os
 import re
@@ -24,14 +26,38 @@ def device_code_object(path: str, td: str):
     return co if r.returncode == 0 and os.path.isfile(co) and os.path.getsize(co) else None
 
 
+def dump_disasm(co: str, outdir: str):
+    """one file per kernel: the llvm-objdump text between the kernel's label and the next symbol's"""
+    txt = subprocess.run([LLVM + "llvm-objdump", "-d", "--no-show-raw-insn", "--no-leading-addr", co], check=True,
+                         capture_output=True, text=True).stdout
+    parts = re.split(r"^<([^>\n]+)>:\n", txt, flags=re.M)          # [head, sym, body, sym, body, ...]
+    syms = parts[1::2]
+    names = subprocess.run(["c++filt"], input="\n".join(syms), capture_output=True, text=True).stdout.split("\n")
+    os.makedirs(outdir, exist_ok=True)
+    for sym, name, body in zip(syms, names, parts[2::2]):
+        body = re.sub(r"// [0-9A-F]+: [0-9A-F ]+", "// ", body.replace(sym, "KERNEL"))
+        body = re.sub(r"(\s*\.\.\.\s*)+$", "\n", body)                      # (padding up to the next symbol)
+        name = name.replace("(anonymous namespace)::", "").replace("void ", "").split("(")[0]
+        with open(os.path.join(outdir, name + ".s"), "w") as f:
+            f.write(body)
+
+
 def main():
-    paths = sys.argv[1:] or sorted(glob.glob("build/obj/*.o"))       # one code object per translation unit
+    args = sys.argv[1:]
+    disasm = None
+    if "--disasm" in args:
+        i = args.index("--disasm")
+        disasm = args[i + 1]
+        del args[i:i + 2]
+    paths = args or sorted(glob.glob("build/obj/*.o"))       # one code object per translation unit
     rows = []
     for path in paths:
         with tempfile.TemporaryDirectory() as td:
             co = device_code_object(path, td)
             if co is None:
                 continue
+            if disasm:
+                dump_disasm(co, disasm)
             txt = subprocess.run([LLVM + "llvm-readelf", "--notes", co], check=True, capture_output=True, text=True).stdout
         for blk in txt.split("- .agpr_count:")[1:]:
             def g(k):

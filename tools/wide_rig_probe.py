@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""The masked-variance sweep for rigs of 5 to 8 cameras (sweep_std_nhwc_v_wide_kernel) against the route such a rig had before:
+"""The masked-variance sweep for rigs of 5 to 8 cameras (sweep_std_nhwc_v_kernel<N>, N > 4) against the route such a rig had before:
 the plane-gather kernel on NCHW features, fp32 vol_raw, streaming post_vol.  One process, hipGraph replays, the two routes
 alternated round by round on the same device; one JSON line per measurement.
 

@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define MVSGI_ABI_VERSION 7   /* 7: mvsgi_resample_bilinear_u8_f32, mvsgi_resample_bilinear_f32, mvsgi_resample_validity_u8, mvsgi_resample_u8_table_f32, mvsgi_rays_equirect_surrogate_f32 (fisheye -> surrogate-view resampler); 6: mvsgi_sweep_max_cams (masked-variance sweep for rigs of up to 8 cameras); 5: mvsgi_softargmin_scaled_f32 (soft-argmin at any interp_scale_factor); 4: mvsgi_instance_norm_f32, mvsgi_instance_norm_ws_bytes (norm_type 'instance'); 3: mvsgi_conv3d_d32_applies, mvsgi_conv3d_up2_d32_applies + MVSGI_CONV_BF16X3_D32; 2: mvsgi_saturation_flags; the symbol set of round 5 */
+#define MVSGI_ABI_VERSION 8   /* 8: mvsgi_reproject_f32 (back-projection: point cloud and warped camera views); 7: mvsgi_resample_bilinear_u8_f32, mvsgi_resample_bilinear_f32, mvsgi_resample_validity_u8, mvsgi_resample_u8_table_f32, mvsgi_rays_equirect_surrogate_f32 (fisheye -> surrogate-view resampler); 6: mvsgi_sweep_max_cams (masked-variance sweep for rigs of up to 8 cameras); 5: mvsgi_softargmin_scaled_f32 (soft-argmin at any interp_scale_factor); 4: mvsgi_instance_norm_f32, mvsgi_instance_norm_ws_bytes (norm_type 'instance'); 3: mvsgi_conv3d_d32_applies, mvsgi_conv3d_up2_d32_applies + MVSGI_CONV_BF16X3_D32; 2: mvsgi_saturation_flags; the symbol set of round 5 */
 
 typedef void* mvsgi_stream_t;
 
@@ -349,6 +349,32 @@ int mvsgi_resample_validity_u8(const float* grid, const unsigned char* ds_mask, 
                                mvsgi_stream_t stream);
 /* the uint8 conversion table of the resampler, RN(k / 255.0f) for k = 0..255, copied to 256 host floats */
 int mvsgi_resample_u8_table_f32(float* table256);
+
+/* ---- back-projection of the prediction (csrc/reproject.hip) ----------------------------------
+ * SphericalSweepStereo._create_warped_inputs (dsta_mvs/model/mvs_model/spherical_sweep_stereo.py:417-471) for double-sphere
+ * and equirectangular cameras: the rig camera's point cloud and the camera images warped into the rig camera's view, one
+ * launch for all frames and cameras.  Per frame b, pixel (i, j) of the H x W map and camera n (fp32, no contraction):
+ *     d = bf / inv[b][i][j]                 (:422, IEEE single division; bf = 96 for the regressor's raw output, 1 for a metric map)
+ *     p = rays[:, i, j] * d                 (:435)  -> xyz
+ *     q = T[n] p                            (the arithmetic of mvsgi_transform_points_f32)
+ *     g, in_fov = projection of camera n    (mvsgi_grid_double_sphere_f32 or mvsgi_grid_equirect_f32 with in_fov = 1)
+ *     valid = in_fov && |gx| <= 1 && |gy| <= 1           (mvsgi_resample_validity_u8; a NaN coordinate is invalid)
+ *     warped = valid ? bilinear_grid_sample(img[b][n], g, align_corners=False) : invalid_value      (mvsgi_resample_bilinear_*)
+ * The result is defined as the bits of that chain of entry points.  The taps of an invalid pixel are not fetched.
+ *   device, in:   inv  [B][H][W] fp32;  rays [3][H][W] fp32, the rig camera's rays (mvsgi_rays_panorama_f32 with dist = [1], or
+ *                 any other table);  imgs: img_kind 0 = uint8 [B*N][Hr][Wr][3] (each byte converted as RN(k / 255.0f)),
+ *                 1 = fp32 [B*N][C][Hr][Wr]; NULL exactly when warped is NULL (img_kind, C, Hr, Wr are then ignored)
+ *   device, out:  xyz [B][3][H][W], warped [B][N][C][H][W], grid [B][N][H][W][2] fp32, valid [B][N][H][W] uint8 (0 / 1); each may be
+ *                 NULL (not computed), not all of them; 16-byte aligned.  inv and rays are 16-byte aligned when W % 4 == 0.
+ *   host:         T [N][16] fp32: row-major 4 x 4 transforms taking rig-camera points into camera n's frame (the fp32 image of
+ *                 the float64 inverse camera pose);  cams [N][10] fp32: model id (0 = double sphere, 1 = equirectangular), xi,
+ *                 alpha, fx, fy, cx, cy, w2, calib_h - 1, calib_w - 1 (the nine after the id are read for model 0 only).
+ *                 Both are copied into the kernel's arguments by the call: no device copy, nothing to keep alive.
+ * 1 <= N <= mvsgi_sweep_max_cams().  Limits of the images as for mvsgi_resample_bilinear_*; H * W < 2^31, B < 2^31. */
+int mvsgi_reproject_f32(const float* inv, const float* rays, const void* imgs, int img_kind, const float* T_host,
+                        const float* cams_host, float* xyz, float* warped, unsigned char* valid, float* grid,
+                        long long B, int N, int C, int Hr, int Wr, int H, int W, float bf, float invalid_value,
+                        mvsgi_stream_t stream);
 
 /* ---- deformable 2-D convolution with a given offset field ------------
  * SphereConvEquirect2d.forward + SphereConvBlk (common/common_modules.py:411-425, :509-547):

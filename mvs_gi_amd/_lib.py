@@ -13,7 +13,7 @@ from ctypes import c_char_p, c_double, c_float, c_int, c_longlong, c_size_t, c_v
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MVSGI_LIB", os.path.join(_HERE, "libmvsgi_hip.so"))   # MVSGI_LIB: diagnostic builds
 
-ABI_VERSION = 7
+ABI_VERSION = 8
 
 
 class MvsgiLibraryMissing(RuntimeError):
@@ -82,6 +82,7 @@ SIGNATURES = {
     "mvsgi_resample_bilinear_f32": (c_int, [_P, _P, _P, _P, c_longlong] + [c_int] * 6 + [c_float, _P]),
     "mvsgi_resample_validity_u8": (c_int, [_P, _P, _P, c_longlong, _P]),
     "mvsgi_resample_u8_table_f32": (c_int, [_P]),
+    "mvsgi_reproject_f32": (c_int, [_P, _P, _P, c_int] + [_P] * 6 + [c_longlong] + [c_int] * 6 + [c_float, c_float, _P]),
     "mvsgi_deform_conv2d_pack_weights_f32": (c_int, [_P, _P] + [c_int] * 4 + [_P]),
     "mvsgi_deform_conv2d_f32": (c_int, [_P, _P, c_int] + [_P] * 5 + [c_int] * 13 + [c_float, _P]),
     "mvsgi_act_split_bytes": (c_size_t, [c_int] * 5),

@@ -7,4 +7,5 @@ from .feature_extractor import (BaseConvBlk2d, ResConvBlk2d, SimpleFeatExtractio
                                 SphereConvBlk, SphereEquirectFeatExtraction)
 from .image_sampler import (DoubleSphereToEquirectSampler, NoOpSampler, equirect_surrogate_rays, sample_masks,  # noqa: F401
                             stack_tables)
+from .reproject import Reprojector  # noqa: F401
 from .install import install, uninstall  # noqa: F401

@@ -941,6 +941,70 @@ def resample_bilinear(imgs, grid, valid, invalid_value: float = 0.0, out=None) -
     return out
 
 
+REPROJECT_CAM_FLOATS = 10     # camera table row: model id (0 double sphere, 1 equirectangular), xi, alpha, fx, fy, cx, cy, w2, calib_h - 1, calib_w - 1
+
+
+def reproject(inv, rays, T, cams, bf: float, imgs=None, invalid_value: float = 0.0, want=("xyz", "warped", "valid"), out=None) -> dict:
+    """Back-projection of an inverse-distance map (spherical_sweep_stereo.py:417-471; include/mvsgi.h: mvsgi_reproject_f32):
+    d = bf / inv, xyz = rays * d, each camera's projection of T[n] xyz, its validity and the camera images sampled there.
+    inv [B, H, W] (or [B, 1, H, W]) fp32 on the device; rays [3, H, W] fp32 on the device; T [N, 4, 4] and cams
+    [N, REPROJECT_CAM_FLOATS] host tensors (fp32); imgs uint8 [B * N, Hr, Wr, 3] or fp32 [B * N, C, Hr, Wr] on the device,
+    needed exactly when "warped" is wanted.  want: the outputs to compute, of "xyz" [B, 3, H, W], "warped" [B, N, C, H, W],
+    "valid" [B, N, H, W] bool and "grid" [B, N, H, W, 2]; out: a dict with tensors to write in place (graph capture).
+    One launch on inv's stream; there is no CPU fallback.  -> dict of the wanted outputs."""
+    inv = _dev(inv, "inv")
+    rays = _dev(rays, "rays")
+    if inv.dim() == 4 and inv.shape[1] == 1:
+        inv = inv.squeeze(1)
+    if inv.dim() != 3 or rays.dim() != 3 or rays.shape[0] != 3 or tuple(rays.shape[1:]) != tuple(inv.shape[1:]) or rays.device != inv.device:
+        raise AssertionError(f"inv must be [B, H, W] and rays [3, H, W] on one device, got {tuple(inv.shape)}, {tuple(rays.shape)}")
+    B, Ho, Wo = inv.shape
+    T = torch.as_tensor(T)
+    cams = torch.as_tensor(cams)
+    if T.is_cuda or cams.is_cuda or T.dtype != torch.float32 or cams.dtype != torch.float32:
+        raise TypeError("T and cams are fp32 host tensors (they travel in the kernel's arguments)")
+    N = T.shape[0] if T.dim() == 3 else -1
+    if tuple(T.shape) != (N, 4, 4) or tuple(cams.shape) != (N, REPROJECT_CAM_FLOATS):
+        raise AssertionError(f"T must be [N, 4, 4] and cams [N, {REPROJECT_CAM_FLOATS}], got {tuple(T.shape)}, {tuple(cams.shape)}")
+    if not 1 <= N <= sweep_max_cams():
+        raise ValueError(f"reproject: {N} cameras (1 ... {sweep_max_cams()} are supported)")
+    T, cams = T.contiguous(), cams.contiguous()
+    want = tuple(want)
+    if not want or set(want) - {"xyz", "warped", "valid", "grid"} or len(set(want)) != len(want):
+        raise ValueError(f"want: a non-empty selection of 'xyz', 'warped', 'valid', 'grid', got {want}")
+    kind, C, Hr, Wr = 0, 0, 0, 0
+    if "warped" in want:
+        if not isinstance(imgs, torch.Tensor) or imgs.dtype not in (torch.uint8, torch.float32):
+            raise TypeError(f"imgs: expected a uint8 [B*N, Hr, Wr, 3] or fp32 [B*N, C, Hr, Wr] tensor, got {getattr(imgs, 'dtype', type(imgs))}")
+        u8 = imgs.dtype == torch.uint8
+        imgs = _dev(imgs, "imgs", imgs.dtype)
+        if imgs.dim() != 4 or imgs.shape[0] != B * N or (u8 and imgs.shape[3] != 3) or imgs.device != inv.device:
+            raise AssertionError(f"imgs must be uint8 [{B * N}, Hr, Wr, 3] or fp32 [{B * N}, C, Hr, Wr] on {inv.device}, got {imgs.dtype} "
+                                 f"{tuple(imgs.shape)} on {imgs.device}")
+        if u8:
+            _, Hr, Wr, C = imgs.shape
+        else:
+            _, C, Hr, Wr = imgs.shape
+        kind = 0 if u8 else 1
+    elif imgs is not None:
+        raise ValueError("reproject: imgs given but 'warped' is not wanted")
+    shapes = {"xyz": ((B, 3, Ho, Wo), torch.float32), "warped": ((B, N, C, Ho, Wo), torch.float32),
+              "valid": ((B, N, Ho, Wo), torch.bool), "grid": ((B, N, Ho, Wo, 2), torch.float32)}
+    res = {}
+    for k in want:
+        shape, dtype = shapes[k]
+        t = None if out is None else out.get(k)
+        if t is None:
+            t = torch.empty(shape, device=inv.device, dtype=dtype)
+        elif tuple(t.shape) != shape or t.dtype != dtype or t.device != inv.device or not t.is_contiguous() or t.data_ptr() % 16:
+            raise AssertionError(f"out['{k}'] must be a contiguous, 16-byte aligned {dtype} {list(shape)} tensor on {inv.device}")
+        res[k] = t
+    _call("mvsgi_reproject_f32", inv.data_ptr(), rays.data_ptr(), _ptr(imgs) if "warped" in want else None, kind, T.data_ptr(),
+          cams.data_ptr(), _ptr(res.get("xyz")), _ptr(res.get("warped")), _ptr(res.get("valid")), _ptr(res.get("grid")), B, N, C, Hr, Wr,
+          Ho, Wo, float(bf), float(invalid_value), _stream_ptr(inv))
+    return res
+
+
 def instance_norm(x, res=None, gamma=None, beta=None, eps: float = 1e-5, neg_slope: float = 1.0, out=None) -> torch.Tensor:
     """Instance norm with input statistics on channels-last x [B, ..., C] (NDHWC or NHWC), per frame and channel over all spatial
     positions (F.instance_norm, biased variance): y = act((x - mean) / sqrt(var + eps) * gamma + beta (+ res)), act(v) = v if

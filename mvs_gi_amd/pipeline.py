@@ -286,9 +286,17 @@ class InferencePipeline:
 
     With `samplers` (one dropin.DoubleSphereToEquirectSampler per camera: the facade's sample_input=True,
     inference_pytorch.py:61-74) the images are the cameras' RAW uint8 frames [N, Hr, Wr, 3]: one resample launch turns them
-    into the fp32 surrogate views [N, 3, H, W] the extractor's fp32 stem reads."""
+    into the fp32 surrogate views [N, 3, H, W] the extractor's fp32 stem reads.
 
-    def __init__(self, cfg: PathConfig, weights, consts, device="cuda", extractor: str = "simple", samplers=None, raw_masks=None):
+    With `reprojector` (a dropin.Reprojector of this rig at the output resolution, bf = 1: the map is metric) one more launch
+    follows the soft-argmin, in forward_device and inside the captured graph: the frame's point cloud and its own input images
+    (the raw frames with samplers -- dropin.Reprojector.from_samplers --, the surrogate views otherwise) warped into the rig
+    camera's view.  The results are `pipe.reprojection` = (xyz [1, 3, H, W], warped [1, N, 3, H, W], valid [1, N, H, W]),
+    static tensors that are valid until the next call.  The rig's transforms and camera table are arguments of that launch, so
+    a captured graph holds their values: another rig is another Reprojector and a new capture()."""
+
+    def __init__(self, cfg: PathConfig, weights, consts, device="cuda", extractor: str = "simple", samplers=None, raw_masks=None,
+                 reprojector=None):
         """extractor: 'simple' = SimpleFeatExtraction (G16V, config29), 'sphere' = SphereEquirectFeatExtraction with the
         sphere-convolution final layer (G16VV, config103; configs/feature_extractor/sphereconv_featext.yaml).
         samplers / raw_masks: per-camera image samplers and raw-resolution masks; with both, consts["masks"] may be omitted
@@ -320,6 +328,11 @@ class InferencePipeline:
         self.feature_extractor = fe.eval().to(self.hot.device)
         self.hot.dist_regressor.post_div = float(cfg.bf)          # inference_class.py:111-114
         self.hot.dist_regressor.return_norm_costs = False         # discarded by inference callers
+        self.reprojector = reprojector
+        self.reprojection = None
+        self._reproj_out = None
+        if reprojector is not None and reprojector.num_cams != cfg.num_cams:
+            raise ValueError(f"the reprojector has {reprojector.num_cams} cameras, the rig {cfg.num_cams}")
 
     @torch.no_grad()
     def __call__(self, input_dict) -> np.ndarray:
@@ -343,12 +356,18 @@ class InferencePipeline:
     def forward_device(self, imgs_u8: torch.Tensor) -> torch.Tensor:
         """uint8 [N, H, W, 3] images of one frame on the device (raw [N, Hr, Wr, 3] with samplers) -> inv_dist / bf
         [1, 1, H, W] on the device."""
+        frame = imgs_u8                                            # the frame's own input images
         if self.samplers is not None:
             if imgs_u8.dtype != torch.uint8:
                 raise TypeError("InferencePipeline expects uint8 HWC camera images")
             imgs_u8 = H.resample_bilinear(imgs_u8, *self._table)   # fp32 [N, 3, H, W]: the fp32 RGB stem's input
         f = self.feature_extractor(imgs_u8)                        # [N, C, Hi, Wi], channels-last storage
         inv, _ = self.hot(f.unsqueeze(0))
+        if self.reprojector is not None:
+            # the output buffers are made once (by the eager warm-up of capture(), outside the graph) and written in place
+            r = self.reprojector.reproject(inv, frame, out=self._reproj_out)
+            self._reproj_out = r
+            self.reprojection = (r["xyz"], r["warped"], r["valid"])
         return inv
 
     # ---- hipGraph replay of the whole chain for one frame (the robot's operating point: one frame at a time) ----

@@ -368,7 +368,8 @@ int mvsgi_resample_u8_table_f32(float* table256);
  *                 NULL (not computed), not all of them; 16-byte aligned.  inv and rays are 16-byte aligned when W % 4 == 0.
  *   host:         T [N][16] fp32: row-major 4 x 4 transforms taking rig-camera points into camera n's frame (the fp32 image of
  *                 the float64 inverse camera pose);  cams [N][10] fp32: model id (0 = double sphere, 1 = equirectangular), xi,
- *                 alpha, fx, fy, cx, cy, w2, calib_h - 1, calib_w - 1 (the nine after the id are read for model 0 only).
+ *                 alpha, fx, fy, cx, cy, w2, calib_h - 1, calib_w - 1 (the nine after the id are read for model 0 only; the last
+ *                 two are whole numbers >= 1, as for the ints of mvsgi_grid_double_sphere_f32).
  *                 Both are copied into the kernel's arguments by the call: no device copy, nothing to keep alive.
  * 1 <= N <= mvsgi_sweep_max_cams().  Limits of the images as for mvsgi_resample_bilinear_*; H * W < 2^31, B < 2^31. */
 int mvsgi_reproject_f32(const float* inv, const float* rays, const void* imgs, int img_kind, const float* T_host,

@@ -34,7 +34,7 @@ unsigned* sat_words() {
 }  // namespace mvsgi
 
 extern "C" int mvsgi_abi_version(void) { return MVSGI_ABI_VERSION; }
-extern "C" int mvsgi_sweep_max_cams(void) { return 8; }      // one validity bit per camera in a byte (csrc/sweep.hip)
+extern "C" int mvsgi_sweep_max_cams(void) { return mvsgi::kMaxCams; }
 extern "C" const char* mvsgi_last_error(void) { return mvsgi::last_error_ref().c_str(); }
 
 extern "C" int mvsgi_saturation_flags(int clear, unsigned* flags) {

@@ -46,6 +46,10 @@ inline hipStream_t as_stream(mvsgi_stream_t s) { return reinterpret_cast<hipStre
 
 inline long long cdiv(long long a, long long b) { return (a + b - 1) / b; }
 
+// cameras of a rig: one validity bit per camera in a byte (csrc/sweep.hip); mvsgi_sweep_max_cams() and the size of the
+// back-projection's camera table (csrc/reproject.hip)
+constexpr int kMaxCams = 8;
+
 // Per-(kernel, device) launch set-up of the persistent kernels: the dynamic-LDS limit is a per-device function
 // attribute and the persistent grid is sized from THAT device's CU count and residency (a process may drive several
 // devices, or a partitioned / smaller one).  Each launcher keeps one `static PersistentGeom[kMaxDevices]`.

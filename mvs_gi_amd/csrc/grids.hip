@@ -12,6 +12,8 @@
 
 namespace {
 
+#include "camera_models.hpp"
+
 // RayMaker_UEPanorama.make_rays_for_candidates (torch_cuda_sweep.py:76-132): rays [3][N][H][W] of the
 // panorama frame (z backward, x left, y down) for N candidate distances on an H x W equirect grid.
 __global__ __launch_bounds__(256) void rays_panorama_kernel(const float* __restrict__ dist, float* __restrict__ rays,
@@ -46,13 +48,8 @@ __global__ __launch_bounds__(256) void transform_points_kernel(const float* __re
     const float x = pb[m], y = pb[M + m], z = pb[2 * M + m];
     float* qb = q + (long long)b * 3 * M;
 #pragma unroll
-    for (int i = 0; i < 3; ++i)   // matmul row (k-ordered accumulation) + translation
-        qb[i * M + m] = fmaf(t[i * 4 + 2], z, fmaf(t[i * 4 + 1], y, t[i * 4 + 0] * x)) + t[i * 4 + 3];
+    for (int i = 0; i < 3; ++i) qb[i * M + m] = transform_row(t + i * 4, x, y, z);
 }
-
-struct DsParams {
-    float xi, alpha, one_minus_alpha, fx, fy, cx, cy, wm1, hm1, neg_w2;
-};
 
 // DoubleSphereSampleGridMaker.make_grid (torch_cuda_sweep.py:262-298): points [B][3][M] ->
 // grid [B][M][2] in [-1, 1] and mask [B][M] (1 = inside the model's field of view).
@@ -66,16 +63,11 @@ __global__ __launch_bounds__(256) void grid_double_sphere_kernel(const float* __
     const long long m = idx - (long long)b * M;
     const float* pb = p + (long long)b * 3 * M;
     const float x = pb[m], y = pb[M + m], z = pb[2 * M + m];
-    const float x2 = x * x, y2 = y * y, z2 = z * z;                      // :276-278
-    const float d1 = sqrtf((x2 + y2) + z2);                             // :280
-    const float s = c.xi * d1 + z;
-    const float d2 = sqrtf((x2 + y2) + s * s);                          // :281
-    const float t = c.alpha * d2 + c.one_minus_alpha * s;               // :283
-    const float ux = ((c.fx / t * x + c.cx) / c.wm1) * 2.0f - 1.0f;     // :287
-    const float uy = ((c.fy / t * y + c.cy) / c.hm1) * 2.0f - 1.0f;     // :288
+    float ux, uy;
+    const bool in_fov = project_double_sphere(c, x, y, z, ux, uy);
     grid[idx * 2] = ux;
     grid[idx * 2 + 1] = uy;
-    mask[idx] = z > c.neg_w2 * d1 ? 1 : 0;                              // :295
+    mask[idx] = in_fov ? 1 : 0;
 }
 
 // EquirectangularSampleGridMaker.make_grid (torch_cuda_sweep.py:305-335): points [B][3][M] -> grid [B][M][2].
@@ -88,11 +80,10 @@ __global__ __launch_bounds__(256) void grid_equirect_kernel(const float* __restr
     const long long m = idx - (long long)b * M;
     const float* pb = p + (long long)b * 3 * M;
     const float x = pb[m], y = pb[M + m], z = pb[2 * M + m];
-    const float xz = sqrtf(x * x + z * z);                              // :316-320
-    const float lon = -1.0f * atan2f(z, x);                             // :325
-    const float lat = atan2f(y, xz);                                    // :326
-    grid[idx * 2] = lon / pi_f;                                         // :331
-    grid[idx * 2 + 1] = (2.0f * lat) / pi_f;                            // :332
+    float ux, uy;
+    project_equirect(x, y, z, pi_f, ux, uy);
+    grid[idx * 2] = ux;
+    grid[idx * 2 + 1] = uy;
 }
 
 // Rays of the pixel centres of an H x W equirectangular surrogate view, [3][H][W]: the inverse of grid_equirect_kernel
@@ -141,7 +132,7 @@ extern "C" int mvsgi_rays_equirect_surrogate_f32(float* rays, int H, int W, mvsg
     unsigned nb;
     if (blocks_for((long long)H * W, &nb)) return 1;
     hipLaunchKernelGGL(rays_equirect_surrogate_kernel, dim3(nb), dim3(256), 0, mvsgi::as_stream(stream), rays, H, W,
-                       3.14159274101257324f /* float32(np.pi) */);
+                       kPiF);
     return mvsgi::check_launch("mvsgi_rays_equirect_surrogate_f32");
 }
 
@@ -162,9 +153,8 @@ extern "C" int mvsgi_grid_double_sphere_f32(const float* points, float* grid, un
     MVSGI_REQUIRE(B > 0 && M > 0 && calib_h > 1 && calib_w > 1, "mvsgi_grid_double_sphere_f32: bad dimension");
     unsigned nb;
     if (blocks_for((long long)B * M, &nb)) return 1;
-    DsParams c{xi, alpha, (float)(1.0 - (double)alpha), fx, fy, cx, cy, (float)(calib_w - 1), (float)(calib_h - 1), -w2};
     hipLaunchKernelGGL(grid_double_sphere_kernel, dim3(nb), dim3(256), 0, mvsgi::as_stream(stream), points, grid, mask, B,
-                       M, c);
+                       M, make_ds_params(xi, alpha, fx, fy, cx, cy, calib_h, calib_w, w2));
     return mvsgi::check_launch("mvsgi_grid_double_sphere_f32");
 }
 
@@ -174,6 +164,6 @@ extern "C" int mvsgi_grid_equirect_f32(const float* points, float* grid, int B, 
     unsigned nb;
     if (blocks_for((long long)B * M, &nb)) return 1;
     hipLaunchKernelGGL(grid_equirect_kernel, dim3(nb), dim3(256), 0, mvsgi::as_stream(stream), points, grid, B, M,
-                       3.14159274101257324f /* float32(np.pi) */);
+                       kPiF);
     return mvsgi::check_launch("mvsgi_grid_equirect_f32");
 }

@@ -4,13 +4,14 @@
 //
 //   d = bf / inv[b][i][j]                                        :422  (IEEE single division)
 //   p = rays[:, i, j] * d                                        :435  -> xyz[b][:, i, j]
-//   q = T_n p                                                    transform_points_kernel   (grids.hip)
-//   (g, in_fov) = double-sphere or equirectangular projection    grid_double_sphere_kernel / grid_equirect_kernel (grids.hip)
-//   valid = in_fov & |gx| <= 1 & |gy| <= 1                       resample_validity_kernel  (resample.hip)
-//   warped = valid ? bilinear_grid_sample(img[b][n], g) : invalid_value          resample_bilinear_kernel (resample.hip)
+//   q = T_n p                                                    transform_row             as transform_points_kernel
+//   (g, in_fov) = double-sphere or equirectangular projection    project_double_sphere / project_equirect   as grid_*_kernel
+//   valid = in_fov & |gx| <= 1 & |gy| <= 1                       grid_valid                as resample_validity_kernel
+//   warped = valid ? bilinear_grid_sample(img[b][n], g) : invalid_value          the stage of resample_bilinear_kernel
 //
-// The result is DEFINED as the bits of that chain of existing kernels, so the closed forms below are copies of theirs, fp32
-// with contraction off, operation by operation (tests/test_gpu_reproject.py compares bit for bit and catches drift).
+// The result is DEFINED as the bits of that chain of existing kernels.  Each step is the function those kernels call
+// (camera_models.hpp, sampling.hpp), fp32 with contraction off, so the two agree by construction; tests/test_gpu_reproject.py
+// compares them bit for bit all the same.
 //
 // One thread owns four consecutive pixels of a row for one camera (blockIdx.y): 16-byte loads of inv and the ray table,
 // 16-byte stores per plane; rows whose length is no multiple of four take the element-wise form of the same thread shape.
@@ -20,15 +21,17 @@
 
 namespace {
 
-constexpr int kMaxCams = 8;          // mvsgi_sweep_max_cams()
+#include "camera_models.hpp"
+#include "sampling.hpp"
+
+using mvsgi::kMaxCams;
 constexpr int kCamFloats = 10;       // host camera table row: model, xi, alpha, fx, fy, cx, cy, w2, calib_h - 1, calib_w - 1
 
 enum ReprojModel { DOUBLE_SPHERE = 0, EQUIRECT = 1 };
-enum ReprojIn { U8HWC3 = 0, F32CHW = 1, NO_IMAGES = 2 };
 
 struct ReprojCam {
     float T[12];                                                    // rows 0..2 of the 4 x 4 transform, row-major
-    float xi, alpha, one_minus_alpha, fx, fy, cx, cy, wm1, hm1, neg_w2;      // DsParams of grids.hip
+    DsParams ds;                                                    // read when model == DOUBLE_SPHERE
     int model, pad;
 };
 struct ReprojRig {
@@ -40,74 +43,6 @@ struct ReprojDims {
     int Wq;           // threads per output row: ceil(W / 4)
 };
 
-struct Bilin {
-    int o00, o01, o10, o11;     // pixel offsets y*W+x, or -1 when the tap is outside
-    float w00, w01, w10, w11;   // weights of (x0,y0), (x0,y1), (x1,y0), (x1,y1)
-};
-
-// resample.hip:27-52 (K1's bilin_setup), verbatim
-__device__ __forceinline__ Bilin bilin_setup(float gx, float gy, int W, int H) {
-#pragma clang fp contract(off)
-    Bilin t;
-    // backports.py:41-42 (align_corners=False)
-    const float x = ((gx + 1.0f) * (float)W - 1.0f) / 2.0f;
-    const float y = ((gy + 1.0f) * (float)H - 1.0f) / 2.0f;
-    const float xf = floorf(x), yf = floorf(y);
-    const float x1f = xf + 1.0f, y1f = yf + 1.0f;
-    // backports.py:52-55: weights from the unclamped coordinates
-    t.w00 = (x1f - x) * (y1f - y);
-    t.w01 = (x1f - x) * (y - yf);
-    t.w10 = (x - xf) * (y1f - y);
-    t.w11 = (x - xf) * (y - yf);
-    // anything further out than one texel is outside anyway; clamping first keeps the
-    // float->int conversion defined for huge or NaN coordinates
-    const int x0 = (int)fminf(fmaxf(xf, -2.0f), (float)W + 1.0f);
-    const int y0 = (int)fminf(fmaxf(yf, -2.0f), (float)H + 1.0f);
-    const int x1 = x0 + 1, y1 = y0 + 1;
-    const bool vx0 = (x0 >= 0) & (x0 < W), vx1 = (x1 >= 0) & (x1 < W);
-    const bool vy0 = (y0 >= 0) & (y0 < H), vy1 = (y1 >= 0) & (y1 < H);
-    t.o00 = (vx0 & vy0) ? y0 * W + x0 : -1;
-    t.o01 = (vx0 & vy1) ? y1 * W + x0 : -1;
-    t.o10 = (vx1 & vy0) ? y0 * W + x1 : -1;
-    t.o11 = (vx1 & vy1) ? y1 * W + x1 : -1;
-    return t;
-}
-
-// resample.hip:55-64 (bilin_fetch for a fp32 plane)
-__device__ __forceinline__ float bilin_fetch(const float* __restrict__ plane, const Bilin& t) {
-#pragma clang fp contract(off)
-    // zero padding: a tap outside the image reads 0 (backports.py:58-72)
-    const float i00 = t.o00 >= 0 ? plane[t.o00] : 0.0f;
-    const float i01 = t.o01 >= 0 ? plane[t.o01] : 0.0f;
-    const float i10 = t.o10 >= 0 ? plane[t.o10] : 0.0f;
-    const float i11 = t.o11 >= 0 ? plane[t.o11] : 0.0f;
-    // backports.py:86: Ia*wa + Ib*wb + Ic*wc + Id*wd, left to right
-    return ((i00 * t.w00 + i01 * t.w01) + i10 * t.w10) + i11 * t.w11;
-}
-
-// resample.hip:67-74: the same for channel c of an interleaved uint8 RGB image; lut[k] = RN(k / 255.0f)
-__device__ __forceinline__ float bilin_fetch_u8(const unsigned char* __restrict__ img, int c, const float* lut, const Bilin& t) {
-#pragma clang fp contract(off)
-    const float i00 = t.o00 >= 0 ? lut[img[t.o00 * 3 + c]] : 0.0f;
-    const float i01 = t.o01 >= 0 ? lut[img[t.o01 * 3 + c]] : 0.0f;
-    const float i10 = t.o10 >= 0 ? lut[img[t.o10 * 3 + c]] : 0.0f;
-    const float i11 = t.o11 >= 0 ? lut[img[t.o11 * 3 + c]] : 0.0f;
-    return ((i00 * t.w00 + i01 * t.w01) + i10 * t.w10) + i11 * t.w11;
-}
-
-typedef float f32x4_t __attribute__((ext_vector_type(4)));
-
-// resample.hip:79-88: RN(k / 255.0f), k = 0..255, evaluated by the host compiler (IEEE single division)
-struct U8Table {
-    float v[256];
-};
-constexpr U8Table make_u8_table() {
-    U8Table t{};
-    for (int k = 0; k < 256; ++k) t.v[k] = (float)k / 255.0f;
-    return t;
-}
-__constant__ U8Table kU8Dev = make_u8_table();
-
 // IN: layout of the camera images, or NO_IMAGES (warped == NULL).  VEC: W % 4 == 0; otherwise element-wise with a row tail.
 template <int IN, bool VEC>
 __global__ __launch_bounds__(256) void reproject_kernel(const float* __restrict__ inv, const float* __restrict__ rays,
@@ -117,10 +52,7 @@ __global__ __launch_bounds__(256) void reproject_kernel(const float* __restrict_
                                                         float invalid_value, float pi_f, int per_cam) {
 #pragma clang fp contract(off)
     __shared__ float lut[IN == U8HWC3 ? 256 : 1];
-    if (IN == U8HWC3) {
-        lut[threadIdx.x] = kU8Dev.v[threadIdx.x];
-        __syncthreads();
-    }
+    stage_u8_table<IN>(lut);
     const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
     if (idx >= s.B * s.H * s.Wq) return;
     const int j = (int)(idx % s.Wq) * 4;
@@ -178,32 +110,18 @@ __global__ __launch_bounds__(256) void reproject_kernel(const float* __restrict_
     bool ok[4];
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
-        // step 3: grids.hip:49-50 (transform_points_kernel): matmul row (k-ordered accumulation) + translation
-        const float x = fmaf(c.T[2], pz[k], fmaf(c.T[1], py[k], c.T[0] * px[k])) + c.T[3];
-        const float y = fmaf(c.T[6], pz[k], fmaf(c.T[5], py[k], c.T[4] * px[k])) + c.T[7];
-        const float z = fmaf(c.T[10], pz[k], fmaf(c.T[9], py[k], c.T[8] * px[k])) + c.T[11];
-        bool in_fov;
-        if (c.model == DOUBLE_SPHERE) {
-            // step 4: grids.hip:69-78 (grid_double_sphere_kernel; torch_cuda_sweep.py:276-295)
-            const float x2 = x * x, y2 = y * y, z2 = z * z;
-            const float d1 = sqrtf((x2 + y2) + z2);
-            const float sd = c.xi * d1 + z;
-            const float d2 = sqrtf((x2 + y2) + sd * sd);
-            const float t = c.alpha * d2 + c.one_minus_alpha * sd;
-            gx[k] = ((c.fx / t * x + c.cx) / c.wm1) * 2.0f - 1.0f;
-            gy[k] = ((c.fy / t * y + c.cy) / c.hm1) * 2.0f - 1.0f;
-            in_fov = z > c.neg_w2 * d1;
-        } else {
-            // step 4: grids.hip:91-95 (grid_equirect_kernel; torch_cuda_sweep.py:316-332)
-            const float xz = sqrtf(x * x + z * z);
-            const float lon = -1.0f * atan2f(z, x);
-            const float lat = atan2f(y, xz);
-            gx[k] = lon / pi_f;
-            gy[k] = (2.0f * lat) / pi_f;
-            in_fov = true;
-        }
-        // step 5: resample.hip:177 (resample_validity_kernel): a NaN coordinate compares false
-        ok[k] = in_fov && fabsf(gx[k]) <= 1.0f && fabsf(gy[k]) <= 1.0f;
+        // step 3: transform_row, once per coordinate
+        const float x = transform_row(c.T, px[k], py[k], pz[k]);
+        const float y = transform_row(c.T + 4, px[k], py[k], pz[k]);
+        const float z = transform_row(c.T + 8, px[k], py[k], pz[k]);
+        // step 4: the camera's projection
+        bool in_fov = true;
+        if (c.model == DOUBLE_SPHERE)
+            in_fov = project_double_sphere(c.ds, x, y, z, gx[k], gy[k]);
+        else
+            project_equirect(x, y, z, pi_f, gx[k], gy[k]);
+        // step 5: grid_valid
+        ok[k] = grid_valid(in_fov, gx[k], gy[k]);
     }
 
     const long long m = b * s.N + cam;                                  // image and per-camera plane of this thread
@@ -230,7 +148,7 @@ __global__ __launch_bounds__(256) void reproject_kernel(const float* __restrict_
     }
     if (IN == NO_IMAGES) return;
 
-    // step 6: resample.hip:137-168 (resample_bilinear_kernel)
+    // step 6: the sampling stage of resample_bilinear_kernel
     Bilin bt[4];
 #pragma unroll
     for (int k = 0; k < 4; ++k) bt[k] = bilin_setup(gx[k], gy[k], s.Wr, s.Hr);
@@ -286,11 +204,7 @@ extern "C" int mvsgi_reproject_f32(const float* inv, const float* rays, const vo
         MVSGI_REQUIRE(C >= 1, "%s: C = %d channels (need C >= 1)", what, C);
         MVSGI_REQUIRE(in != U8HWC3 || C == 3, "%s: uint8 images have C = 3 channels, got C = %d", what, C);
         MVSGI_REQUIRE(Hr >= 1 && Wr >= 1, "%s: non-positive dimension (image %d x %d)", what, Hr, Wr);
-        // tap offsets are 32-bit, as in the resampler: (y * Wr + x) * 3 + c for the interleaved bytes, y up to Hr + 1
-        const long long row_bytes = (long long)Wr * (in == U8HWC3 ? 3 : 4);
-        MVSGI_REQUIRE(row_bytes < (1ll << 23) && ((long long)Hr + 2) * row_bytes < (1ll << 31),
-                      "%s: image %d x %d: row bytes %lld (limit 2^23) or image bytes beyond the 32-bit tap offsets", what, Hr, Wr,
-                      row_bytes);
+        if (check_tap_offsets(what, "image", in, Hr, Wr)) return 1;
     }
     MVSGI_REQUIRE((long long)H * W < (1ll << 31) && B < (1ll << 31), "%s: map %d x %d or batch %lld too large", what, H, W, B);
     ReprojRig rig;
@@ -303,12 +217,11 @@ extern "C" int mvsgi_reproject_f32(const float* inv, const float* rays, const vo
         c.model = (int)t[0];
         memcpy(c.T, T_host + k * 16, sizeof(c.T));
         if (c.model == DOUBLE_SPHERE) {
-            MVSGI_REQUIRE(t[8] >= 1.0f && t[9] >= 1.0f, "%s: camera %d: calib shape (%g, %g) (need calib > 1)", what, k,
+            // calib_h - 1 and calib_w - 1 of an integer shape: whole numbers a float holds exactly, so the casts below are exact
+            auto size_m1 = [](float v) { return v >= 1.0f && v < 16777216.0f && v == truncf(v); };
+            MVSGI_REQUIRE(size_m1(t[8]) && size_m1(t[9]), "%s: camera %d: calib shape (%g, %g) (need calib > 1)", what, k,
                           (double)t[8] + 1.0, (double)t[9] + 1.0);
-            // DsParams as mvsgi_grid_double_sphere_f32 fills them (grids.hip:165)
-            c.xi = t[1], c.alpha = t[2], c.one_minus_alpha = (float)(1.0 - (double)t[2]);
-            c.fx = t[3], c.fy = t[4], c.cx = t[5], c.cy = t[6];
-            c.neg_w2 = -t[7], c.hm1 = t[8], c.wm1 = t[9];
+            c.ds = make_ds_params(t[1], t[2], t[3], t[4], t[5], t[6], (int)t[8] + 1, (int)t[9] + 1, t[7]);
         }
     }
     MVSGI_REQUIRE(aligned16(xyz) && aligned16(warped) && aligned16(valid) && aligned16(grid),
@@ -323,13 +236,11 @@ extern "C" int mvsgi_reproject_f32(const float* inv, const float* rays, const vo
     hipStream_t st = mvsgi::as_stream(stream);
 #define MVSGI_REPROJECT_LAUNCH(IN, VEC)                                                                                      \
     hipLaunchKernelGGL((reproject_kernel<IN, VEC>), blocks, dim3(256), 0, st, inv, rays, imgs, xyz, warped, valid, grid, rig, s, \
-                       bf, invalid_value, 3.14159274101257324f /* float32(np.pi) */, per_cam)
-    if (in == U8HWC3) {
-        if (vec) MVSGI_REPROJECT_LAUNCH(U8HWC3, true); else MVSGI_REPROJECT_LAUNCH(U8HWC3, false);
-    } else if (in == F32CHW) {
-        if (vec) MVSGI_REPROJECT_LAUNCH(F32CHW, true); else MVSGI_REPROJECT_LAUNCH(F32CHW, false);
-    } else {
+                       bf, invalid_value, kPiF, per_cam)
+    if (in == NO_IMAGES) {
         if (vec) MVSGI_REPROJECT_LAUNCH(NO_IMAGES, true); else MVSGI_REPROJECT_LAUNCH(NO_IMAGES, false);
+    } else {
+        MVSGI_LAUNCH_IMAGE_KIND_VEC(MVSGI_REPROJECT_LAUNCH, in, vec);
     }
 #undef MVSGI_REPROJECT_LAUNCH
     return mvsgi::check_launch(what);

@@ -18,76 +18,10 @@
 
 namespace {
 
-struct Bilin {
-    int o00, o01, o10, o11;     // pixel offsets y*W+x, or -1 when the tap is outside
-    float w00, w01, w10, w11;   // weights of (x0,y0), (x0,y1), (x1,y0), (x1,y1)
-};
+#include "camera_models.hpp"
+#include "sampling.hpp"
 
-// K1's bilin_setup (sweep.hip), verbatim
-__device__ __forceinline__ Bilin bilin_setup(float gx, float gy, int W, int H) {
-#pragma clang fp contract(off)
-    Bilin t;
-    // backports.py:41-42 (align_corners=False)
-    const float x = ((gx + 1.0f) * (float)W - 1.0f) / 2.0f;
-    const float y = ((gy + 1.0f) * (float)H - 1.0f) / 2.0f;
-    const float xf = floorf(x), yf = floorf(y);
-    const float x1f = xf + 1.0f, y1f = yf + 1.0f;
-    // backports.py:52-55: weights from the unclamped coordinates
-    t.w00 = (x1f - x) * (y1f - y);
-    t.w01 = (x1f - x) * (y - yf);
-    t.w10 = (x - xf) * (y1f - y);
-    t.w11 = (x - xf) * (y - yf);
-    // anything further out than one texel is outside anyway; clamping first keeps the
-    // float->int conversion defined for huge or NaN coordinates
-    const int x0 = (int)fminf(fmaxf(xf, -2.0f), (float)W + 1.0f);
-    const int y0 = (int)fminf(fmaxf(yf, -2.0f), (float)H + 1.0f);
-    const int x1 = x0 + 1, y1 = y0 + 1;
-    const bool vx0 = (x0 >= 0) & (x0 < W), vx1 = (x1 >= 0) & (x1 < W);
-    const bool vy0 = (y0 >= 0) & (y0 < H), vy1 = (y1 >= 0) & (y1 < H);
-    t.o00 = (vx0 & vy0) ? y0 * W + x0 : -1;
-    t.o01 = (vx0 & vy1) ? y1 * W + x0 : -1;
-    t.o10 = (vx1 & vy0) ? y0 * W + x1 : -1;
-    t.o11 = (vx1 & vy1) ? y1 * W + x1 : -1;
-    return t;
-}
-
-// K1's bilin_fetch for a fp32 plane
-__device__ __forceinline__ float bilin_fetch(const float* __restrict__ plane, const Bilin& t) {
-#pragma clang fp contract(off)
-    // zero padding: a tap outside the image reads 0 (backports.py:58-72)
-    const float i00 = t.o00 >= 0 ? plane[t.o00] : 0.0f;
-    const float i01 = t.o01 >= 0 ? plane[t.o01] : 0.0f;
-    const float i10 = t.o10 >= 0 ? plane[t.o10] : 0.0f;
-    const float i11 = t.o11 >= 0 ? plane[t.o11] : 0.0f;
-    // backports.py:86: Ia*wa + Ib*wb + Ic*wc + Id*wd, left to right
-    return ((i00 * t.w00 + i01 * t.w01) + i10 * t.w10) + i11 * t.w11;
-}
-
-// the same for channel c of an interleaved uint8 RGB image; lut[k] = RN(k / 255.0f)
-__device__ __forceinline__ float bilin_fetch_u8(const unsigned char* __restrict__ img, int c, const float* lut, const Bilin& t) {
-#pragma clang fp contract(off)
-    const float i00 = t.o00 >= 0 ? lut[img[t.o00 * 3 + c]] : 0.0f;
-    const float i01 = t.o01 >= 0 ? lut[img[t.o01 * 3 + c]] : 0.0f;
-    const float i10 = t.o10 >= 0 ? lut[img[t.o10 * 3 + c]] : 0.0f;
-    const float i11 = t.o11 >= 0 ? lut[img[t.o11 * 3 + c]] : 0.0f;
-    return ((i00 * t.w00 + i01 * t.w01) + i10 * t.w10) + i11 * t.w11;
-}
-
-typedef float f32x4_t __attribute__((ext_vector_type(4)));
-
-// RN(k / 255.0f), k = 0..255, evaluated by the host compiler (IEEE single division)
-struct U8Table {
-    float v[256];
-};
-constexpr U8Table make_u8_table() {
-    U8Table t{};
-    for (int k = 0; k < 256; ++k) t.v[k] = (float)k / 255.0f;
-    return t;
-}
 constexpr U8Table kU8Host = make_u8_table();
-__constant__ U8Table kU8Dev = make_u8_table();
-
-enum ResampleIn { U8HWC3 = 0, F32CHW = 1 };
 
 struct ResampleDims {
     long long M;      // images
@@ -102,10 +36,7 @@ __global__ __launch_bounds__(256) void resample_bilinear_kernel(const void* __re
                                                                 float* __restrict__ out, ResampleDims s, float invalid_value) {
 #pragma clang fp contract(off)
     __shared__ float lut[IN == U8HWC3 ? 256 : 1];
-    if (IN == U8HWC3) {
-        lut[threadIdx.x] = kU8Dev.v[threadIdx.x];
-        __syncthreads();
-    }
+    stage_u8_table<IN>(lut);
     const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
     if (idx >= s.M * s.H * s.Wq) return;
     const int j = (int)(idx % s.Wq) * 4;
@@ -174,7 +105,7 @@ __global__ __launch_bounds__(256) void resample_validity_kernel(const float* __r
     const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
     if (idx >= n) return;
     const float gx = grid[idx * 2], gy = grid[idx * 2 + 1];
-    valid[idx] = (ds_mask[idx] != 0 && fabsf(gx) <= 1.0f && fabsf(gy) <= 1.0f) ? 1 : 0;
+    valid[idx] = grid_valid(ds_mask[idx] != 0, gx, gy) ? 1 : 0;
 }
 
 int launch_resample(const char* what, int in, const void* imgs, const float* grid, const unsigned char* valid, float* out,
@@ -183,11 +114,7 @@ int launch_resample(const char* what, int in, const void* imgs, const float* gri
     MVSGI_REQUIRE(T >= 1, "%s: T = %d tables (need T >= 1)", what, T);
     MVSGI_REQUIRE(M >= 1 && M % T == 0, "%s: M = %lld images is no multiple of T = %d tables", what, M, T);
     MVSGI_REQUIRE(C >= 1 && Hr >= 1 && Wr >= 1 && H >= 1 && W >= 1, "%s: non-positive dimension", what);
-    // tap offsets are 32-bit: (y * Wr + x) * 3 + c for the interleaved bytes, y * Wr + x within a fp32 plane, y up to Hr + 1
-    const long long row_bytes = (long long)Wr * (in == U8HWC3 ? 3 : 4);
-    MVSGI_REQUIRE(row_bytes < (1ll << 23) && ((long long)Hr + 2) * row_bytes < (1ll << 31),
-                  "%s: raw image %d x %d: row bytes %lld (limit 2^23) or image bytes beyond the 32-bit tap offsets", what, Hr, Wr,
-                  row_bytes);
+    if (check_tap_offsets(what, "raw image", in, Hr, Wr)) return 1;
     MVSGI_REQUIRE((long long)H * W < (1ll << 31) && M < (1ll << 31), "%s: view %d x %d or batch %lld too large", what, H, W, M);
     const bool vec = W % 4 == 0;
     if (vec)
@@ -200,11 +127,7 @@ int launch_resample(const char* what, int in, const void* imgs, const float* gri
 #define MVSGI_RESAMPLE_LAUNCH(IN, VEC)                                                                                      \
     hipLaunchKernelGGL((resample_bilinear_kernel<IN, VEC>), dim3((unsigned)nb), dim3(256), 0, st, imgs, grid, valid, out, s, \
                        invalid_value)
-    if (in == U8HWC3) {
-        if (vec) MVSGI_RESAMPLE_LAUNCH(U8HWC3, true); else MVSGI_RESAMPLE_LAUNCH(U8HWC3, false);
-    } else {
-        if (vec) MVSGI_RESAMPLE_LAUNCH(F32CHW, true); else MVSGI_RESAMPLE_LAUNCH(F32CHW, false);
-    }
+    MVSGI_LAUNCH_IMAGE_KIND_VEC(MVSGI_RESAMPLE_LAUNCH, in, vec);
 #undef MVSGI_RESAMPLE_LAUNCH
     return mvsgi::check_launch(what);
 }

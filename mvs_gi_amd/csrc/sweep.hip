@@ -26,41 +26,11 @@ namespace {
 
 #include "split_fmt.hpp"
 
-struct Bilin {
-    int o00, o01, o10, o11;     // plane offsets y*W+x, or -1 when the tap is outside
-    float w00, w01, w10, w11;   // weights of (x0,y0), (x0,y1), (x1,y0), (x1,y1)
-};
+#include "sampling.hpp"
 
 #ifndef MVSGI_SWEEP_SKIP_CAM
 #define MVSGI_SWEEP_SKIP_CAM 1      // 0: every tap of every camera is gathered (diagnostic builds: the A/B of the wave-uniform skips)
 #endif
-__device__ __forceinline__ Bilin bilin_setup(float gx, float gy, int W, int H) {
-#pragma clang fp contract(off)
-    Bilin t;
-    // backports.py:41-42 (align_corners=False)
-    const float x = ((gx + 1.0f) * (float)W - 1.0f) / 2.0f;
-    const float y = ((gy + 1.0f) * (float)H - 1.0f) / 2.0f;
-    const float xf = floorf(x), yf = floorf(y);
-    const float x1f = xf + 1.0f, y1f = yf + 1.0f;
-    // backports.py:52-55: weights from the unclamped coordinates
-    t.w00 = (x1f - x) * (y1f - y);
-    t.w01 = (x1f - x) * (y - yf);
-    t.w10 = (x - xf) * (y1f - y);
-    t.w11 = (x - xf) * (y - yf);
-    // anything further out than one texel is outside anyway; clamping first keeps the
-    // float->int conversion defined for huge or NaN coordinates
-    const int x0 = (int)fminf(fmaxf(xf, -2.0f), (float)W + 1.0f);
-    const int y0 = (int)fminf(fmaxf(yf, -2.0f), (float)H + 1.0f);
-    const int x1 = x0 + 1, y1 = y0 + 1;
-    const bool vx0 = (x0 >= 0) & (x0 < W), vx1 = (x1 >= 0) & (x1 < W);
-    const bool vy0 = (y0 >= 0) & (y0 < H), vy1 = (y1 >= 0) & (y1 < H);
-    t.o00 = (vx0 & vy0) ? y0 * W + x0 : -1;
-    t.o01 = (vx0 & vy1) ? y1 * W + x0 : -1;
-    t.o10 = (vx1 & vy0) ? y0 * W + x1 : -1;
-    t.o11 = (vx1 & vy1) ? y1 * W + x1 : -1;
-    return t;
-}
-
 // bilin_setup with the four taps as BYTE offsets into a channels-last image of C4 = 4 C bytes per texel and rowB = W C4
 // bytes per row; a tap outside the image gets an offset no buffer descriptor covers (the hardware range check reads 0).
 __device__ __forceinline__ Bilin bilin_setup_bytes(float gx, float gy, int W, int H, int C4, int rowB) {
@@ -87,18 +57,6 @@ __device__ __forceinline__ Bilin bilin_setup_bytes(float gx, float gy, int W, in
     return t;
 }
 
-__device__ __forceinline__ float bilin_fetch(const float* __restrict__ plane, const Bilin& t) {
-#pragma clang fp contract(off)
-    // zero padding: a tap outside the image reads 0 (backports.py:58-72)
-    const float i00 = t.o00 >= 0 ? plane[t.o00] : 0.0f;
-    const float i01 = t.o01 >= 0 ? plane[t.o01] : 0.0f;
-    const float i10 = t.o10 >= 0 ? plane[t.o10] : 0.0f;
-    const float i11 = t.o11 >= 0 ? plane[t.o11] : 0.0f;
-    // backports.py:86: Ia*wa + Ib*wb + Ic*wc + Id*wd, left to right
-    return ((i00 * t.w00 + i01 * t.w01) + i10 * t.w10) + i11 * t.w11;
-}
-
-typedef float f32x4_t __attribute__((ext_vector_type(4)));
 typedef float f32x2_t __attribute__((ext_vector_type(2)));
 
 // Correctly rounded x / d for a small positive integer-valued d, given inv = RN(1 / d):
@@ -478,7 +436,7 @@ __global__ __launch_bounds__(256, NCAM <= 4 ? MVSGI_SWEEP_WAVES : MVSGI_SWEEP_WI
     const float* __restrict__ feats, const float* __restrict__ grids, const unsigned char* __restrict__ vmask, float* __restrict__ vol,
     SweepDims s, int dchunk, int nd, int rig_shared, unsigned char* __restrict__ vol_split, unsigned* __restrict__ sat) {
 #pragma clang fp contract(off)
-    static_assert(NCAM >= 1 && NCAM <= 8, "one or two cameras per lane of a quad, one validity bit per camera in a byte");
+    static_assert(NCAM >= 1 && NCAM <= mvsgi::kMaxCams, "one or two cameras per lane of a quad, one validity bit per camera in a byte");
     constexpr bool WIDE = NCAM > 4;            // two grid points per lane and candidate, two groups of (up to) four cameras
     float satm = 0.f;          // fp16 split output: running maximum |value written| (range report, csrc/split_fmt.hpp)
     const int q = threadIdx.x & 3;
@@ -803,7 +761,7 @@ extern "C" int mvsgi_sweep_std_f32(const float* feats, const float* grids, const
     if (check_dims(s, "mvsgi_sweep_std_f32")) return 1;
     MVSGI_REQUIRE(Hm > 0 && Wm > 0, "mvsgi_sweep_std_f32: non-positive mask size");
     MVSGI_REQUIRE(feats && grids && grid_masks && masks && vol, "mvsgi_sweep_std_f32: null pointer");
-    MVSGI_REQUIRE(N >= 1 && N <= 8, "mvsgi_sweep_std_f32: num_cams %d not in [1, 8]", N);
+    MVSGI_REQUIRE(N >= 1 && N <= mvsgi::kMaxCams, "mvsgi_sweep_std_f32: num_cams %d not in [1, %d]", N, mvsgi::kMaxCams);
     const long long total = (long long)B * D * Ho * Wo;
     const dim3 grid((unsigned)mvsgi::cdiv(total, 256)), block(256);
     const unsigned char* g8 = grid_mask_is_f32 ? nullptr : static_cast<const unsigned char*>(grid_masks);
@@ -896,7 +854,7 @@ extern "C" int mvsgi_sweep_validity_u8(const float* grids, const void* grid_mask
     if (check_dims(s, "mvsgi_sweep_validity_u8")) return 1;
     MVSGI_REQUIRE(Hm > 0 && Wm > 0, "mvsgi_sweep_validity_u8: non-positive mask size");
     MVSGI_REQUIRE(grids && grid_masks && masks && vmask, "mvsgi_sweep_validity_u8: null pointer");
-    MVSGI_REQUIRE(N >= 1 && N <= 8, "mvsgi_sweep_validity_u8: num_cams %d not in [1, 8]", N);
+    MVSGI_REQUIRE(N >= 1 && N <= mvsgi::kMaxCams, "mvsgi_sweep_validity_u8: num_cams %d not in [1, %d]", N, mvsgi::kMaxCams);
     const long long total = (long long)B * D * Ho * Wo;
     MVSGI_REQUIRE(mvsgi::cdiv(total, 256) < (1ll << 31), "mvsgi_sweep_validity_u8: too many voxels");
     const unsigned char* g8 = grid_mask_is_f32 ? nullptr : static_cast<const unsigned char*>(grid_masks);
@@ -917,7 +875,7 @@ int sweep_std_nhwc_valid_impl(const float* feats, const float* grids, const unsi
     if (check_dims(s, "mvsgi_sweep_std_nhwc_valid_f32")) return 1;
     MVSGI_REQUIRE(feats && grids && vmask && (vol || vol_split), "mvsgi_sweep_std_nhwc_valid_f32: null pointer");
     MVSGI_REQUIRE(!vol_split || C == 16, "mvsgi_sweep_std_nhwc_valid_split: the split-padded output needs C == 16 (got %d)", C);
-    MVSGI_REQUIRE(N >= 1 && N <= 8, "mvsgi_sweep_std_nhwc_valid_f32: num_cams %d not in [1, 8]", N);
+    MVSGI_REQUIRE(N >= 1 && N <= mvsgi::kMaxCams, "mvsgi_sweep_std_nhwc_valid_f32: num_cams %d not in [1, %d]", N, mvsgi::kMaxCams);
     MVSGI_REQUIRE(C % 4 == 0, "mvsgi_sweep_std_nhwc_valid_f32: C=%d must be a multiple of 4", C);
     // candidates per block: as many as keeps >= ~8k blocks in the launch (latency hiding across d
     // needs a few; filling 256 CUs x 4 resident blocks needs the rest)

@@ -75,9 +75,7 @@ class DoubleSphereToEquirectSampler:
         pts = transform_3D_points_torch(T.to(torch.float32).unsqueeze(0).to(self.device), rays.view(1, 3, 1, Ho, Wo))
         grid, ds_mask = self.grid_maker.make_grid(pts)
         grid = grid.view(Ho, Wo, 2)
-        ds_u8 = ds_mask.view(Ho, Wo).to(torch.uint8)
-        valid = torch.empty((Ho, Wo), device=self.device, dtype=torch.uint8)
-        H._call("mvsgi_resample_validity_u8", grid.data_ptr(), ds_u8.data_ptr(), valid.data_ptr(), Ho * Wo, H._stream_ptr(grid))
+        valid = H.resample_validity(grid, ds_mask.view(Ho, Wo))
         self.rays, self.R, self.ds_mask = rays, R, ds_mask.view(Ho, Wo)
         self._grid, self._valid = grid, valid.view(torch.bool)
         self._table1 = (grid.unsqueeze(0), self._valid.unsqueeze(0))

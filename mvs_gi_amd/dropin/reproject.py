@@ -10,7 +10,8 @@
 
 One launch of csrc/reproject.hip for all frames and cameras; its result is the bits of the chain of the separate kernels
 (mvsgi_rays_panorama_f32 -> multiply -> mvsgi_transform_points_f32 -> make_grid -> mvsgi_resample_validity_u8 ->
-mvsgi_resample_bilinear_*).  The reference projects through mvs_utils camera models and samples with F.grid_sample; here the
+mvsgi_resample_bilinear_*), which Reprojector.reproject_chain executes: the definition the tests and tools/reproject_probe.py
+compare the kernel with.  The reference projects through mvs_utils camera models and samples with F.grid_sample; here the
 projection is the reference's own grid makers and the sampler its backports.bilinear_grid_sample, as everywhere in this build.
 
 The rig (poses, camera parameters, rays) is fixed at construction: the transforms and the camera table travel in the kernel's
@@ -24,7 +25,7 @@ import numpy as np
 import torch
 
 from .. import hip_ops as H
-from .sweep_grids import DoubleSphereSampleGridMaker, EquirectangularSampleGridMaker, RayMaker_UEPanorama
+from .sweep_grids import DoubleSphereSampleGridMaker, EquirectangularSampleGridMaker, RayMaker_UEPanorama, transform_3D_points_torch
 
 MODEL_DOUBLE_SPHERE, MODEL_EQUIRECT = 0, 1
 
@@ -92,6 +93,7 @@ class Reprojector:
         self.bf = float(bf)
         self.cams = camera_table(self.grid_makers)
         self.T = compose_transforms(poses, R_raw)
+        self._T_dev = None               # reproject_chain's device copy, made at its first call
         Ho, Wo = self.out_shape
         if rays is None:
             if long_range is None or lat_range is None:
@@ -141,6 +143,27 @@ class Reprojector:
         if imgs is not None:
             imgs = self._imgs(imgs, inv.shape[0])
         return H.reproject(inv, self.rays, self.T, self.cams, self.bf, imgs=imgs, invalid_value=invalid_pixel_value, want=want, out=out)
+
+    def reproject_chain(self, inv, imgs=None, invalid_pixel_value: float = 0.0, want=("xyz", "warped", "valid")) -> dict:
+        """The definition of reproject(), executed: the separate launches whose bits the fused kernel returns, same arguments
+        (but `out`) and same dictionary.  Its first call copies the transforms to the device; later calls can be captured."""
+        inv = H._dev(self._inv(inv), "inv")
+        B, (Ho, Wo), N = inv.shape[0], self.out_shape, self.num_cams
+        if self._T_dev is None:
+            self._T_dev = self.T.to(self.device)
+        xyz = self.rays.unsqueeze(0) * (torch.full_like(inv, self.bf) / inv).unsqueeze(1)          # an IEEE division, then :435
+        grids, valids = [], []
+        for n, gm in enumerate(self.grid_makers):
+            g = gm.make_grid(transform_3D_points_torch(self._T_dev[n].expand(B, 4, 4).contiguous(), xyz.unsqueeze(2)))
+            g, fov = g if isinstance(g, tuple) else (g, torch.ones((B, 1, Ho, Wo), dtype=torch.bool, device=self.device))
+            grids.append(g[:, 0])
+            valids.append(H.resample_validity(g, fov)[:, 0].view(torch.bool))
+        res = dict(xyz=xyz, grid=torch.stack(grids, dim=1), valid=torch.stack(valids, dim=1))
+        if "warped" in want:
+            warped = H.resample_bilinear(self._imgs(imgs, B), res["grid"].view(B * N, Ho, Wo, 2), res["valid"].view(B * N, Ho, Wo),
+                                         invalid_value=invalid_pixel_value)
+            res["warped"] = warped.view(B, N, -1, Ho, Wo)
+        return {k: res[k] for k in want}
 
     def point_cloud(self, inv) -> torch.Tensor:
         return self.reproject(inv, want=("xyz",))["xyz"]

@@ -905,27 +905,53 @@ def resize_trilinear(x, size) -> torch.Tensor:
     return y
 
 
+def _images(imgs, m: str, count=None, device=None):
+    """The images of resample_bilinear and reproject: uint8 [m, Hr, Wr, 3] or fp32 [m, C, Hr, Wr] on the device (`count` of them,
+    on `device`, where given) -> (imgs, u8, C, Hr, Wr); `m` is the leading dimension's name in the messages."""
+    if not isinstance(imgs, torch.Tensor) or imgs.dtype not in (torch.uint8, torch.float32):
+        raise TypeError(f"imgs: expected a uint8 [{m}, Hr, Wr, 3] or fp32 [{m}, C, Hr, Wr] tensor, got {getattr(imgs, 'dtype', type(imgs))}")
+    u8 = imgs.dtype == torch.uint8
+    imgs = _dev(imgs, "imgs", imgs.dtype)
+    if imgs.dim() != 4 or (u8 and imgs.shape[3] != 3) or (count is not None and imgs.shape[0] != count) or \
+            (device is not None and imgs.device != device):
+        lead = m if count is None else count
+        where, got_where = ("", "") if device is None else (f" on {device}", f" on {imgs.device}")
+        raise AssertionError(f"imgs must be uint8 [{lead}, Hr, Wr, 3] or fp32 [{lead}, C, Hr, Wr]{where}, got {imgs.dtype} "
+                             f"{tuple(imgs.shape)}{got_where}")
+    C, Hr, Wr = (imgs.shape[3], imgs.shape[1], imgs.shape[2]) if u8 else tuple(imgs.shape[1:])
+    return imgs, u8, C, Hr, Wr
+
+
+def resample_validity(grid, in_fov) -> torch.Tensor:
+    """Validity of a sampling table: in_fov & |gx| <= 1 & |gy| <= 1 (a NaN coordinate is invalid) -> uint8 of in_fov's shape.
+    grid [..., 2] fp32 in grid_sample coordinates; in_fov [...] bool or uint8 (the projection's field-of-view mask).  One launch
+    on the grid's stream."""
+    if not isinstance(grid, torch.Tensor) or grid.dtype != torch.float32:
+        raise TypeError(f"grid: expected a fp32 tensor, got {getattr(grid, 'dtype', type(grid))}")
+    if not isinstance(in_fov, torch.Tensor) or in_fov.dtype not in (torch.bool, torch.uint8):
+        raise TypeError(f"in_fov: expected a bool or uint8 tensor, got {getattr(in_fov, 'dtype', type(in_fov))}")
+    if grid.dim() < 2 or grid.shape[-1] != 2 or tuple(in_fov.shape) != tuple(grid.shape[:-1]) or in_fov.device != grid.device:
+        raise AssertionError(f"grid must be [..., 2] and in_fov its leading shape on one device, got {tuple(grid.shape)} on {grid.device}, "
+                             f"{tuple(in_fov.shape)} on {in_fov.device}")
+    grid, in_fov = _dev(grid, "grid"), _dev(in_fov, "in_fov", in_fov.dtype)
+    valid = torch.empty(in_fov.shape, device=grid.device, dtype=torch.uint8)
+    _call("mvsgi_resample_validity_u8", grid.data_ptr(), in_fov.data_ptr(), valid.data_ptr(), valid.numel(), _stream_ptr(grid))
+    return valid
+
+
 def resample_bilinear(imgs, grid, valid, invalid_value: float = 0.0, out=None) -> torch.Tensor:
     """Raw camera images through a per-camera sampling table -> fp32 planar views [M, C, H, W]:
     out = valid ? bilinear_grid_sample(img, grid, align_corners=False) : invalid_value (backports.py:11-86 arithmetic).
     imgs: uint8 [M, Hr, Wr, 3] (each byte / 255 first) or fp32 [M, C, Hr, Wr]; grid [T, H, W, 2] fp32; valid [T, H, W] bool or
     uint8.  Image m uses table m % T.  One launch on the images' stream; `out`, when given, is written in place."""
-    if not isinstance(imgs, torch.Tensor) or imgs.dtype not in (torch.uint8, torch.float32):
-        raise TypeError(f"imgs: expected a uint8 [M, Hr, Wr, 3] or fp32 [M, C, Hr, Wr] tensor, got {getattr(imgs, 'dtype', type(imgs))}")
-    u8 = imgs.dtype == torch.uint8
-    imgs = _dev(imgs, "imgs", imgs.dtype)
+    imgs, u8, C, Hr, Wr = _images(imgs, "M")
+    M = imgs.shape[0]
     grid = _dev(grid, "grid")
     if not isinstance(valid, torch.Tensor) or valid.dtype not in (torch.bool, torch.uint8):
         raise TypeError(f"valid: expected a bool or uint8 tensor, got {getattr(valid, 'dtype', type(valid))}")
     valid = _dev(valid, "valid", valid.dtype)
-    if imgs.dim() != 4 or (u8 and imgs.shape[3] != 3):
-        raise AssertionError(f"imgs must be uint8 [M, Hr, Wr, 3] or fp32 [M, C, Hr, Wr], got {imgs.dtype} {tuple(imgs.shape)}")
     if grid.dim() != 4 or grid.shape[3] != 2 or tuple(valid.shape) != tuple(grid.shape[:3]):
         raise AssertionError(f"grid must be [T, H, W, 2] and valid [T, H, W], got {tuple(grid.shape)}, {tuple(valid.shape)}")
-    if u8:
-        M, Hr, Wr, C = imgs.shape
-    else:
-        M, C, Hr, Wr = imgs.shape
     T, Ho, Wo = valid.shape
     if out is None:
         out = torch.empty((M, C, Ho, Wo), device=imgs.device, dtype=torch.float32)
@@ -974,17 +1000,7 @@ def reproject(inv, rays, T, cams, bf: float, imgs=None, invalid_value: float = 0
         raise ValueError(f"want: a non-empty selection of 'xyz', 'warped', 'valid', 'grid', got {want}")
     kind, C, Hr, Wr = 0, 0, 0, 0
     if "warped" in want:
-        if not isinstance(imgs, torch.Tensor) or imgs.dtype not in (torch.uint8, torch.float32):
-            raise TypeError(f"imgs: expected a uint8 [B*N, Hr, Wr, 3] or fp32 [B*N, C, Hr, Wr] tensor, got {getattr(imgs, 'dtype', type(imgs))}")
-        u8 = imgs.dtype == torch.uint8
-        imgs = _dev(imgs, "imgs", imgs.dtype)
-        if imgs.dim() != 4 or imgs.shape[0] != B * N or (u8 and imgs.shape[3] != 3) or imgs.device != inv.device:
-            raise AssertionError(f"imgs must be uint8 [{B * N}, Hr, Wr, 3] or fp32 [{B * N}, C, Hr, Wr] on {inv.device}, got {imgs.dtype} "
-                                 f"{tuple(imgs.shape)} on {imgs.device}")
-        if u8:
-            _, Hr, Wr, C = imgs.shape
-        else:
-            _, C, Hr, Wr = imgs.shape
+        imgs, u8, C, Hr, Wr = _images(imgs, "B*N", count=B * N, device=inv.device)
         kind = 0 if u8 else 1
     elif imgs is not None:
         raise ValueError("reproject: imgs given but 'warped' is not wanted")

@@ -56,30 +56,6 @@ def _reprojector(name, bf):
     return dropin.Reprojector(_makers(c["N"], c["all_eq"]), RC.poses(name), c["hw"], RC.LON, RC.LAT, bf=bf, device=DEV)
 
 
-def chain(rp, inv, imgs, invalid=0.0):
-    """The definition: mvsgi_rays_panorama_f32([1]) (rp.rays) -> torch multiply by bf / inv -> transform_3D_points_torch ->
-    make_grid -> mvsgi_resample_validity_u8 -> hip_ops.resample_bilinear with T = B * N tables."""
-    B, Ho, Wo = inv.shape
-    N = rp.num_cams
-    xyz = rp.rays.unsqueeze(0) * (torch.full_like(inv, rp.bf) / inv).unsqueeze(1)          # an IEEE division, then :435
-    grids, valids = [], []
-    for n, gm in enumerate(rp.grid_makers):
-        pts = SG.transform_3D_points_torch(rp.T[n].unsqueeze(0).expand(B, 4, 4).contiguous().to(DEV), xyz.unsqueeze(2))
-        g = gm.make_grid(pts)
-        g, fov = g if isinstance(g, tuple) else (g, torch.ones((B, 1, Ho, Wo), dtype=torch.bool, device=DEV))
-        fov = fov.to(torch.uint8).contiguous()
-        v = torch.empty((B, Ho, Wo), device=DEV, dtype=torch.uint8)
-        H._call("mvsgi_resample_validity_u8", g.data_ptr(), fov.data_ptr(), v.data_ptr(), B * Ho * Wo, H._stream_ptr(g))
-        grids.append(g[:, 0])
-        valids.append(v.view(torch.bool))
-    grid, valid = torch.stack(grids, dim=1).contiguous(), torch.stack(valids, dim=1).contiguous()
-    out = dict(xyz=xyz, grid=grid, valid=valid)
-    if imgs is not None:
-        w = H.resample_bilinear(imgs, grid.view(B * N, Ho, Wo, 2), valid.view(B * N, Ho, Wo), invalid_value=invalid)
-        out["warped"] = w.view(B, N, -1, Ho, Wo)
-    return out
-
-
 def _same_bits(got: torch.Tensor, want: torch.Tensor) -> bool:
     """Equal element for element, NaN positions included (a NaN where `want` holds a number -- an unwritten element -- fails)."""
     got, want = got.cpu(), want.cpu()
@@ -104,8 +80,8 @@ def test_kernel_is_the_bits_of_the_chain(arena, name, bf):
     rp = _reprojector(name, bf)
     inv, imgs = _inputs(arena, name, scale=96.0 / bf)                   # bf = 1 runs on inv / 96, the pipeline's metric map
     with arena.paused():
-        want = chain(rp, inv, imgs)
-        want_neg = chain(rp, inv, imgs, RC.INVALID_OTHER)["warped"]
+        want = rp.reproject_chain(inv, imgs, want=OUTPUTS)
+        want_neg = rp.reproject_chain(inv, imgs, RC.INVALID_OTHER, want=("warped",))["warped"]
     full = rp.reproject(inv, imgs, want=OUTPUTS)
     for k in OUTPUTS:
         assert full[k].dtype == want[k].dtype and torch.equal(full[k], want[k]), k
@@ -125,6 +101,21 @@ def test_kernel_is_the_bits_of_the_chain(arena, name, bf):
     res = rp.reproject(inv, imgs.view(inv.shape[0], rp.num_cams, *imgs.shape[1:]), want=OUTPUTS, out=out)
     for k in OUTPUTS:
         assert res[k] is out[k] and torch.equal(out[k], want[k]), k
+
+
+def test_chain_returns_the_dictionary_of_reproject(arena):
+    """Reprojector.reproject_chain and Reprojector.reproject: the same keys in the same order, dtypes, shapes and device, for the
+    default selection, for every output and without images (the bits are test_kernel_is_the_bits_of_the_chain's)."""
+    rp = _reprojector("tail_u8", RC.BF)
+    inv, imgs = _inputs(arena, "tail_u8")
+    with arena.paused():
+        pairs = [(rp.reproject_chain(inv, imgs), rp.reproject(inv, imgs), ("xyz", "warped", "valid")),
+                 (rp.reproject_chain(inv, imgs, 7.25, want=OUTPUTS), rp.reproject(inv, imgs, 7.25, want=OUTPUTS), OUTPUTS),
+                 (rp.reproject_chain(inv.unsqueeze(1), want=("grid", "xyz")), rp.reproject(inv.unsqueeze(1), want=("grid", "xyz")), ("grid", "xyz"))]
+    for chain, fused, want in pairs:
+        assert isinstance(chain, dict) and tuple(chain) == tuple(fused) == want
+        for k in want:
+            assert chain[k].dtype == fused[k].dtype and chain[k].shape == fused[k].shape and chain[k].device == fused[k].device, k
 
 
 # ------------------------------------------------------------------------------ 2. pinned to the reference's closed forms
@@ -171,7 +162,7 @@ def test_values_nobody_should_pass(arena, name, bf):
     flat[pos] = bad.repeat(4)
     inv, imgs = arena.guarded(inv.to(DEV)), arena.guarded(imgs.to(DEV))
     with arena.paused():
-        want = chain(rp, inv, imgs, 7.25)
+        want = rp.reproject_chain(inv, imgs, 7.25, want=OUTPUTS)
     got = rp.reproject(inv, imgs, 7.25, want=OUTPUTS)
     torch.cuda.synchronize()                                            # no HIP error
     for k in OUTPUTS:
@@ -234,7 +225,7 @@ def test_large_offsets_reproject(arena, big):
     assert warped.numel() >= (1 << 31) + 2 * N * C * Ho * Wo
     for b in (0, B - 2, B - 1):
         with arena.paused():
-            want = chain(rp, inv[b:b + 1].clone(), imgs[b * N:(b + 1) * N].clone(), -2.0)
+            want = rp.reproject_chain(inv[b:b + 1].clone(), imgs[b * N:(b + 1) * N].clone(), -2.0, want=("warped", "valid"))
         assert not bool(torch.isnan(warped[b]).any())
         assert torch.equal(warped[b:b + 1], want["warped"]) and torch.equal(valid[b:b + 1], want["valid"])
         assert 0.5 < float(want["valid"].float().mean()) < 1.0

@@ -71,6 +71,22 @@ def _bits_equal(got: torch.Tensor, want: torch.Tensor) -> bool:
         bool(torch.equal(torch.nan_to_num(got, nan=0.0), torch.nan_to_num(want, nan=0.0)))
 
 
+# ------------------------------------------------------------------------------ 0. the validity rule
+def test_resample_validity_on_the_edges_of_the_rule(arena):
+    """hip_ops.resample_validity on a 1 x 8 table: in_fov & |gx| <= 1 & |gy| <= 1 with the bounds included, one ulp beyond them
+    excluded, NaN and inf invalid -- equal to the same expression evaluated by torch on the CPU."""
+    up, down = float(np.nextafter(np.float32(1), np.float32(2))), float(np.nextafter(np.float32(-1), np.float32(-2)))
+    grid = torch.tensor([[[1.0, 0.0], [-1.0, 0.0], [up, 0.0], [0.0, down], [float("nan"), 0.0], [0.0, float("inf")], [0.25, -0.5],
+                          [0.25, -0.5]]], dtype=torch.float32)
+    in_fov = torch.tensor([[1, 1, 1, 1, 1, 1, 0, 1]], dtype=torch.bool)
+    assert up > 1.0 and down < -1.0 and tuple(grid.shape) == (1, 8, 2)
+    want = (in_fov & (grid[..., 0].abs() <= 1) & (grid[..., 1].abs() <= 1)).to(torch.uint8)
+    assert want.tolist() == [[1, 1, 0, 0, 0, 0, 0, 1]]
+    for fov in (in_fov, in_fov.to(torch.uint8)):
+        got = H.resample_validity(arena.guarded(grid.to(DEV)), arena.guarded(fov.to(DEV)))
+        assert got.dtype == torch.uint8 and got.device.type == "cuda" and torch.equal(got.cpu(), want)
+
+
 # ------------------------------------------------------------------------------ 1. the kernel, bit-exact
 @pytest.mark.parametrize("name", list(RC.CASES))
 def test_kernel_is_bit_exact_against_the_goldens(arena, z, extra, name):

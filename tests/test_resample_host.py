@@ -131,3 +131,20 @@ def test_hip_ops_entry_raises_on_cpu_tensors():
         H.resample_bilinear(torch.zeros((1, 8, 12, 3), dtype=torch.uint8), torch.zeros((1, 4, 4, 2)), torch.ones((1, 4, 4), dtype=torch.bool))
     with pytest.raises(TypeError):
         H.resample_bilinear(torch.zeros((1, 8, 12, 3), dtype=torch.int16), torch.zeros((1, 4, 4, 2)), torch.ones((1, 4, 4), dtype=torch.bool))
+
+
+def test_resample_validity_wrapper_rejects_bad_arguments():
+    """hip_ops.resample_validity: a CPU tensor, a wrong dtype of either argument, a mask that is not the grid's leading shape."""
+    from mvs_gi_amd import hip_ops as H
+    grid, fov = torch.zeros((1, 8, 2)), torch.ones((1, 8), dtype=torch.bool)
+    with pytest.raises(RuntimeError, match="GPU only"):          # there is no CPU fallback
+        H.resample_validity(grid, fov)
+    for bad in (grid.double(), grid.to(torch.uint8), None):
+        with pytest.raises(TypeError, match="grid: expected a fp32 tensor"):
+            H.resample_validity(bad, fov)
+    for bad in (fov.float(), fov.to(torch.int32), [[True] * 8]):
+        with pytest.raises(TypeError, match="in_fov: expected a bool or uint8 tensor"):
+            H.resample_validity(grid, bad)
+    for bad_grid, bad_fov in ((grid, fov[:, :7]), (grid, fov[0]), (torch.zeros((1, 8, 3)), fov), (torch.zeros((2,)), torch.ones((), dtype=torch.bool))):
+        with pytest.raises(AssertionError, match="grid must be"):
+            H.resample_validity(bad_grid, bad_fov)

@@ -8,7 +8,8 @@ round; one JSON line per measurement, also appended to profiles/reproject_probe.
              -> point cloud + three warped views + validity, with three 512 x 2048 uint8 surrogate views (equirectangular
              cameras) and with three 1028 x 1224 raw frames (double-sphere cameras behind R_raw_fisheye):
                fused   one launch of mvsgi_reproject_f32
-               chain   the launches it is defined by: divide, multiply, N x (transform, projection, validity), stack, resample
+               chain   Reprojector.reproject_chain, the launches it is defined by: divide, multiply, N x (transform, projection,
+                       validity), stack, resample
              Bytes per frame (fused): inv read, xyz + warped + valid written; the image gathers are counted as the
              images' size (an upper bound of the HBM traffic: the taps of one frame's map touch a fraction of them).
   pipeline   the one-frame InferencePipeline replay with a reprojector against the same replay without one.
@@ -100,26 +101,6 @@ def rotation_y(a):
     return np.array([[math.cos(a), 0, math.sin(a)], [0, 1, 0], [-math.sin(a), 0, math.cos(a)]])
 
 
-def chain(rp, inv, imgs):
-    """The launches the fused kernel is defined by (tests/test_gpu_reproject.py compares the two bit for bit)."""
-    B, Ho, Wo = inv.shape
-    N = rp.num_cams
-    xyz = rp.rays.unsqueeze(0) * (torch.full_like(inv, rp.bf) / inv).unsqueeze(1)
-    grids, valids = [], []
-    for n, gm in enumerate(rp.grid_makers):
-        pts = SG.transform_3D_points_torch(rp.T_dev[n].unsqueeze(0).expand(B, 4, 4).contiguous(), xyz.unsqueeze(2))
-        g = gm.make_grid(pts)
-        g, fov = g if isinstance(g, tuple) else (g, rp.ones.expand(B, 1, Ho, Wo))
-        fov = fov.to(torch.uint8).contiguous()
-        v = torch.empty((B, Ho, Wo), device=DEV, dtype=torch.uint8)
-        H._call("mvsgi_resample_validity_u8", g.data_ptr(), fov.data_ptr(), v.data_ptr(), B * Ho * Wo, H._stream_ptr(g))
-        grids.append(g[:, 0])
-        valids.append(v.view(torch.bool))
-    grid, valid = torch.stack(grids, dim=1), torch.stack(valids, dim=1)
-    w = H.resample_bilinear(imgs, grid.view(B * N, Ho, Wo, 2), valid.view(B * N, Ho, Wo))
-    return xyz, w.view(B, N, -1, Ho, Wo), valid
-
-
 def make_reprojector(kind, out_hw, bf):
     poses = ring_poses(CAMS)
     if kind == "views_512x2048":
@@ -129,8 +110,6 @@ def make_reprojector(kind, out_hw, bf):
         rp = dropin.Reprojector([SG.DoubleSphereSampleGridMaker(DS, (1028, 1224)) for _ in range(CAMS)], poses, out_hw, LON, LAT, bf=bf,
                                 R_raw=[rotation_y(2 * math.pi * k / CAMS) for k in range(CAMS)], device=DEV)
         img_hw = (1028, 1224)
-    rp.T_dev = rp.T.to(DEV)
-    rp.ones = torch.ones((1, 1, 1, 1), dtype=torch.bool, device=DEV)
     return rp, img_hw
 
 
@@ -145,8 +124,8 @@ def reproject_rows(frames, rounds, steps):
                 inv = torch.full_like(d, 96.0) / d
                 out = {k: v for k, v in rp.reproject(inv, imgs).items()}
                 routes = {"fused": Replay(lambda inv=inv, imgs=imgs, out=out: rp.reproject(inv, imgs, out=out)),
-                          "chain": Replay(lambda inv=inv, imgs=imgs: chain(rp, inv, imgs))}
-                same = all(bool(torch.equal(a, b)) for a, b in zip((out["xyz"], out["warped"], out["valid"]), routes["chain"].out))
+                          "chain": Replay(lambda inv=inv, imgs=imgs: rp.reproject_chain(inv, imgs))}
+                same = all(bool(torch.equal(out[k], routes["chain"].out[k])) for k in ("xyz", "warped", "valid"))
                 med, raw = alternate(routes, rounds, steps)
                 px = Fr * out_hw[0] * out_hw[1]
                 nbytes = px * (4 + 12 + CAMS * (12 + 1)) + 3 * out_hw[0] * out_hw[1] * 4 + Fr * CAMS * img_hw[0] * img_hw[1] * 3

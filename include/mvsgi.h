@@ -87,6 +87,9 @@ const char* mvsgi_last_error(void);
  */
 #define MVSGI_SAT_SWEEP 1u     /* the sweep's split-padded cost volume (the one un-normalised tensor of the path) reached +-65504 */
 #define MVSGI_SAT_SPLIT 2u     /* an activation written or staged in fp16 pieces by a conv layer reached +-65504                */
+/* (MVSGI_SAT_SPLIT, out of range: the Winograd-form polyphase layer's fp16-pair output saturates hi and lo separately and can reach
+ * 2 x 65504; its fp32-record output, mvsgi_conv3d_up2_poly_rec32, is unclamped and mvsgi_conv3d_head_rec32_f16 clamps what it loads
+ * to exactly +-65504 -- the bit is raised in both forms, by the writer in the first and by the reader in the second.) */
 #define MVSGI_SAT_WINO  4u     /* an activation of the Winograd level reached +-16376, or a transformed sum of four +-65504      */
 int mvsgi_saturation_flags(int clear, unsigned* flags);
 int mvsgi_saturation_words(unsigned* words8);      /* diagnostics: the 8 raw words (a kernel only ever stores 1 into one of them) */
@@ -467,6 +470,15 @@ int mvsgi_conv3d_head_split(const void* x_split, const void* w_packed, float sca
 int mvsgi_conv3d_head_split_pack_weights_f16(const float* w_oidhw, void* w_packed, int Cin, mvsgi_stream_t stream);
 int mvsgi_conv3d_head_split_f16(const void* x_split, const void* w_packed, float scale, float shift, float* y, int B, int Cin,
                             int D, int H, int W, float neg_slope, mvsgi_stream_t stream);
+/* the hand-over between the two as FP32 RECORDS (fp16 split, Winograd-form main kernel: D == 8, H even, W a multiple of 32, an error
+ * elsewhere): y_rec32 [B][2D+2][2H+2][2W+2][16 fp32], the same padded geometry (64 bytes per voxel, zero border never written),
+ * the activated values neither clamped nor split; mvsgi_conv3d_head_rec32_f16 reads such records (Cin fp32 per voxel) and splits
+ * every value it loads into the fp16 pair mvsgi_conv3d_head_split_f16 would have read (weights:
+ * mvsgi_conv3d_head_split_pack_weights_f16).  Inside +-65504 the costs are bit for bit those of the pair of calls above. */
+int mvsgi_conv3d_up2_poly_rec32(const void* x_split, const void* plan_dev, const float* scale, const float* shift, void* y_rec32,
+                                int B, int D, int H, int W, float neg_slope, mvsgi_stream_t stream);
+int mvsgi_conv3d_head_rec32_f16(const void* x_rec32, const void* w_packed, float scale, float shift, float* y, int B, int Cin,
+                                int D, int H, int W, float neg_slope, mvsgi_stream_t stream);
 size_t mvsgi_conv3d_up2_poly_plan_bytes(int D, int H, int W);
 int mvsgi_conv3d_up2_poly_plan(const float* w_oidhw_host, void* plan_host, int D, int H, int W);
 int mvsgi_conv3d_up2_poly_f32(const void* x_split, const void* plan_dev, const float* scale, const float* shift, float* y,

@@ -104,6 +104,8 @@ SIGNATURES = {
     "mvsgi_conv3d_head_split": (c_int, [_P, _P, c_float, c_float, _P] + [c_int] * 5 + [c_float, _P]),
     "mvsgi_conv3d_head_split_pack_weights_f16": (c_int, [_P, _P, c_int, _P]),
     "mvsgi_conv3d_head_split_f16": (c_int, [_P, _P, c_float, c_float, _P] + [c_int] * 5 + [c_float, _P]),
+    "mvsgi_conv3d_head_rec32_f16": (c_int, [_P, _P, c_float, c_float, _P] + [c_int] * 5 + [c_float, _P]),
+    "mvsgi_conv3d_up2_poly_rec32": (c_int, [_P] * 5 + [c_int] * 4 + [c_float, _P]),
     "mvsgi_conv3d_up2_poly_plan_bytes": (c_size_t, [c_int] * 3),
     "mvsgi_conv3d_up2_poly_plan": (c_int, [_P, _P] + [c_int] * 3),
     "mvsgi_conv3d_up2_poly_f32": (c_int, [_P] * 5 + [c_int] * 4 + [c_float, _P]),

@@ -13,6 +13,17 @@
 //   * two MFMAs per (16-tap tile, 16-voxel tile) give all three product terms:  A1 = [w_hi | w_hi]  ->  x_hi w_hi + x_lo w_hi,
 //     A2 = [w_lo | 0]  ->  x_hi w_lo;  2 x 2 x 16 cycles per 16 voxels instead of 8 x 64 cycles per 32 voxels of the exact-fp32
 //     v_mfma_f32_32x32x2_f32 head, which ran at 40 % of the fp32-MFMA peak and was bound by it.
+//
+// X32 (fp16 split): the input holds FP32 RECORDS in the same padded geometry (16 plain fp32 = 64 bytes per 16-channel slice, as the
+// Winograd-form polyphase layer writes them, csrc/conv3d_wino_up2.hip OF32) and the head splits what it loads: the split leaves the
+// serial epilogue of a kernel that is bound by vector issue.  The loads are the pair form's: lane (voxel, kg) takes piece kg of the
+// voxel's record, now fp32 channels 4 kg .. 4 kg + 3.  Every lane makes hi and lo of its four channels (clamp to +-65504, range
+// report): H = (H0, H1, H2, H3) and L = (L0, L1, L2, L3) by 16-lane row.  v_permlane32_swap gives (H0, H1, L0, L1), (H2, H3, L2, L3);
+// v_permlane16_swap on those gives (H0, H2, L0, L2), (H1, H3, L1, L3) = the first and the second half of the B operand
+// [hi 0-7 | hi 8-15 | lo 0-7 | lo 8-15] by row: the K order of the pair form, so the same sums.  Every byte is loaded once, by the same
+// instructions as before.  The head is not idle on its vector unit (two waves per SIMD issue on 0.9 of the cycles): ~110 more vector
+// instructions per wave and plane in front of the next request cost it 95 - 130 us per 128 frames, so this form goes tile by tile
+// (split, request of the same tile of the next unit, MFMAs), which needs 142 registers instead of 204 and runs three workgroups per CU.
 #include "common.hpp"
 
 namespace {
@@ -23,6 +34,8 @@ typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef unsigned short u16x8 __attribute__((ext_vector_type(8)));
 
+#include "split_fmt.hpp"
+
 struct HeadArgs {
     const unsigned char* x;     // split-padded [B][D+2][H+2][W+2][Cin * 4 bytes]
     const bf16x8* wp;           // [Cin/16][2 tap tiles][A1 | A2][64 lanes]
@@ -31,6 +44,7 @@ struct HeadArgs {
     float neg_slope;
     int B, Cin, D, H, W;
     int tiles_h, tiles_w;
+    unsigned* sat;              // the range report's words (csrc/api.cpp): X32 only
 };
 
 __device__ __forceinline__ int hs_xcd_remap(int bid, int n) {
@@ -67,8 +81,11 @@ __global__ void head_split_pack_kernel(const float* __restrict__ w, bf16x8* __re
     wp[((cs * 2 + tt) * 2 + 1) * 64 + lane] = __builtin_bit_cast(bf16x8, a2);
 }
 
-template <bool F16>
-__global__ __launch_bounds__(256) void conv3d_head_split_kernel(HeadArgs a, int dchunk, int nd) {
+// (X32: three workgroups per CU -- with a tile's split, its MFMAs and the request of the same tile of the next unit taken tile by tile,
+// one converted operand is live at a time and the kernel fits 168 registers; the pair form keeps its allocation)
+template <bool F16, bool X32 = false>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(X32 ? 3 : 1, X32 ? 3 : 8))) void conv3d_head_split_kernel(HeadArgs a, int dchunk, int nd) {
+    static_assert(F16 || !X32, "fp32 records are split into fp16 pairs");
     constexpr int TH = 8, TW = 32, ITH = TH + 2, ITW = TW + 2, PV = ITH * ITW;     // 10 x 34 halo window = 340 voxels
     constexpr int NT = (PV + 15) / 16;               // 22 voxel tiles of 16
     constexpr int TPW = (NT + 3) / 4;                // 6 per wave
@@ -132,33 +149,68 @@ __global__ __launch_bounds__(256) void conv3d_head_split_kernel(HeadArgs a, int 
     int p = p0, cs = 0;
     float pend = 0.f;
     long long pend_vox = -1;
+    [[maybe_unused]] float satm = 0.f;                // running maximum |clamped value| (range report, csrc/split_fmt.hpp): X32 only
     for (int u = 0; u < U; ++u) {
         int ncs = cs + 1, np = p;
         if (ncs == nchunks) { ncs = 0; np = p + 1; }
-        bf16x8 cx[TPW], cw[2][2];
-#pragma unroll
-        for (int k = 0; k < TPW; ++k) cx[k] = __builtin_bit_cast(bf16x8, xr[k]);
+        bf16x8 cw[2][2];
 #pragma unroll
         for (int tt = 0; tt < 2; ++tt) { cw[tt][0] = wa[tt][0]; cw[tt][1] = wa[tt][1]; }
         if (pend_vox >= 0) {            // a finished output is stored at the START of the next step, ahead of that step's loads
             a.y[pend_vox] = pend;
             pend_vox = -1;
         }
-        {   // the next unit's operands, requested before this unit is multiplied (past the end: this unit again, unused)
-            const int fp = u + 1 < U ? np : p, fcs = u + 1 < U ? ncs : cs;
+        // the next unit's operands, requested before this unit is multiplied (past the end: this unit again, unused)
+        const int fp = u + 1 < U ? np : p, fcs = u + 1 < U ? ncs : cs;
+        if constexpr (X32) {
+            // tile by tile: split the records of tile k, request tile k of the next unit into the registers they came in, multiply
+            const __amdgpu_buffer_rsrc_t d_ = __builtin_amdgcn_make_buffer_rsrc(
+                const_cast<unsigned char*>(xb) + (long long)(fp + 1) * plane_bytes, 0, (int)plane_bytes, 0x00020000);
+#pragma unroll
+            for (int tt = 0; tt < 2; ++tt) {
+                wa[tt][0] = a.wp[((fcs * 2 + tt) * 2) * 64 + lane];
+                wa[tt][1] = a.wp[((fcs * 2 + tt) * 2 + 1) * 64 + lane];
+            }
+#pragma unroll
+            for (int k = 0; k < TPW; ++k) {
+                if (wave + 4 * k < NT) {                 // wave-uniform
+                    sf_u32x2 h, l;
+                    sf_split4<true>(__builtin_bit_cast(sf_f32x4, xr[k]), h, l, satm);
+                    xr[k] = __builtin_amdgcn_raw_buffer_load_b128(d_, goff[k] + (unsigned)(fcs * 64), 0, 0);
+                    u32x4 op;
+#pragma unroll
+                    for (int i = 0; i < 2; ++i) {
+                        // rows 2, 3 of the first operand <-> rows 0, 1 of the second, then rows 1, 3 of the first <-> rows 0, 2 of the second
+                        const auto s32 = __builtin_amdgcn_permlane32_swap(h[i], l[i], false, false);
+                        const auto s16 = __builtin_amdgcn_permlane16_swap(s32[0], s32[1], false, false);
+                        op[i] = s16[0];
+                        op[2 + i] = s16[1];
+                    }
+                    const f16x8 cxk = __builtin_bit_cast(f16x8, op);
+#pragma unroll
+                    for (int tt = 0; tt < 2; ++tt) {
+                        acc[k][tt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, cw[tt][1]), cxk, acc[k][tt], 0, 0, 0);
+                        acc[k][tt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, cw[tt][0]), cxk, acc[k][tt], 0, 0, 0);
+                    }
+                }
+            }
+        } else {
+            bf16x8 cx[TPW];
+#pragma unroll
+            for (int k = 0; k < TPW; ++k) cx[k] = __builtin_bit_cast(bf16x8, xr[k]);
             HS_FETCH(fp, fcs)
-        }
 #pragma unroll
-        for (int k = 0; k < TPW; ++k) {
-            if (wave + 4 * k < NT) {                 // wave-uniform
+            for (int k = 0; k < TPW; ++k) {
+                if (wave + 4 * k < NT) {                 // wave-uniform
 #pragma unroll
-                for (int tt = 0; tt < 2; ++tt) {
-                    if constexpr (F16) {
-                        acc[k][tt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, cw[tt][1]), __builtin_bit_cast(f16x8, cx[k]), acc[k][tt], 0, 0, 0);
-                        acc[k][tt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, cw[tt][0]), __builtin_bit_cast(f16x8, cx[k]), acc[k][tt], 0, 0, 0);
-                    } else {
-                        acc[k][tt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(cw[tt][1], cx[k], acc[k][tt], 0, 0, 0);
-                        acc[k][tt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(cw[tt][0], cx[k], acc[k][tt], 0, 0, 0);
+                    for (int tt = 0; tt < 2; ++tt) {
+                        if constexpr (F16) {
+                            acc[k][tt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, cw[tt][1]), __builtin_bit_cast(f16x8, cx[k]), acc[k][tt], 0, 0, 0);
+                            acc[k][tt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, cw[tt][0]), __builtin_bit_cast(f16x8, cx[k]), acc[k][tt], 0, 0, 0);
+                        } else {
+                            acc[k][tt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(cw[tt][1], cx[k], acc[k][tt], 0, 0, 0);
+                            acc[k][tt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(cw[tt][0], cx[k], acc[k][tt], 0, 0, 0);
+                        }
                     }
                 }
             }
@@ -208,6 +260,7 @@ __global__ __launch_bounds__(256) void conv3d_head_split_kernel(HeadArgs a, int 
         const float r = run[0] * a.scale + a.shift;
         a.y[vox] = r > 0.f ? r : r * a.neg_slope;
     }
+    if constexpr (X32) sf_sat_report(a.sat, kSatSplit, satm, kF16Max);
 #undef HS_FETCH
 }
 
@@ -228,7 +281,7 @@ int head_pack(const float* w_oidhw, void* w_packed, int Cin, bool f16, mvsgi_str
 }
 
 int head_launch(const void* x_split, const void* w_packed, float scale, float shift, float* y, int B, int Cin, int D, int H, int W,
-                float neg_slope, bool f16, mvsgi_stream_t stream, const char* who) {
+                float neg_slope, bool f16, bool rec32, mvsgi_stream_t stream, const char* who) {
     MVSGI_REQUIRE(x_split && w_packed && y, "%s: null pointer", who);
     MVSGI_REQUIRE(B > 0 && D > 0 && H > 0 && W > 0 && Cin > 0 && Cin % 16 == 0, "%s: bad dims (Cin %% 16 == 0)", who);
     MVSGI_REQUIRE((long long)(H + 2) * (W + 2) * Cin * 4 < (1ll << 31), "%s: plane too large for 32-bit offsets", who);
@@ -249,7 +302,11 @@ int head_launch(const void* x_split, const void* w_packed, float scale, float sh
     const long long nt = windows * nd;
     MVSGI_REQUIRE(nt < (1ll << 31), "%s: too many tiles", who);
     constexpr size_t lds_bytes = (size_t)27 * 360 * sizeof(float);
-    if (f16)
+    if (rec32) {
+        MVSGI_SAT_WORDS(sat_words_);
+        a.sat = sat_words_;
+        hipLaunchKernelGGL((conv3d_head_split_kernel<true, true>), dim3((unsigned)nt), dim3(256), lds_bytes, mvsgi::as_stream(stream), a, dchunk, (int)nd);
+    } else if (f16)
         hipLaunchKernelGGL(conv3d_head_split_kernel<true>, dim3((unsigned)nt), dim3(256), lds_bytes, mvsgi::as_stream(stream), a, dchunk, (int)nd);
     else
         hipLaunchKernelGGL(conv3d_head_split_kernel<false>, dim3((unsigned)nt), dim3(256), lds_bytes, mvsgi::as_stream(stream), a, dchunk, (int)nd);
@@ -272,9 +329,16 @@ extern "C" int mvsgi_conv3d_head_split_pack_weights_f16(const float* w_oidhw, vo
 // (BaseConvBlk3d with NoOp norm: scale 1, shift = bias); neg_slope 1 = no activation (out_costs.1 has none).
 extern "C" int mvsgi_conv3d_head_split(const void* x_split, const void* w_packed, float scale, float shift, float* y, int B, int Cin,
                                        int D, int H, int W, float neg_slope, mvsgi_stream_t stream) {
-    return head_launch(x_split, w_packed, scale, shift, y, B, Cin, D, H, W, neg_slope, false, stream, "mvsgi_conv3d_head_split");
+    return head_launch(x_split, w_packed, scale, shift, y, B, Cin, D, H, W, neg_slope, false, false, stream, "mvsgi_conv3d_head_split");
 }
 extern "C" int mvsgi_conv3d_head_split_f16(const void* x_split, const void* w_packed, float scale, float shift, float* y, int B, int Cin,
                                            int D, int H, int W, float neg_slope, mvsgi_stream_t stream) {
-    return head_launch(x_split, w_packed, scale, shift, y, B, Cin, D, H, W, neg_slope, true, stream, "mvsgi_conv3d_head_split_f16");
+    return head_launch(x_split, w_packed, scale, shift, y, B, Cin, D, H, W, neg_slope, true, false, stream, "mvsgi_conv3d_head_split_f16");
+}
+// the head in the fp16 split on FP32 RECORDS: x_rec32 [B][D+2][H+2][W+2][Cin fp32] (zero border), e.g. the output of
+// mvsgi_conv3d_up2_poly_rec32; the kernel splits every value it loads into the fp16 pair mvsgi_conv3d_head_split_f16 would have
+// read (clamped to +-65504 first; a clamp that engages raises MVSGI_SAT_SPLIT).  Weights: mvsgi_conv3d_head_split_pack_weights_f16.
+extern "C" int mvsgi_conv3d_head_rec32_f16(const void* x_rec32, const void* w_packed, float scale, float shift, float* y, int B, int Cin,
+                                           int D, int H, int W, float neg_slope, mvsgi_stream_t stream) {
+    return head_launch(x_rec32, w_packed, scale, shift, y, B, Cin, D, H, W, neg_slope, true, true, stream, "mvsgi_conv3d_head_rec32_f16");
 }

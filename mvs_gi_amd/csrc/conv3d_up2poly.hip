@@ -477,8 +477,9 @@ namespace {
 // output is a split-padded tensor [B][2D+2][2H+2][2W+2][64 B] (the corrections use its voxel records as fp32 until the main
 // kernel overwrites them with the split result)
 // form: 0 = the dispatcher's choice of main kernel, 1 = the direct register-stationary kernel always, 2 = the Winograd form always (A/B, tests)
+// rec32 (form 2 only): the main kernel writes fp32 records, 16 plain fp32 per voxel, where it would write fp16 pairs
 int poly_launch(const void* x_split, const void* plan_dev, const float* scale, const float* shift, void* y, int ob, int B, int D, int H,
-                int W, float neg_slope, int fmt, hipStream_t st, int form = 0) {
+                int W, float neg_slope, int fmt, hipStream_t st, int form = 0, bool rec32 = false) {
     MVSGI_REQUIRE(x_split && plan_dev && scale && shift && y, "mvsgi_conv3d_up2_poly: null pointer");
     MVSGI_REQUIRE(fmt == 0 || fmt == MVSGI_SPLIT_F16, "mvsgi_conv3d_up2_poly: fmt %d not in {0, MVSGI_SPLIT_F16}", fmt);
     MVSGI_REQUIRE(B > 0 && D > 0 && H > 0 && W > 0, "mvsgi_conv3d_up2_poly: bad dims");
@@ -546,7 +547,7 @@ int poly_launch(const void* x_split, const void* plan_dev, const float* scale, c
                   "D == 8, H %% 2 == 0 and W %% 32 == 0 (got D, H, W = %d, %d, %d)", D, H, W);
     if (form == 2)
         return mvsgi::wino_up2_launch(x_split, P + h.off_wino, reinterpret_cast<const float*>(P + h.off_wino_unscale), scale, shift, y,
-                                      B, D, H, W, neg_slope, st);
+                                      B, D, H, W, neg_slope, rec32, st);
     if (fmt && ob && form == 0 && h.off_wino) {
         const long long units = (long long)B * (H / 2) * (W / 32);
         long long nwalk = cus / 16;
@@ -555,7 +556,7 @@ int poly_launch(const void* x_split, const void* plan_dev, const float* scale, c
         const long long rounds = mvsgi::cdiv(mvsgi::cdiv(units, 8), nwalk);
         if (10 * units >= 7 * rounds * 8 * nwalk)
             return mvsgi::wino_up2_launch(x_split, P + h.off_wino, reinterpret_cast<const float*>(P + h.off_wino_unscale), scale, shift, y,
-                                          B, D, H, W, neg_slope, st);
+                                          B, D, H, W, neg_slope, false, st);
     }
     return mvsgi::rs32_up2_launch(x_split, P + h.off_main, scale, shift, y, ob, B, D, H, W, neg_slope, fmt != 0, st);
 }
@@ -586,6 +587,14 @@ extern "C" int mvsgi_conv3d_up2_poly_fmt(const void* x_split, const void* plan_d
                   y_is_split);
     return poly_launch(x_split, plan_dev, scale, shift, y, y_is_split ? 1 : 0, B, D, H, W, neg_slope, fmt, mvsgi::as_stream(stream),
                        y_is_split == 3 ? 1 : (y_is_split == 5 ? 2 : 0));
+}
+
+// The fp16 split's Winograd form (an error where it does not apply: D == 8, H even, W a multiple of 32) with the result as FP32
+// RECORDS in the padded layout: y_rec32 [B][2D+2][2H+2][2W+2][16 fp32] (zero border, never written), the activated values neither
+// clamped nor split -- the input of mvsgi_conv3d_head_rec32_f16, which splits what it loads.  x_split and the plan hold fp16 pairs.
+extern "C" int mvsgi_conv3d_up2_poly_rec32(const void* x_split, const void* plan_dev, const float* scale, const float* shift, void* y_rec32,
+                                           int B, int D, int H, int W, float neg_slope, mvsgi_stream_t stream) {
+    return poly_launch(x_split, plan_dev, scale, shift, y_rec32, 1, B, D, H, W, neg_slope, MVSGI_SPLIT_F16, mvsgi::as_stream(stream), 2, true);
 }
 
 // the main kernel the dispatcher launches for a split-padded fp16 output of this geometry and batch: 1 = the Winograd form

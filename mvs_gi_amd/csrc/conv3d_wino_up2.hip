@@ -44,7 +44,7 @@ typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 struct WinoUp2Args {
     const unsigned char* x;    // low resolution, split-padded fp16 pairs [B][D+2][H+2][W+2][128 B]
-    unsigned char* y;          // high resolution, split-padded fp16 pairs [B][2D+2][2H+2][2W+2][64 B]; holds the raw face corrections on entry
+    unsigned char* y;          // high resolution, padded [B][2D+2][2H+2][2W+2][64 B]: fp16 pairs, or (OF32) 16 plain fp32; holds the raw face corrections on entry
     const u32x4* wp;           // [ph 2][a 4][b 4][kd 3][pw 2][hi | lo][64 lanes] 16-byte fragments
     const float* unw;          // [ph 2][pw 2][16]: inverse of the Winograd weights' power-of-two pre-scaling
     const float* scale;        // [16] (carries the inverse of the plan's pre-scaling)
@@ -90,6 +90,10 @@ __device__ __forceinline__ void split_pair_ovfl(float v0, float v1, unsigned& hi
     lo = sf_cvt_pk<true>(mix_sub_lo(v0, hi), mix_sub_hi(v1, hi));
 }
 
+// OF32: the output records are the 16 activated fp32 values of a voxel, unsplit and unclamped -- the hand-over to a cost head that
+// splits what it loads (csrc/conv3d_headsplit.hip, X32): the epilogue, the serial part of a step, loses its two splits per column
+// phase and half of its stores
+template <bool OF32>
 __global__ __launch_bounds__(256, 1) void conv3d_wino_up2_kernel(WinoUp2Args a) {
     using namespace wu;
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
@@ -150,7 +154,8 @@ __global__ __launch_bounds__(256, 1) void conv3d_wino_up2_kernel(WinoUp2Args a) 
                            *reinterpret_cast<const f32x4*>(a.unw + (ph * 2 + 1) * 16 + kg * 4) * esc_};
     __builtin_amdgcn_sched_barrier(0);
 
-    const int lane_out = (2 * n) * 128 + (kg >> 1) * 16 + (kg & 1) * 8;       // this lane's 8-byte hi piece of cell 2 n's voxel pair, pw = 0
+    // this lane's 8-byte hi piece of cell 2 n's voxel pair, pw = 0 (OF32: its 16 bytes, couts 4 kg .. 4 kg + 3)
+    const int lane_out = OF32 ? (2 * n) * 128 + kg * 16 : (2 * n) * 128 + (kg >> 1) * 16 + (kg & 1) * 8;
     // fragment reads: this lane's hi piece (slice kg >> 1, channel half kg & 1) of column 2 n in patch rows i0 / i1, image 0
     const int rd0 = ((kg & 1) * SUB + (i0 * 2 * HALF + n) * PITCH + (kg >> 1) * 2) * 16;
     const int rd1 = ((kg & 1) * SUB + (i1 * 2 * HALF + n) * PITCH + (kg >> 1) * 2) * 16;
@@ -317,12 +322,16 @@ __global__ __launch_bounds__(256, 1) void conv3d_wino_up2_kernel(WinoUp2Args a) 
         _Pragma("unroll") for (int e_ = 0; e_ < 4; ++e_)                                                    \
             t_[e_] = __builtin_fmaf(t_[e_], ema_[c_][e_], __builtin_fmaf(rf_[c_][e_], esc_[e_], esh_[e_])); \
         _Pragma("unroll") for (int e_ = 0; e_ < 4; ++e_) t_[e_] = __builtin_fmaxf(t_[e_], t_[e_] * a.neg_slope); \
-        unsigned h0_, l0_, h1_, l1_;                                                                        \
-        split_pair_ovfl(t_[0], t_[1], h0_, l0_, satm);                                                      \
-        split_pair_ovfl(t_[2], t_[3], h1_, l1_, satm);                                                      \
         unsigned char* q_ = yb + (long long)((O) + 1) * oplane_bytes + lane_out + c_ * 64;                  \
-        *reinterpret_cast<u32x2*>(q_) = u32x2{h0_, h1_};                                                    \
-        *reinterpret_cast<u32x2*>(q_ + 32) = u32x2{l0_, l1_};                                               \
+        if constexpr (OF32) {                                                                               \
+            *reinterpret_cast<f32x4*>(q_) = t_;                                                             \
+        } else {                                                                                            \
+            unsigned h0_, l0_, h1_, l1_;                                                                    \
+            split_pair_ovfl(t_[0], t_[1], h0_, l0_, satm);                                                  \
+            split_pair_ovfl(t_[2], t_[3], h1_, l1_, satm);                                                  \
+            *reinterpret_cast<u32x2*>(q_) = u32x2{h0_, h1_};                                                \
+            *reinterpret_cast<u32x2*>(q_ + 32) = u32x2{l0_, l1_};                                           \
+        }                                                                                                   \
     }
 // one MFMA and the pieces that ride behind it (conv3d_wino.hip's order: term-major inside a depth tap, the accumulators finished in
 // this step first).  Depth taps on the zero border of the UPSAMPLED grid have no MFMAs.
@@ -357,7 +366,7 @@ __global__ __launch_bounds__(256, 1) void conv3d_wino_up2_kernel(WinoUp2Args a) 
 // vh / vl[VB]; V_up[S + 1] goes to vh / vl[VB ^ 1] piece by piece behind this plane's MFMAs.  Open output planes: S + 1 in slot SI,
 // S in slot SM, S - 1 in slot SF (leaves through the exchange at the end of the step).  Requests of the step, in issue order:
 // [6: a low-resolution plane, in some steps] [3: the corrections of plane S, for the epilogue one step later]; then, behind the
-// barrier, the 4 output stores of plane S - 1.
+// barrier, the 4 (OF32: 2) output stores of plane S - 1.
 #define KU_STEP(S, SI, SM, SF, VB)                                                                          \
     {                                                                                                       \
         unsigned char* rim_ = lds + RB + rprev * RES_LDS;                                                   \
@@ -384,12 +393,13 @@ __global__ __launch_bounds__(256, 1) void conv3d_wino_up2_kernel(WinoUp2Args a) 
         ri = ri == NRES - 1 ? 0 : ri + 1;                                                                   \
     }
 // the unit's last output plane (its slot got the last contribution in step 15: plane 16 is the zero border).  Its corrections were
-// requested in step 15, in front of nothing else but that step's 4 output stores.
+// requested in step 15, in front of nothing else but that step's 4 (OF32: 2) output stores.
 #define KU_FINISH(SF)                                                                                       \
     {                                                                                                       \
         unsigned char* rim_ = lds + RB + rprev * RES_LDS;                                                   \
         KU_OUT_WRITE(SF, (DEPTH - 1) & 1)                                                                   \
-        asm volatile("s_waitcnt vmcnt(4) lgkmcnt(0)" ::: "memory");                                         \
+        if constexpr (OF32) asm volatile("s_waitcnt vmcnt(2) lgkmcnt(0)" ::: "memory");                     \
+        else asm volatile("s_waitcnt vmcnt(4) lgkmcnt(0)" ::: "memory");                                    \
         __builtin_amdgcn_s_barrier();                                                                       \
         KU_EPI_READS((DEPTH - 1) & 1)                                                                       \
         KU_EPILOGUE(DEPTH - 1)                                                                              \
@@ -494,9 +504,11 @@ bool wino_up2_applies(int D, int H, int W) {
 }
 
 // the main kernel of the polyphase layer in this form: x_split low-res fp16 pairs, y_split the split-padded hi-res output holding the
-// face / edge kernels' raw corrections; w_roles / unw from the plan (conv3d_up2poly.hip)
-int wino_up2_launch(const void* x_split, const void* w_roles, const float* unw, const float* scale16, const float* shift16, void* y_split,
-                    int B, int D, int H, int W, float neg_slope, hipStream_t st) {
+// face / edge kernels' raw corrections (out_f32: written as fp32 records, not as fp16 pairs); w_roles / unw from the plan
+// (conv3d_up2poly.hip)
+template <bool OF32>
+static int wino_up2_launch_t(const void* x_split, const void* w_roles, const float* unw, const float* scale16, const float* shift16,
+                             void* y_split, int B, int D, int H, int W, float neg_slope, hipStream_t st) {
     MVSGI_REQUIRE(wino_up2_applies(D, H, W), "mvsgi_conv3d_up2_poly(winograd): needs D == 8, H %% 2 == 0, W %% 32 == 0 (got %d, %d, %d)", D, H, W);
     WinoUp2Args a;
     memset(&a, 0, sizeof(a));
@@ -517,14 +529,20 @@ int wino_up2_launch(const void* x_split, const void* w_roles, const float* unw, 
     a.sat = sat_words_;
     static PersistentGeom geo_cache[kMaxDevices] = {};
     PersistentGeom geo;
-    if (persistent_geometry(conv3d_wino_up2_kernel, 256, wu::LDS_BYTES, 1, geo_cache, "conv3d(winograd up2)", geo)) return 1;
+    if (persistent_geometry(conv3d_wino_up2_kernel<OF32>, 256, wu::LDS_BYTES, 1, geo_cache, "conv3d(winograd up2)", geo)) return 1;
     // grid = 8 XCDs x 2 row phases x walkers: one workgroup per CU, never more walkers than the largest XCD share has units
     long long nwalk = geo.cus / 16;
     const long long most = cdiv(units, 8);
     if (nwalk > most) nwalk = most;
     if (nwalk < 1) nwalk = 1;
-    hipLaunchKernelGGL(conv3d_wino_up2_kernel, dim3((unsigned)(16 * nwalk)), dim3(256), wu::LDS_BYTES, st, a);
+    hipLaunchKernelGGL(conv3d_wino_up2_kernel<OF32>, dim3((unsigned)(16 * nwalk)), dim3(256), wu::LDS_BYTES, st, a);
     return check_launch("mvsgi_conv3d_up2_poly(winograd main)");
+}
+
+int wino_up2_launch(const void* x_split, const void* w_roles, const float* unw, const float* scale16, const float* shift16, void* y_split,
+                    int B, int D, int H, int W, float neg_slope, bool out_f32, hipStream_t st) {
+    return out_f32 ? wino_up2_launch_t<true>(x_split, w_roles, unw, scale16, shift16, y_split, B, D, H, W, neg_slope, st)
+                   : wino_up2_launch_t<false>(x_split, w_roles, unw, scale16, shift16, y_split, B, D, H, W, neg_slope, st);
 }
 
 }  // namespace mvsgi

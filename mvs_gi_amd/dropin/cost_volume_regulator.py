@@ -166,6 +166,8 @@ _HEAD_SPLIT = os.environ.get("MVSGI_HEAD_SPLIT", "1") != "0"      # 0: polyphase
 # 2 frames 0.779 vs 0.766, 4 frames 1.150 vs 1.167, 64 frames 12.57 vs 13.28 -- three launches and a prologue + two drain phases
 # per workgroup need ~4 frames to pay)
 _POLY_MIN_UNITS = 1600
+# MVSGI_TAIL_F32=0: the polyphase layer's Winograd form hands fp16 pairs to the cost head (its form before fp32 records)
+_TAIL_F32 = os.environ.get("MVSGI_TAIL_F32", "1") != "0"
 
 
 def _poly_tail(self, x: Tensor, skip: Tensor):
@@ -190,6 +192,9 @@ def _poly_tail(self, x: Tensor, skip: Tensor):
     if _HEAD_SPLIT and Lh.head_split_ok() and Lh.cin == 16:
         hi = cm._owned_split_buffer(self, "_mvsgi_poly_bufs", (B, 4 * Dl, 4 * Hl, 4 * Wl, "hi", x.device),
                                     lambda: H.SplitAct(B, 4 * Dl, 4 * Hl, 4 * Wl, 16, x.device))
+        # where the Winograd form will run (fp16 split, its geometry, enough units) it writes the activated fp32 values and the head
+        # splits what it loads: the vector unit is that kernel's bottleneck and idle in the head.  Same operands, same costs.
+        hi.rec = "f32" if (_TAIL_F32 and xs.fmt == "f16" and H.conv3d_up2_poly_wino_pays(B, 2 * Dl, 2 * Hl, 2 * Wl)) else "pairs"
         return Lh.run_head_split(Lo.run_up2_poly_split(xs, hi))
     return Lh.run(Lo.run_up2_poly(xs))
 

@@ -525,9 +525,17 @@ def conv3d_up2_poly_split(x: "SplitAct", plan: torch.Tensor, scale, shift, out: 
                           wino: bool = False) -> "SplitAct":
     """conv3d_up2_poly with the result written split-padded into `out` (B, 2D, 2H, 2W, 16).  In the fp16 split the library picks
     the main kernel: the Winograd form where conv3d_up2_poly_wino_pays(), else the direct kernel; `direct` (or MVSGI_POLY_WINO=0)
-    keeps the direct kernel, `wino` forces the Winograd form (an error where it does not apply)."""
+    keeps the direct kernel, `wino` forces the Winograd form (an error where it does not apply).  `out.rec == "f32"` (set by the
+    caller): the Winograd form writes fp32 records for conv3d_head_split instead of pairs -- an error where that form cannot run."""
     if x.C != 32 or scale.numel() != 16 or out.shape != (x.B, 2 * x.D, 2 * x.H, 2 * x.W, 16):
         raise AssertionError(f"conv3d_up2_poly_split: input {x.shape}, output {out.shape}")
+    if out.rec == "f32":          # the caller asked for fp32 records (SplitAct.rec): only the Winograd form writes them
+        if x.fmt != "f16" or direct or not POLY_WINO:
+            raise AssertionError(f"conv3d_up2_poly_split: fp32 records need the fp16 split's Winograd form (input holds {x.fmt} pieces, direct={direct})")
+        _call("mvsgi_conv3d_up2_poly_rec32", x.buf.data_ptr(), plan.data_ptr(), scale.data_ptr(), shift.data_ptr(), out.buf.data_ptr(),
+              x.B, x.D, x.H, x.W, float(neg_slope), _stream_ptr(x.buf))
+        out.fmt = x.fmt
+        return out
     _call("mvsgi_conv3d_up2_poly_fmt", x.buf.data_ptr(), plan.data_ptr(), scale.data_ptr(), shift.data_ptr(), out.buf.data_ptr(),
           5 if wino else (3 if (direct or not POLY_WINO) else 1), x.B, x.D, x.H, x.W, float(neg_slope), _fmt_code(x.fmt), _stream_ptr(x.buf))
     out.fmt = x.fmt
@@ -564,13 +572,16 @@ def pack_head_split_weights_f16(w_oidhw: torch.Tensor):
 
 def conv3d_head_split(x: "SplitAct", w_packed, scale: float, shift: float, neg_slope=1.0, out=None, f16: bool = False) -> torch.Tensor:
     """Cost head (Cout = 1) on a split-padded input -> fp32 [B, D, H, W, 1] = act(conv(x) * scale + shift).  f16: input and weights
-    in the fp16 split."""
+    in the fp16 split; a buffer of fp32 records (x.rec == 'f32') is split by the kernel as it loads."""
     if x.fmt != ("f16" if f16 else "bf16"):
         raise AssertionError(f"conv3d_head_split(f16={f16}) on a split-padded buffer holding {x.fmt} pieces")
+    if x.rec == "f32" and not f16:
+        raise AssertionError("conv3d_head_split: fp32 records are read in the fp16 split only")
     y = out if out is not None else torch.empty((x.B, x.D, x.H, x.W, 1), device=x.buf.device, dtype=torch.float32)
     if tuple(y.shape) != (x.B, x.D, x.H, x.W, 1) or not y.is_contiguous():
         raise AssertionError(f"head output {tuple(y.shape)} does not match {(x.B, x.D, x.H, x.W, 1)}")
-    _call("mvsgi_conv3d_head_split_f16" if f16 else "mvsgi_conv3d_head_split", x.buf.data_ptr(), w_packed.data_ptr(), float(scale),
+    _call("mvsgi_conv3d_head_rec32_f16" if x.rec == "f32" else ("mvsgi_conv3d_head_split_f16" if f16 else "mvsgi_conv3d_head_split"),
+          x.buf.data_ptr(), w_packed.data_ptr(), float(scale),
           float(shift), y.data_ptr(), x.B, x.C, x.D, x.H, x.W, float(neg_slope), _stream_ptr(x.buf))
     return y
 
@@ -598,11 +609,15 @@ def conv3d_variant(B, Cin, Din, Hin, Win, Cout, stride=1, impl=CONV_AUTO) -> str
 # --------------------------------------------------------------------------------------
 class SplitAct:
     """A split-padded activation buffer plus its logical geometry (B, D, H, W, C)."""
-    __slots__ = ("buf", "B", "D", "H", "W", "C", "fmt")
+    __slots__ = ("buf", "B", "D", "H", "W", "C", "fmt", "rec")
 
     def __init__(self, B, D, H, W, C, device, buf=None):
         self.B, self.D, self.H, self.W, self.C = int(B), int(D), int(H), int(W), int(C)
         self.fmt = "bf16"          # element type of the (hi | lo) pieces: set by the kernel that writes the buffer, checked by its reader
+        # encoding of a voxel's record: "pairs" = (hi | lo) pieces of `fmt`; "f32" = C plain fp32 in the same bytes, the hand-over
+        # conv3d_up2_poly_split (Winograd form) -> conv3d_head_split.  Set by the CALLER on the buffer before the writing call (`fmt`
+        # keeps naming the split of the arithmetic around it); every other reader and writer takes pairs
+        self.rec = "pairs"
         if buf is None:
             buf = torch.zeros((self.B, self.D + 2, self.H + 2, self.W + 2, self.C), device=device, dtype=torch.int32)
         self.buf = buf
@@ -628,6 +643,8 @@ def act_to_split(x_ndhwc: torch.Tensor, out: Optional[SplitAct] = None, fmt: str
 
 
 def act_from_split(x: SplitAct, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    if x.rec != "pairs":
+        raise AssertionError("act_from_split reads (hi | lo) pairs; this buffer holds fp32 records")
     y = out if out is not None else torch.empty(x.shape, device=x.buf.device, dtype=torch.float32)
     _call("mvsgi_act_split_to_f32_fmt", x.buf.data_ptr(), y.data_ptr(), x.B, x.C, x.D, x.H, x.W, _fmt_code(x.fmt), _stream_ptr(x.buf))
     return y

@@ -44,6 +44,15 @@ __device__ __forceinline__ Axis2 axis2(int dst, int in, int scale) {
     return a;
 }
 
+// The blend of the multi-pass forms (D > 32 per pixel, DMAX = 0 per row pair / band), which compute it once per pass (max,
+// sums, norm_costs).  Left to the compiler, each pass is contracted on its own (the scalar tail stores of norm_costs fused the
+// outer sum where the two passes before did not), and norm_costs were quotients of other exponentials than the sum holds:
+// the winner's exp(v' - m) was exp(-ulp(v)) instead of 1 -- 2e-3 low at |cost| ~ 3e4 -- and sum_d p_d missed 1 by the blend's
+// rounding (4e-6 at |cost| ~ 40) instead of the sum's (D + 2) 2^-24.  Every rounding is fixed here: all passes see one value.
+__device__ __forceinline__ float sa_blend(float ly0, float ly1, float lx0, float lx1, float a0, float a1, float b0, float b1) {
+    return fmaf(ly1, fmaf(lx1, b1, lx0 * b0), ly0 * fmaf(lx1, a1, lx0 * a0));
+}
+
 // One output pixel of either thread-per-pixel kernel; axis(dst, in) is the coordinate rule (axis2 | axis2f).
 template <class Axis>
 __device__ __forceinline__ void softargmin_pixel(const float* __restrict__ costs, const float* __restrict__ inv_idx,
@@ -57,9 +66,14 @@ __device__ __forceinline__ void softargmin_pixel(const float* __restrict__ costs
     const long long o00 = (long long)ay.i0 * W + ax.i0, o01 = (long long)ay.i0 * W + ax.i1;
     const long long o10 = (long long)ay.i1 * W + ax.i0, o11 = (long long)ay.i1 * W + ax.i1;
 
+    // A tap under a weight of exactly 0 is not blended: it enters the expression as 0, whatever it holds.  Every pixel at scale 1
+    // and the centre-aligned pixels of an odd factor have such a tap (l1 == 0, i1 = i0 + 1), and 0 * c would turn a -inf or NaN
+    // cost of the NEIGHBOURING pixel into a NaN here.  Finite costs give the same bits as before (0 * c = 0 * 0).
+    const bool x1 = ax.l1 == 0.f, y1 = ay.l1 == 0.f;
     auto sample = [&](int d) {
         const float* p = cb + d * HW;
-        return ay.l0 * (ax.l0 * p[o00] + ax.l1 * p[o01]) + ay.l1 * (ax.l0 * p[o10] + ax.l1 * p[o11]);
+        const float p01 = x1 ? 0.f : p[o01], p10 = y1 ? 0.f : p[o10], p11 = (x1 || y1) ? 0.f : p[o11];
+        return ay.l0 * (ax.l0 * p[o00] + ax.l1 * p01) + ay.l1 * (ax.l0 * p10 + ax.l1 * p11);
     };
 
     if (D <= 32) {
@@ -91,11 +105,16 @@ __device__ __forceinline__ void softargmin_pixel(const float* __restrict__ costs
         }
         return;
     }
+    auto sample_mp = [&](int d) {                // the same taps; one rounding order for all three passes, see sa_blend()
+        const float* p = cb + d * HW;
+        const float p01 = x1 ? 0.f : p[o01], p10 = y1 ? 0.f : p[o10], p11 = (x1 || y1) ? 0.f : p[o11];
+        return sa_blend(ay.l0, ay.l1, ax.l0, ax.l1, p[o00], p01, p10, p11);
+    };
     float m = -INFINITY;
-    for (int d = 0; d < D; ++d) m = fmaxf(m, sample(d));
+    for (int d = 0; d < D; ++d) m = fmaxf(m, sample_mp(d));
     float s = 0.f, t = 0.f;
     for (int d = 0; d < D; ++d) {
-        const float e = expf(sample(d) - m);
+        const float e = expf(sample_mp(d) - m);
         s += e;
         t = fmaf(e, inv_idx[d], t);
     }
@@ -104,7 +123,7 @@ __device__ __forceinline__ void softargmin_pixel(const float* __restrict__ costs
     if (norm_costs) {
         const long long OHW = (long long)OH * OW;
         float* np = norm_costs + (long long)b * D * OHW + (long long)oy * OW + ox;
-        for (int d = 0; d < D; ++d) np[d * OHW] = expf(sample(d) - m) / s;
+        for (int d = 0; d < D; ++d) np[d * OHW] = expf(sample_mp(d) - m) / s;
     }
 }
 
@@ -216,8 +235,12 @@ __global__ __launch_bounds__(DMAX == 32 ? 512 : 640) void softargmin_rows_kernel
         const float at0[4] = {a0, am[0], am[0], am[1]}, at1[4] = {am[0], am[1], am[1], a3};
         const float bt0[4] = {b0, bm[0], bm[0], bm[1]}, bt1[4] = {bm[0], bm[1], bm[1], b3};
 #pragma unroll
-        for (int e = 0; e < 4; ++e)
-            o[e] = ay.l0 * (l0[e] * at0[e] + l1[e] * at1[e]) + ay.l1 * (l0[e] * bt0[e] + l1[e] * bt1[e]);
+        for (int e = 0; e < 4; ++e) {
+            if constexpr (DMAX == 0)             // blended again in every pass: the roundings are spelled out, see sa_blend()
+                o[e] = sa_blend(ay.l0, ay.l1, l0[e], l1[e], at0[e], at1[e], bt0[e], bt1[e]);
+            else
+                o[e] = ay.l0 * (l0[e] * at0[e] + l1[e] * at1[e]) + ay.l1 * (l0[e] * bt0[e] + l1[e] * bt1[e]);
+        }
     };
     const long long OHW = (long long)OH * OW;
     const long long idx = ((long long)b * OH + oy) * OW + 2 * c0;
@@ -352,6 +375,8 @@ __global__ __launch_bounds__(256) void softargmin_scaled_kernel(const float* __r
 // the taps are selected from them by the offsets axis2f() gave (computed once per item, with the horizontal weights);
 // X4 (S == 4, the full-resolution case) knows the taps at compile time and has no selects.
 // The arithmetic of a pixel is softargmin_scaled_kernel's expression term for term, taps and weights from the same axis2f().
+// (including its rule that a tap under a weight of exactly 0 -- the right / lower tap of a centre-aligned pixel of an odd S --
+// is not blended; X4 and the x2 kernel have such taps only at the clamped image border and blend them as before).
 // DMAX as above.
 // ---------------------------------------------------------------------------------------------
 template <int DMAX, bool X4>
@@ -444,7 +469,19 @@ __global__ __launch_bounds__(256) void softargmin_band_kernel(const float* __res
             for (int e = 0; e < 4; ++e) {
                 const float at0 = s0[e] ? a1 : a0, at1 = s1[e] == 0 ? a0 : (s1[e] == 1 ? a1 : a2);
                 const float bt0 = s0[e] ? b1 : b0, bt1 = s1[e] == 0 ? b0 : (s1[e] == 1 ? b1 : b2);
-                o[e] = ay.l0 * (l0[e] * at0 + l1[e] * at1) + ay.l1 * (l0[e] * bt0 + l1[e] * bt1);
+                if constexpr (X4) {              // no weight of an interior tap is 0 at S = 4 (phases 1/8, 3/8, 5/8, 7/8)
+                    if constexpr (DMAX == 0)     // blended again in every pass: the roundings are spelled out, see sa_blend()
+                        o[e] = sa_blend(ay.l0, ay.l1, l0[e], l1[e], at0, at1, bt0, bt1);
+                    else
+                        o[e] = ay.l0 * (l0[e] * at0 + l1[e] * at1) + ay.l1 * (l0[e] * bt0 + l1[e] * bt1);
+                } else {                         // a tap under a weight of exactly 0 enters as 0, as in softargmin_pixel()
+                    const float at1z = l1[e] == 0.f ? 0.f : at1, bt0z = ay.l1 == 0.f ? 0.f : bt0;
+                    const float bt1z = (l1[e] == 0.f || ay.l1 == 0.f) ? 0.f : bt1;
+                    if constexpr (DMAX == 0)
+                        o[e] = sa_blend(ay.l0, ay.l1, l0[e], l1[e], at0, at1z, bt0z, bt1z);
+                    else
+                        o[e] = ay.l0 * (l0[e] * at0 + l1[e] * at1z) + ay.l1 * (l0[e] * bt0z + l1[e] * bt1z);
+                }
             }
         };
         const long long idx = ((long long)b * OH + oy) * OW + ox0;

@@ -220,14 +220,11 @@ __global__ __launch_bounds__(256) void conv2d_stem_u8_mfma_kernel(StemArgs a) {
             const unsigned* rp = rows + (2 * ry + ky) * kStemRowDw + dq;
             const unsigned d0 = rp[0], d1 = rp[1], d2 = rp[2];
             const unsigned lo = __builtin_amdgcn_alignbit(d1, d0, shb), hi = __builtin_amdgcn_alignbit(d2, d1, shb);
-            typedef float f2_t __attribute__((ext_vector_type(2)));
-            typedef __bf16 b2_t __attribute__((ext_vector_type(2)));
-            typedef unsigned u4_t __attribute__((ext_vector_type(4)));
-            u4_t pk;
-            pk[0] = __builtin_bit_cast(unsigned, __builtin_convertvector(f2_t{(float)(lo & 0xffu), (float)((lo >> 8) & 0xffu)}, b2_t));
-            pk[1] = __builtin_bit_cast(unsigned, __builtin_convertvector(f2_t{(float)((lo >> 16) & 0xffu), (float)(lo >> 24)}, b2_t));
-            pk[2] = __builtin_bit_cast(unsigned, __builtin_convertvector(f2_t{(float)(hi & 0xffu), (float)((hi >> 8) & 0xffu)}, b2_t));
-            pk[3] = __builtin_bit_cast(unsigned, __builtin_convertvector(f2_t{(float)((hi >> 16) & 0xffu), (float)(hi >> 24)}, b2_t));
+            u32x4 pk;
+            pk[0] = __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2{(float)(lo & 0xffu), (float)((lo >> 8) & 0xffu)}, bf16x2));
+            pk[1] = __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2{(float)((lo >> 16) & 0xffu), (float)(lo >> 24)}, bf16x2));
+            pk[2] = __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2{(float)(hi & 0xffu), (float)((hi >> 8) & 0xffu)}, bf16x2));
+            pk[3] = __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2{(float)((hi >> 16) & 0xffu), (float)(hi >> 24)}, bf16x2));
             const bf16x8 xb = __builtin_bit_cast(bf16x8, pk);
 #pragma unroll
             for (int pc = 2; pc >= 0; --pc) acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wA[ks][pc], xb, acc, 0, 0, 0);   // small pieces first
@@ -241,12 +238,11 @@ __global__ __launch_bounds__(256) void conv2d_stem_u8_mfma_kernel(StemArgs a) {
             // one 16-byte store per lane and a contiguous KiB per wave, as the fp32 form has
             u32x2 hi, lo;
             split_bf16x4(r, hi, lo);
-            typedef unsigned u32x4s __attribute__((ext_vector_type(4)));
             const u32x2 sa = __builtin_amdgcn_permlane16_swap(hi[0], lo[0], false, false);
             const u32x2 sb = __builtin_amdgcn_permlane16_swap(hi[1], lo[1], false, false);
             if (ox < a.Wo && oy < a.Ho)        // nt: 1.6 GB per 96 images that this launch never reads back
-                __builtin_nontemporal_store(u32x4s{sa[0], sb[0], sa[1], sb[1]},
-                    reinterpret_cast<u32x4s*>(a.ys + (((long long)b * (a.Ho + 4) + oy + 2) * (a.Wo + 4) + ox + 2) * 64 + (g & 1) * 32 + (g >> 1) * 16));
+                __builtin_nontemporal_store(u32x4{sa[0], sb[0], sa[1], sb[1]},
+                    reinterpret_cast<u32x4*>(a.ys + (((long long)b * (a.Ho + 4) + oy + 2) * (a.Wo + 4) + ox + 2) * 64 + (g & 1) * 32 + (g >> 1) * 16));
         } else if (ox < a.Wo && oy < a.Ho) {
             *reinterpret_cast<f32x4*>(a.y + (((long long)b * a.Ho + oy) * a.Wo + ox) * 16 + 4 * g) = r;
         }

@@ -61,7 +61,6 @@ __global__ void pack_head_weights_kernel(const float* __restrict__ w, float* __r
 //      the compiler spilled).
 // The loads of plane p+1 are in flight while plane p is reduced.
 // ----------------------------------------------------------------------------------------
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 __global__ __launch_bounds__(256) void conv3d_head_kernel(ConvArgs a, int dchunk, int nd) {
     constexpr int TH = 8, TW = 32, ITH = TH + 2, ITW = TW + 2, PV = ITH * ITW;

@@ -37,11 +37,6 @@
 
 #include "split_fmt.hpp"      // the range report of the fp16 split (sf_sat_acc / sf_sat_report)
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x2v __attribute__((ext_vector_type(2)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
 constexpr int kVSB = 80;      // LDS bytes per staged voxel
 
 // x = hi + lo for four fp32 values, hi = bf16(x) (RNE), lo = bf16(x - hi), packed two per dword:
@@ -52,15 +47,15 @@ constexpr int kVSB = 80;      // LDS bytes per staged voxel
 __device__ __forceinline__ void split_bf16x4(const f32x4 x, u32x2& hi, u32x2& lo) {
 #pragma unroll
     for (int p = 0; p < 2; ++p) {
-        const f32x2v v = {x[2 * p], x[2 * p + 1]};
+        const f32x2 v = {x[2 * p], x[2 * p + 1]};
         const unsigned hb = __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2));
-        const f32x2v hf = {__builtin_bit_cast(float, hb << 16), __builtin_bit_cast(float, hb & 0xffff0000u)};
+        const f32x2 hf = {__builtin_bit_cast(float, hb << 16), __builtin_bit_cast(float, hb & 0xffff0000u)};
         hi[p] = hb;
 #ifndef MVSGI_PK
         float r0 = v[0] - hf[0], r1 = v[1] - hf[1];
         asm volatile("" : "+v"(r0));
         asm volatile("" : "+v"(r1));
-        lo[p] = __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2v{r0, r1}, bf16x2));
+        lo[p] = __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2{r0, r1}, bf16x2));
 #else
         lo[p] = __builtin_bit_cast(unsigned, __builtin_convertvector(v - hf, bf16x2));
 #endif
@@ -89,18 +84,16 @@ __device__ __forceinline__ f32x4 fma4(const f32x4 a, const f32x4 b, const f32x4 
 // v_med3_f32; fp32's range in the bf16 split), and lo parts below 2^-14 are fp16 subnormals (honoured by the matrix cores of gfx950,
 // tools/ubench/mfma_f16_denorm.hip; absolute quantum 2^-24 -- why the host pre-scales the weights by a power of two per output
 // channel, undone in the epilogue's per-channel scale).
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x2v __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ void split_f16x4(const f32x4 x, u32x2& hi, u32x2& lo) {
 #pragma unroll
     for (int p = 0; p < 2; ++p) {
-        const f32x2v v = {__builtin_amdgcn_fmed3f(x[2 * p], -65504.f, 65504.f), __builtin_amdgcn_fmed3f(x[2 * p + 1], -65504.f, 65504.f)};
-        const f16x2v h = __builtin_convertvector(v, f16x2v);               // v_cvt_pk_f16_f32 (RNE)
+        const f32x2 v = {__builtin_amdgcn_fmed3f(x[2 * p], -65504.f, 65504.f), __builtin_amdgcn_fmed3f(x[2 * p + 1], -65504.f, 65504.f)};
+        const f16x2 h = __builtin_convertvector(v, f16x2);               // v_cvt_pk_f16_f32 (RNE)
         hi[p] = __builtin_bit_cast(unsigned, h);
         float r0 = v[0] - (float)h[0], r1 = v[1] - (float)h[1];            // exact in fp32
         asm volatile("" : "+v"(r0));
         asm volatile("" : "+v"(r1));
-        lo[p] = __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2v{r0, r1}, f16x2v));
+        lo[p] = __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2{r0, r1}, f16x2));
     }
 }
 template <bool F16>
@@ -123,9 +116,8 @@ __device__ __forceinline__ f32x4 mfma16(const bf16x8 a, const bf16x8 b, const f3
     if constexpr (F16) return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
     else return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
 }
-typedef float f32x16v __attribute__((ext_vector_type(16)));
 template <bool F16>
-__device__ __forceinline__ f32x16v mfma32(const bf16x8 a, const bf16x8 b, const f32x16v c) {
+__device__ __forceinline__ f32x16 mfma32(const bf16x8 a, const bf16x8 b, const f32x16 c) {
     if constexpr (F16) return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
     else return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
 }
@@ -141,7 +133,6 @@ __device__ __forceinline__ void split_weight(float v, bool f16, unsigned short& 
         lo = __builtin_bit_cast(unsigned short, (__bf16)(v - (float)h));
     }
 }
-typedef unsigned short u16x8 __attribute__((ext_vector_type(8)));
 
 constexpr int pairs_of(int kd) { return (kd * 9 + 1) / 2; }      // KD = 3: 14 pairs of 27 taps; KD = 1 (2-D 3x3): 5 of 9
 
@@ -261,13 +252,6 @@ __global__ void pack_weights_bf16x3_v32_kernel(const float* __restrict__ w, bf16
     const long long o = ((((long long)cc * CT + ct) * 27 + tap) * 2) * 64 + lane;
     wp[o] = __builtin_bit_cast(bf16x8, hi);
     wp[o + 64] = __builtin_bit_cast(bf16x8, lo);
-}
-
-// bijective XCD-aware remap of a flat block id (cdna_hip_programming.md T1): blocks b, b+8, ...
-// share an XCD; give each XCD a contiguous run of the logical index space.
-__device__ __forceinline__ int xcd_remap(int bid, int n) {
-    const int q = n >> 3, r = n & 7, x = bid & 7, i = bid >> 3;
-    return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + i;
 }
 
 // KD = 3: 3x3x3 convolution of a volume; KD = 1: 3x3 convolution of images (a volume with D planes
@@ -625,12 +609,12 @@ __device__ __forceinline__ void conv3d_x3_body(const ConvArgs& a) {
         const char* wsrc = reinterpret_cast<const char*>(a.wp) + (wave - 4) * 1024 + lane * 16;
         // WARM: the packed weights as a buffer ([cin slice][cout tile][pair][hi | lo][64 lanes][16 B]; requests past its end move nothing)
         const __amdgpu_buffer_rsrc_t wdesc = __builtin_amdgcn_make_buffer_rsrc(
-            const_cast<void*>(reinterpret_cast<const void*>(a.wp)), 0, WARM ? (int)((long long)nchunks * CT * kPairs * 2048) : 0, 0x00020000);
+            const_cast<void*>(reinterpret_cast<const void*>(a.wp)), 0, WARM ? (int)((long long)nchunks * CT * kPairs * 2048) : 0, kRawBufferFlags);
         (void)wdesc;
         int pct0 = 0;            // first cout tile of the unit the plan stands at
         int wct0 = 0;            // WARM: the same for units of WN * NW tiles
         (void)wct0;
-        __amdgpu_buffer_rsrc_t xdesc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.x), 0, 0, 0x00020000);
+        __amdgpu_buffer_rsrc_t xdesc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.x), 0, 0, kRawBufferFlags);
         unsigned cpk[NIT];       // id | ih << 8 | iw << 16
 #pragma unroll
         for (int it = 0; it < NIT; ++it) {
@@ -662,7 +646,7 @@ __device__ __forceinline__ void conv3d_x3_body(const ConvArgs& a) {
                                                        : ibase[it] + bbase_;                           \
             }                                                                                           \
             xdesc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.x) + (long long)b_ * a.Din * a.Hin * a.Win * a.Cin, 0, \
-                                                      a.Din * a.Hin * a.Win * a.Cin * 4, 0x00020000);  \
+                                                      a.Din * a.Hin * a.Win * a.Cin * 4, kRawBufferFlags);  \
         }
         // request the next unit in walking order (k2, cc2) into a register set; the plan moves on with it
         int k2 = 0, cc2 = 0;
@@ -684,8 +668,7 @@ __device__ __forceinline__ void conv3d_x3_body(const ConvArgs& a) {
         if constexpr (WARM) {                                                                           \
             const unsigned wo_ = (unsigned)(((long long)cc2 * CT + wct0) * (kPairs * 2048)) + (unsigned)((wave - 4) * 1024 + lane * 16); \
             _Pragma("unroll") for (int it = 0; it < WN * NW * kPairs * 2048 / 4096; ++it)               \
-                __builtin_amdgcn_raw_ptr_buffer_load_lds(wdesc, (__attribute__((address_space(3))) void*)(ldsb + WARM_LDS + (wave - 4) * 1024), \
-                                                         16, wo_ + it * 4096u, 0, 0, 0);                \
+                LDS_DMA16(wdesc, ldsb + WARM_LDS + (wave - 4) * 1024, wo_ + it * 4096u, 0, 0);          \
         }
 #define MVSGI_WPUT(WPRE, DST)                                                                           \
         if constexpr (WLDS) {                                                                           \
@@ -816,7 +799,6 @@ __device__ __forceinline__ void conv3d_x3_body(const ConvArgs& a) {
         }
     } else if constexpr (V32) {
         // =========================== consumers, 32x32x16 schedule ===========================
-        typedef float f32x16 __attribute__((ext_vector_type(16)));
         const int wm = wave % WM, wn = wave / WM;
         const int n32 = lane & 31, kh2 = lane >> 5;
         const char* wpb = reinterpret_cast<const char*>(a.wp);

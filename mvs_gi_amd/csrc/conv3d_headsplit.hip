@@ -28,12 +28,6 @@
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned short u16x8 __attribute__((ext_vector_type(8)));
-
 #include "split_fmt.hpp"
 
 struct HeadArgs {
@@ -46,11 +40,6 @@ struct HeadArgs {
     int tiles_h, tiles_w;
     unsigned* sat;              // the range report's words (csrc/api.cpp): X32 only
 };
-
-__device__ __forceinline__ int hs_xcd_remap(int bid, int n) {
-    const int q = n >> 3, r = n & 7, x = bid & 7, i = bid >> 3;
-    return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + i;
-}
 
 // [1][Cin][27] fp32 -> [Cin/16][tt 2][A1 | A2][64 lanes][8 bf16]; lane = (kg << 4) | i, tap = tt * 16 + i (taps >= 27: zero)
 //   A1: w_hi[tap][16 cs + 8 (kg & 1) + j]  (kg 0, 1 meet x_hi, kg 2, 3 meet x_lo);  A2: kg < 2: w_lo[tap][16 cs + 8 kg + j], else 0
@@ -95,7 +84,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(X32 ? 3 : 1
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int col = lane & 15, kg = lane >> 4;
-    int t = hs_xcd_remap((int)blockIdx.x, (int)gridDim.x);
+    int t = xcd_remap((int)blockIdx.x, (int)gridDim.x);
     const int tw_i = t % a.tiles_w;
     t /= a.tiles_w;
     const int th_i = t % a.tiles_h;
@@ -128,7 +117,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(X32 ? 3 : 1
 #define HS_FETCH(P, CS)                                                                                             \
     {                                                                                                               \
         const __amdgpu_buffer_rsrc_t d_ = __builtin_amdgcn_make_buffer_rsrc(                                        \
-            const_cast<unsigned char*>(xb) + (long long)((P) + 1) * plane_bytes, 0, (int)plane_bytes, 0x00020000); \
+            const_cast<unsigned char*>(xb) + (long long)((P) + 1) * plane_bytes, 0, (int)plane_bytes, kRawBufferFlags); \
         _Pragma("unroll") for (int k = 0; k < TPW; ++k)                                                             \
             xr[k] = __builtin_amdgcn_raw_buffer_load_b128(d_, goff[k] + (unsigned)((CS) * 64), 0, 0);               \
         _Pragma("unroll") for (int tt = 0; tt < 2; ++tt) {                                                          \
@@ -165,7 +154,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(X32 ? 3 : 1
         if constexpr (X32) {
             // tile by tile: split the records of tile k, request tile k of the next unit into the registers they came in, multiply
             const __amdgpu_buffer_rsrc_t d_ = __builtin_amdgcn_make_buffer_rsrc(
-                const_cast<unsigned char*>(xb) + (long long)(fp + 1) * plane_bytes, 0, (int)plane_bytes, 0x00020000);
+                const_cast<unsigned char*>(xb) + (long long)(fp + 1) * plane_bytes, 0, (int)plane_bytes, kRawBufferFlags);
 #pragma unroll
             for (int tt = 0; tt < 2; ++tt) {
                 wa[tt][0] = a.wp[((fcs * 2 + tt) * 2) * 64 + lane];
@@ -174,8 +163,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(X32 ? 3 : 1
 #pragma unroll
             for (int k = 0; k < TPW; ++k) {
                 if (wave + 4 * k < NT) {                 // wave-uniform
-                    sf_u32x2 h, l;
-                    sf_split4<true>(__builtin_bit_cast(sf_f32x4, xr[k]), h, l, satm);
+                    u32x2 h, l;
+                    sf_split4<true>(__builtin_bit_cast(f32x4, xr[k]), h, l, satm);
                     xr[k] = __builtin_amdgcn_raw_buffer_load_b128(d_, goff[k] + (unsigned)(fcs * 64), 0, 0);
                     u32x4 op;
 #pragma unroll

@@ -44,15 +44,7 @@
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2v __attribute__((ext_vector_type(2)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef unsigned short u16x8 __attribute__((ext_vector_type(8)));
-
-#include "split_fmt.hpp"
+#include "split_fmt.hpp"       // (brings device_prims.hpp: the vector types, xcd_remap, WINDOW_DESC, LDS_DMA16)
 
 // ---------------------------------------------------------------------------------------------
 // format conversion (module boundaries, tests): fp32 NDHWC <-> split-padded.  One thread per (voxel, 8 channels).
@@ -130,10 +122,15 @@ struct RsArgs {
     unsigned* sat;             // the range report's words (csrc/api.cpp): written when a clamp of the fp16 split engaged
 };
 
-__device__ __forceinline__ int rs_xcd_remap(int bid, int n) {
-    const int q = n >> 3, r = n & 7, x = bid & 7, i = bid >> 3;
-    return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + i;
-}
+// the split's conversions inside the generated schedules (tools/gen_rs*_schedule.py), for both kernels; RS_LRELU_MAX is LeakyReLU's
+// max, RS_CLAMP the fp16 split's range clamp on a split output: one v_med3_f32 BEHIND the activation (round 5 folded the upper end
+// into the activation's max as med3(t, t * slope, 65504), which passes t unclamped when t * slope > 65504: every t > 65504 at slope 1)
+#define RS_W_LO(U) sf_widen_lo<F16>(U)
+#define RS_W_HI(U) sf_widen_hi<F16>(U)
+#define RS_CVT_PK(A, B) sf_cvt_pk<F16>(A, B)
+#define RS_F_F16(...) if constexpr (F16) { __VA_ARGS__ }
+#define RS_CLAMP(T) __builtin_amdgcn_fmed3f(T, -kF16Max, kF16Max)
+#define RS_LRELU_MAX(T, U) __builtin_fmaxf(T, U)
 
 namespace rs {
 constexpr int TD = 2, TH = 4, TW = 16;        // brick: 128 output voxels = 2 planes x 4 rows x 16
@@ -326,7 +323,7 @@ __global__ __launch_bounds__(256, 1) void conv3d_rs32_kernel(RsArgs a) {
     } else {
         n = (total - (int)blockIdx.x + G - 1) / G;       // bricks of this workgroup (the same for its 4 waves)
         // The walk: logical ids id0 + k * step (XCD-contiguous remap, cdna_hip_programming.md T1; G % 8 == 0 or G == total)
-        id0 = rs_xcd_remap((int)blockIdx.x, total);
+        id0 = xcd_remap((int)blockIdx.x, total);
         step = G == total ? 0 : G >> 3;
     }
     // logical order (b, oh, od, ow), ow fastest: the bricks stacked along D share two of their four / six input planes and
@@ -368,24 +365,13 @@ __global__ __launch_bounds__(256, 1) void conv3d_rs32_kernel(RsArgs a) {
 // branch inside the phase body splits it into basic blocks, and hipcc then permutes the accumulators between registers at
 // the block boundaries (v_accvgpr_mov right in front of an asm MFMA it cannot see: an unpadded hazard, wrong sums).
 #define RS_DESC(PTR, U, VALID)                                                                                   \
-    ({                                                                                                           \
-        const long long off_ = (long long)(U).b * frame_bytes +                                                  \
-                               ((long long)(((U).od + up_od) * TD * Hp + (U).oh * TH) * Wp + (U).ow * TW) * 128; \
-        const long long left_ = total_bytes - off_;                                                              \
-        const int rec_ = left_ > 0x7fffff00ll ? 0x7fffff00 : (int)left_;                                         \
-        const int ok_ = (int)(VALID) & (int)(left_ > 0);                                                         \
-        __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned char*>(PTR) + off_, 0, ok_ ? rec_ : 0, 0x00020000); \
-    })
-#define RS_DESC_OUT(U, VALID)                                                                                   \
-    ({                                                                                                           \
-        const long long off_ = (long long)(U).b * oframe_bytes +                                                 \
-            (UP2 ? ((long long)((2 * up_od * TD + up_pd + OB) * Hh + 2 * (U).oh * TH + up_ph + OB) * Wh + 2 * (U).ow * TW + OB) * 64 \
-                 : ((long long)((U).od * TD * a.H + (U).oh * TH) * a.W + (U).ow * TW) * 128);                    \
-        const long long left_ = (long long)a.B * oframe_bytes - off_;                                            \
-        const int rec_ = left_ > 0x7fffff00ll ? 0x7fffff00 : (int)left_;                                         \
-        const int ok_ = (int)(VALID) & (int)(left_ > 0);                                                         \
-        __builtin_amdgcn_make_buffer_rsrc(a.y + off_, 0, ok_ ? rec_ : 0, 0x00020000);                            \
-    })
+    WINDOW_DESC(PTR, (long long)(U).b * frame_bytes +                                                            \
+                     ((long long)(((U).od + up_od) * TD * Hp + (U).oh * TH) * Wp + (U).ow * TW) * 128, total_bytes, VALID)
+#define RS_DESC_OUT(U, VALID)                                                                                    \
+    WINDOW_DESC(a.y, (long long)(U).b * oframe_bytes +                                                           \
+        (UP2 ? ((long long)((2 * up_od * TD + up_pd + OB) * Hh + 2 * (U).oh * TH + up_ph + OB) * Wh + 2 * (U).ow * TW + OB) * 64 \
+             : ((long long)((U).od * TD * a.H + (U).oh * TH) * a.W + (U).ow * TW) * 128),                        \
+                (long long)a.B * oframe_bytes, VALID)
 #define RS_F_SPL(...) if constexpr (!OUTF32) { __VA_ARGS__ }
 #define RS_F_F32(...) if constexpr (OUTF32) { __VA_ARGS__ }
 #define RS_F_UP2(...) if constexpr (UP2) { __VA_ARGS__ }
@@ -394,9 +380,7 @@ __global__ __launch_bounds__(256, 1) void conv3d_rs32_kernel(RsArgs a) {
 // the "residual" descriptor: the residual tensor, or (polyphase mode) the OUTPUT tensor, whose face voxels hold the corrections
 #define RS_DSC_R(U, VALID) (UP2 ? RS_DESC_OUT(U, VALID) : RS_DESC(a.res, U, (int)(a.res != nullptr) & (int)(VALID)))
 #define RS_RES_OFF(I) (UP2 ? voc[I] : voy0[I])
-#define RS_DMA(M)                                                                                                \
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(dsc_x, (__attribute__((address_space(3))) void*)(lds + nxt_img + (wave + 4 * (M)) * 1024), \
-                                             16, voff[M], 0, 0, 0);
+#define RS_DMA(M) LDS_DMA16(dsc_x, lds + nxt_img + (wave + 4 * (M)) * 1024, voff[M], 0, 0);
 // The MFMAs are inline asm so that the weight operands can be pinned to the accumulator half of the register file
 // ("a"): hipcc keeps A/B operands of the builtin form in VGPRs and would shuttle the 224 weight registers through
 // v_accvgpr_read every brick.  hipcc pads no hazards around asm: the schedule keeps >= 3 MFMAs between an accumulator's
@@ -410,15 +394,6 @@ __global__ __launch_bounds__(256, 1) void conv3d_rs32_kernel(RsArgs a) {
 #define RS_MF0(ACC, WREG, XREG)                                                                                        \
     if constexpr (F16) { asm volatile("v_mfma_f32_16x16x32_f16 %0, %1, %2, 0" : "+a"(ACC) : "a"(WREG), "v"(XREG)); }   \
     else { asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, 0" : "+a"(ACC) : "a"(WREG), "v"(XREG)); }
-// the split's conversions inside the generated schedules (tools/gen_rs*_schedule.py); RS_LRELU_MAX is LeakyReLU's max, RS_CLAMP the
-// fp16 split's range clamp on a split output: one v_med3_f32 BEHIND the activation (round 5 folded the upper end into the
-// activation's max as med3(t, t * slope, 65504), which passes t unclamped when t * slope > 65504: every t > 65504 at slope 1)
-#define RS_W_LO(U) sf_widen_lo<F16>(U)
-#define RS_W_HI(U) sf_widen_hi<F16>(U)
-#define RS_CVT_PK(A, B) sf_cvt_pk<F16>(A, B)
-#define RS_F_F16(...) if constexpr (F16) { __VA_ARGS__ }
-#define RS_CLAMP(T) __builtin_amdgcn_fmed3f(T, -kF16Max, kF16Max)
-#define RS_LRELU_MAX(T, U) __builtin_fmaxf(T, U)
 
 // diagnostic builds only: MVSGI_RS_ABL bit 1 drops the fragment reads, 2 the epilogue, 4 the LDS-DMA (results are wrong)
 #ifndef MVSGI_RS_ABL
@@ -496,7 +471,7 @@ __global__ __launch_bounds__(256, 1) void conv3d_rs32_kernel(RsArgs a) {
 
     f32x4 pt0, pt1, pt2, pt3, t0, t1_, t2, t3;
     u32x2 sa0, sb0, sa1, sb1, sa2, sb2, sa3, sb3, hb0, hb1, hb2, hb3, lb0, lb1, lb2, lb3;
-    f32x2v hf0, hf1, hf2, hf3;
+    f32x2 hf0, hf1, hf2, hf3;
     float rh0, rl0, u0, rh1, rl1, u1, rh2, rl2, u2, rh3, rl3, u3;
     float satm = 0.f;          // fp16 split, split output: running maximum |value written| (range report)
 #define t1 t1_
@@ -506,7 +481,7 @@ __global__ __launch_bounds__(256, 1) void conv3d_rs32_kernel(RsArgs a) {
     __amdgpu_buffer_rsrc_t dsc_x, dsc_r, dsc_y;
     unsigned voy[2] = {0xffffff00u, 0xffffff00u};
     unsigned voc[2] = {0xffffff00u, 0xffffff00u};
-    dsc_x = dsc_r = dsc_y = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned char*>(a.x), 0, 0, 0x00020000);
+    dsc_x = dsc_r = dsc_y = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned char*>(a.x), 0, 0, kRawBufferFlags);
 // stores of the brick two phases back: voxels outside the volume (ragged sizes) are sent out of range
 #define RS_VOY()                                                                                     \
     {                                                                                                \
@@ -565,12 +540,6 @@ __global__ __launch_bounds__(256, 1) void conv3d_rs32_kernel(RsArgs a) {
 #undef RS_PIN_WEIGHTS
 #undef RS_MF
 #undef RS_MF0
-#undef RS_W_LO
-#undef RS_W_HI
-#undef RS_CVT_PK
-#undef RS_F_F16
-#undef RS_CLAMP
-#undef RS_LRELU_MAX
 #undef RS_DMA
 #undef RS_DESC
 #undef RS_DESC_OUT
@@ -705,7 +674,7 @@ __global__ __launch_bounds__(LOADERS ? 512 : 256, 1) void conv3d_rs16_kernel(Rs1
 
     const int total = a.total_units, G = gridDim.x;
     const int n = (total - (int)blockIdx.x + G - 1) / G;
-    const int id0 = rs_xcd_remap((int)blockIdx.x, total);
+    const int id0 = xcd_remap((int)blockIdx.x, total);
     const int step = G == total ? 0 : G >> 3;
     // logical order (b, oh, od, ow), ow fastest: the bricks stacked along D share two of their four / six input planes and
     // follow each other within one XCD round (tiles_w ids apart), the bricks above / below a round or two later -- in the
@@ -739,26 +708,13 @@ __global__ __launch_bounds__(LOADERS ? 512 : 256, 1) void conv3d_rs16_kernel(Rs1
     }
     RS16_STEP(nx, c0)
 #define RS16_DESC(U, VALID)                                                                                      \
-    ({                                                                                                           \
-        const long long off_ = (long long)(U).b * frame_bytes +                                                  \
-                               ((long long)((U).od * TD * Hp + (U).oh * TH) * Wp + (U).ow * TW) * 64;            \
-        const long long left_ = total_bytes - off_;                                                              \
-        const int rec_ = left_ > 0x7fffff00ll ? 0x7fffff00 : (int)left_;                                         \
-        const int ok_ = (int)(VALID) & (int)(left_ > 0);                                                         \
-        __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned char*>(a.x) + off_, 0, ok_ ? rec_ : 0, 0x00020000); \
-    })
+    WINDOW_DESC(a.x, (long long)(U).b * frame_bytes + ((long long)((U).od * TD * Hp + (U).oh * TH) * Wp + (U).ow * TW) * 64, \
+                total_bytes, VALID)
 #define RS16_DESC_OUT(U, VALID)                                                                                  \
-    ({                                                                                                           \
-        const long long off_ = OSPLIT ? (long long)(U).b * frame_bytes + ((long long)((U).od * TD * Hp + (U).oh * TH) * Wp + (U).ow * TW) * 64 \
-                                      : (long long)(U).b * oframe + ((long long)((U).od * TD * a.H + (U).oh * TH) * a.W + (U).ow * TW) * 64; \
-        const long long left_ = (OSPLIT ? total_bytes : ototal) - off_;                                          \
-        const int rec_ = left_ > 0x7fffff00ll ? 0x7fffff00 : (int)left_;                                         \
-        const int ok_ = (int)(VALID) & (int)(left_ > 0);                                                         \
-        __builtin_amdgcn_make_buffer_rsrc(a.y + off_, 0, ok_ ? rec_ : 0, 0x00020000);                            \
-    })
-#define RS16_DMA(M)                                                                                              \
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(dsc_x, (__attribute__((address_space(3))) void*)(lds + nxt_img + (wave + 4 * (M)) * 1024), \
-                                             16, voff[M], 0, 0, 0);
+    WINDOW_DESC(a.y, OSPLIT ? (long long)(U).b * frame_bytes + ((long long)((U).od * TD * Hp + (U).oh * TH) * Wp + (U).ow * TW) * 64 \
+                            : (long long)(U).b * oframe + ((long long)((U).od * TD * a.H + (U).oh * TH) * a.W + (U).ow * TW) * 64, \
+                OSPLIT ? total_bytes : ototal, VALID)
+#define RS16_DMA(M) LDS_DMA16(dsc_x, lds + nxt_img + (wave + 4 * (M)) * 1024, voff[M], 0, 0);
 #define RS16_VOY()                                                                                               \
     {                                                                                                            \
         const int hok_ = c1.oh * TH + wave < a.H;                                                                \
@@ -782,15 +738,6 @@ __global__ __launch_bounds__(LOADERS ? 512 : 256, 1) void conv3d_rs16_kernel(Rs1
         else { asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, 0" : "+v"(ACC) : "a"(WREG), "v"(XREG)); }            \
     } else if constexpr (F16) { asm volatile("v_mfma_f32_16x16x32_f16 %0, %1, %2, 0" : "+a"(ACC) : "a"(WREG), "v"(XREG)); }   \
     else { asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, 0" : "+a"(ACC) : "a"(WREG), "v"(XREG)); }
-// the split's conversions inside the generated schedules (tools/gen_rs*_schedule.py); RS_LRELU_MAX is LeakyReLU's max, RS_CLAMP the
-// fp16 split's range clamp on a split output: one v_med3_f32 BEHIND the activation (round 5 folded the upper end into the
-// activation's max as med3(t, t * slope, 65504), which passes t unclamped when t * slope > 65504: every t > 65504 at slope 1)
-#define RS_W_LO(U) sf_widen_lo<F16>(U)
-#define RS_W_HI(U) sf_widen_hi<F16>(U)
-#define RS_CVT_PK(A, B) sf_cvt_pk<F16>(A, B)
-#define RS_F_F16(...) if constexpr (F16) { __VA_ARGS__ }
-#define RS_CLAMP(T) __builtin_amdgcn_fmed3f(T, -kF16Max, kF16Max)
-#define RS_LRELU_MAX(T, U) __builtin_fmaxf(T, U)
 #define RS_PIN_V(V) asm volatile("" : "+v"(V));
 #define RS_F_STORE16(V, D, O) __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, V), D, O, 0, MVSGI_RS16_NT);
 #define RS16_F_SPL(...) if constexpr (OSPLIT) { __VA_ARGS__ }
@@ -831,11 +778,11 @@ __global__ __launch_bounds__(LOADERS ? 512 : 256, 1) void conv3d_rs16_kernel(Rs1
 #define RS16_F_OWN(...) if constexpr (!LOADERS) { __VA_ARGS__ }
     __amdgpu_buffer_rsrc_t dsc_x, dsc_y;
     u32x2 hb0, hb1, hb2, hb3, lb0, lb1, lb2, lb3, sa0, sa1, sa2, sa3, sb0, sb1, sb2, sb3;
-    f32x2v hf0, hf1, hf2, hf3;
+    f32x2 hf0, hf1, hf2, hf3;
     hb0 = hb1 = hb2 = hb3 = lb0 = lb1 = lb2 = lb3 = sa0 = sa1 = sa2 = sa3 = sb0 = sb1 = sb2 = sb3 = u32x2{0u, 0u};
-    hf0 = hf1 = hf2 = hf3 = f32x2v{0.f, 0.f};
+    hf0 = hf1 = hf2 = hf3 = f32x2{0.f, 0.f};
     unsigned voy[4] = {0xffffff00u, 0xffffff00u, 0xffffff00u, 0xffffff00u};
-    dsc_y = __builtin_amdgcn_make_buffer_rsrc(a.y, 0, 0, 0x00020000);
+    dsc_y = __builtin_amdgcn_make_buffer_rsrc(a.y, 0, 0, kRawBufferFlags);
     if constexpr (!LOADERS) {   // prologue: image 0 <- brick 0
         dsc_x = RS16_DESC(c0, 1);
         const int nxt_img = 0;
@@ -883,12 +830,6 @@ __global__ __launch_bounds__(LOADERS ? 512 : 256, 1) void conv3d_rs16_kernel(Rs1
 #undef RS16_VOY
 #undef RS_MF
 #undef RS_MF0
-#undef RS_W_LO
-#undef RS_W_HI
-#undef RS_CVT_PK
-#undef RS_F_F16
-#undef RS_CLAMP
-#undef RS_LRELU_MAX
 #undef RS_PIN_V
 #undef RS_F_STORE16
 #undef RS16_F_SPL

@@ -27,14 +27,6 @@
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2v __attribute__((ext_vector_type(2)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef unsigned short u16x8 __attribute__((ext_vector_type(8)));
-
 #include "split_fmt.hpp"
 
 // LeakyReLU for slopes in [0, 1] as mul + max (plain asm max: __builtin_fmaxf first canonicalises an MFMA result with a third op)
@@ -45,17 +37,8 @@ __device__ __forceinline__ float lrelu(const float v, const float slope) {
     return r;
 }
 
-// one LDS-DMA piece: 64 lanes x 16 B from per-lane offsets of a buffer into 1 KiB of LDS.  (A plain function on purpose: in the
-// kernel TEMPLATE below the builtin's operands would be value-dependent, and hipcc's host pass then drops the kernel's stub
-// without a diagnostic.)
-__device__ __forceinline__ void s2_dma_piece(const __amdgpu_buffer_rsrc_t dsc, unsigned char* lds_dst, const unsigned voff) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(dsc, (__attribute__((address_space(3))) void*)lds_dst, 16, voff, 0, 0, 0);
-}
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t s2_desc(const unsigned char* base, const long long off, const long long total) {
-    const long long left = total - off;
-    const int rec = left > 0x7fffff00ll ? 0x7fffff00 : (int)left;
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned char*>(base) + off, 0, rec, 0x00020000);
-}
+// (windows and LDS-DMA pieces go through the FUNCTIONS of device_prims.hpp, window_desc / lds_dma16: in the kernel TEMPLATE below the
+// builtins' operands would be value-dependent, and hipcc's host pass then drops the kernel's stub without a diagnostic)
 __device__ __forceinline__ void s2_store16(const u32x4 v, const __amdgpu_buffer_rsrc_t dsc, const unsigned voff, const int soff) {
     __builtin_amdgcn_raw_buffer_store_b128(v, dsc, voff, soff, MVSGI_S2RS_ST_AUX);
 }
@@ -126,11 +109,6 @@ struct S2Args {
     unsigned* sat;             // the range report's words (csrc/api.cpp)
 };
 
-__device__ __forceinline__ int s2_xcd_remap(int bid, int n) {
-    const int q = n >> 3, r = n & 7, x = bid & 7, i = bid >> 3;
-    return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + i;
-}
-
 // NBUF = 2: one workgroup per CU (TH = 4), the window of brick u + 1 in flight under brick u.  NBUF = 1: ONE window per workgroup and
 // two workgroups per CU -- the next window is requested when the workgroup is done with the current one, and the partner workgroup's
 // request is in flight meanwhile (~1.6 windows in flight per CU instead of 1).  Measured the same within 2 % (565 vs 577 us per 64
@@ -154,7 +132,7 @@ __global__ __launch_bounds__(256, (TH == 4 && NBUF == 2) ? 1 : 2) void conv3d_s2
     const long long oframe_bytes = (long long)(a.Do + 2) * Hop * Wop * 128, ototal_bytes = oframe_bytes * a.B;
     const int total = a.total_units, Gd = gridDim.x;
     const int nmine = (total - (int)blockIdx.x + Gd - 1) / Gd;
-    const int id0 = Gd == total ? (int)blockIdx.x : s2_xcd_remap((int)blockIdx.x, total);
+    const int id0 = Gd == total ? (int)blockIdx.x : xcd_remap((int)blockIdx.x, total);
     const int idstep = Gd == total ? 0 : Gd >> 3;
 
     // ---- this wave's weights (cout tile ct), resident ----
@@ -208,8 +186,8 @@ __global__ __launch_bounds__(256, (TH == 4 && NBUF == 2) ? 1 : 2) void conv3d_s2
     // window of brick (b, od, oh0, ow0): origin = padded input voxel (2 od, 2 oh0, 2 ow0)
 #define S2_STAGE(IMGOFF, B_, OD, OH, OW)                                                                         \
     {                                                                                                            \
-        const auto dsc_ = s2_desc(a.x, (long long)(B_) * frame_bytes + (((long long)(2 * (OD)) * Hp + 2 * (OH)) * Wp + 2 * (OW)) * 64, total_bytes); \
-        _Pragma("unroll") for (int m = 0; m < DPW; ++m) s2_dma_piece(dsc_, lds + (IMGOFF) + (wave + 4 * m) * 1024, voff[m]); \
+        const auto dsc_ = window_desc(a.x, (long long)(B_) * frame_bytes + (((long long)(2 * (OD)) * Hp + 2 * (OH)) * Wp + 2 * (OW)) * 64, total_bytes); \
+        _Pragma("unroll") for (int m = 0; m < DPW; ++m) lds_dma16(dsc_, lds + (IMGOFF) + (wave + 4 * m) * 1024, voff[m]); \
     }
     int b_, od, oh0, ow0;
     S2_DECODE(id0, b_, od, oh0, ow0)
@@ -225,10 +203,10 @@ __global__ __launch_bounds__(256, (TH == 4 && NBUF == 2) ? 1 : 2) void conv3d_s2
         // the CU's address path in front of the MFMAs (MVSGI_S2RS_DMA_SPREAD=0 restores the burst: 559 vs 486 us per 64 frames).
         // Four different issue points inside a pair for the four waves instead of one: 501 vs 493 us -- not kept
         const bool more = u + 1 < nmine;
-        const auto dsc_n = s2_desc(a.x, (long long)nb * frame_bytes + (((long long)(2 * nod) * Hp + 2 * noh) * Wp + 2 * now) * 64, total_bytes);
+        const auto dsc_n = window_desc(a.x, (long long)nb * frame_bytes + (((long long)(2 * nod) * Hp + 2 * noh) * Wp + 2 * now) * 64, total_bytes);
         constexpr bool SPREAD = NBUF == 2 && MVSGI_S2RS_DMA_SPREAD && DPW <= kPairs;
         if constexpr (NBUF == 2 && !SPREAD)
-            if (more) { _Pragma("unroll") for (int m = 0; m < DPW; ++m) s2_dma_piece(dsc_n, lds + (IMG - img) + (wave + 4 * m) * 1024, voff[m]); }
+            if (more) { _Pragma("unroll") for (int m = 0; m < DPW; ++m) lds_dma16(dsc_n, lds + (IMG - img) + (wave + 4 * m) * 1024, voff[m]); }
         // three accumulators per tile, one per product term: a tile's consecutive MFMAs then never wait for each other (with one
         // accumulator per tile a wave has two dependent chains and the matrix pipe idles half of the time)
         f32x4 acc[TPW], acc1[TPW], acc2[TPW];
@@ -251,7 +229,7 @@ __global__ __launch_bounds__(256, (TH == 4 && NBUF == 2) ? 1 : 2) void conv3d_s2
             if constexpr (SPREAD) {
                 if (p < DPW) {
                     __builtin_amdgcn_sched_barrier(0);
-                    if (more) s2_dma_piece(dsc_n, lds + (IMG - img) + (wave + 4 * p) * 1024, voff[p]);
+                    if (more) lds_dma16(dsc_n, lds + (IMG - img) + (wave + 4 * p) * 1024, voff[p]);
                     __builtin_amdgcn_sched_barrier(0);
                 }
             }
@@ -269,7 +247,7 @@ __global__ __launch_bounds__(256, (TH == 4 && NBUF == 2) ? 1 : 2) void conv3d_s2
             if (u + 1 < nmine) S2_STAGE(0, nb, nod, noh, now)
         }
         {
-            const auto dsc_ = s2_desc(a.y, (long long)b_ * oframe_bytes + (((long long)(od + 1) * Hop + oh0 + 1) * Wop + ow0 + 1) * 128, ototal_bytes);
+            const auto dsc_ = window_desc(a.y, (long long)b_ * oframe_bytes + (((long long)(od + 1) * Hop + oh0 + 1) * Wop + ow0 + 1) * 128, ototal_bytes);
             const bool okc = ow0 + col < a.Wo;
 #pragma unroll
             for (int i = 0; i < TPW; ++i) {

@@ -21,9 +21,6 @@
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 #include "split_fmt.hpp"
 
 enum { FIRST = 0, INT = 1, LAST = 2, ONLY = 3 };
@@ -236,7 +233,7 @@ __global__ __launch_bounds__(512, 2) void up2_face_kernel(const unsigned char* _
         const int run = rt * 16 + col;
         const bool ok = run < nrun;
         const __amdgpu_buffer_rsrc_t dx = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned char*>(x) + (long long)b * x_frame, 0,
-                                                                            (int)x_frame, 0x00020000);
+                                                                            (int)x_frame, kRawBufferFlags);
         const unsigned xo = ok ? (unsigned)(x_base + o0 * x_s0 + run * x_srun + lane_x) : 0xffffff00u;
         u32x4 fh[9], fl[9];
 #pragma unroll

@@ -29,11 +29,6 @@
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned short u16x8 __attribute__((ext_vector_type(8)));
-
 #include "split_fmt.hpp"
 
 struct WinoArgs {
@@ -194,22 +189,19 @@ __global__ __launch_bounds__(256, 1) void conv3d_wino32_kernel(WinoArgs a) {
         const int r_ = t_ % a.tiles_h, b_ = t_ / a.tiles_h;                                                 \
         const long long off_ = (LIVE) ? b_ * frame_bytes + ((long long)(2 * r_) * Wp + 32 * c_) * 128 : 0;  \
         const long long left_ = total_bytes - off_;                                                         \
-        __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned char*>(a.x) + off_, 0,                        \
-                                          (LIVE) ? (left_ > 0x7fffff00ll ? 0x7fffff00 : (int)left_) : 0, 0x00020000); \
+        window_desc(a.x + off_, 0, left_, LIVE);                                                            \
     })
 // Staging: input plane (P + 3) of the plane stream -- of this unit, or of the next one from P = D - 3 on -- goes to image (P + 3) % 4
 // (D % 4 == 0: the images keep their phase over units); the residual records of plane P to image `ri` of a ring of three.
 #define WN_DMA_ISSUE(P3, K0, K1)                                                                            \
     _Pragma("unroll") for (int k_ = (K0); k_ < (K1); ++k_)                                                  \
-        __builtin_amdgcn_raw_ptr_buffer_load_lds((P3) < DEPTH ? dsc : dsc_next,                             \
-                                                 (__attribute__((address_space(3))) void*)(lds + (wv + 4 * k_ < NDMA ? ((P3) % NBUF) * PLANE_LDS + (wv + 4 * k_) * 1024 : DUMMY)), \
-                                                 16, voff[k_], (unsigned)(((P3) % DEPTH + 1) * plane_bytes), 0, 0);
+        LDS_DMA16((P3) < DEPTH ? dsc : dsc_next, lds + (wv + 4 * k_ < NDMA ? ((P3) % NBUF) * PLANE_LDS + (wv + 4 * k_) * 1024 : DUMMY), \
+                  voff[k_], (unsigned)(((P3) % DEPTH + 1) * plane_bytes), 0);
 #define WN_RES_DMA(IMG, OPLANE)                                                                             \
     {                                                                                                       \
         const unsigned so_ = (unsigned)(((OPLANE) + 1) * plane_bytes);                                      \
         _Pragma("unroll") for (int k_ = 0; k_ < RDPW; ++k_)                                                 \
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rdsc, (__attribute__((address_space(3))) void*)(lds + RB + (IMG) * RES_LDS + (wv + 4 * k_) * 1024), \
-                                                     16, rvoff[k_], so_, 0, 0);                             \
+            LDS_DMA16(rdsc, lds + RB + (IMG) * RES_LDS + (wv + 4 * k_) * 1024, rvoff[k_], so_, 0);          \
     }
 #define WN_READ(BUF_)                                                                                       \
     {                                                                                                       \
@@ -456,8 +448,7 @@ __global__ __launch_bounds__(256, 1) void conv3d_wino32_kernel(WinoArgs a) {
                                   : a.y + b * frame_bytes + ((long long)(2 * r + pa + 1) * Wp + 32 * c + q + 1) * 128;
         const long long roff = b * frame_bytes + ((long long)(2 * r + 1) * Wp + 32 * c + 1) * 128;      // the unit's output rows in the residual tensor
         const long long rleft = total_bytes - roff;
-        const auto rdsc = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned char*>(RES ? a.res : a.x) + roff, 0,
-                                                            rleft > 0x7fffff00ll ? 0x7fffff00 : (int)rleft, 0x00020000);
+        const auto rdsc = window_desc((RES ? a.res : a.x) + roff, 0, rleft);
         dsc_next = WN_DESC(u + ustep, k + 1 < nmine);
         // slots follow the plane mod 3, the V pair the plane mod 2
 #define WN_STEPP(P) WN_STEP(P, ((P) + 1) % 3, (P) % 3, ((P) + 2) % 3, (P) & 1)

@@ -34,11 +34,6 @@
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
 #include "split_fmt.hpp"
 #include "conv3d_wino_common.hpp"
 
@@ -203,22 +198,19 @@ __global__ __launch_bounds__(256, 1) void conv3d_wino_up2_kernel(WinoUp2Args a) 
         const int r_ = t_ % a.tiles_h, b_ = t_ / a.tiles_h;                                                 \
         const long long off_ = (LIVE) ? b_ * frame_bytes + ((long long)(2 * r_) * Wp + 32 * c_) * 128 : 0;  \
         const long long left_ = total_bytes - off_;                                                         \
-        __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned char*>(a.x) + off_, 0,                        \
-                                          (LIVE) ? (left_ > 0x7fffff00ll ? 0x7fffff00 : (int)left_) : 0, 0x00020000); \
+        window_desc(a.x + off_, 0, left_, LIVE);                                                            \
     })
 // low-resolution plane Q (0 .. 7 of this unit, 8 | 9 = planes 0 | 1 of the next) -> image Q & 1, pieces K0 .. K1 - 1 of this wave
 #define KU_DMA_ISSUE(Q, K0, K1)                                                                             \
     _Pragma("unroll") for (int k_ = (K0); k_ < (K1); ++k_)                                                  \
-        __builtin_amdgcn_raw_ptr_buffer_load_lds((Q) < 8 ? dsc : dsc_next,                                  \
-                                                 (__attribute__((address_space(3))) void*)(lds + (wv + 4 * k_ < NDMA ? ((Q) & 1) * PLANE_LDS + (wv + 4 * k_) * 1024 : DUMMY)), \
-                                                 16, voff[k_], (unsigned)(((Q) % 8 + 1) * plane_bytes), 0, 0);
+        LDS_DMA16((Q) < 8 ? dsc : dsc_next, lds + (wv + 4 * k_ < NDMA ? ((Q) & 1) * PLANE_LDS + (wv + 4 * k_) * 1024 : DUMMY), \
+                  voff[k_], (unsigned)(((Q) % 8 + 1) * plane_bytes), 0);
 // the raw corrections of output plane O of this unit -> image IMG of the ring (zeros where the cell is not on a face)
 #define KU_RES_DMA(IMG, O)                                                                                  \
     {                                                                                                       \
         const unsigned so_ = (unsigned)(((O) + 1) * oplane_bytes);                                          \
         _Pragma("unroll") for (int k_ = 0; k_ < RDPW; ++k_)                                                 \
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rdsc, (__attribute__((address_space(3))) void*)(lds + RB + (IMG) * RES_LDS + (wv + 4 * k_) * 1024), \
-                                                     16, rvu[k_], so_, 0, 0);                               \
+            LDS_DMA16(rdsc, lds + RB + (IMG) * RES_LDS + (wv + 4 * k_) * 1024, rvu[k_], so_, 0);            \
     }
 #define KU_READ(BUF_)                                                                                       \
     {                                                                                                       \
@@ -433,7 +425,7 @@ __global__ __launch_bounds__(256, 1) void conv3d_wino_up2_kernel(WinoUp2Args a) 
         // the unit's cells in the output tensor, row pa = 0, pw = 0 of column 32 c: where the raw corrections sit
         const long long roff = b * oframe_bytes + ((long long)(2 * (2 * r) + ph + 1) * Wq + 2 * (32 * c) + 1) * 64;
         const long long rleft = ototal_bytes - roff;
-        const auto rdsc = __builtin_amdgcn_make_buffer_rsrc(a.y + roff, 0, rleft > 0x7fffff00ll ? 0x7fffff00 : (int)rleft, 0x00020000);
+        const auto rdsc = window_desc(a.y + roff, 0, rleft);
         // only cells on an H or W face of the volume hold a correction: everything else is requested out of range (zeros)
         unsigned rvu[RDPW];
 #pragma unroll

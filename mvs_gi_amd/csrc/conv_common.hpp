@@ -2,7 +2,7 @@
 #pragma once
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+#include "device_prims.hpp"
 
 struct ConvArgs {
     const float* x;

@@ -20,7 +20,7 @@
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+#include "device_prims.hpp"
 
 struct DeformArgs {
     const float* x;

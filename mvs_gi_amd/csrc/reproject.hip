@@ -69,10 +69,10 @@ __global__ __launch_bounds__(256) void reproject_kernel(const float* __restrict_
     {
         float rx[4], ry[4], rz[4];
         if (VEC) {
-            const f32x4_t v4 = *reinterpret_cast<const f32x4_t*>(inv + b * HW + pix);
-            const f32x4_t x4 = *reinterpret_cast<const f32x4_t*>(rays + pix);
-            const f32x4_t y4 = *reinterpret_cast<const f32x4_t*>(rays + HW + pix);
-            const f32x4_t z4 = *reinterpret_cast<const f32x4_t*>(rays + 2 * HW + pix);
+            const f32x4 v4 = *reinterpret_cast<const f32x4*>(inv + b * HW + pix);
+            const f32x4 x4 = *reinterpret_cast<const f32x4*>(rays + pix);
+            const f32x4 y4 = *reinterpret_cast<const f32x4*>(rays + HW + pix);
+            const f32x4 z4 = *reinterpret_cast<const f32x4*>(rays + 2 * HW + pix);
 #pragma unroll
             for (int k = 0; k < 4; ++k) v[k] = v4[k], rx[k] = x4[k], ry[k] = y4[k], rz[k] = z4[k];
         } else {
@@ -94,9 +94,9 @@ __global__ __launch_bounds__(256) void reproject_kernel(const float* __restrict_
     if (xyz && cam == 0) {
         float* o = xyz + (b * 3) * HW + pix;
         if (VEC) {
-            *reinterpret_cast<f32x4_t*>(o) = f32x4_t{px[0], px[1], px[2], px[3]};
-            *reinterpret_cast<f32x4_t*>(o + HW) = f32x4_t{py[0], py[1], py[2], py[3]};
-            *reinterpret_cast<f32x4_t*>(o + 2 * HW) = f32x4_t{pz[0], pz[1], pz[2], pz[3]};
+            *reinterpret_cast<f32x4*>(o) = f32x4{px[0], px[1], px[2], px[3]};
+            *reinterpret_cast<f32x4*>(o + HW) = f32x4{py[0], py[1], py[2], py[3]};
+            *reinterpret_cast<f32x4*>(o + 2 * HW) = f32x4{pz[0], pz[1], pz[2], pz[3]};
         } else {
 #pragma unroll
             for (int k = 0; k < 4; ++k)
@@ -128,8 +128,8 @@ __global__ __launch_bounds__(256) void reproject_kernel(const float* __restrict_
     if (grid) {
         float* o = grid + (m * HW + pix) * 2;
         if (VEC) {
-            *reinterpret_cast<f32x4_t*>(o) = f32x4_t{gx[0], gy[0], gx[1], gy[1]};
-            *reinterpret_cast<f32x4_t*>(o + 4) = f32x4_t{gx[2], gy[2], gx[3], gy[3]};
+            *reinterpret_cast<f32x4*>(o) = f32x4{gx[0], gy[0], gx[1], gy[1]};
+            *reinterpret_cast<f32x4*>(o + 4) = f32x4{gx[2], gy[2], gx[3], gy[3]};
         } else {
 #pragma unroll
             for (int k = 0; k < 4; ++k)
@@ -167,7 +167,7 @@ __global__ __launch_bounds__(256) void reproject_kernel(const float* __restrict_
             }
         }
         if (VEC) {
-            *reinterpret_cast<f32x4_t*>(o + ch * HW) = f32x4_t{r[0], r[1], r[2], r[3]};
+            *reinterpret_cast<f32x4*>(o + ch * HW) = f32x4{r[0], r[1], r[2], r[3]};
         } else {
 #pragma unroll
             for (int k = 0; k < 4; ++k)

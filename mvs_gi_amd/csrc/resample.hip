@@ -50,8 +50,8 @@ __global__ __launch_bounds__(256) void resample_bilinear_kernel(const void* __re
     float gx[4], gy[4];
     bool ok[4];
     if (VEC) {
-        const f32x4_t g0 = *reinterpret_cast<const f32x4_t*>(grid + tab * 2);
-        const f32x4_t g1 = *reinterpret_cast<const f32x4_t*>(grid + tab * 2 + 4);
+        const f32x4 g0 = *reinterpret_cast<const f32x4*>(grid + tab * 2);
+        const f32x4 g1 = *reinterpret_cast<const f32x4*>(grid + tab * 2 + 4);
         const unsigned v = *reinterpret_cast<const unsigned*>(valid + tab);
         gx[0] = g0.x, gy[0] = g0.y, gx[1] = g0.z, gy[1] = g0.w;
         gx[2] = g1.x, gy[2] = g1.y, gx[3] = g1.z, gy[3] = g1.w;
@@ -84,7 +84,7 @@ __global__ __launch_bounds__(256) void resample_bilinear_kernel(const void* __re
             }
         }
         if (VEC) {
-            *reinterpret_cast<f32x4_t*>(o + c * HW) = f32x4_t{r[0], r[1], r[2], r[3]};
+            *reinterpret_cast<f32x4*>(o + c * HW) = f32x4{r[0], r[1], r[2], r[3]};
         } else {
 #pragma unroll
             for (int k = 0; k < 4; ++k)

@@ -31,19 +31,14 @@
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2v __attribute__((ext_vector_type(2)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
+#include "device_prims.hpp"
 
 __device__ __forceinline__ void split4(const f32x4 x, u32x2& hi, u32x2& lo) {
 #pragma unroll
     for (int p = 0; p < 2; ++p) {
-        const f32x2v v = {x[2 * p], x[2 * p + 1]};
+        const f32x2 v = {x[2 * p], x[2 * p + 1]};
         const unsigned hb = __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2));
-        const f32x2v hf = {__builtin_bit_cast(float, hb << 16), __builtin_bit_cast(float, hb & 0xffff0000u)};
+        const f32x2 hf = {__builtin_bit_cast(float, hb << 16), __builtin_bit_cast(float, hb & 0xffff0000u)};
         hi[p] = hb;
         lo[p] = __builtin_bit_cast(unsigned, __builtin_convertvector(v - hf, bf16x2));
     }
@@ -169,11 +164,6 @@ struct RbArgs {
     unsigned long long* dbg;   // MVSGI_RS_STAMPS diagnostic build only
 };
 
-__device__ __forceinline__ int rb_xcd_remap(int bid, int n) {
-    const int q = n >> 3, r = n & 7, x = bid & 7, i = bid >> 3;
-    return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + i;
-}
-
 // The epilogues are the kernel's VALU bill (two waves per SIMD share one issue port with the MFMAs), so everything that can
 // be is done elsewhere: scale in the weights, shift as the accumulators' start value, the skip connection as ONE more MFMA per
 // tile (A = [I | I]: hi + lo of the window's centre pixel, read as one 16-byte fragment while the window is still there),
@@ -192,7 +182,7 @@ __global__ __launch_bounds__(256, 2) void resblock2d_rs_kernel(RbArgs a) {
     const int total = a.total_units, G = gridDim.x;
     // bricks of this workgroup: logical ids remap(blockIdx) + k * (G / 8) -- XCD x walks a contiguous eighth of the bricks
     const int nmine = (total - (int)blockIdx.x + G - 1) / G;
-    const int id0 = G == total ? (int)blockIdx.x : rb_xcd_remap((int)blockIdx.x, total);
+    const int id0 = G == total ? (int)blockIdx.x : xcd_remap((int)blockIdx.x, total);
     const int idstep = G == total ? 0 : G >> 3;
 
     // ---- both weight sets, resident ----
@@ -271,16 +261,8 @@ __global__ __launch_bounds__(256, 2) void resblock2d_rs_kernel(RbArgs a) {
         OW = (a.patch * C_ + px_) * TOW;                                                 \
     }
     // window of brick (n, oh0, ow0): origin = padded pixel (oh0, ow0) = image pixel (oh0 - 2, ow0 - 2)
-#define RB_DESC(N_, OH, OW)                                                                                      \
-    ({                                                                                                           \
-        const long long off_ = (((long long)(N_) * Hp + (OH)) * Wp + (OW)) * 64;                                 \
-        const long long left_ = total_bytes - off_;                                                              \
-        const int rec_ = left_ > 0x7fffff00ll ? 0x7fffff00 : (int)left_;                                         \
-        __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned char*>(a.x) + off_, 0, rec_, 0x00020000);          \
-    })
-#define RB_PIECE(DSC, M)                                                                                         \
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(DSC, (__attribute__((address_space(3))) void*)(lds + (wave + 4 * (M)) * 1024), \
-                                             16, voff[M], 0, 0, MVSGI_RB_LD_AUX);
+#define RB_DESC(N_, OH, OW) window_desc(a.x, (((long long)(N_) * Hp + (OH)) * Wp + (OW)) * 64, total_bytes)
+#define RB_PIECE(DSC, M) LDS_DMA16(DSC, lds + (wave + 4 * (M)) * 1024, voff[M], 0, MVSGI_RB_LD_AUX);
 #define RB_STAGE(N_, OH, OW)                                                                                     \
     {                                                                                                            \
         const auto dsc_ = RB_DESC(N_, OH, OW);                                                                   \
@@ -387,7 +369,8 @@ __global__ __launch_bounds__(256, 2) void resblock2d_rs_kernel(RbArgs a) {
         const long long ooff_ = OUTF32 ? (((long long)n_ * a.H + oh0) * a.W + ow0) * 64
                                        : (((long long)n_ * Hp + oh0 + PAD) * Wp + ow0 + PAD) * 64;
         const long long oleft_ = out_bytes - ooff_;
-        const auto dsc_o = __builtin_amdgcn_make_buffer_rsrc(a.y + ooff_, 0, oleft_ > 0x7fffff00ll ? 0x7fffff00 : (int)oleft_, 0x00020000);
+        // (written out: through window_desc() the OUTF32 kernel comes out with another instruction stream, tools/isa_diff.py)
+        const auto dsc_o = __builtin_amdgcn_make_buffer_rsrc(a.y + ooff_, 0, WINDOW_RECORDS(oleft_), kRawBufferFlags);
         const bool okc = 16 * hf + col < TOW && ow0 + 16 * hf + col < a.W;
 #define RB_EPI_B(K)                                                                                              \
         {                                                                                                        \
@@ -517,10 +500,6 @@ struct C2sArgs {
     float neg_slope;
 };
 
-__device__ __forceinline__ void c2s_dma_piece(const __amdgpu_buffer_rsrc_t dsc, unsigned char* lds_dst, const unsigned voff) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(dsc, (__attribute__((address_space(3))) void*)lds_dst, 16, voff, 0, 0, 0);
-}
-
 __global__ __launch_bounds__(256, 2) void conv2d_s2rs_kernel(C2sArgs a) {
     using namespace c2s;
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
@@ -531,7 +510,7 @@ __global__ __launch_bounds__(256, 2) void conv2d_s2rs_kernel(C2sArgs a) {
     const long long total_bytes = (long long)a.N * Hp * Wp * 64, ototal_bytes = (long long)a.N * Hop * Wop * 64;
     const int total = a.total_units, G = gridDim.x;
     const int nmine = (total - (int)blockIdx.x + G - 1) / G;
-    const int id0 = G == total ? (int)blockIdx.x : rb_xcd_remap((int)blockIdx.x, total);
+    const int id0 = G == total ? (int)blockIdx.x : xcd_remap((int)blockIdx.x, total);
     const int idstep = G == total ? 0 : G >> 3;
 
     bf16x8 wh[5], wl[5];
@@ -572,19 +551,13 @@ __global__ __launch_bounds__(256, 2) void conv2d_s2rs_kernel(C2sArgs a) {
         N_ = t_ / a.tiles_h;                                     \
     }
     // window of brick (n, oh0, ow0): origin = padded input pixel (2 oh0 + 1, 2 ow0 + 1) = image pixel (2 oh0 - 1, 2 ow0 - 1)
-#define C2S_DESC(N_, OH, OW)                                                                                     \
-    ({                                                                                                           \
-        const long long off_ = (((long long)(N_) * Hp + 2 * (OH) + 1) * Wp + 2 * (OW) + 1) * 64;                 \
-        const long long left_ = total_bytes - off_;                                                              \
-        const int rec_ = left_ > 0x7fffff00ll ? 0x7fffff00 : (int)left_;                                         \
-        __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned char*>(a.x) + off_, 0, rec_, 0x00020000);          \
-    })
+#define C2S_DESC(N_, OH, OW) window_desc(a.x, (((long long)(N_) * Hp + 2 * (OH) + 1) * Wp + 2 * (OW) + 1) * 64, total_bytes)
     int n_, oh0, ow0;
     C2S_DECODE(id0, n_, oh0, ow0)
     {
         const auto d0_ = C2S_DESC(n_, oh0, ow0);
 #pragma unroll
-        for (int m = 0; m < DPW; ++m) c2s_dma_piece(d0_, lds + (wave + 4 * m) * 1024, voff[m]);
+        for (int m = 0; m < DPW; ++m) lds_dma16(d0_, lds + (wave + 4 * m) * 1024, voff[m]);
     }
     for (int u = 0; u < nmine; ++u) {
         int nn, noh, now;
@@ -611,7 +584,7 @@ __global__ __launch_bounds__(256, 2) void conv2d_s2rs_kernel(C2sArgs a) {
 #define C2S_DMA(K)                                                                                               \
     if ((K) < DPW) {                                                                                             \
         __builtin_amdgcn_sched_barrier(0);                                                                       \
-        if (more) c2s_dma_piece(dsc_n, lds + (IMG - img) + (wave + 4 * (K)) * 1024, voff[K]);                    \
+        if (more) lds_dma16(dsc_n, lds + (IMG - img) + (wave + 4 * (K)) * 1024, voff[K]);                        \
         __builtin_amdgcn_sched_barrier(0);                                                                       \
     }
         C2S_READ(0, 0)
@@ -630,10 +603,7 @@ __global__ __launch_bounds__(256, 2) void conv2d_s2rs_kernel(C2sArgs a) {
 #undef C2S_READ
 #undef C2S_DMA
         {
-            const long long off_ = (((long long)n_ * Hop + oh0 + rb::PAD) * Wop + ow0 + rb::PAD) * 64;
-            const long long left_ = ototal_bytes - off_;
-            const int rec_ = left_ > 0x7fffff00ll ? 0x7fffff00 : (int)left_;
-            const auto dsc_ = __builtin_amdgcn_make_buffer_rsrc(a.y + off_, 0, rec_, 0x00020000);
+            const auto dsc_ = window_desc(a.y, (((long long)n_ * Hop + oh0 + rb::PAD) * Wop + ow0 + rb::PAD) * 64, ototal_bytes);
             const bool okc = ow0 + col < a.Wo;
 #pragma unroll
             for (int i = 0; i < 2; ++i) {

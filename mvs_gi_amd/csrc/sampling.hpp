@@ -6,6 +6,8 @@
 // Include inside the translation unit's anonymous namespace, after common.hpp.
 #pragma once
 
+#include "device_prims.hpp"
+
 struct Bilin {
     int o00, o01, o10, o11;     // pixel offsets y*W+x, or -1 when the tap is outside
     float w00, w01, w10, w11;   // weights of (x0,y0), (x0,y1), (x1,y0), (x1,y1)
@@ -59,8 +61,6 @@ __device__ __forceinline__ float bilin_fetch_u8(const unsigned char* __restrict_
     const float i11 = t.o11 >= 0 ? lut[img[t.o11 * 3 + c]] : 0.0f;
     return ((i00 * t.w00 + i01 * t.w01) + i10 * t.w10) + i11 * t.w11;
 }
-
-typedef float f32x4_t __attribute__((ext_vector_type(4)));
 
 // RN(k / 255.0f), k = 0..255, evaluated by the host compiler (IEEE single division): a uint8 image is converted as the
 // facade does (api/inference_pytorch.py:58-59: .float() / 255.0)

@@ -20,6 +20,8 @@
 
 namespace {
 
+#include "device_prims.hpp"
+
 struct Axis2 {
     int i0, i1;
     float l0, l1;
@@ -151,13 +153,6 @@ __global__ __launch_bounds__(256) void softargmin_kernel(const float* __restrict
 // Logical unit order (b, k, x-tile) walks XCD-contiguously: the unit of row pair k + 1 finds row k + 1 in its XCD's L2.
 // DMAX = 16 | 32: the blended candidates of the four pixels live in registers; DMAX = 0: any D, three passes over LDS.
 // ---------------------------------------------------------------------------------------------
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ int sa_xcd_remap(int bid, int n) {
-    const int q = n >> 3, r = n & 7, x = bid & 7, i = bid >> 3;
-    return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + i;
-}
 
 template <int DMAX>
 __global__ __launch_bounds__(DMAX == 32 ? 512 : 640) void softargmin_rows_kernel(const float* __restrict__ costs, const float* __restrict__ inv_idx,
@@ -166,7 +161,7 @@ __global__ __launch_bounds__(DMAX == 32 ? 512 : 640) void softargmin_rows_kernel
                                                                float post_div, int contiguous) {
     extern __shared__ __attribute__((aligned(16))) float sa_lds[];
     const int tid = threadIdx.x, nthr = blockDim.x;
-    const int u = contiguous ? sa_xcd_remap((int)blockIdx.x, units) : (int)blockIdx.x;
+    const int u = contiguous ? xcd_remap((int)blockIdx.x, units) : (int)blockIdx.x;
     const int xtile = u % xtiles;
     int tq = u / xtiles;
     const int k = tq % (H + 1) - 1;
@@ -386,7 +381,7 @@ __global__ __launch_bounds__(256) void softargmin_band_kernel(const float* __res
                                                               float post_div) {
     extern __shared__ __attribute__((aligned(16))) float sa_lds[];
     const int tid = threadIdx.x, nthr = blockDim.x;
-    const int u = sa_xcd_remap((int)blockIdx.x, units);
+    const int u = xcd_remap((int)blockIdx.x, units);
     const int xtile = u % xtiles;
     const int tq = u / xtiles;
     const int k = tq % (H + 1) - 1;

@@ -9,33 +9,27 @@
 // Include inside the translation unit's anonymous namespace.
 #pragma once
 
-typedef float sf_f32x4 __attribute__((ext_vector_type(4)));
-typedef float sf_f32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned sf_u32x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 sf_bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 sf_bf16x2 __attribute__((ext_vector_type(2)));
-typedef _Float16 sf_f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 sf_f16x2 __attribute__((ext_vector_type(2)));
+#include "device_prims.hpp"     // the vector types
 
 constexpr float kF16Max = 65504.f;
 
 // the low / high 16-bit half of a packed dword as fp32: one VALU instruction each (shift | and; v_cvt_f32_f16 | its SDWA form)
 template <bool F16>
 __device__ __forceinline__ float sf_widen_lo(const unsigned u) {
-    if constexpr (F16) return (float)__builtin_bit_cast(sf_f16x2, u)[0];
+    if constexpr (F16) return (float)__builtin_bit_cast(f16x2, u)[0];
     else return __builtin_bit_cast(float, u << 16);
 }
 template <bool F16>
 __device__ __forceinline__ float sf_widen_hi(const unsigned u) {
-    if constexpr (F16) return (float)__builtin_bit_cast(sf_f16x2, u)[1];
+    if constexpr (F16) return (float)__builtin_bit_cast(f16x2, u)[1];
     else return __builtin_bit_cast(float, u & 0xffff0000u);
 }
 // two fp32 values -> one packed dword, round to nearest even (v_cvt_pk_bf16_f32 | v_cvt_pk_f16_f32); no range handling
 template <bool F16>
 __device__ __forceinline__ unsigned sf_cvt_pk(const float a, const float b) {
-    const sf_f32x2 v = {a, b};
-    if constexpr (F16) return __builtin_bit_cast(unsigned, __builtin_convertvector(v, sf_f16x2));
-    else return __builtin_bit_cast(unsigned, __builtin_convertvector(v, sf_bf16x2));
+    const f32x2 v = {a, b};
+    if constexpr (F16) return __builtin_bit_cast(unsigned, __builtin_convertvector(v, f16x2));
+    else return __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2));
 }
 // the range clamp of the fp16 split (identity for bf16): one v_med3_f32
 template <bool F16>
@@ -64,7 +58,7 @@ __device__ __forceinline__ void sf_sat_report(unsigned* __restrict__ words, cons
 
 // x = hi + lo for four fp32 values (clamped first in the fp16 split)
 template <bool F16>
-__device__ __forceinline__ void sf_split4(const sf_f32x4 x, sf_u32x2& hi, sf_u32x2& lo) {
+__device__ __forceinline__ void sf_split4(const f32x4 x, u32x2& hi, u32x2& lo) {
 #pragma unroll
     for (int p = 0; p < 2; ++p) {
         const float a = sf_clamp<F16>(x[2 * p]), b = sf_clamp<F16>(x[2 * p + 1]);
@@ -75,7 +69,7 @@ __device__ __forceinline__ void sf_split4(const sf_f32x4 x, sf_u32x2& hi, sf_u32
 }
 // the same, keeping the lane's running maximum |clamped value| for the range report (fp16 split only)
 template <bool F16>
-__device__ __forceinline__ void sf_split4(const sf_f32x4 x, sf_u32x2& hi, sf_u32x2& lo, float& sat) {
+__device__ __forceinline__ void sf_split4(const f32x4 x, u32x2& hi, u32x2& lo, float& sat) {
 #pragma unroll
     for (int p = 0; p < 2; ++p) {
         const float a = sf_clamp<F16>(x[2 * p]), b = sf_clamp<F16>(x[2 * p + 1]);
@@ -86,8 +80,8 @@ __device__ __forceinline__ void sf_split4(const sf_f32x4 x, sf_u32x2& hi, sf_u32
     }
 }
 template <bool F16>
-__device__ __forceinline__ sf_f32x4 sf_join4(const sf_u32x2 hi, const sf_u32x2 lo) {
-    sf_f32x4 r;
+__device__ __forceinline__ f32x4 sf_join4(const u32x2 hi, const u32x2 lo) {
+    f32x4 r;
 #pragma unroll
     for (int p = 0; p < 2; ++p) {
         r[2 * p] = sf_widen_lo<F16>(hi[p]) + sf_widen_lo<F16>(lo[p]);
@@ -97,8 +91,8 @@ __device__ __forceinline__ sf_f32x4 sf_join4(const sf_u32x2 hi, const sf_u32x2 l
 }
 // one matrix instruction of the split product; operands travel as 16-byte fragments whatever their element type
 template <bool F16>
-__device__ __forceinline__ sf_f32x4 sf_mfma16(const sf_bf16x8 a, const sf_bf16x8 b, const sf_f32x4 c) {
-    if constexpr (F16) return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(sf_f16x8, a), __builtin_bit_cast(sf_f16x8, b), c, 0, 0, 0);
+__device__ __forceinline__ f32x4 sf_mfma16(const bf16x8 a, const bf16x8 b, const f32x4 c) {
+    if constexpr (F16) return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
     else return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
 }
 // a weight -> (hi, lo) bit patterns of either split, on the device (pack kernels) and on the host (plan builders); no clamp: weights

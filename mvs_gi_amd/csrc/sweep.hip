@@ -57,8 +57,6 @@ __device__ __forceinline__ Bilin bilin_setup_bytes(float gx, float gy, int W, in
     return t;
 }
 
-typedef float f32x2_t __attribute__((ext_vector_type(2)));
-
 // Correctly rounded x / d for a small positive integer-valued d, given inv = RN(1 / d):
 // q = RN(x * inv); r = x - d*q (exact in an fma); q' = RN(q + r * inv)  (Markstein).  Identical to
 // IEEE division for normal-range results; the (never observed) tiny / huge / non-finite cases
@@ -193,15 +191,15 @@ __global__ __launch_bounds__(256) void sweep_cat_kernel(const float* __restrict_
 // sample, validity) is computed once -- lane q of a quad takes camera q -- and shared through
 // quad shuffles.  Arithmetic is unchanged (bit-identical output).
 // ------------------------------------------------------------------------------------------
-__device__ __forceinline__ f32x4_t ld4(const float* p) { return *reinterpret_cast<const f32x4_t*>(p); }
+__device__ __forceinline__ f32x4 ld4(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
 
-__device__ __forceinline__ f32x4_t bilin_fetch4(const float* __restrict__ img, int C, const Bilin& t) {
+__device__ __forceinline__ f32x4 bilin_fetch4(const float* __restrict__ img, int C, const Bilin& t) {
 #pragma clang fp contract(off)
-    const f32x4_t z = {0.f, 0.f, 0.f, 0.f};
-    const f32x4_t i00 = t.o00 >= 0 ? ld4(img + t.o00 * C) : z;      // o < Hi*Wi, o*C fits 32 bits (checked on host)
-    const f32x4_t i01 = t.o01 >= 0 ? ld4(img + t.o01 * C) : z;
-    const f32x4_t i10 = t.o10 >= 0 ? ld4(img + t.o10 * C) : z;
-    const f32x4_t i11 = t.o11 >= 0 ? ld4(img + t.o11 * C) : z;
+    const f32x4 z = {0.f, 0.f, 0.f, 0.f};
+    const f32x4 i00 = t.o00 >= 0 ? ld4(img + t.o00 * C) : z;      // o < Hi*Wi, o*C fits 32 bits (checked on host)
+    const f32x4 i01 = t.o01 >= 0 ? ld4(img + t.o01 * C) : z;
+    const f32x4 i10 = t.o10 >= 0 ? ld4(img + t.o10 * C) : z;
+    const f32x4 i11 = t.o11 >= 0 ? ld4(img + t.o11 * C) : z;
     return ((i00 * t.w00 + i01 * t.w01) + i10 * t.w10) + i11 * t.w11;
 }
 
@@ -209,12 +207,12 @@ __device__ __forceinline__ f32x4_t bilin_fetch4(const float* __restrict__ img, i
 // per-image descriptor and an out-of-image tap (offset -1 -> huge unsigned) is answered with
 // zeros by the hardware range check, which IS the reference's zero padding: no 64-bit address
 // arithmetic and no selects per tap.
-__device__ __forceinline__ f32x4_t bilin_fetch4_buf(__amdgpu_buffer_rsrc_t img, int c, int C, const Bilin& t) {
+__device__ __forceinline__ f32x4 bilin_fetch4_buf(__amdgpu_buffer_rsrc_t img, int c, int C, const Bilin& t) {
 #pragma clang fp contract(off)
-    const f32x4_t i00 = __builtin_bit_cast(f32x4_t, __builtin_amdgcn_raw_buffer_load_b128(img, (t.o00 * C + c) * 4, 0, 0));
-    const f32x4_t i01 = __builtin_bit_cast(f32x4_t, __builtin_amdgcn_raw_buffer_load_b128(img, (t.o01 * C + c) * 4, 0, 0));
-    const f32x4_t i10 = __builtin_bit_cast(f32x4_t, __builtin_amdgcn_raw_buffer_load_b128(img, (t.o10 * C + c) * 4, 0, 0));
-    const f32x4_t i11 = __builtin_bit_cast(f32x4_t, __builtin_amdgcn_raw_buffer_load_b128(img, (t.o11 * C + c) * 4, 0, 0));
+    const f32x4 i00 = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(img, (t.o00 * C + c) * 4, 0, 0));
+    const f32x4 i01 = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(img, (t.o01 * C + c) * 4, 0, 0));
+    const f32x4 i10 = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(img, (t.o10 * C + c) * 4, 0, 0));
+    const f32x4 i11 = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(img, (t.o11 * C + c) * 4, 0, 0));
     return ((i00 * t.w00 + i01 * t.w01) + i10 * t.w10) + i11 * t.w11;
 }
 
@@ -233,11 +231,6 @@ __device__ __forceinline__ float bilin_fetch_buf(__amdgpu_buffer_rsrc_t plane, c
 // the blocks resident on an XCD at any time share a few feature-map rows of one frame in its L2.
 // With the plain (x, y, z) order every XCD walked every frame's whole feature map (8x the fabric
 // reads; measured FETCH_SIZE, profiles/).
-__device__ __forceinline__ int sweep_xcd_remap(int bid, int n) {
-    const int q = n >> 3, r = n & 7, x = bid & 7, i = bid >> 3;
-    return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + i;
-}
-
 // grid = ceil(Wo / 64) * D * Ho * B blocks (flat); block = 64 voxels x 4 lanes.  No per-lane integer
 // division: (b, ho, d, w-tile) come from the (scalar) block index, wo from the thread index.
 template <int NCAM>
@@ -251,7 +244,7 @@ __global__ __launch_bounds__(256) void sweep_std_nhwc_kernel(const float* __rest
     static_assert(NCAM <= 4, "one camera per lane of a quad");
     const int q = threadIdx.x & 3;
     const int WT = (s.Wo + 63) >> 6;
-    int L = sweep_xcd_remap((int)blockIdx.x, (int)gridDim.x);
+    int L = xcd_remap((int)blockIdx.x, (int)gridDim.x);
     const int wt = L % WT;
     L /= WT;
     const int d = L % s.D;
@@ -280,7 +273,7 @@ __global__ __launch_bounds__(256) void sweep_std_nhwc_kernel(const float* __rest
 #pragma unroll
     for (int cam = 0; cam < NCAM; ++cam)
         img[cam] = __builtin_amdgcn_make_buffer_rsrc(
-            const_cast<float*>(feats + (long long)(b * NCAM + cam) * HWi * s.C), 0, HWi * s.C * 4, 0x00020000);
+            const_cast<float*>(feats + (long long)(b * NCAM + cam) * HWi * s.C), 0, HWi * s.C * 4, kRawBufferFlags);
     Bilin ft[NCAM];
     float vf[NCAM];
     float n = 0.0f;
@@ -303,10 +296,10 @@ __global__ __launch_bounds__(256) void sweep_std_nhwc_kernel(const float* __rest
     const float inv = 1.0f / cnt;
     float* out = vol + ((((long long)b * s.D + d) * s.Ho + ho) * s.Wo + wo) * s.C;
     for (int c = q * 4; c < s.C; c += 16) {
-        f32x4_t sv[NCAM];
+        f32x4 sv[NCAM];
 #pragma unroll
         for (int cam = 0; cam < NCAM; ++cam) sv[cam] = bilin_fetch4_buf(img[cam], c, s.C, ft[cam]);
-        f32x4_t r;
+        f32x4 r;
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
             float sum = 0.0f;
@@ -323,7 +316,7 @@ __global__ __launch_bounds__(256) void sweep_std_nhwc_kernel(const float* __rest
             var = div_small(var, cnt, inv);
             r[k] = ok ? var : 0.0f;
         }
-        if (live) *reinterpret_cast<f32x4_t*>(out + c) = r;
+        if (live) *reinterpret_cast<f32x4*>(out + c) = r;
     }
 }
 
@@ -392,24 +385,24 @@ __device__ __forceinline__ void quad_bcast_group(Bilin (&ft)[NG], const Bilin& m
 
 // The four texels of one camera's taps t at channel byte cb (far: 0, or the sign bit, which sends the requests out of the
 // descriptor's range), and their blend on channel pairs (backports.py:86, left to right)
-__device__ __forceinline__ void gather4(f32x4_t (&tx)[4], __amdgpu_buffer_rsrc_t img, const Bilin t, int cb, int far) {
-    tx[0] = __builtin_bit_cast(f32x4_t, __builtin_amdgcn_raw_buffer_load_b128(img, (t.o00 + cb) | far, 0, 0));
-    tx[1] = __builtin_bit_cast(f32x4_t, __builtin_amdgcn_raw_buffer_load_b128(img, (t.o01 + cb) | far, 0, 0));
-    tx[2] = __builtin_bit_cast(f32x4_t, __builtin_amdgcn_raw_buffer_load_b128(img, (t.o10 + cb) | far, 0, 0));
-    tx[3] = __builtin_bit_cast(f32x4_t, __builtin_amdgcn_raw_buffer_load_b128(img, (t.o11 + cb) | far, 0, 0));
+__device__ __forceinline__ void gather4(f32x4 (&tx)[4], __amdgpu_buffer_rsrc_t img, const Bilin t, int cb, int far) {
+    tx[0] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(img, (t.o00 + cb) | far, 0, 0));
+    tx[1] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(img, (t.o01 + cb) | far, 0, 0));
+    tx[2] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(img, (t.o10 + cb) | far, 0, 0));
+    tx[3] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(img, (t.o11 + cb) | far, 0, 0));
 }
-__device__ __forceinline__ f32x2_t blend4(const f32x4_t (&tx)[4], const Bilin t, int p) {
+__device__ __forceinline__ f32x2 blend4(const f32x4 (&tx)[4], const Bilin t, int p) {
 #pragma clang fp contract(off)
-    const f32x2_t W00 = {t.w00, t.w00}, W01 = {t.w01, t.w01}, W10 = {t.w10, t.w10}, W11 = {t.w11, t.w11};
-    const f32x2_t i00 = {tx[0][2 * p], tx[0][2 * p + 1]}, i01 = {tx[1][2 * p], tx[1][2 * p + 1]};
-    const f32x2_t i10 = {tx[2][2 * p], tx[2][2 * p + 1]}, i11 = {tx[3][2 * p], tx[3][2 * p + 1]};
+    const f32x2 W00 = {t.w00, t.w00}, W01 = {t.w01, t.w01}, W10 = {t.w10, t.w10}, W11 = {t.w11, t.w11};
+    const f32x2 i00 = {tx[0][2 * p], tx[0][2 * p + 1]}, i01 = {tx[1][2 * p], tx[1][2 * p + 1]};
+    const f32x2 i10 = {tx[2][2 * p], tx[2][2 * p + 1]}, i11 = {tx[3][2 * p], tx[3][2 * p + 1]};
     return ((i00 * W00 + i01 * W01) + i10 * W10) + i11 * W11;
 }
 
 // Per-frame kernel with the validity byte, for rigs of 1 to 8 cameras.  A block owns 64 consecutive wo of one (b, ho) row and
 // walks `dchunk` candidates, fetching the NEXT candidate's grid point(s) and validity byte before the texel gathers of the
 // current one, so a voxel costs one exposed memory round trip instead of three.  Logical block order (b, ho, d-chunk, w-tile),
-// XCD-contiguous (see sweep_xcd_remap).
+// XCD-contiguous (see xcd_remap).
 //
 // Lane q of a quad walks the grid of camera q and, for rigs of 5 to 8 cameras, of camera q + 4 as well (two grid points per
 // candidate), works out their taps as BYTE offsets and broadcasts them through the quad.  What depends on the rig's size:
@@ -441,7 +434,7 @@ __global__ __launch_bounds__(256, NCAM <= 4 ? MVSGI_SWEEP_WAVES : MVSGI_SWEEP_WI
     float satm = 0.f;          // fp16 split output: running maximum |value written| (range report, csrc/split_fmt.hpp)
     const int q = threadIdx.x & 3;
     const int WT = (s.Wo + 63) >> 6;
-    int L = sweep_xcd_remap((int)blockIdx.x, (int)gridDim.x);
+    int L = xcd_remap((int)blockIdx.x, (int)gridDim.x);
     const int wt = L % WT;
     L /= WT;
     const int dc = L % nd;
@@ -460,7 +453,7 @@ __global__ __launch_bounds__(256, NCAM <= 4 ? MVSGI_SWEEP_WAVES : MVSGI_SWEEP_WI
 #pragma unroll
     for (int cam = 0; cam < NCAM; ++cam)
         img[cam] = __builtin_amdgcn_make_buffer_rsrc(
-            const_cast<float*>(feats + (long long)(b * NCAM + cam) * HWi * s.C), 0, HWi * s.C * 4, 0x00020000);
+            const_cast<float*>(feats + (long long)(b * NCAM + cam) * HWi * s.C), 0, HWi * s.C * 4, kRawBufferFlags);
     // lane q walks the grids of cameras q and q + 4 (lanes beyond the rig re-read the last camera; unused).
     // rig_shared: one grid / validity set for the whole batch (the rig constants of api/inference_class.py:40-45 are the
     // same for every frame): all frames read frame 0's, which then stay in L2 instead of streaming B copies from HBM
@@ -499,13 +492,13 @@ __global__ __launch_bounds__(256, NCAM <= 4 ? MVSGI_SWEEP_WAVES : MVSGI_SWEEP_WI
         if constexpr (WIDE) mine1 = bilin_setup_bytes(gxy1.x, gxy1.y, s.Wi, s.Hi, C4, rowB);
         else quad_bcast_group(ft, mine);
         bool val[NCAM];
-        f32x2_t VF[NCAM];
+        f32x2 VF[NCAM];
         float n = 0.0f;
 #pragma unroll
         for (int cam = 0; cam < NCAM; ++cam) {
             val[cam] = ((vm >> cam) & 1u) != 0;
             const float vf = val[cam] ? 1.0f : 0.0f;
-            VF[cam] = f32x2_t{vf, vf};
+            VF[cam] = f32x2{vf, vf};
             n = n + vf;
         }
         const bool ok = n > 1.0f;
@@ -528,7 +521,7 @@ __global__ __launch_bounds__(256, NCAM <= 4 ? MVSGI_SWEEP_WAVES : MVSGI_SWEEP_WI
         // RN(1 / cnt) for the camera counts there are: exactly what the division 1.0f / cnt returns
         const float inv = cnt == 2.0f ? 0.5f : cnt == 3.0f ? 0x1.555556p-2f : cnt == 4.0f ? 0.25f : !WIDE ? 1.0f : cnt == 5.0f ? 0x1.99999ap-3f :
                           cnt == 6.0f ? 0x1.555556p-3f : cnt == 7.0f ? 0x1.24924ap-3f : cnt == 8.0f ? 0.125f : 1.0f;
-        const f32x2_t INV = {inv, inv}, NCNT = {-cnt, -cnt};
+        const f32x2 INV = {inv, inv}, NCNT = {-cnt, -cnt};
 #pragma unroll 1
         // C16: one trip, the tap offsets die with the loads.  WIDE: every lane of a quad makes every trip -- the taps travel by DPP
         // INSIDE the loop, and a lane that had left it would broadcast nothing: with C = 8 lanes 2 and 3 have no channels, yet
@@ -536,7 +529,7 @@ __global__ __launch_bounds__(256, NCAM <= 4 ? MVSGI_SWEEP_WAVES : MVSGI_SWEEP_WI
         for (int cb0 = WIDE ? 0 : q * 16; cb0 < (C16 ? 64 : C4); cb0 += 64) {
             const int cb = WIDE ? cb0 + q * 16 : cb0;
             const bool mych = !WIDE || C16 || cb < C4;
-            f32x4_t tx[WIDE ? 1 : NCAM][4];              // !WIDE: the texels of all cameras
+            f32x4 tx[WIDE ? 1 : NCAM][4];              // !WIDE: the texels of all cameras
             if constexpr (!WIDE) {
 #pragma unroll
                 for (int cam = 0; cam < NCAM; ++cam) {
@@ -545,14 +538,14 @@ __global__ __launch_bounds__(256, NCAM <= 4 ? MVSGI_SWEEP_WAVES : MVSGI_SWEEP_WI
                     // or mask) is not gathered at all: the kernel is bound by the texture addresser's instruction rate
                     // (profiles/r04_sweep_texture_path_counters.txt), and a range-checked-away gather still costs its instruction
                     if (__builtin_amdgcn_ballot_w64(val[cam] & ok) == 0) {
-                        tx[cam][0] = tx[cam][1] = tx[cam][2] = tx[cam][3] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+                        tx[cam][0] = tx[cam][1] = tx[cam][2] = tx[cam][3] = f32x4{0.f, 0.f, 0.f, 0.f};
                         continue;
                     }
 #endif
                     gather4(tx[cam], img[cam], ft[cam], cb, 0);
                 }
             }
-            f32x2_t sv[NCAM][2];
+            f32x2 sv[NCAM][2];
             if constexpr (!WIDE) {
 #pragma unroll
                 for (int cam = 0; cam < NCAM; ++cam) {
@@ -565,7 +558,7 @@ __global__ __launch_bounds__(256, NCAM <= 4 ? MVSGI_SWEEP_WAVES : MVSGI_SWEEP_WI
                     constexpr int G = decltype(G_)::value, base = 4 * G, NGC = NCAM - base < 4 ? NCAM - base : 4;
                     Bilin ft[NGC];
                     quad_bcast_group(ft, G ? mine1 : mine);
-                    f32x4_t tx[NGC][4];
+                    f32x4 tx[NGC][4];
 #pragma unroll
                     for (int c = 0; c < NGC; ++c) {
                         const bool need = val[base + c] & ok;
@@ -574,7 +567,7 @@ __global__ __launch_bounds__(256, NCAM <= 4 ? MVSGI_SWEEP_WAVES : MVSGI_SWEEP_WI
                         // or mask) is not gathered at all: the kernel is bound by the texture addresser's instruction rate
                         // (profiles/r04_sweep_texture_path_counters.txt), and a range-checked-away gather still costs its instruction
                         if (__builtin_amdgcn_ballot_w64(need) == 0) {
-                            tx[c][0] = tx[c][1] = tx[c][2] = tx[c][3] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+                            tx[c][0] = tx[c][1] = tx[c][2] = tx[c][3] = f32x4{0.f, 0.f, 0.f, 0.f};
                             continue;
                         }
 #endif
@@ -603,8 +596,8 @@ __global__ __launch_bounds__(256, NCAM <= 4 ? MVSGI_SWEEP_WAVES : MVSGI_SWEEP_WI
             // cnt = 3: r / 3 is a multiple of ulp / 3, never near a rounding boundary, down to the subnormals).  Sums beyond 1e30 (and
             // infinities) take the hardware division; from 5 cameras on so do tiny non-zero operands: a quotient x / 6 below 1e-30
             // can be an exact tie between two subnormals, which the sequence rounds the wrong way.
-            f32x2_t sum[2], var[2];
-            f32x4_t r;
+            f32x2 sum[2], var[2];
+            f32x4 r;
             float big = 0.0f;
             bool rare = false;
 #pragma unroll
@@ -612,16 +605,16 @@ __global__ __launch_bounds__(256, NCAM <= 4 ? MVSGI_SWEEP_WAVES : MVSGI_SWEEP_WI
                 sum[p] = sv[0][p] * VF[0];
 #pragma unroll
                 for (int cam = 1; cam < NCAM; ++cam) sum[p] = sum[p] + sv[cam][p] * VF[cam];
-                const f32x2_t qa = sum[p] * INV;
-                const f32x2_t avg = __builtin_elementwise_fma(__builtin_elementwise_fma(NCNT, qa, sum[p]), INV, qa);
+                const f32x2 qa = sum[p] * INV;
+                const f32x2 avg = __builtin_elementwise_fma(__builtin_elementwise_fma(NCNT, qa, sum[p]), INV, qa);
 #pragma unroll
                 for (int cam = 0; cam < NCAM; ++cam) {
-                    const f32x2_t t = {val[cam] ? sv[cam][p].x : avg.x, val[cam] ? sv[cam][p].y : avg.y};   // :119
-                    const f32x2_t df = t - avg;
+                    const f32x2 t = {val[cam] ? sv[cam][p].x : avg.x, val[cam] ? sv[cam][p].y : avg.y};   // :119
+                    const f32x2 df = t - avg;
                     var[p] = cam == 0 ? df * df : var[p] + df * df;                                           // :122
                 }
-                const f32x2_t qv = var[p] * INV;
-                const f32x2_t v = __builtin_elementwise_fma(__builtin_elementwise_fma(NCNT, qv, var[p]), INV, qv);
+                const f32x2 qv = var[p] * INV;
+                const f32x2 v = __builtin_elementwise_fma(__builtin_elementwise_fma(NCNT, qv, var[p]), INV, qv);
                 r[2 * p] = ok ? v.x : 0.0f;                                                                   // :125
                 r[2 * p + 1] = ok ? v.y : 0.0f;
                 if constexpr (!WIDE) {
@@ -665,12 +658,11 @@ __global__ __launch_bounds__(256, NCAM <= 4 ? MVSGI_SWEEP_WAVES : MVSGI_SWEEP_WI
                         hi[p] = hb;
                         lo[p] = sf_cvt_pk<true>(a_ - sf_widen_lo<true>(hb), b_ - sf_widen_hi<true>(hb));
                     } else {
-                        typedef __bf16 b2_t __attribute__((ext_vector_type(2)));
-                        const f32x2_t v = {r[2 * p], r[2 * p + 1]};
-                        const unsigned hb = __builtin_bit_cast(unsigned, __builtin_convertvector(v, b2_t));
-                        const f32x2_t hf = {__builtin_bit_cast(float, hb << 16), __builtin_bit_cast(float, hb & 0xffff0000u)};
+                        const f32x2 v = {r[2 * p], r[2 * p + 1]};
+                        const unsigned hb = __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2));
+                        const f32x2 hf = {__builtin_bit_cast(float, hb << 16), __builtin_bit_cast(float, hb & 0xffff0000u)};
                         hi[p] = hb;
-                        lo[p] = __builtin_bit_cast(unsigned, __builtin_convertvector(v - hf, b2_t));
+                        lo[p] = __builtin_bit_cast(unsigned, __builtin_convertvector(v - hf, bf16x2));
                     }
                 }
                 // even lanes keep their hi and take the odd neighbour's hi; odd lanes take the even neighbour's lo
@@ -679,7 +671,7 @@ __global__ __launch_bounds__(256, NCAM <= 4 ? MVSGI_SWEEP_WAVES : MVSGI_SWEEP_WI
                 const unsigned r1 = (unsigned)__builtin_amdgcn_mov_dpp((int)(odd ? hi[1] : lo[1]), 0xB1, 0xf, 0xf, true);
                 const uint4 piece = odd ? make_uint4(r0, r1, lo[0], lo[1]) : make_uint4(hi[0], hi[1], r0, r1);
                 if (live) *reinterpret_cast<uint4*>(os) = piece;
-            } else if (live & mych) *reinterpret_cast<f32x4_t*>(reinterpret_cast<char*>(o) + cb) = r;
+            } else if (live & mych) *reinterpret_cast<f32x4*>(reinterpret_cast<char*>(o) + cb) = r;
         }
     };
     // two candidates per trip with ping-pong registers (A, B): the loads of the next candidate are
@@ -713,7 +705,7 @@ __global__ __launch_bounds__(256) void sweep_cat_nhwc_kernel(const float* __rest
 #pragma clang fp contract(off)
     const int q = threadIdx.x & 3;
     const int WT = (s.Wo + 63) >> 6;
-    int L = sweep_xcd_remap((int)blockIdx.x, (int)gridDim.x);
+    int L = xcd_remap((int)blockIdx.x, (int)gridDim.x);
     const int wt = L % WT;
     L /= WT;
     const int cam = L % s.N;
@@ -731,7 +723,7 @@ __global__ __launch_bounds__(256) void sweep_cat_nhwc_kernel(const float* __rest
     const long long vox = (((long long)b * s.D + d) * s.Ho + ho) * s.Wo + wo;
     float* out = vol + vox * ((long long)s.N * s.C) + (long long)cam * s.C;
     const __amdgpu_buffer_rsrc_t img = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<float*>(feats + (long long)(b * s.N + cam) * HWi * s.C), 0, HWi * s.C * 4, 0x00020000);
+        const_cast<float*>(feats + (long long)(b * s.N + cam) * HWi * s.C), 0, HWi * s.C * 4, kRawBufferFlags);
     // (skipping the taps that lie outside the image for a whole wave, as the masked-variance kernel skips cameras, measured 2-4 %
     // SLOWER here: 1628 vs 1590 us per 16 4cam-32 frames, 1358 vs 1303 us per 64 E8 frames -- few waves of these rigs are
     // entirely outside a camera and the four wave-uniform branches cost more than they save.  Round 5: chunks of 2 / 3 / 4 consecutive
@@ -740,7 +732,7 @@ __global__ __launch_bounds__(256) void sweep_cat_nhwc_kernel(const float* __rest
     // 4cam-32 frames, 1301 / 1487 / 1514 against 1201 per 64 E8 frames (profiles/r05_sweep_cat_variants.txt): a request that moves no
     // data still costs its instruction, and the instruction count is what bounds the texture path)
     for (int c = q * 4; c < s.C; c += 16)
-        *reinterpret_cast<f32x4_t*>(out + c) = bilin_fetch4_buf(img, c, s.C, ft);
+        *reinterpret_cast<f32x4*>(out + c) = bilin_fetch4_buf(img, c, s.C, ft);
 }
 
 int check_dims(const SweepDims& s, const char* who) {

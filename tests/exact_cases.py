@@ -228,8 +228,47 @@ def _exactly_one_lo(a, b, fmt):
     return ahi.double(), alo.double(), bhi.double(), blo.double()
 
 
+def frame_index(B: int, F: int, seed: int) -> np.ndarray:
+    """A length-B sequence over range(F), drawn from the seed (redrawn until the conditions hold; asserted):
+      - idx[b] != idx[b - 1] for every b: neighbouring frames always differ, so a read across a frame boundary, or a shift by ANY
+        fixed number of frames, cannot land on an identical frame everywhere (the sequence is not periodic);
+      - every frame occurs;
+      - for B >= 32 (and F <= 4: 12 ordered pairs at most), every ordered pair of distinct frames occurs as neighbours."""
+    assert 1 <= F <= B
+    if F == 1:
+        assert B == 1, "a sequence over one frame repeats it"
+        return np.zeros(1, dtype=np.int64)
+    rng = np.random.default_rng([seed, B, F])
+    want_pairs = B >= 32 and F <= 4
+    for _ in range(10000):
+        idx = np.empty(B, dtype=np.int64)
+        idx[:F] = rng.permutation(F)
+        for b in range(F, B):
+            idx[b] = (idx[b - 1] + 1 + rng.integers(0, F - 1)) % F
+        pairs = set(zip(idx[:-1].tolist(), idx[1:].tolist()))
+        periodic = any(np.array_equal(idx[p:], idx[:-p]) for p in range(1, B // 2 + 1)) if B > F >= 3 else False
+        if (not want_pairs or len(pairs) == F * (F - 1)) and not periodic:
+            break
+    else:
+        raise AssertionError(f"no frame sequence for B = {B}, F = {F}")
+    check_frame_index(idx, B, F)
+    return idx
+
+
+def check_frame_index(idx, B: int, F: int) -> None:
+    idx = np.asarray(idx)
+    assert idx.shape == (B,) and idx.min() >= 0 and idx.max() < F
+    assert bool((idx[1:] != idx[:-1]).all()), "two neighbouring frames are the same frame"
+    assert set(idx.tolist()) == set(range(F)), "a frame does not occur"
+    if B >= 32 and F <= 4:
+        pairs = set(zip(idx[:-1].tolist(), idx[1:].tolist()))
+        assert len(pairs) == F * (F - 1), "an ordered pair of distinct frames never occurs as neighbours"
+    for p in range(1, B // 2 + 1) if B > F >= 3 else ():      # (two frames can only alternate)
+        assert not np.array_equal(idx[p:], idx[:-p]), f"the sequence repeats with period {p}"
+
+
 def make_case(fmt, regime, B, Cin, Cout, dims, stride=1, res=False, slope=0.25, up2=False, wino=False, poly=False, polywino=False,
-              bound=None, k=3, shift=True, fold_scale=False, seed=0):
+              bound=None, k=3, shift=True, fold_scale=False, seed=0, frames=None):
     """Operands, float64 reference and conditions (a)-(c) of act(conv(x [, upsampled x2]) * scale + shift (+ res)).
 
     fmt: 'bf16' | 'f16' (the split the kernel multiplies in) | 'f32' (an fp32 kernel: no split, no regimes needed but both run).
@@ -238,9 +277,20 @@ def make_case(fmt, regime, B, Cin, Cout, dims, stride=1, res=False, slope=0.25, 
     break the split's conditions are drawn again (a few in a million folded weights need 9 bits).  polywino: the Winograd form of
     the polyphase layer multiplies the case: wide operands of 8 bits, and (a) and the split are ALSO met in its own domain
     (polywino_operands).  Returns a namespace of float32 tensors in NC(D)HW order (x, w, scale, shift,
-    r) plus `acc` and `ref` (float64) and the figures of the conditions."""
+    r) plus `acc` and `ref` (float64) and the figures of the conditions.
+
+    frames=F: a launch-size case.  Operands, the convolution and every condition above are built and asserted for min(F, B) DISTINCT
+    frames; the kernel sees them B times in the irregular order `idx` (frame_index), x = x_F[idx], and the reference is expanded by
+    the same index.  Frames of a batch are independent and (a)-(c), the split identities and "ATen fp32 == float64" are per-frame
+    properties: they hold for the batch when they hold for the F frames.  The residual is NOT periodic: it is drawn for all B
+    frames and added to the expanded accumulator (a frame mix-up in the residual's addressing shows); (b) and (c) are asserted on
+    the expanded stages.  The case also carries idx, n_frames and the F-frame operands x_frames."""
     assert regime in REGIMES and slope in SLOPES
     nd = len(dims)
+    idx = None
+    if frames is not None:
+        idx = frame_index(B, min(frames, B), seed)
+        B_all, B = B, min(frames, B)
     xshape, wshape = (B, Cin, *dims), (Cout, Cin) + (k,) * nd
     w_unit = 4 if wino else 1
     wmax = POLYWINO_WIDE_MAX[regime] if polywino else None
@@ -322,6 +372,12 @@ def make_case(fmt, regime, B, Cin, Cout, dims, stride=1, res=False, slope=0.25, 
     # ---- ATen in fp32 (another summation order) returns the float64 bits
     aten = _conv(_up2(x.float()) if up2 else x.float(), w.float(), stride)
     assert torch.equal(aten.double(), acc), "ATen fp32 != float64"
+    if idx is not None:      # the batch the kernel sees: the F frames in the order idx (the residual below is drawn for all B frames)
+        c.idx, c.n_frames, c.x_frames = idx, B, c.x
+        sel = torch.from_numpy(idx)
+        c.x, c.acc = c.x[sel], acc[sel]
+        c.xin = None                     # (per-frame intermediates are not expanded)
+        acc, B = c.acc, B_all
     # ---- epilogue: power-of-two scale per channel, integer shift / residual; (b) at every stage, (c) on the result
     amax = float(acc.abs().max())
     k2 = 0
@@ -498,7 +554,7 @@ def ids(family: str):
 RESBLOCK_REGIMES = REGIMES + ("w2_wide",)
 
 
-def make_resblock_case(B, H, W, regime, seed, slope=0.25):
+def make_resblock_case(B, H, W, regime, seed, slope=0.25, frames=None):
     """ResConvBlk2d on 16 channels in the bf16 split: y = act(conv2(m) * s2 + b2 + x), m = act(conv1(x) * s1 + b1).  The kernels
     hold m in 16-bit pieces, so m must be a bf16 hi + lo pair itself (asserted: split_join(m) == m).  Three regimes:
       x_wide, w_wide   conv1's wide operand; m comes out wide (a lo part), so w2 is narrow: the cross terms lo(x) hi(w1), hi(x) lo(w1)
@@ -507,6 +563,10 @@ def make_resblock_case(B, H, W, regime, seed, slope=0.25):
                        lo part, and w2 is wide: the cross term hi(m) lo(w2), the lo stream of conv2's weights."""
     assert regime in RESBLOCK_REGIMES and (regime != "w2_wide" or slope in (0.0, 1.0))
     bc = (1, -1, 1, 1)
+    idx = None
+    if frames is not None:      # a launch-size case (make_case): built and asserted on F frames, presented B times in the order idx
+        idx = torch.from_numpy(frame_index(B, min(frames, B), seed))
+        B = min(frames, B)
     for halvings in range(9):
         density = 0.5 ** halvings
         rng = np.random.default_rng(seed)
@@ -546,9 +606,12 @@ def make_resblock_case(B, H, W, regime, seed, slope=0.25):
     y = torch.where(stages[-1] > 0, stages[-1], stages[-1] * slope)
     for i, v in enumerate(stages + [y]):
         assert representable(v), f"condition (b): resblock stage {i}"
-    return types.SimpleNamespace(regime=regime, density=density, x=x.float(), w1=w1.float(), w2=w2.float(), s1=s1.float(), s2=s2.float(),
-                                 b1=b1.float(), b2=b2.float(), ref=y, slope=slope, abs_sum_frac=max(sums) / TWO24,
-                                 m_has_lo=bool(ml.any()), w2_has_lo=bool(w2l.any()))
+    c = types.SimpleNamespace(regime=regime, density=density, x=x.float(), w1=w1.float(), w2=w2.float(), s1=s1.float(), s2=s2.float(),
+                              b1=b1.float(), b2=b2.float(), ref=y, slope=slope, abs_sum_frac=max(sums) / TWO24,
+                              m_has_lo=bool(ml.any()), w2_has_lo=bool(w2l.any()))
+    if idx is not None:         # (the block's residual is its own input: it follows the frame)
+        c.idx, c.n_frames, c.x_frames, c.x, c.ref = idx.numpy(), B, c.x, c.x[idx], y[idx]
+    return c
 
 
 RESBLOCK_IDS = [f"{s}-{rg}" for s in RESBLOCK2D_SHAPES for rg in RESBLOCK_REGIMES]
@@ -624,3 +687,265 @@ def resize_case(i: int):
     ref = F.interpolate(x, size=size, mode="trilinear", align_corners=False)
     assert representable(ref) and torch.equal(F.interpolate(x.float(), size=size, mode="trilinear", align_corners=False).double(), ref)
     return types.SimpleNamespace(x=x.float(), size=size, ref=ref, lsb=1.0 / (2 * f) ** 3)
+
+
+# ================================================================================================ launch-size cases
+# tests/test_gpu_exact_launches.py: the same operands and conditions at the sizes where the dispatcher takes its many-frame
+# variants, where the launcher skips border planes and where a persistent workgroup walks a second and later unit.  Every case is
+# built on FRAMES distinct frames presented B times (make_case(frames=...), frame_index).  Recorded for 256 CUs, like
+# tests/golden/conv3d_dispatch_pin.json.
+FRAMES = 4
+LAUNCH_CUS = 256
+
+
+def cdiv(a: int, b: int) -> int:
+    return -(-a // b)
+
+
+# ---- the streaming kernel and the exact-fp32 MFMA kernel: one shape per row of csrc/conv3d_variants.inc at which
+# H.conv3d_variant / H.conv3d_up2_variant names the row (the cheapest of a search over frames of H in {6, 8, 10, 12, 15}, W in
+# {24, 40} -- ragged against the 16-wide bricks, 8 mod 16 for the 10 x 8 ones -- three or five planes deep unless the row is a one-
+# or two-plane form; up2: the low-resolution size).
+# (row, entry point, B, Cin, Cout, D, H, W, stride, layout)
+VARIANT_ROWS = [
+    ("V_S1_N16_B256", "conv", 1, 16, 16, 3, 6, 24, 1, "mfma"),
+    ("V_S1_N32_B256", "conv", 320, 16, 32, 3, 6, 24, 1, "mfma"),
+    ("V_S1_N32_B64", "conv", 1, 16, 32, 3, 6, 24, 1, "mfma"),
+    ("V_S1_N64_B128", "conv", 160, 16, 128, 3, 6, 24, 1, "mfma"),
+    ("V_S1_N64_B64", "conv", 1, 16, 64, 3, 6, 24, 1, "mfma"),
+    ("V_S2_N32_B64", "conv", 1, 16, 16, 3, 6, 24, 2, "mfma"),
+    ("V_S2_N64_B64", "conv", 1, 16, 64, 3, 6, 24, 2, "mfma"),
+    ("B3_N16", "conv", 1, 16, 16, 3, 6, 24, 1, "generic"),
+    ("B3_N32", "conv", 48, 16, 32, 5, 6, 24, 1, "generic"),
+    ("B3_N48", "conv", 1, 16, 48, 3, 6, 24, 1, "generic"),
+    ("B3_N64", "conv", 24, 16, 64, 3, 6, 24, 1, "generic"),
+    ("B3_N64_H5", "conv", 20, 16, 64, 3, 15, 24, 1, "generic"),
+    ("B3_N96", "conv", 48, 16, 96, 3, 6, 24, 1, "generic"),
+    ("B3_N96_H5", "conv", 32, 16, 96, 3, 15, 24, 1, "generic"),
+    ("B3_N128_P", "conv", 96, 16, 128, 1, 6, 24, 1, "generic"),
+    ("B3_N128_PH5", "conv", 24, 16, 128, 1, 15, 24, 1, "generic"),
+    ("B3_N192_PH5", "conv", 64, 16, 192, 1, 15, 24, 1, "generic"),
+    ("B3_N64_S", "conv", 12, 16, 64, 3, 6, 24, 1, "generic"),
+    ("B3_N16_TW", "conv", 1, 16, 64, 3, 6, 24, 1, "generic"),
+    ("B3_N32_TB", "conv", 1, 16, 32, 3, 6, 24, 1, "generic"),
+    ("B3_S2_N32B", "conv", 1, 16, 16, 3, 6, 24, 2, "generic"),
+    ("B3_S2_N64", "conv", 48, 16, 96, 3, 6, 24, 2, "generic"),
+    ("B3_S2_N96", "conv", 64, 16, 192, 3, 10, 24, 2, "generic"),
+    ("B3_S2_N128", "conv", 64, 16, 128, 5, 10, 24, 2, "generic"),
+    ("B3_S2_N192", "conv", 64, 16, 192, 5, 10, 24, 2, "generic"),
+    ("B3_N64_W8", "conv", 24, 16, 64, 3, 10, 24, 1, "generic"),
+    ("B3_N96_W8", "conv", 48, 16, 96, 3, 10, 24, 1, "generic"),
+    ("B3_N128_PW8", "conv", 32, 16, 128, 1, 10, 24, 1, "generic"),
+    ("B3_N192_PW8", "conv", 96, 16, 192, 1, 10, 24, 1, "generic"),
+    ("B3U_N16", "up2", 1, 16, 16, 2, 3, 12, 1, "generic"),
+    ("B3U_N32", "up2", 40, 16, 32, 2, 3, 12, 1, "generic"),
+    ("B3U_N32_M", "up2", 1, 16, 32, 2, 3, 12, 1, "generic"),
+    ("B3U_N48", "up2", 1, 16, 48, 2, 3, 12, 1, "generic"),
+    ("B3U_N64", "up2", 12, 16, 64, 2, 3, 12, 1, "generic"),
+    ("B3U_N96", "up2", 48, 16, 96, 2, 3, 12, 1, "generic"),
+    ("B3U_N32_TB", "up2", 1, 16, 64, 2, 3, 12, 1, "generic"),
+    ("B3P_N16", "conv", 1, 16, 16, 3, 6, 24, 1, "c16"),
+    ("B3PU_N16", "up2", 1, 16, 16, 2, 3, 12, 1, "c16"),
+    ("B3V_N32", "conv", 48, 16, 32, 5, 6, 24, 1, "v32"),
+    ("B3V_N64", "conv", 24, 16, 96, 3, 6, 24, 1, "v32"),
+    ("B3VU_N32", "up2", 48, 16, 32, 3, 3, 12, 1, "v32"),
+    ("B3VU_N64", "up2", 48, 16, 64, 2, 3, 12, 1, "v32"),
+    ("B3D_N64", "conv", 24, 32, 64, 3, 6, 24, 1, "d32"),
+    ("B3D_N64_H5", "conv", 20, 32, 64, 3, 15, 24, 1, "d32"),
+    ("B3D_N64_W8", "conv", 24, 32, 64, 3, 10, 24, 1, "d32"),
+    ("B3D_N96", "conv", 48, 32, 96, 3, 6, 24, 1, "d32"),
+    ("B3D_N96_H5", "conv", 32, 32, 96, 3, 15, 24, 1, "d32"),
+    ("B3D_N96_W8", "conv", 48, 32, 96, 3, 10, 24, 1, "d32"),
+    ("B3D_N128_P", "conv", 96, 32, 128, 1, 6, 24, 1, "d32"),
+    ("B3D_N128_PH5", "conv", 24, 32, 128, 1, 15, 24, 1, "d32"),
+    ("B3D_N128_PW8", "conv", 32, 32, 128, 1, 10, 24, 1, "d32"),
+    ("B3D_N192_PH5", "conv", 64, 32, 192, 1, 15, 24, 1, "d32"),
+    ("B3D_N192_PW8", "conv", 96, 32, 192, 1, 10, 24, 1, "d32"),
+    ("B3D_N32_TB", "conv", 1, 32, 32, 3, 6, 24, 1, "d32"),
+    ("B3D_N64_S", "conv", 12, 32, 64, 3, 6, 24, 1, "d32"),
+    ("B3D2_N64", "conv", 40, 32, 64, 2, 6, 24, 1, "d32"),
+    ("B3D2_N64_H5", "conv", 40, 32, 64, 2, 15, 24, 1, "d32"),
+    ("B3D2_N64_W8", "conv", 48, 32, 64, 2, 10, 24, 1, "d32"),
+    ("B3D2_N96", "conv", 96, 32, 96, 2, 6, 24, 1, "d32"),
+    ("B3D2_N96_H5", "conv", 64, 32, 96, 2, 15, 24, 1, "d32"),
+    ("B3D2_N96_W8", "conv", 96, 32, 96, 2, 10, 24, 1, "d32"),
+    ("B3D2_N32_TB", "conv", 1, 32, 32, 2, 6, 24, 1, "d32"),
+    ("B3D2_N64_S", "conv", 20, 32, 64, 2, 6, 24, 1, "d32"),
+    ("B3DU_N64", "up2", 12, 32, 64, 2, 3, 12, 1, "d32"),
+    ("B3DU_N96", "up2", 48, 32, 96, 2, 3, 12, 1, "d32"),
+    ("B3DU2_N64", "up2", 24, 32, 64, 1, 3, 12, 1, "d32"),
+    ("B3DU2_N96", "up2", 96, 32, 96, 1, 3, 12, 1, "d32"),
+]
+# the unit walk of the streaming kernel (units >= 2 R + r, R = 512): the plain, the _d32 and the fused-upsample 2 x 4 x 16 bricks
+VARIANT_ROWS += [
+    ("B3_N64", "conv", 130, 16, 64, 3, 6, 24, 1, "generic"),
+    ("B3D_N64", "conv", 130, 32, 64, 3, 6, 24, 1, "d32"),
+    ("B3U_N64", "up2", 130, 16, 64, 2, 3, 12, 1, "generic"),
+]
+WALK_VARIANT_IDS = ("B3_N64-130", "B3D_N64-130", "B3U_N64-130")
+
+
+def variant_row_id(row) -> str:
+    return f"{row[0]}-{row[2]}"
+
+
+def parse_variants_inc(path):
+    """csrc/conv3d_variants.inc -> {row: (kind 'MFMA' | 'B3', kernel suffix, [template arguments])} in file order."""
+    import re
+    out = {}
+    with open(path) as f:
+        for line in f:
+            m = re.match(r"MVSGI_(B3|MFMA)\((\w+), (.*)\)\s*$", line)
+            if m:
+                kind, row, rest = m.groups()
+                suffix, args = rest.split(", ", 1) if kind == "B3" else ("", rest)
+                out[row] = (kind, suffix, args)
+    return out
+
+
+def variant_kernel_name(variants, row: str, fmt: str) -> str:
+    """The name csrc/conv3d.hip:variant_name reports for a row in a split ('bf16' | 'f16'; 'f32' for the MFMA rows)."""
+    kind, suffix, args = variants[row]
+    if kind == "MFMA":
+        return f"conv3d_mfma_kernel<{args}>"
+    return f"conv3d_{'f16x3' if fmt == 'f16' else 'bf16x3'}{suffix}<{args}>"
+
+
+def streaming_units(variants, row: str, B, Do, Ho, Wo, Cout) -> int:
+    """launch_bf16x3 (csrc/conv3d_bf16x3.hpp:1455-1477): B * tiles_d * tiles_h * tiles_w * cdiv(CT, WN * NW), CT = Cout / 16 (32 for
+    the 32x32x16 schedule).  Template arguments: NW, MW, WM, WN, TD, TH, TW, ..."""
+    a = variants[row][2].split(", ")
+    NW, _, _, WN, TD, TH, TW = (int(v) for v in a[:7])
+    v32 = len(a) > 11 and a[11] == "true"
+    return B * cdiv(Do, TD) * cdiv(Ho, TH) * cdiv(Wo, TW) * cdiv(Cout // (32 if v32 else 16), WN * NW)
+
+
+def variant_case(row, fmt: str, regime: str):
+    name, fn, B, ci, co, D, Hh, W, s, lay = row
+    i = [r for r in VARIANT_ROWS].index(row)
+    return make_case(fmt, regime, B, ci, co, (D, Hh, W), stride=s, res=bool(i % 2), slope=_slope(i), up2=(fn == "up2"),
+                     seed=2000 + i, frames=FRAMES)
+
+
+# ---- the border-plane skip (launch_bf16x3, csrc/conv3d_bf16x3.hpp:1461-1475): the 2 x 4 x 16 bricks of the 32-channel-slice kernels
+# in a volume FOUR planes deep whose layer of bricks, B * cdiv(H, 4) * cdiv(W, 16) * cdiv(Cout / 16, WN * NW), is at least 4 rounds of
+# the chip (4 * CUs).  The variant's name does not say that the skip ran: the tests restate this condition.
+# (row, entry point, B, Cin, Cout, D, H, W of the OUTPUT volume's input: low resolution for up2, skip expected)
+BORDER_ROWS = [
+    ("B3D_N64", "conv", 256, 32, 64, 4, 8, 32, True),
+    ("B3D_N96", "conv", 256, 32, 96, 4, 8, 32, True),
+    ("B3DU_N64", "up2", 256, 32, 64, 2, 4, 16, True),
+    ("B3DU_N96", "up2", 256, 32, 96, 2, 4, 16, True),
+    ("B3D_N64", "conv", 255, 32, 64, 4, 8, 32, False),      # the control: one frame below the condition, the same variant
+]
+
+
+def border_layer(variants, row: str, B, Ho, Wo, Cout) -> int:
+    a = [int(v) for v in variants[row][2].split(", ")[:7]]
+    NW, MW, WM, WN, TD, TH, TW = a
+    assert (TD, WM, MW, TH, TW) == (2, 2, 4, 4, 16), "kBorderSplit (conv3d_bf16x3.hpp:1461)"
+    return B * cdiv(Ho, TH) * cdiv(Wo, TW) * cdiv(Cout // 16, WN * NW)
+
+
+def border_case(row, fmt: str, regime: str):
+    name, fn, B, ci, co, D, Hh, W, _ = row
+    i = BORDER_ROWS.index(row)
+    return make_case(fmt, regime, B, ci, co, (D, Hh, W), res=bool(i % 2), slope=_slope(i + 1), up2=(fn == "up2"), seed=2200 + i, frames=FRAMES)
+
+
+# ---- unit walks: every persistent family at units >= 2 R + r, R = CUs x (the launcher's max_wgs_per_cu argument to
+# persistent_geometry), 0 < r < R: every workgroup walks a second unit behind its first (weights resident, the next unit's image
+# staged during the current one's matrix work) and the last round is ragged.  units_of restates each launcher's tile counts.
+# family -> (B, D, H, W) or (B, H, W); (units per frame, max_wgs_per_cu, source)
+WALKS = {
+    "conv3d_rs": ((65, 3, 5, 17), lambda d, h, w: cdiv(d, 2) * cdiv(h, 4) * cdiv(w, 16), 1, "conv3d_rs.hip:925-928, 955"),
+    "conv3d_rs16": ((65, 5, 5, 17), lambda d, h, w: cdiv(d, 4) * cdiv(h, 4) * cdiv(w, 16), 1, "conv3d_rs.hip:1050-1053, 1069"),
+    # (input size; the units are counted on the stride-2 output)
+    "conv3d_s2rs": ((65, 3, 9, 33), lambda d, h, w: cdiv(d, 2) * cdiv(cdiv(h, 2), 4) * cdiv(cdiv(w, 2), 16), 1, "conv3d_s2rs.hip:278-282, 289"),
+    "conv3d_wino": ((130, 8, 4, 64), lambda d, h, w: (h // 2) * (w // 32), 1, "conv3d_wino.hip:573-575, 474-475"),
+    # per role: 4 (H, W) phases x tiles_d depth roles share the grid, 8 XCDs x walkers workgroups each, walkers = CUs / (8 * 4 * tiles_d)
+    "conv3d_up2_poly": ((35, 2, 5, 17), lambda d, h, w: cdiv(h, 4) * cdiv(w, 16), 0.25, "conv3d_rs.hip:1003-1006, 1019-1025"),
+    # per row phase: 8 XCDs x (CUs / 16) walkers
+    "conv3d_up2_poly_wino": ((260, 8, 2, 32), lambda d, h, w: (h // 2) * (w // 32), 0.5, "conv3d_wino_up2.hip:515-517, 526-530"),
+    "resblock2d": ((258, 15, 31), lambda h, w: cdiv(h, 14) * cdiv(w, 30), 2, "conv2d.hip:439-441, 447; resblock2d_rs.hip:713-715, 443"),
+    # (input size; units on the stride-2 output)
+    "conv2d_s2_split": ((258, 17, 33), lambda h, w: cdiv(cdiv(h, 2), 8) * cdiv(cdiv(w, 2), 16), 2, "resblock2d_rs.hip:645-647, 652"),
+}
+
+
+def walk_units(family: str):
+    """-> (units, R): asserts units >= 2 R + r with 0 < r < R for R = CUs x max_wgs_per_cu AND for one workgroup per CU."""
+    shape, per_frame, wgs, _ = WALKS[family]
+    units, R = shape[0] * per_frame(*shape[1:]), int(LAUNCH_CUS * wgs)
+    assert units >= 2 * R and units % R != 0 and units % max(1, int(LAUNCH_CUS * min(wgs, 1))) != 0, (family, units, R)
+    return units, R
+
+
+WALK_FMTS = {"conv3d_rs": ("bf16", "f16"), "conv3d_rs16": ("bf16", "f16"), "conv3d_s2rs": ("bf16", "f16"), "conv3d_wino": ("f16",),
+             "conv3d_up2_poly": ("bf16", "f16"), "conv3d_up2_poly_wino": ("f16",), "conv2d_s2_split": ("bf16",)}
+RESBLOCK_WALK_SEED = 2500
+
+
+def walk_case(family: str, fmt: str, regime: str):
+    shape = WALKS[family][0]
+    i = list(WALKS).index(family)
+    assert fmt in WALK_FMTS[family]
+    cin, cout, kw = {"conv3d_rs": (32, 32, dict(res=True)), "conv3d_rs16": (16, 16, {}), "conv3d_s2rs": (16, 32, dict(stride=2, fold_scale=True)),
+                     "conv3d_wino": (32, 32, dict(res=True, wino=True)), "conv3d_up2_poly": (32, 16, dict(up2=True, poly=True)),
+                     "conv3d_up2_poly_wino": (32, 16, dict(up2=True, poly=True, polywino=True)),
+                     "conv2d_s2_split": (16, 16, dict(stride=2, fold_scale=True))}[family]
+    # the range of the delivered output, as in the small-shape table
+    bound = {"conv3d_s2rs": F32P_MAX if fmt == "f16" else None, "conv3d_wino": F32P_MAX, "conv2d_s2_split": None}.get(
+        family, F16_MAX if fmt == "f16" else None)
+    return make_case(fmt, regime, shape[0], cin, cout, tuple(shape[1:]), slope=_slope(i), seed=2400 + i, frames=FRAMES, bound=bound, **kw)
+
+
+def resblock_walk_case(regime: str):
+    B, h, w = WALKS["resblock2d"][0]
+    return make_resblock_case(B, h, w, regime, RESBLOCK_WALK_SEED, slope=0.0 if regime == "w2_wide" else 0.25, frames=FRAMES)
+
+
+# ---- the split cost head's whole-depth march: nd = 1 once B * cdiv(H, 8) * cdiv(W, 32) >= 1024 windows
+# (conv3d_headsplit.hip:283-290); D odd, ragged windows, one and two channel slices
+HEAD_MARCH_SHAPES = [(256, 16, 3, 9, 33), (256, 32, 3, 9, 33)]
+
+
+def head_march_case(shape, fmt: str, regime: str):
+    B, ci, d, h, w = shape
+    assert B * cdiv(h, 8) * cdiv(w, 32) >= 1024 and d % 2 == 1
+    return make_case(fmt, regime, B, ci, 1, (d, h, w), slope=1.0, seed=2600 + HEAD_MARCH_SHAPES.index(shape), frames=FRAMES)
+
+
+def launch_cases():
+    """(id, builder) of every launch-size case built with make_case, in the order the GPU module runs them."""
+    out = []
+    for row in VARIANT_ROWS:
+        for fmt in (("f32",) if row[9] == "mfma" else ("bf16", "f16")):
+            for rg in REGIMES:
+                out.append((f"variant-{variant_row_id(row)}-{fmt}-{rg}", functools.partial(variant_case, row, fmt, rg)))
+    for row in BORDER_ROWS:
+        for fmt in ("bf16", "f16"):
+            for rg in REGIMES:
+                out.append((f"border-{row[0]}-{row[2]}-{fmt}-{rg}", functools.partial(border_case, row, fmt, rg)))
+    for family, fmts in WALK_FMTS.items():
+        for fmt in fmts:
+            for rg in REGIMES:
+                out.append((f"walk-{family}-{fmt}-{rg}", functools.partial(walk_case, family, fmt, rg)))
+    for shape in HEAD_MARCH_SHAPES:
+        for fmt in ("bf16", "f16"):
+            for rg in REGIMES:
+                out.append((f"head-{shape}-{fmt}-{rg}", functools.partial(head_march_case, shape, fmt, rg)))
+    return out
+
+
+def direct_reference(c, frames):
+    """act(conv(x [upsampled]) * scale + shift (+ r)) of the frames `frames` of the BATCH the kernel sees, in float64, from the
+    case's delivered fp32 tensors alone: no frame index, no expansion."""
+    sel = torch.as_tensor(list(frames))
+    x = c.x[sel].double()
+    acc = _conv(_up2(x) if c.up2 else x, c.w.double(), c.stride)
+    bc = (1, -1) + (1,) * (x.dim() - 2)
+    v = acc * c.scale.double().view(bc) + c.shift.double().view(bc)
+    if c.r is not None:
+        v = v + c.r[sel].double()
+    return torch.where(v > 0, v, v * c.slope)

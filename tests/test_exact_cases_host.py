@@ -5,7 +5,9 @@ which a correct kernel must return the float64 bits.  For every case of the tabl
   * condition (a) on |hi| + |lo|, (b) at every epilogue stage, (c) on the delivered output;
   * hi*hi + hi*lo + lo*hi in float64 equals the full convolution;
   * ATen's fp32 convolution (another summation order) equals float64.
-The tests below build every case, check the figures make_case() reports, and pin the helpers themselves."""
+The tests below build every case, check the figures make_case() reports, and pin the helpers themselves.  The launch-size cases
+of tests/test_gpu_exact_launches.py (E.launch_cases) are built here too: the conditions on their distinct frames, the properties of
+the frame sequence, and the expanded reference against a direct float64 evaluation of frames of the batch itself."""
 import numpy as np
 import pytest
 import torch
@@ -130,3 +132,80 @@ def test_a_dropped_cross_term_under_the_old_bar_is_not_exact():
     rel = float((broken - c.acc).abs().max() / c.acc.abs().max())       # _rel() of tests/test_gpu_parity.py
     assert 0.0 < rel < 1e-4, rel
     assert "differ" in E.mismatch_report(broken.numpy(), c.acc.numpy())
+
+
+# ------------------------------------------------------------------------------------------------ launch-size cases
+LAUNCH = E.launch_cases()
+# the direct float64 evaluation runs on the FULL batch for these three, on two frames of the sequence for every other case
+FULL_BATCH = ("variant-B3_N64_S-12-bf16-x_wide", "variant-B3DU2_N64-24-f16-w_wide", "walk-conv3d_rs16-bf16-x_wide")
+
+
+def test_full_batch_rows_exist():
+    assert set(FULL_BATCH) <= {i for i, _ in LAUNCH}
+
+
+@pytest.mark.parametrize("cid,build", LAUNCH, ids=[i for i, _ in LAUNCH])
+def test_launch_case_meets_the_conditions_and_expands_to_the_direct_reference(cid, build):
+    c = build()                                      # (a)-(c), the split identities and ATen == float64 on the distinct frames
+    B = c.x.shape[0]
+    assert c.n_frames == min(E.FRAMES, B) and c.x_frames.shape[0] == c.n_frames and c.ref.shape[0] == B
+    E.check_frame_index(c.idx, B, c.n_frames)
+    assert torch.equal(c.x, c.x_frames[torch.from_numpy(c.idx)])
+    assert 0.0 < c.abs_sum_frac < 1.0 and E.representable(c.ref) and (c.bound is None or c.out_max < c.bound)
+    assert c.r is None or c.r.shape[0] == B
+    if c.r is not None and B > c.n_frames:           # the residual is not periodic: two occurrences of a frame carry different ones
+        b0, b1 = (int(b) for b in np.flatnonzero(c.idx == c.idx[0])[:2])
+        assert not torch.equal(c.r[b0], c.r[b1])
+    if cid in FULL_BATCH:
+        frames = range(B)
+    else:                                            # the last frame and the one before it (always two different frames)
+        frames = sorted({B - 1, max(B - 2, 0)})
+    assert torch.equal(E.direct_reference(c, frames), c.ref[list(frames)])
+
+
+@pytest.mark.parametrize("regime", E.RESBLOCK_REGIMES)
+def test_resblock_walk_case(regime):
+    c = E.resblock_walk_case(regime)
+    B = c.x.shape[0]
+    E.check_frame_index(c.idx, B, c.n_frames)
+    assert c.n_frames == E.FRAMES and c.ref.dtype == torch.float64
+    assert torch.equal(c.x, c.x_frames[torch.from_numpy(c.idx)]) and 0.0 < c.abs_sum_frac < 1.0 and E.representable(c.ref)
+    bc = (1, -1, 1, 1)
+    for b in (B - 1, B - 2):                          # the block evaluated directly on a frame of the batch
+        x = c.x[b:b + 1].double()
+        m = F.conv2d(x, c.w1.double(), padding=1) * c.s1.double().view(bc) + c.b1.double().view(bc)
+        m = torch.where(m > 0, m, m * c.slope)
+        y = F.conv2d(m, c.w2.double(), padding=1) * c.s2.double().view(bc) + c.b2.double().view(bc) + x
+        assert torch.equal(torch.where(y > 0, y, y * c.slope), c.ref[b:b + 1])
+
+
+def test_frame_index_properties():
+    for B, Fr in ((2, 2), (3, 3), (5, 4), (12, 4), (32, 4), (130, 4), (260, 4), (7, 7)):
+        idx = E.frame_index(B, Fr, seed=B)
+        E.check_frame_index(idx, B, Fr)
+        assert np.array_equal(idx, E.frame_index(B, Fr, seed=B))            # drawn from the seed alone
+    assert E.frame_index(1, 1, 0).tolist() == [0]
+    with pytest.raises(AssertionError, match="neighbouring"):
+        E.check_frame_index([0, 1, 1, 2, 3], 5, 4)
+    with pytest.raises(AssertionError, match="does not occur"):
+        E.check_frame_index([0, 1, 0, 1, 2], 5, 4)
+    with pytest.raises(AssertionError, match="ordered pair"):
+        E.check_frame_index(([0, 1, 2, 3] * 9)[:33] , 33, 4)
+
+
+def test_launch_tables_name_every_variant_row_once_and_count_their_units():
+    import os
+    variants = E.parse_variants_inc(os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "mvs_gi_amd", "csrc", "conv3d_variants.inc"))
+    assert len(variants) == 67 and {r[0] for r in E.VARIANT_ROWS} == set(variants)
+    assert E.variant_kernel_name(variants, "B3D_N128_PW8", "f16") == "conv3d_f16x3_d32_dk_kernel<2, 5, 1, 4, 1, 10, 8>"
+    assert E.variant_kernel_name(variants, "V_S2_N64_B64", "f32") == "conv3d_mfma_kernel<2, 2, 2, 2, 2, 4, 8, 2>"
+    for family in E.WALKS:
+        units, R = E.walk_units(family)
+        assert units >= 2 * R + 1 and 0 < units % R < R
+    for row in E.VARIANT_ROWS[-3:]:                    # the streaming kernel's walk rows: R = 2 workgroups x 256 CUs
+        up = 2 if row[1] == "up2" else 1
+        units = E.streaming_units(variants, row[0], row[2], up * row[5], up * row[6], up * row[7], row[4])
+        assert E.variant_row_id(row) in E.WALK_VARIANT_IDS and units == 1040 and units >= 2 * 512 + 1 and units % 512 and units % 256
+    for row in E.BORDER_ROWS:
+        up = 2 if row[1] == "up2" else 1
+        assert (E.border_layer(variants, row[0], row[2], up * row[6], up * row[7], row[4]) >= 4 * E.LAUNCH_CUS) == row[8] and up * row[5] == 4

@@ -29,12 +29,11 @@ trilinear resize             H.resize_trilinear x2, x4                          
 uint8 stem                   LEFT OUT: csrc/conv2d.hip:112 divides every pixel by 255.0f and :177 every weight (w / 255 in three
                              bf16 pieces): 1/255 is not dyadic, no operand makes the products exact.  It keeps its tolerance test
                              (test_gpu_parity.py::test_conv2d_stem_uint8_on_the_matrix_cores).
-large-launch variants        STAY AT THEIR TOLERANCE TESTS, not for inexactness but for size: the border-plane-skip kernels (`_brd_`:
-                             csrc/conv3d.hip picks them for volumes four planes deep in layers of >= 4 rounds of bricks, 48 frames in
-                             test_conv3d_mfma_and_direct_vs_oracle), the many-frame brick variants of CONV_SHAPES (2 x 5 x 16,
-                             2 x 10 x 8, one-plane 128- / 192-cout units: 24 to 96 frames) and conv3d_up2 with _V32 in the fp16 split
-                             (no test of any kind runs it; no model path selects _V32).  A float64 reference of those shapes
-                             takes minutes on the CPU; the same template code runs here at the smallest shape of each layout.
+launch-size variants         tests/test_gpu_exact_launches.py: the same operands and comparison on batches built from four distinct
+                             frames -- every row of csrc/conv3d_variants.inc in both splits (the many-frame bricks, the one-plane
+                             and depth-skip units, conv3d_up2 with _V32 in the fp16 split), the border-plane-skip kernels under
+                             their restated launch condition, a second and later unit of every persistent kernel, the cost
+                             head's whole-depth march.  This module keeps the smallest shape of each layout.
 """
 import numpy as np
 import pytest
@@ -159,6 +158,33 @@ def _pack3d(wg, sc, fmt, layout=H.CONV_BF16X3):
     return wp, sc * un, layout | F16
 
 
+def split_layouts(dims, stride):
+    """The weight layouts test_conv3d_split_kernels_every_layout runs a case in (also read by the coverage test of
+    tests/test_gpu_exact_launches.py)."""
+    B, Cin, Cout, D, Hh, W = dims
+    layouts = [H.CONV_BF16X3]
+    if H.conv3d_d32_applies(B, Cin, D, Hh, W, Cout, stride):
+        layouts.append(H.CONV_BF16X3_D32)
+    if Cout == 16 and stride == 1:
+        layouts.append(H.CONV_BF16X3_C16)
+    if H.conv3d_v32_applies(B, Cin, D, Hh, W, Cout, stride):
+        layouts.append(H.CONV_BF16X3_V32)
+    return layouts
+
+
+def up2_layouts(dims, fmt):
+    """... and test_conv3d_up2 (low-resolution sizes)."""
+    B, Cin, Cout, Dl, Hl, Wl = dims
+    layouts = [H.CONV_BF16X3]
+    if Cout == 16:
+        layouts.append(H.CONV_BF16X3_C16)
+    if H.conv3d_up2_d32_applies(B, Cin, Dl, Hl, Wl, Cout):      # 32-channel slices; the depth-skip form out of a one-plane level
+        layouts.append(H.CONV_BF16X3_D32)
+    if fmt == "bf16" and Cout % 32 == 0 and H.conv3d_v32_applies(B, Cin, 2 * Dl, 2 * Hl, 2 * Wl, Cout, 1):
+        layouts.append(H.CONV_BF16X3_V32)
+    return layouts
+
+
 @pytest.mark.parametrize("fmt", ["bf16", "f16"])
 @pytest.mark.parametrize("name", E.ids("conv3d_bf16"))
 def test_conv3d_split_kernels_every_layout(name, fmt):
@@ -168,13 +194,11 @@ def test_conv3d_split_kernels_every_layout(name, fmt):
     want = _want(c)
     kname = f"conv3d_{'f16x3' if fmt == 'f16' else 'bf16x3'}"
     # the template's last four arguments: fused upsample, plane schedule (_C16), 32x32x16 schedule (_V32), weight slice through LDS
-    layouts = [(H.CONV_BF16X3, lambda n: n.startswith(kname + "_kernel<") and n.endswith(("false, false, false, false>", "false, false, false, true>")))]
-    if H.conv3d_d32_applies(B, Cin, D, Hh, W, Cout, c.stride):
-        layouts.append((H.CONV_BF16X3_D32, lambda n: n.startswith(kname + "_d32")))
-    if Cout == 16 and c.stride == 1:
-        layouts.append((H.CONV_BF16X3_C16, lambda n: n.startswith(kname + "_kernel<") and n.endswith("false, true, false, false>")))
-    if H.conv3d_v32_applies(B, Cin, D, Hh, W, Cout, c.stride):
-        layouts.append((H.CONV_BF16X3_V32, lambda n: n.startswith(kname + "_kernel<") and n.endswith("false, false, true, false>")))
+    name_oks = {H.CONV_BF16X3: lambda n: n.startswith(kname + "_kernel<") and n.endswith(("false, false, false, false>", "false, false, false, true>")),
+                H.CONV_BF16X3_D32: lambda n: n.startswith(kname + "_d32"),
+                H.CONV_BF16X3_C16: lambda n: n.startswith(kname + "_kernel<") and n.endswith("false, true, false, false>"),
+                H.CONV_BF16X3_V32: lambda n: n.startswith(kname + "_kernel<") and n.endswith("false, false, true, false>")}
+    layouts = [(layout, name_oks[layout]) for layout in split_layouts((B, Cin, Cout, D, Hh, W), c.stride)]
     if (B, Cin, Cout, D, Hh, W, c.stride, c.r is not None) in E.CONV3D_V32_SHAPES:
         assert len(layouts) == 2, "the 32x32x16 schedule must take this shape"
     if (B, Cin, Cout) == (1, 128, 128):
@@ -210,13 +234,11 @@ def test_conv3d_up2(name, fmt):
     xg, rg, wg, sc, sh = _cl(c.x), _cl(c.r), _g(c.w), _g(c.scale), _g(c.shift)
     want = _want(c)
     kname = f"conv3d_{'f16x3' if fmt == 'f16' else 'bf16x3'}"
-    layouts = [(H.CONV_BF16X3, kname + "_kernel<", "true, false, false, false>")]
-    if Cout == 16:
-        layouts.append((H.CONV_BF16X3_C16, kname + "_kernel<", "true, true, false, false>"))
-    if H.conv3d_up2_d32_applies(B, Cin, Dl, Hl, Wl, Cout):      # 32-channel slices; the depth-skip form out of a one-plane level
-        layouts.append((H.CONV_BF16X3_D32, kname + ("_d32u_dk_kernel<" if Dl == 1 else "_d32u_kernel<"), ">"))
-    if fmt == "bf16" and Cout % 32 == 0 and H.conv3d_v32_applies(B, Cin, 2 * Dl, 2 * Hl, 2 * Wl, Cout, 1):
-        layouts.append((H.CONV_BF16X3_V32, kname + "_kernel<", "true, false, true, false>"))
+    heads = {H.CONV_BF16X3: (kname + "_kernel<", "true, false, false, false>"),
+             H.CONV_BF16X3_C16: (kname + "_kernel<", "true, true, false, false>"),
+             H.CONV_BF16X3_D32: (kname + ("_d32u_dk_kernel<" if Dl == 1 else "_d32u_kernel<"), ">"),
+             H.CONV_BF16X3_V32: (kname + "_kernel<", "true, false, true, false>")}
+    layouts = [(layout, *heads[layout]) for layout in up2_layouts((B, Cin, Cout, Dl, Hl, Wl), fmt)]
     if (B, Cin, Cout, Dl, Hl, Wl) in ((1, 32, 96, 3, 10, 24), (3, 32, 96, 1, 10, 24)) or (fmt == "bf16" and (B, Cin, Cout) == (6, 16, 64)):
         assert len(layouts) == 2, "this shape is in the table for its second layout"
     for layout, head, tail in layouts:

@@ -2,7 +2,11 @@
 // the double-sphere and the equirectangular projection into grid_sample coordinates, and the validity rule of the image
 // sampler.  The element-wise kernels of grids.hip and resample.hip and the fused back-projection (reproject.hip) all call
 // these, fp32 with contraction off and the operation order of the reference's torch expressions, so the fused kernel is the
-// bits of the chain by construction.  Include inside the translation unit's anonymous namespace.
+// bits of the chain by construction.  One step is not the reference's: it writes `self.fx / t` with a Python float on the left,
+// which torch evaluates as reciprocal(t) * fx (two roundings); project_double_sphere divides once (fx / t, one rounding, the
+// more accurate of the two).  The mask is the reference's bit for bit, the grid its last bits only: tests/grid_exact_cases.py
+// emulates this file operation by operation and tests/test_grid_exact_host.py counts the golden elements either form
+// reproduces.  Include inside the translation unit's anonymous namespace.
 #pragma once
 
 constexpr float kPiF = 3.14159274101257324f;      // float32(np.pi)

@@ -47,7 +47,7 @@ deform_conv2d_f32 (shared and per-image offsets)           test_deform_conv2d
 rejections leave the output alone                          test_rejections_leave_memory_alone
 whole path, guarded inputs, twice                          test_whole_path_guarded
 graph-held rig constants (found by the guards)             test_graph_held_rig_constants_survive_another_batch_size
-frame bases beyond 2^31 elements (part C)                  test_large_offsets_*
+frame bases beyond 2^31 elements (part C)                  test_large_offsets_* (the grid generators included)
 the harness itself                                         test_guard_hits_on_the_device_are_reported
 
 No family is left open.
@@ -838,7 +838,8 @@ def test_instance_norm(arena, C, S):
 def test_grid_generators(arena, golden_dir):
     """rays_panorama, transform_points, grid_double_sphere, grid_equirect on guarded inputs: at the goldens' shapes against the
     reference's outputs (the bars of test_sweep_grid_generator_vs_reference_goldens), and at a shape odd in every axis (5
-    candidates, 7 x 13, two poses) against float64 where a closed form is at hand (R p + t), bit-equal to the plain call everywhere."""
+    candidates, 7 x 13, two poses) against float64 where a closed form is at hand (R p + t), bit-equal to the plain call everywhere.
+    (Element for element: tests/test_gpu_grids_exact.py.)"""
     import os
     from mvs_gi_amd.dropin import sweep_grids as SG
     z = np.load(os.path.join(golden_dir, "sweep_grids.npz"))
@@ -1386,3 +1387,62 @@ def test_large_offsets_sweep_one_rig(arena, big):
     Bs = _b_for(10 * 10 * 34 * 16)
     _run_or_refused(run_split, Bs, "sweep one rig, split output")
     _report_peak(f"sweep_std_nhwc_valid_split B={Bs}")
+
+
+def test_large_offsets_grid_generators(arena, big):
+    """transform_points and grid_double_sphere with 3 B M (points) and 2 B M (grid) beyond 2^31 elements, a different transform
+    per batch element: the first and the last window of 4096 points bit for bit against the host emulation
+    (tests/grid_exact_cases.py).  rays_panorama with 3 N H W beyond 2^31 (the z plane starts at 2 N H W): the first and the last
+    4096 elements of every plane within the per-element bounds of the float64 closed form.  Nothing between the windows is
+    read back."""
+    import grid_exact_cases as GC
+    from mvs_gi_amd.dropin import sweep_grids as SG
+    WIN = 4096
+    M = (1 << 20) + 77                                       # points per batch element: odd, no multiple of the 256-thread block
+    B = _b_for(2 * M)
+    assert 2 * B * M >= (1 << 31) + 2 * WIN
+    p = _big_randn((B, 3, 1, 1, M), 30)
+    rng = np.random.default_rng(30)
+    T = np.tile(np.eye(4, dtype=np.float32), (B, 1, 1))
+    T[:, :3, :3] = np.linalg.qr(rng.standard_normal((B, 3, 3)))[0].astype(np.float32)
+    T[:, :3, 3] = rng.standard_normal((B, 3)).astype(np.float32)
+    windows = [(0, slice(0, WIN)), (B - 1, slice(M - WIN, M))]
+    q = SG.transform_3D_points_torch(_g(T), p)
+    for b, sl in windows:
+        got = q[b:b + 1, :, 0, 0, sl].cpu().numpy()
+        want = GC.transform(T[b:b + 1], p[b:b + 1, :, 0, 0, sl].cpu().numpy())
+        assert GC.same_bits(got, want), f"transform_points, batch element {b}: {GC.first_difference(got, want)}"
+    del p
+    _report_peak(f"transform_points B={B} M={M}")
+    ds = SG.DoubleSphereSampleGridMaker()
+    grid, mask = ds.make_grid(q)
+    assert grid.numel() > (1 << 31) and tuple(mask.shape) == (B, 1, 1, M)
+    for b, sl in windows:
+        want_grid, want_mask = GC.double_sphere(q[b:b + 1, :, 0, 0, sl].cpu().numpy(), *GC.ds_args("default"))
+        got_grid, got_mask = grid[b:b + 1, 0, 0, sl].cpu().numpy(), mask[b:b + 1, 0, 0, sl].cpu().numpy()
+        assert np.array_equal(got_mask, want_mask), f"grid_double_sphere mask, batch element {b}: {GC.first_difference(got_mask, want_mask)}"
+        assert GC.same_bits(got_grid, want_grid), f"grid_double_sphere, batch element {b}: {GC.first_difference(got_grid, want_grid)}"
+    del q, grid, mask
+    _report_peak(f"grid_double_sphere B={B} M={M}")
+    gc.collect()
+    torch.cuda.empty_cache()
+
+    Hh, W = 257, 1021
+    N = _b_for(3 * Hh * W)
+    total = N * Hh * W
+    assert 3 * total >= (1 << 31) + WIN and 2 * total < (1 << 31)             # the z plane crosses 2^31
+    lat, lon = GC.PANORAMA_RANGES["full_sphere"]
+    dist = np.geomspace(0.5, 100.0, N).astype(np.float32)
+    rm = SG.RayMaker_UEPanorama(dist, lon, lat, device=DEV)
+    rays = rm.make_rays_for_candidates((Hh, W))
+    assert rays.numel() == 3 * total
+    phi, theta = GC.panorama_args(N, Hh, W, lat, lon)
+    flat = rays.view(3, total)
+    for idx in (np.arange(WIN), np.arange(total - WIN, total)):
+        got = flat[:, int(idx[0]):int(idx[-1]) + 1].cpu().numpy()
+        exact = GC.panorama_exact_at(dist, phi, theta, idx)
+        units = GC.UNITS_PANORAMA.reshape(3, 1)
+        ok, worst = GC.check_bound(got, exact, units)
+        print(f"[large-offset] rays_panorama elements {idx[0]}..{idx[-1]} of each plane: worst {worst:.2f} x 2^-23 |exact|")
+        assert ok.all(), GC.describe_failures(ok, got, exact, units)
+    _report_peak(f"rays_panorama N={N}")

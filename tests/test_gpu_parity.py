@@ -1275,7 +1275,9 @@ def test_inference_pipeline_with_sphere_extractor(conv_mode):
 def test_sweep_grid_generator_vs_reference_goldens(golden_dir):
     """HIP closed forms (dropin/sweep_grids.py, reference class names) vs the reference's own outputs.
     Tolerances: device sin/cos/atan2/sqrt are within ~2 ulp of the host libm; projections are compared
-    where they are well conditioned (inside the field of view, away from the atan2 branch cut)."""
+    where they are well conditioned (inside the field of view, away from the atan2 branch cut).  The per-element check -- bit for
+    bit for the transform and the double sphere, ulp bounds for the trigonometric kernels, nothing masked out -- is
+    tests/test_gpu_grids_exact.py."""
     from mvs_gi_amd.dropin import sweep_grids as SG
     z = _load(golden_dir, "sweep_grids")
     for name in ("g16", "e8_full_sphere"):

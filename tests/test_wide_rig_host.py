@@ -8,6 +8,7 @@ import pytest
 import torch
 
 import wide_rig_cases as W
+from grid_exact_cases import fma_f32
 from mvs_gi_amd import hip_ops as H
 from oracle import mvsgi_oracle as O
 
@@ -59,30 +60,12 @@ def test_predicates():
 
 
 # ------------------------------------------------------------------------------ the division sequence
-def _fma_f32(a, b, c):
-    """RN_f32(a * b + c) for float32 arrays, exactly.  The product of two float32 is exact in float64; the float64 sum s and its
-    exact error e (two-sum) are the exact sum.  Rounding s to float32 is then wrong only where s sits exactly half-way between two
-    neighbouring float32 and e != 0: there the sign of e decides, not the tie rule."""
-    p = a.astype(np.float64) * b.astype(np.float64)
-    c = c.astype(np.float64)
-    s = p + c
-    bb = s - p
-    e = (p - (s - bb)) + (c - bb)
-    r = s.astype(np.float32)
-    rb = r.astype(np.float64)
-    other = np.where(rb > s, np.nextafter(r, np.float32(-np.inf)), np.nextafter(r, np.float32(np.inf))).astype(np.float32)
-    ob = other.astype(np.float64)
-    mid = (rb != s) & ((rb + ob) / 2 == s)
-    lo, hi = np.minimum(r, other), np.maximum(r, other)
-    return np.where(mid & (e > 0), hi, np.where(mid & (e < 0), lo, r)).astype(np.float32)
-
-
 def _markstein(x, d):
     inv = np.float32(1.0) / np.float32(d)
     dd = np.full_like(x, np.float32(d))
     q = (x.astype(np.float64) * np.float64(inv)).astype(np.float32)
-    r = _fma_f32(-dd, q, x)
-    return _fma_f32(r, np.full_like(x, inv), q)
+    r = fma_f32(-dd, q, x)
+    return fma_f32(r, np.full_like(x, inv), q)
 
 
 @pytest.mark.parametrize("d", [5, 6, 7, 8])

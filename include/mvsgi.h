@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define MVSGI_ABI_VERSION 8   /* 8: mvsgi_reproject_f32 (back-projection: point cloud and warped camera views); 7: mvsgi_resample_bilinear_u8_f32, mvsgi_resample_bilinear_f32, mvsgi_resample_validity_u8, mvsgi_resample_u8_table_f32, mvsgi_rays_equirect_surrogate_f32 (fisheye -> surrogate-view resampler); 6: mvsgi_sweep_max_cams (masked-variance sweep for rigs of up to 8 cameras); 5: mvsgi_softargmin_scaled_f32 (soft-argmin at any interp_scale_factor); 4: mvsgi_instance_norm_f32, mvsgi_instance_norm_ws_bytes (norm_type 'instance'); 3: mvsgi_conv3d_d32_applies, mvsgi_conv3d_up2_d32_applies + MVSGI_CONV_BF16X3_D32; 2: mvsgi_saturation_flags; the symbol set of round 5 */
+#define MVSGI_ABI_VERSION 8   /* 8: mvsgi_reproject_f32 (back-projection: point cloud and warped camera views), and, added later without a new number (an addition: older callers are unaffected, and the binding refuses a library that lacks a symbol it binds), mvsgi_metrics_f32, mvsgi_metrics_ws_bytes (validation metrics); 7: mvsgi_resample_bilinear_u8_f32, mvsgi_resample_bilinear_f32, mvsgi_resample_validity_u8, mvsgi_resample_u8_table_f32, mvsgi_rays_equirect_surrogate_f32 (fisheye -> surrogate-view resampler); 6: mvsgi_sweep_max_cams (masked-variance sweep for rigs of up to 8 cameras); 5: mvsgi_softargmin_scaled_f32 (soft-argmin at any interp_scale_factor); 4: mvsgi_instance_norm_f32, mvsgi_instance_norm_ws_bytes (norm_type 'instance'); 3: mvsgi_conv3d_d32_applies, mvsgi_conv3d_up2_d32_applies + MVSGI_CONV_BF16X3_D32; 2: mvsgi_saturation_flags; the symbol set of round 5 */
 
 typedef void* mvsgi_stream_t;
 
@@ -551,6 +551,46 @@ int mvsgi_conv3d_wino32_f16(const void* x_split, const void* w_packed, const flo
 size_t mvsgi_instance_norm_ws_bytes(int B, int S, int C);
 int mvsgi_instance_norm_f32(const float* x, const float* res, const float* gamma, const float* beta, float* y, float* ws,
                             int B, int S, int C, float eps, float neg_slope, mvsgi_stream_t stream);
+
+/* ---- validation metrics (csrc/metrics.hip) ----------------------------------------------------------------------------
+ * dsta_mvs/support/loss_function/metrics.py: RMSEMetric, MAEMetric, BadPixelRatioMetric and SSIMMetric, each also behind
+ * InverseMetricWrapper, as validation_step (model/mvs_model/spherical_sweep_stereo_2024.py:145-231) applies them -- for every frame
+ * of a batch and pooled, forward only, in at most four launches, without atomics: the same inputs give the same bits.
+ * preds, target: [B][H][W] fp32, 16-byte aligned; preds is the regressor's raw output (not divided by bf).  Per pixel, in fp32
+ * without contraction, p = preds[b][i][j], t = target[b][i][j]:
+ *   direct form     P = p / bf, T = clamp(t, cmin, cmax) / bf                  (MVSMetric.clamp_and_scale, :27-37; torch.clamp: a
+ *                   NaN stays a NaN); cmin / cmax = min / max(bf / Tensor(dist_list)) as fp32, computed by the caller (:23-25)
+ *   distance form   the same on p' = 1.0f / p, t' = 1.0f / t                   (InverseMetricWrapper, :160-183, literally: the
+ *                   clamp to the inverse-distance range is applied to 1 / t)
+ *   validity v      mask_kind MVSGI_METRICS_MASK_NONE: every pixel; _TENSOR: mask[b][i][j] != 0 (bytes; 4-byte aligned); _RANGE:
+ *                   lo <= t <= hi on the raw t for both forms (validation_step's mask_labels, :198-199).  A select: a NaN
+ *                   at an invalid pixel changes nothing.
+ *   e = P - T, a = |e|, s = e * e; over the valid pixels of a frame S2 = sum s, S1 = sum a (float64, compensated: the sums
+ *   of the fp32 addends to ~2^-100 relative, rounded once), n = count, NB = #{a > thresh} (thresh for the direct form, thresh_dist for the other)
+ *   rmse = sqrt(S2 / n), mae = S1 / n (n = 0: NaN), bad = n > 0 ? NB / n : 1.0; with MVSGI_METRICS_MASK_NONE bad = NB / (H * W)
+ *   (:145-156, literally)
+ *   ssim            in float64, the mask is not used (:59-60): R = max(maxP - minP, maxT - minT) over the frame
+ *                   (MVSGI_METRICS_RANGE_FRAME) or the launch (MVSGI_METRICS_RANGE_BATCH: what one call of the reference on B frames
+ *                   uses), c1 = (0.01 R)^2, c2 = (0.03 R)^2, g_u = exp(-(u / 1.5)^2 / 2), u = -5 .. 5, normalised to sum 1;
+ *                   at every pixel whose 11 x 11 window lies inside the image mu_X = sum_uv g_u g_v X[i + u][j + v] for X in
+ *                   {P, T, PP, TT, PT}; map = (2 mu_P mu_T + c1)(2 s_PT + c2) / ((mu_P^2 + mu_T^2 + c1)(s_P + s_T + c2)) with
+ *                   s_P = mu_PP - mu_P^2, s_T = mu_TT - mu_T^2, s_PT = mu_PT - mu_P mu_T; ssim = the mean of the map over those
+ *                   (H - 10)(W - 10) pixels (structural_similarity_index_measure with its defaults, whose reflect padding is cropped
+ *                   off again before the mean); H < 11 or W < 11: NaN
+ * out: [B + 1][9] float64, columns rmse, mae, bad, ssim, rmse_dist, mae_dist, bad_dist, ssim_dist, n.  Row B is the reference's
+ * value for the batch as one call: sums and counts added over the frames (unmasked bad over H * W, as the reference divides),
+ * ssim the mean of the frames' means.  Row b < B depends on frame b alone in MVSGI_METRICS_RANGE_FRAME.
+ * ws: caller-owned device scratch of ws_bytes >= mvsgi_metrics_ws_bytes(B, H, W) bytes (0 = invalid dimensions), 8-byte aligned;
+ * B < 65535. */
+#define MVSGI_METRICS_MASK_NONE   0
+#define MVSGI_METRICS_MASK_TENSOR 1
+#define MVSGI_METRICS_MASK_RANGE  2
+#define MVSGI_METRICS_RANGE_FRAME 0
+#define MVSGI_METRICS_RANGE_BATCH 1
+size_t mvsgi_metrics_ws_bytes(int B, int H, int W);
+int mvsgi_metrics_f32(const float* preds, const float* target, const unsigned char* mask, int mask_kind, float lo, float hi,
+                      float bf, float cmin, float cmax, float thresh, float thresh_dist, int range_scope, void* ws,
+                      size_t ws_bytes, double* out, int B, int H, int W, mvsgi_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -130,6 +130,8 @@ SIGNATURES = {
     "mvsgi_nvc_to_ncv_f32": (c_int, [_P, _P, c_int, c_int, c_longlong, _P]),
     "mvsgi_instance_norm_ws_bytes": (c_size_t, [c_int] * 3),
     "mvsgi_instance_norm_f32": (c_int, [_P] * 6 + [c_int] * 3 + [c_float, c_float, _P]),
+    "mvsgi_metrics_ws_bytes": (c_size_t, [c_int] * 3),
+    "mvsgi_metrics_f32": (c_int, [_P, _P, _P, c_int] + [c_float] * 7 + [c_int, _P, c_size_t, _P] + [c_int] * 3 + [_P]),
 }
 
 _lib = None

@@ -7,7 +7,8 @@ Two situations:
   (dsta_mvs.model.cost_volume_builder[.spherical_sweep_avg|.spherical_sweep],
    dsta_mvs.model.cost_volume_regulator[.unet_regulator],
    dsta_mvs.model.distance_regressor[.distance_regressor],
-   dsta_mvs.model.common[.common_modules], dsta_mvs.model.mvs_model.torch_only),
+   dsta_mvs.model.common[.common_modules], dsta_mvs.model.mvs_model.torch_only,
+   dsta_mvs.support.loss_function[.metrics]: the validation metrics, which the checkpoints pickle too),
   so that checkpoints which pickle whole module objects
   (spherical_sweep_stereo.py:74; consumers api/inference_pytorch.py:87-101,
   dsta_mvs/test/utils.py:221-230) unpickle into the drop-in classes;
@@ -28,8 +29,10 @@ from . import cost_volume_regulator as _reg
 from . import distance_regressor as _dr
 from . import torch_only as _to
 from . import feature_extractor as _fe
+from . import metrics as _met
 
 _ALIAS_FLAG = "__mvsgi_alias__"
+_METRIC_CLASSES = ["MVSMetric", "SSIMMetric", "RMSEMetric", "MAEMetric", "BadPixelRatioMetric", "InverseMetricWrapper"]
 _state = {"mode": None, "saved": []}
 
 
@@ -84,6 +87,13 @@ def _install_aliases():
     reg.unet_regulator = leaf("dsta_mvs.model.cost_volume_regulator.unet_regulator", _reg)
     dr.distance_regressor = leaf("dsta_mvs.model.distance_regressor.distance_regressor", _dr)
     mm.torch_only = leaf("dsta_mvs.model.mvs_model.torch_only", _to)
+    # the validation metrics (configs/base_model.yaml:40-79 names them as dsta_mvs.support.loss_function.<Class>)
+    support = _pkg("dsta_mvs.support")
+    lf = _pkg("dsta_mvs.support.loss_function")
+    _export(lf, _met, _METRIC_CLASSES)
+    mods.update({"dsta_mvs.support": support, "dsta_mvs.support.loss_function": lf})
+    lf.metrics = leaf("dsta_mvs.support.loss_function.metrics", _met)
+    root.support, support.loss_function = support, lf
     root.model = model
     model.common, model.cost_volume_builder, model.cost_volume_regulator = common, cvb, reg
     model.distance_regressor, model.mvs_model, model.feature_extractor = dr, mm, fe
@@ -134,6 +144,15 @@ def _patch_reference():
         mm = None
     if mm is not None:
         rebind(mm.SphericalSweepStereoBase, forward=_to.reference_forward)
+    # the validation metrics: the reference's module imports torchmetrics, which need not be installed
+    try:
+        lm = importlib.import_module("dsta_mvs.support.loss_function.metrics")
+    except Exception:
+        lm = None
+    if lm is not None:
+        for n in ("SSIMMetric", "RMSEMetric", "MAEMetric", "BadPixelRatioMetric"):
+            rebind(getattr(lm, n), forward=_met.metric_forward, __getstate__=gs)
+        rebind(lm.InverseMetricWrapper, forward=_met.inverse_forward)
     _state["saved"] = saved
 
 

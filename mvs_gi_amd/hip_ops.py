@@ -1071,6 +1071,84 @@ def instance_norm(x, res=None, gamma=None, beta=None, eps: float = 1e-5, neg_slo
     return out
 
 
+METRICS_COLUMNS = ("rmse", "mae", "bad", "ssim", "rmse_dist", "mae_dist", "bad_dist", "ssim_dist", "n")
+METRICS_MASK_NONE, METRICS_MASK_TENSOR, METRICS_MASK_RANGE = 0, 1, 2        # MVSGI_METRICS_MASK_* of include/mvsgi.h
+METRICS_RANGE_SCOPES = {"frame": 0, "batch": 1}                              # MVSGI_METRICS_RANGE_*
+METRICS_EVALUATIONS = 0       # calls of mvsgi_metrics_f32 by this process (tests count evaluations with it)
+# the slab of csrc/metrics.hip, restated: a reduce block per 4096 pixels of a frame (at most 64), 20 doubles per record; SSIM tiles
+# of 16 x 32 windows
+_METRICS_REC, _METRICS_PIX_PER_BLOCK, _METRICS_MAX_BLOCKS, _METRICS_TILE = 20, 4096, 64, (16, 32)
+
+
+def metrics_ws_layout(B: int, H: int, W: int) -> dict:
+    """The workspace of metrics(), in doubles: offsets of its four parts, reduce blocks per frame G, SSIM tiles per frame T."""
+    G = min(max(-(-(H * W) // _METRICS_PIX_PER_BLOCK), 1), _METRICS_MAX_BLOCKS)
+    T = (-(-(H - 10) // _METRICS_TILE[0])) * (-(-(W - 10) // _METRICS_TILE[1])) if H >= 11 and W >= 11 else 0
+    rec = 0
+    fsum = rec + B * G * _METRICS_REC
+    consts = fsum + B * _METRICS_REC
+    tiles = consts + B * 4
+    return dict(G=G, T=T, records=rec, frame_sums=fsum, consts=consts, tiles=tiles, total=tiles + 2 * B * T)
+
+
+def metrics_ws(B: int, H: int, W: int, device) -> torch.Tensor:
+    """A workspace for metrics() at this shape (float64; its owner keeps it: a captured graph holds its address)."""
+    n = _lib.load().mvsgi_metrics_ws_bytes(B, H, W)
+    if n == 0:
+        raise ValueError(f"metrics: unsupported shape (B {B}, H {H}, W {W})")
+    return torch.empty(n // 8, device=device, dtype=torch.float64)
+
+
+def metrics(preds, target, bf: float, cmin: float, cmax: float, valid_mask=None, label_range=None, thresh: float = 0.1,
+            thresh_dist: float = 0.1, range_scope: str = "frame", ws=None, out=None) -> torch.Tensor:
+    """The validation metrics of dsta_mvs/support/loss_function/metrics.py for every frame and pooled (include/mvsgi.h,
+    "validation metrics"): preds / target [B, 1, H, W] or [B, H, W] fp32 -> float64 [B + 1, 9] with METRICS_COLUMNS, row B pooled.
+    valid_mask: [B, 1, H, W] bool / uint8, or label_range = (lo, hi) on the raw target, or neither.  At most four launches on
+    preds' stream, nothing else: with `ws` (metrics_ws) and `out` given the call allocates nothing and can be captured."""
+    global METRICS_EVALUATIONS
+    preds = _dev(preds, "preds")
+    target = _dev(target, "target")
+    if preds.dim() == 4 and preds.shape[1] == 1:
+        preds = preds[:, 0]
+    if target.dim() == 4 and target.shape[1] == 1:
+        target = target[:, 0]
+    if preds.dim() != 3 or tuple(target.shape) != tuple(preds.shape):
+        raise AssertionError(f"preds and target must both be [B, 1, H, W] or [B, H, W], got {tuple(preds.shape)} and {tuple(target.shape)}")
+    B, Hh, W = (int(v) for v in preds.shape)
+    if valid_mask is not None and label_range is not None:
+        raise ValueError("metrics: a valid_mask or a label_range, not both")
+    kind, lo, hi, mptr = METRICS_MASK_NONE, 0.0, 0.0, None
+    if valid_mask is not None:
+        if valid_mask.dtype not in (torch.bool, torch.uint8):
+            raise TypeError(f"valid_mask: expected bool or uint8, got {valid_mask.dtype}")
+        if valid_mask.numel() != preds.numel() or valid_mask.device != preds.device:
+            raise AssertionError(f"valid_mask {tuple(valid_mask.shape)} on {valid_mask.device} does not match preds {tuple(preds.shape)}")
+        valid_mask = valid_mask.contiguous()
+        if valid_mask.dtype == torch.bool:
+            valid_mask = valid_mask.view(torch.uint8)
+        if valid_mask.data_ptr() % 4:
+            valid_mask = valid_mask.clone()
+        kind, mptr = METRICS_MASK_TENSOR, valid_mask.data_ptr()
+    elif label_range is not None:
+        kind, lo, hi = METRICS_MASK_RANGE, float(label_range[0]), float(label_range[1])
+    if range_scope not in METRICS_RANGE_SCOPES:
+        raise ValueError(f"range_scope: 'frame' or 'batch', got {range_scope!r}")
+    if ws is None:
+        ws = metrics_ws(B, Hh, W, preds.device)
+    elif ws.device != preds.device or not ws.is_contiguous():
+        raise AssertionError("ws must be a contiguous tensor on preds' device")
+    if out is None:
+        out = torch.empty((B + 1, len(METRICS_COLUMNS)), device=preds.device, dtype=torch.float64)
+    elif out.dtype != torch.float64 or tuple(out.shape) != (B + 1, len(METRICS_COLUMNS)) or not out.is_contiguous() \
+            or out.device != preds.device:
+        raise AssertionError(f"out must be a contiguous float64 [{B + 1}, {len(METRICS_COLUMNS)}] tensor on {preds.device}")
+    _call("mvsgi_metrics_f32", preds.data_ptr(), target.data_ptr(), mptr, kind, lo, hi, float(bf), float(cmin), float(cmax), float(thresh),
+          float(thresh_dist), METRICS_RANGE_SCOPES[range_scope], ws.data_ptr(), ws.numel() * ws.element_size(), out.data_ptr(), B, Hh, W,
+          _stream_ptr(preds))
+    METRICS_EVALUATIONS += 1
+    return out
+
+
 SA_AUTO, SA_PIXEL, SA_BAND = 0, 1, 2        # MVSGI_SA_* of include/mvsgi.h
 
 

@@ -42,7 +42,7 @@ constexpr int kVSB = 80;      // LDS bytes per staged voxel
 // x = hi + lo for four fp32 values, hi = bf16(x) (RNE), lo = bf16(x - hi), packed two per dword:
 // 2 x (v_cvt_pk_bf16_f32, shift, and, 2 v_sub_f32, v_cvt_pk_bf16_f32) VALU instructions (converting element by element
 // cost 16).  The subtraction and the blends below are SCALAR fp32 on purpose: beside the consumers' MFMAs the packed forms
-// (v_pk_add_f32 / v_pk_fma_f32, -DMVSGI_PK) are slower -- out_costs.0 2683 vs 2538 us, down.0.first 739 vs 712 us per 64 frames,
+// (v_pk_add_f32 / v_pk_fma_f32) were measured slower -- out_costs.0 2683 vs 2538 us, down.0.first 739 vs 712 us per 64 frames,
 // the step 4689 vs 4742 frames/s (tools/ab_bench.py, one box, 3 rounds; MI355X_MICROARCH.md's packed-VALU-beside-MFMA note)
 __device__ __forceinline__ void split_bf16x4(const f32x4 x, u32x2& hi, u32x2& lo) {
 #pragma unroll
@@ -51,19 +51,14 @@ __device__ __forceinline__ void split_bf16x4(const f32x4 x, u32x2& hi, u32x2& lo
         const unsigned hb = __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2));
         const f32x2 hf = {__builtin_bit_cast(float, hb << 16), __builtin_bit_cast(float, hb & 0xffff0000u)};
         hi[p] = hb;
-#ifndef MVSGI_PK
         float r0 = v[0] - hf[0], r1 = v[1] - hf[1];
         asm volatile("" : "+v"(r0));
         asm volatile("" : "+v"(r1));
         lo[p] = __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2{r0, r1}, bf16x2));
-#else
-        lo[p] = __builtin_bit_cast(unsigned, __builtin_convertvector(v - hf, bf16x2));
-#endif
     }
 }
-// a * b + c on four lanes' worth of channels: four v_fma_f32 (two v_pk_fma_f32 in the -DMVSGI_PK diagnostic build, see above)
+// a * b + c on four lanes' worth of channels: four v_fma_f32 (not two v_pk_fma_f32, see above)
 __device__ __forceinline__ f32x4 fma4(const f32x4 a, const f32x4 b, const f32x4 c) {
-#ifndef MVSGI_PK
     f32x4 r;
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
@@ -72,9 +67,6 @@ __device__ __forceinline__ f32x4 fma4(const f32x4 a, const f32x4 b, const f32x4 
         r[e] = t;
     }
     return r;
-#else
-    return __builtin_elementwise_fma(a, b, c);
-#endif
 }
 // ---- the second 16-bit split: fp16 ("f16x3") ----
 // hi = fp16(x), lo = fp16(x - hi): 11 + 11 significant bits per operand instead of bf16's 8 + 8, the same three products at the same
@@ -328,23 +320,16 @@ __device__ __forceinline__ void conv3d_x3_body(const ConvArgs& a) {
     // fragments of (nearly) a whole slice are kept in flight -- 16 / 8 buffers instead of 4.
     constexpr int WB = WLDS ? (MW * NW == 1 ? 8 : 4) :         // = XB: weight and activation fragments of a slot travel together
                        (KD == 3 && !PLANE && !V32 && MW * NW == 1) ? 16 : (KD == 3 && !PLANE && !V32 && MW * NW == 2) ? 8 :
-#ifndef MVSGI_WBX
-#define MVSGI_WBX 5      // five buffers (four slots ahead) for the 2 x 4-tile variants: 214 + 16 registers; measured against 4 and 6
-#endif
-                       (KD == 3 && !PLANE && !V32 && NW == 2 && MW == 4) ? MVSGI_WBX :
+                       (KD == 3 && !PLANE && !V32 && NW == 2 && MW == 4) ? 5 :      // five buffers (four slots ahead) for the 2 x 4-tile variants: 214 + 16 registers; measured against 4 and 6
                        NW <= 2 ? 4 : 2;      // NW = 3: three buffers (8 spilled registers) measured 2 % slower
     constexpr int LA = WB - 1;
     constexpr int NSLOT = ((kPairs + WB - 1) / WB) * WB;
     static_assert(NSLOT % WB == 0 && NSLOT >= kPairs, "pipeline geometry");
     constexpr bool RPRE = MW * NW <= 8;            // residual tiles requested during the last slot (register budget)
-    // the producers' third register set (requests three units ahead) for the small-launch variants (one or two tiles per wave): an
-    // experiment (-DMVSGI_PF3=1), measured round 6 -- 64 -> 64 on one [4, 20, 80] frame 12.9 vs 12.7 us, 128 -> 128 on [2, 10, 40]
-    // 15.2 vs 13.8 (its LDS-staged weight sets spill), the one-frame step 0.498 vs 0.482 ms: the one-frame layers are not bound by
-    // the age of their loads
-#ifndef MVSGI_PF3
-#define MVSGI_PF3 0
-#endif
-    constexpr bool PF3 = MVSGI_PF3 && KD == 3 && !UPS && !PLANE && !V32 && S == 1 && MW * NW <= 2;
+    // (a third register set for the producers of the small-launch variants, one or two tiles per wave -- requests three units ahead:
+    // a slice's MFMAs are 0.3-0.7 us, a global-load round trip 1.5-2 us, profiles/r06_b1_kernel_stats.txt -- was measured in round 6
+    // and not kept: 64 -> 64 on one [4, 20, 80] frame 12.9 vs 12.7 us, 128 -> 128 on [2, 10, 40] 15.2 vs 13.8 (its LDS-staged weight
+    // sets spill), the one-frame step 0.498 vs 0.482 ms: the one-frame layers are not bound by the age of their loads)
     // WARM (an experiment, -DMVSGI_WARM=1): in the small launches (one or two tiles per wave, weights straight from L2) the idle
     // producers pull the weight slice of the unit they are staging through L2 with LDS-DMA requests into a dummy KiB per wave, on
     // the theory that the consumers' fragment requests (LA slots = 700 cycles of MFMAs ahead) meet cold lines.  Measured round 6:
@@ -390,13 +375,9 @@ __device__ __forceinline__ void conv3d_x3_body(const ConvArgs& a) {
 #endif
     STAMP()      // kernel entry (stamp 0 of every wave; the exit stamp is its last)
 
-// digit order of a unit id above the w-tile: D before H (bricks stacked along D share halo planes and stay an XCD round apart)
-// or, in the -DMVSGI_ORDER_HD diagnostic build, H before D (round 1's order)
-#ifdef MVSGI_ORDER_HD
-#define MVSGI_DECODE_DH(T, OD, OH, B) { OH = (T % a.tiles_h) * TH; T /= a.tiles_h; OD = (T % a.tiles_d) * TD + a.od_off; B = T / a.tiles_d; }
-#else
+// digit order of a unit id above the w-tile: D before H (bricks stacked along D share halo planes and stay an XCD round apart;
+// round 1's order was H before D)
 #define MVSGI_DECODE_DH(T, OD, OH, B) { OD = (T % a.tiles_d) * TD + a.od_off; T /= a.tiles_d; OH = (T % a.tiles_h) * TH; B = T / a.tiles_h; }
-#endif
 #define MVSGI_DECODE(ID, CB, B, OD, OH, OW)                       \
     {                                                             \
         int t_ = xcd_remap((ID), total);                          \
@@ -723,43 +704,6 @@ __device__ __forceinline__ void conv3d_x3_body(const ConvArgs& a) {
         }
         STAMP()
         MVSGI_PLAN((int)blockIdx.x)
-        if constexpr (PF3) {
-            // Small launches (one or two tiles per wave: a frame to a few): a slice's MFMAs are 0.3-0.7 us, a global-load round trip
-            // 1.5-2 us, and with two register sets a step waits for loads that are ONE step old -- the step time was the load latency
-            // (profiles/r06_b1_kernel_stats.txt: 12.7-13.7 us per layer for 4-8 slices of ~0.4 us of MFMAs).  Three sets: the loads
-            // of unit u+3 go out while unit u+1, requested TWO steps ago, is split and written.
-            f32x4 preC[NIT], wpreC[WNIT];
-            (void)wpreC;
-            unsigned okC = 0;
-            (void)okC;
-            MVSGI_ISSUE(preA, okA, wpreA)                  // unit 0
-            MVSGI_PUT(preA, okA, ldsb)
-            MVSGI_WPUT(wpreA, ldsb)
-            MVSGI_ISSUE(preA, okA, wpreA)                  // unit 1 in flight (unconditional requests: see below)
-            MVSGI_ISSUE(preB, okB, wpreB)                  // unit 2 in flight
-            STAMP()
-            __syncthreads();                               // image 0 holds unit 0
-            STAMP()
-            for (int u = 0; u < U; u += 3) {
-                // A holds unit u+1, B unit u+2 (both in flight); request u+3 into C, then finish u+1
-                MVSGI_STEP(preC, okC, preA, okA, ldsb + ((u + 1) & 1) * BUFW, u + 1 < U && !(MVSGI_ABL & 8), wpreC, wpreA)
-                STAMP()
-                __syncthreads();                           // unit u multiplied, image of unit u+1 complete
-                STAMP()
-                if (u + 1 < U) {
-                    MVSGI_STEP(preA, okA, preB, okB, ldsb + ((u + 2) & 1) * BUFW, u + 2 < U && !(MVSGI_ABL & 8), wpreA, wpreB)
-                    STAMP()
-                    __syncthreads();
-                    STAMP()
-                }
-                if (u + 2 < U) {
-                    MVSGI_STEP(preB, okB, preC, okC, ldsb + ((u + 3) & 1) * BUFW, u + 3 < U && !(MVSGI_ABL & 8), wpreB, wpreC)
-                    STAMP()
-                    __syncthreads();
-                    STAMP()
-                }
-            }
-        } else {
         MVSGI_ISSUE(preA, okA, wpreA)                      // unit 0
         MVSGI_PUT(preA, okA, ldsb)
         MVSGI_WPUT(wpreA, ldsb)
@@ -782,7 +726,6 @@ __device__ __forceinline__ void conv3d_x3_body(const ConvArgs& a) {
                 __syncthreads();
                 STAMP()
             }
-        }
         }
 #undef MVSGI_ISSUE
 #undef MVSGI_WISSUE
@@ -971,11 +914,6 @@ __device__ __forceinline__ void conv3d_x3_body(const ConvArgs& a) {
         // =========================== consumers: LDS + L2 weights -> MFMA ===========================
         const int wm = wave % WM, wn = wave / WM;
         const int col = lane & 15, kg = lane >> 4;
-#ifndef MVSGI_DHW
-#define MVSGI_DHW 0      // 1: the 10 x 8 bricks' tiles as one row of BOTH planes (conflict-free fragment reads, measured 0-1.7 %: DESIGN.md section 3);
-                         // off since the depth skip (DK) wants every wave's tiles in ONE plane
-#endif
-        constexpr bool DHW = MVSGI_DHW && TW == 8 && TD == 2 && S == 1 && !PLANE && !V32 && (ITH * ITW * (kVSB / 16)) % 16 == 8;
         // BRD, the border-plane skip of the 2 x 4 x 16 bricks on 32-channel slices: a brick at the bottom of a volume (BRD = 1) spends the
         // kd = 0 taps of its plane 0 on the zero padding, a brick at the top (BRD = 2) the kd = 2 taps of its plane 1 -- a sixth of such
         // a brick's MFMAs.  Each wave owns two rows of BOTH planes (tiles 0, 1 in plane 0, tiles 2, 3 in plane 1) and the nine slots of
@@ -992,10 +930,11 @@ __device__ __forceinline__ void conv3d_x3_body(const ConvArgs& a) {
 #pragma unroll
         for (int i = 0; i < MW; ++i) {
             const int v = (wm * MW + i) * 16 + col;
-            // stride-1 two-plane bricks 8 wide: a tile is the SAME row of both planes (voxel order h, d, w) -- its halves are a plane
-            // apart (ITH * ITW * 5 sixteen-byte units = 8 mod 16 for the 10 x 8 bricks: the two halves take disjoint units of a
-            // bank row) where two rows of one plane (50 units = 2 mod 16 apart) collide on two of eight units
-            const int w_ = v % TW, h_ = BSK ? 2 * wm + (i & 1) : DHW ? v / (TW * TD) : (v / TW) % TH, d_ = BSK ? (BRD == 2 ? 1 - (i >> 1) : (i >> 1)) : DHW ? (v / TW) % TD : v / (TW * TH);
+            // (for the stride-1 two-plane bricks 8 wide, a tile as the SAME row of both planes -- voxel order h, d, w: its halves a
+            // plane apart take disjoint units of a bank row, where two rows of one plane, 50 units = 2 mod 16 apart, collide on two of
+            // eight units -- gave conflict-free fragment reads and was measured at 0-1.7 %: DESIGN.md section 3; not kept, the depth
+            // skip (DK) wants every wave's tiles in ONE plane)
+            const int w_ = v % TW, h_ = BSK ? 2 * wm + (i & 1) : (v / TW) % TH, d_ = BSK ? (BRD == 2 ? 1 - (i >> 1) : (i >> 1)) : v / (TW * TH);
             base[i] = (((d_ * SD) * ITH + h_ * S) * ITW + w_ * S) * kVSB + (kg >> 1) * 16;
         }
         // position of this lane's voxel of each tile inside the brick (unit-independent)
@@ -1004,11 +943,10 @@ __device__ __forceinline__ void conv3d_x3_body(const ConvArgs& a) {
         for (int i = 0; i < MW; ++i) {
             const int v = PLANE ? (i * TH + wm) * TW + col : (wm * MW + i) * 16 + col;     // PLANE: tile i = plane i of row wm
             twv[i] = v % TW;
-            thv[i] = BSK ? 2 * wm + (i & 1) : DHW ? v / (TW * TD) : (v / TW) % TH;
-            tdv[i] = BSK ? (BRD == 2 ? 1 - (i >> 1) : (i >> 1)) : DHW ? (v / TW) % TD : v / (TW * TH);
+            thv[i] = BSK ? 2 * wm + (i & 1) : (v / TW) % TH;
+            tdv[i] = BSK ? (BRD == 2 ? 1 - (i >> 1) : (i >> 1)) : v / (TW * TH);
         }
         if constexpr (D32 && DK < 3 && !DKU) {      // (the launcher checked a.Do == DK: one brick along D, its origin plane 0)
-            static_assert(!DHW, "depth skip: plane-pure waves");
             const int kd_lo = (TD == 2 ? wm : 0) == 0 ? 1 : 0;      // plane 0 starts at kd = 1, plane 1 of a two-plane volume at kd = 0
             wpb += kd_lo * 9 * 2048;
 #pragma unroll

@@ -26,15 +26,6 @@
 //   x = hi + lo, hi = bf16(x) (RNE), lo = bf16(x - hi): 16-17 significant bits, the same 4 B per element as fp32;
 //   the border voxels are zero and never written (the convolution's padding).
 #include "common.hpp"
-#ifndef MVSGI_RS_NT0
-#define MVSGI_RS_NT0 0       // cache policy of the 32 -> 32 layers' output stores (2 = nt: measured slower, the next layer reads them)
-#endif
-#ifndef MVSGI_RS_NT3
-#define MVSGI_RS_NT3 0       // cache policy of the polyphase layer's output stores (2 = nt: measured slower, 1742 -> 1772 us)
-#endif
-#ifndef MVSGI_RS16_NT
-#define MVSGI_RS16_NT 2      // post_vol's output stores: nt (276 -> 272 us, and the stride-2 kernel behind it 491 -> 484)
-#endif
 
 #include <cstring>
 #ifdef MVSGI_RS_STAMPS
@@ -45,6 +36,11 @@
 namespace {
 
 #include "split_fmt.hpp"       // (brings device_prims.hpp: the vector types, xcd_remap, WINDOW_DESC, LDS_DMA16)
+
+// cache policy (the aux operand of raw_buffer_store) of the output stores: 0 = default, 2 = nt
+constexpr int kRsNt0 = 0;       // the 32 -> 32 layers (nt: measured slower, the next layer reads them)
+constexpr int kRsNt3 = 0;       // the polyphase layer (nt: measured slower, 1742 -> 1772 us)
+constexpr int kRs16Nt = 2;      // post_vol: nt (276 -> 272 us, and the stride-2 kernel behind it 491 -> 484)
 
 // ---------------------------------------------------------------------------------------------
 // format conversion (module boundaries, tests): fp32 NDHWC <-> split-padded.  One thread per (voxel, 8 channels).
@@ -122,7 +118,7 @@ struct RsArgs {
     unsigned* sat;             // the range report's words (csrc/api.cpp): written when a clamp of the fp16 split engaged
 };
 
-// the split's conversions inside the generated schedules (tools/gen_rs*_schedule.py), for both kernels; RS_LRELU_MAX is LeakyReLU's
+// the split's conversions inside the generated schedules (tools/gen_rs_schedule.py), for both kernels; RS_LRELU_MAX is LeakyReLU's
 // max, RS_CLAMP the fp16 split's range clamp on a split output: one v_med3_f32 BEHIND the activation (round 5 folded the upper end
 // into the activation's max as med3(t, t * slope, 65504), which passes t unclamped when t * slope > 65504: every t > 65504 at slope 1)
 #define RS_W_LO(U) sf_widen_lo<F16>(U)
@@ -238,27 +234,26 @@ __global__ __launch_bounds__(256, 1) void conv3d_rs32_kernel(RsArgs a) {
     unsigned long long t_entry_;      // kernel entry: stamp 0 of every wave (tools/rs_stamps.py)
     asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_entry_)::"memory");
 #endif
-#ifndef MVSGI_RS_WEIGHTS_FIRST
-#define MVSGI_RS_WEIGHTS_FIRST 1      // 0: the weights behind the plans and the first image's requests (an experiment, round 6: slower)
-#endif
-#define RS_PIN_WEIGHTS()                                                                             \
-    _Pragma("unroll") for (int p = 0; p < kPairs; ++p)                                               \
-        _Pragma("unroll") for (int j = 0; j < 2; ++j) {                                              \
-            const bf16x8* q = a.wp + ((long long)((s * 2 + j) * kPairs + p) * 2) * 64 + lane;        \
-            wh[p][j] = q[0];                                                                         \
-            wl[p][j] = q[64];                                                                        \
-        }                                                                                            \
-    _Pragma("unroll") for (int p = 0; p < kPairs; ++p)                                               \
-        _Pragma("unroll") for (int j = 0; j < 2; ++j) asm volatile("" : "+a"(wh[p][j]), "+a"(wl[p][j])); \
-    __builtin_amdgcn_sched_barrier(0);
-    // ---- weights: resident in the accumulator half of the register file for the whole launch.  At one frame a workgroup lives for
-    // one or two bricks and this prologue is a fifth of it (in-kernel stamps of [8,40,160] x 1 frame, tools/rs_stamps.py 1 8 40 160,
+    // ---- weights first: resident in the accumulator half of the register file for the whole launch.  At one frame a workgroup lives
+    // for one or two bricks and this prologue is a fifth of it (in-kernel stamps of [8,40,160] x 1 frame, tools/rs_stamps.py 1 8 40 160,
     // cycles from kernel entry: weights resident 5.0-7.8 k, first image landed 8.8 k, phase 0 from 10.2 k, two phases of 6.9 k,
-    // two drain phases of 3.5 k, exit 33.9 k).  Requesting them BEHIND the first image's LDS-DMA (-DMVSGI_RS_WEIGHTS_FIRST=0) is
-    // slower: the plans (3.4 k cycles of index arithmetic) then run before any request is out instead of under the weights'
-    // 56 KiB per wave -- phase 0 from 11.9 k, exit 35.5 k ----
+    // two drain phases of 3.5 k, exit 33.9 k).  Requesting them BEHIND the first image's LDS-DMA was measured slower: the plans
+    // (3.4 k cycles of index arithmetic) then run before any request is out instead of under the weights' 56 KiB per wave --
+    // phase 0 from 11.9 k, exit 35.5 k ----
     bf16x8 wh[kPairs][2], wl[kPairs][2];
-    if constexpr (MVSGI_RS_WEIGHTS_FIRST) { RS_PIN_WEIGHTS() }
+#pragma unroll
+    for (int p = 0; p < kPairs; ++p)
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            const bf16x8* q = a.wp + ((long long)((s * 2 + j) * kPairs + p) * 2) * 64 + lane;
+            wh[p][j] = q[0];
+            wl[p][j] = q[64];
+        }
+#pragma unroll
+    for (int p = 0; p < kPairs; ++p)
+#pragma unroll
+        for (int j = 0; j < 2; ++j) asm volatile("" : "+a"(wh[p][j]), "+a"(wl[p][j]));
+    __builtin_amdgcn_sched_barrier(0);
 
     // ---- fragment read bases (image 0, HI region); group 0 = own tiles (rows 2s, 2s+1), group 1 = the partner's ----
     const int chunk = 2 * s + half;
@@ -383,8 +378,8 @@ __global__ __launch_bounds__(256, 1) void conv3d_rs32_kernel(RsArgs a) {
 #define RS_DMA(M) LDS_DMA16(dsc_x, lds + nxt_img + (wave + 4 * (M)) * 1024, voff[M], 0, 0);
 // The MFMAs are inline asm so that the weight operands can be pinned to the accumulator half of the register file
 // ("a"): hipcc keeps A/B operands of the builtin form in VGPRs and would shuttle the 224 weight registers through
-// v_accvgpr_read every brick.  hipcc pads no hazards around asm: the schedule keeps >= 3 MFMAs between an accumulator's
-// last MFMA and its first read, and nothing else reads or writes MFMA operands.
+// v_accvgpr_read every brick.  hipcc pads no hazards around asm: the schedule keeps REST MFMAs (tools/gen_rs_schedule.py)
+// between an accumulator's last MFMA and its first read, and nothing else reads or writes MFMA operands.
 #define RS_MF(ACC, WREG, XREG)                                                                                         \
     if constexpr (F16) { asm volatile("v_mfma_f32_16x16x32_f16 %0, %1, %2, %0" : "+a"(ACC) : "a"(WREG), "v"(XREG)); }  \
     else { asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0" : "+a"(ACC) : "a"(WREG), "v"(XREG)); }
@@ -417,7 +412,7 @@ __global__ __launch_bounds__(256, 1) void conv3d_rs32_kernel(RsArgs a) {
 #if MVSGI_RS_ABL & 8      // no output stores (the value is kept alive)
 #define RS_F_STORE(V, D, O) { u32x4 v_ = V; asm volatile("" ::"v"(v_)); }
 #else
-#define RS_F_STORE(V, D, O) __builtin_amdgcn_raw_buffer_store_b128(V, D, O, 0, (MODE == 3 ? MVSGI_RS_NT3 : MVSGI_RS_NT0));
+#define RS_F_STORE(V, D, O) __builtin_amdgcn_raw_buffer_store_b128(V, D, O, 0, (MODE == 3 ? kRsNt3 : kRsNt0));
 #endif
 #if MVSGI_RS_ABL & 16     // no residual requests
 #define RS_F_RES(R, D, O)
@@ -443,7 +438,7 @@ __global__ __launch_bounds__(256, 1) void conv3d_rs32_kernel(RsArgs a) {
 
 #ifdef MVSGI_RS_STAMPS
     if (a.dbg && blockIdx.x == 8) { if (lane == 0) a.dbg[wave * 256] = t_entry_; nst = 1; }
-    STAMP()      // plans made (MVSGI_RS_WEIGHTS_FIRST: weights resident too)
+    STAMP()      // weights resident, plans made
 #endif
     // prologue: image 0 <- brick 0
     {
@@ -452,7 +447,6 @@ __global__ __launch_bounds__(256, 1) void conv3d_rs32_kernel(RsArgs a) {
 #pragma unroll
         for (int m = 0; m < DPW; ++m) RS_DMA(m)
     }
-    if constexpr (!MVSGI_RS_WEIGHTS_FIRST) { RS_PIN_WEIGHTS() }
     f32x4 acc[8], keepA[4], keepB[4], snd[4];
     bf16x8 xh[2][4], xl[2][4];
     u32x4 rres[4], rresB[4], outp[4];
@@ -537,7 +531,6 @@ __global__ __launch_bounds__(256, 1) void conv3d_rs32_kernel(RsArgs a) {
 #undef RS_RES_OFF
 #undef t1
 #undef STAMP
-#undef RS_PIN_WEIGHTS
 #undef RS_MF
 #undef RS_MF0
 #undef RS_DMA
@@ -608,23 +601,19 @@ __global__ void rs16_pack_weights_kernel(const float* __restrict__ w, bf16x8* __
 
 // OSPLIT: the output goes to a split-padded tensor of the input's geometry (the hand-over to csrc/conv3d_s2rs.hip, which stages
 // pre-split voxels by LDS-DMA) instead of plain fp32 channels-last.
-// LOADERS (round 6, an experiment: -DMVSGI_RS16_LOADERS=1): the workgroup has four more waves, one per SIMD, that do nothing but issue
-// the LDS-DMA pieces of the next brick (wave 4 + r those of compute wave r).  An issuing wave sits 100-185 cycles on every 1 KiB piece
-// (with ONE wave per SIMD the 14 pieces per phase were 23 % of a phase in which the matrix pipe got nothing: 866 vs 1127 us
-// per 64 frames without the DMA); the idea was that a loader wave sits there beside a compute wave whose MFMAs keep issuing (the
-// kernel's 240 registers fit two waves per SIMD once the accumulators live in ordinary registers).  Measured, 16 frames of
-// [16, 80, 320], same box: fp32 output 278 vs 288 us, split-padded output (the product's) 329 vs 324 us with the pieces paced
-// 3 x 64 cycles apart; a burst (no pacing) and 5 x 64 are slower on both.  The stall is not hidden by a sibling wave: not kept.
-#ifndef MVSGI_RS16_LOADER_SLEEP
-#define MVSGI_RS16_LOADER_SLEEP 3      // x 64 cycles between a loader wave's pieces
-#endif
-template <bool OSPLIT, bool F16 = false, bool LOADERS = false>
-__global__ __launch_bounds__(LOADERS ? 512 : 256, 1) void conv3d_rs16_kernel(Rs16Args a) {
+// (Four more waves per workgroup, one per SIMD, that only issue the LDS-DMA pieces of the next brick were measured: an issuing wave
+// sits 100-185 cycles on every 1 KiB piece -- DESIGN.md: with ONE wave per SIMD the 14 pieces per phase were 23 % of a phase in which
+// the matrix pipe got nothing, 866 vs 1127 us per 64 frames without the DMA -- and the idea was that a loader wave sits there beside a
+// compute wave whose MFMAs keep issuing.  16 frames of [16, 80, 320], same box: fp32 output 278 vs 288 us, split-padded output (the
+// product's) 329 vs 324 us with the pieces paced 3 x 64 cycles apart; a burst and 5 x 64 were slower on both.  The stall is not
+// hidden by a sibling wave: not kept; profiles/r06_post_vol_loader_waves.txt.)
+template <bool OSPLIT, bool F16 = false>
+__global__ __launch_bounds__(256, 1) void conv3d_rs16_kernel(Rs16Args a) {
     using namespace rs16;
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
     const int tid = threadIdx.x, lane = tid & 63;
-    const int wave8 = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wave = wave8 & 3;                                      // = the brick's h-row of this wave (compute), or of its compute wave (loader)
+    // = the brick's h-row of this wave (& 3 states the range of a four-wave workgroup: the compiler folds the plans' bounds tests with it)
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6) & 3;
     const int col = lane & 15, kg = lane >> 4;
     const bool second = kg & 1;
     const int half = kg >> 1;
@@ -721,61 +710,18 @@ __global__ __launch_bounds__(LOADERS ? 512 : 256, 1) void conv3d_rs16_kernel(Rs1
         _Pragma("unroll") for (int o = 0; o < 4; ++o)                                                            \
             voy[o] = (hok_ & (int)(c1.od * TD + o < a.D) & (int)(c1.ow * TW + col < a.W)) ? voy0[o] : 0xffffff00u; \
     }
-// (LOADERS: two waves per SIMD = 256 registers per wave, which hipcc splits 128 / 128 between the two files: the 120 weight registers
-// stay in the accumulator file, the four accumulators move to ordinary registers)
 #define RS_MF(ACC, WREG, XREG)                                                                                         \
-    if constexpr (LOADERS) {                                                                                           \
-        if constexpr (F16) { asm volatile("v_mfma_f32_16x16x32_f16 %0, %1, %2, %0" : "+v"(ACC) : "a"(WREG), "v"(XREG)); }  \
-        else { asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0" : "+v"(ACC) : "a"(WREG), "v"(XREG)); }           \
-    } else if constexpr (F16) { asm volatile("v_mfma_f32_16x16x32_f16 %0, %1, %2, %0" : "+a"(ACC) : "a"(WREG), "v"(XREG)); }  \
+    if constexpr (F16) { asm volatile("v_mfma_f32_16x16x32_f16 %0, %1, %2, %0" : "+a"(ACC) : "a"(WREG), "v"(XREG)); }  \
     else { asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0" : "+a"(ACC) : "a"(WREG), "v"(XREG)); }
 // first MFMA of a brick on an accumulator: C = 0.  Declared read-write all the same ("+a"): a fresh definition would let the
 // allocator move the accumulator to other registers and reconcile with v_accvgpr_mov at the loop's back edge -- directly in
 // front of asm MFMAs whose hazards it cannot pad
 #define RS_MF0(ACC, WREG, XREG)                                                                                        \
-    if constexpr (LOADERS) {                                                                                           \
-        if constexpr (F16) { asm volatile("v_mfma_f32_16x16x32_f16 %0, %1, %2, 0" : "+v"(ACC) : "a"(WREG), "v"(XREG)); }   \
-        else { asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, 0" : "+v"(ACC) : "a"(WREG), "v"(XREG)); }            \
-    } else if constexpr (F16) { asm volatile("v_mfma_f32_16x16x32_f16 %0, %1, %2, 0" : "+a"(ACC) : "a"(WREG), "v"(XREG)); }   \
+    if constexpr (F16) { asm volatile("v_mfma_f32_16x16x32_f16 %0, %1, %2, 0" : "+a"(ACC) : "a"(WREG), "v"(XREG)); }   \
     else { asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, 0" : "+a"(ACC) : "a"(WREG), "v"(XREG)); }
 #define RS_PIN_V(V) asm volatile("" : "+v"(V));
-#define RS_F_STORE16(V, D, O) __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, V), D, O, 0, MVSGI_RS16_NT);
-#define RS16_F_SPL(...) if constexpr (OSPLIT) { __VA_ARGS__ }
-#define RS16_F_F32(...) if constexpr (!OSPLIT) { __VA_ARGS__ }
+#define RS_F_STORE16(V, D, O) __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, V), D, O, 0, kRs16Nt);
 
-    if constexpr (LOADERS) {
-        if (wave8 >= 4) {
-            // ---- a loader wave: brick 0 -> image 0, then during phase ph brick ph + 1 -> the other image; the same barriers as the
-            // compute waves (one behind the prologue, one per phase).  The image filled in phase ph was read in phase ph - 1: every
-            // compute wave passed that phase's barrier behind its last fragment read. ----
-            {
-                const auto dsc_x = RS16_DESC(c0, 1);
-                const int nxt_img = 0;
-#pragma unroll
-                for (int m = 0; m < DPW; ++m) RS16_DMA(m)
-            }
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            __builtin_amdgcn_s_barrier();
-            for (int ph = 0; ph < n; ++ph) {
-                const int nxt_img = (ph & 1) ? 0 : BUF1;
-                const auto dsc_x = RS16_DESC(nx, (int)(ph + 1 < n));
-#pragma unroll
-                for (int m = 0; m < DPW; ++m) {
-                    RS16_DMA(m)
-                    // paced over the phase (~5300 cycles): in a burst the workgroup's 56 requests queue up in the CU's address path
-                    // in front of the compute waves' fragment reads
-                    __builtin_amdgcn_s_sleep(MVSGI_RS16_LOADER_SLEEP);
-                    __builtin_amdgcn_sched_barrier(0);
-                }
-                c0 = nx;
-                RS16_STEP(nx, c0)
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                __builtin_amdgcn_s_barrier();
-            }
-            return;
-        }
-    }
-#define RS16_F_OWN(...) if constexpr (!LOADERS) { __VA_ARGS__ }
     __amdgpu_buffer_rsrc_t dsc_x, dsc_y;
     u32x2 hb0, hb1, hb2, hb3, lb0, lb1, lb2, lb3, sa0, sa1, sa2, sa3, sb0, sb1, sb2, sb3;
     f32x2 hf0, hf1, hf2, hf3;
@@ -783,13 +729,11 @@ __global__ __launch_bounds__(LOADERS ? 512 : 256, 1) void conv3d_rs16_kernel(Rs1
     hf0 = hf1 = hf2 = hf3 = f32x2{0.f, 0.f};
     unsigned voy[4] = {0xffffff00u, 0xffffff00u, 0xffffff00u, 0xffffff00u};
     dsc_y = __builtin_amdgcn_make_buffer_rsrc(a.y, 0, 0, kRawBufferFlags);
-    if constexpr (!LOADERS) {   // prologue: image 0 <- brick 0
+    {   // prologue: image 0 <- brick 0
         dsc_x = RS16_DESC(c0, 1);
         const int nxt_img = 0;
 #pragma unroll
         for (int m = 0; m < DPW; ++m) RS16_DMA(m)
-    } else {
-        dsc_x = RS16_DESC(c0, 1);
     }
     f32x4 acc[4], fin[4];
     bf16x8 xh[3][2], xl[3][2];
@@ -832,9 +776,6 @@ __global__ __launch_bounds__(LOADERS ? 512 : 256, 1) void conv3d_rs16_kernel(Rs1
 #undef RS_MF0
 #undef RS_PIN_V
 #undef RS_F_STORE16
-#undef RS16_F_SPL
-#undef RS16_F_F32
-#undef RS16_F_OWN
 }
 
 }  // namespace
@@ -1055,21 +996,14 @@ int rs16_run(const void* x, const void* w_packed_rs, const float* scale, const f
     a.total_units = (int)nb;
     MVSGI_SAT_WORDS(sat_words_);
     a.sat = sat_words_;
-    // -DMVSGI_RS16_LOADERS=1 builds the eight-wave kernel (four compute + four loader waves, LOADERS above): measured equal within
-    // +-3 % (profiles/r06_post_vol_loader_waves.txt) -- the product stays on four waves
-#ifndef MVSGI_RS16_LOADERS
-#define MVSGI_RS16_LOADERS 0
-#endif
-    constexpr bool kLoaders = MVSGI_RS16_LOADERS != 0;
     static mvsgi::PersistentGeom geo_cache[4][mvsgi::kMaxDevices] = {};
     mvsgi::PersistentGeom geo;
-    void (*kern)(Rs16Args) = fmt ? (y_is_split ? conv3d_rs16_kernel<true, true, kLoaders> : conv3d_rs16_kernel<false, true, kLoaders>)
-                                 : (y_is_split ? conv3d_rs16_kernel<true, false, kLoaders> : conv3d_rs16_kernel<false, false, kLoaders>);
-    constexpr int kThreads = kLoaders ? 512 : 256;
-    if (mvsgi::persistent_geometry(kern, kThreads, rs16::LDS_BYTES, 1, geo_cache[(y_is_split ? 1 : 0) + (fmt ? 2 : 0)], "mvsgi_conv3d_rs16_split", geo))
+    void (*kern)(Rs16Args) = fmt ? (y_is_split ? conv3d_rs16_kernel<true, true> : conv3d_rs16_kernel<false, true>)
+                                 : (y_is_split ? conv3d_rs16_kernel<true, false> : conv3d_rs16_kernel<false, false>);
+    if (mvsgi::persistent_geometry(kern, 256, rs16::LDS_BYTES, 1, geo_cache[(y_is_split ? 1 : 0) + (fmt ? 2 : 0)], "mvsgi_conv3d_rs16_split", geo))
         return 1;
     const long long resident = (long long)geo.cus / 8 * 8 > 0 ? (long long)geo.cus / 8 * 8 : 8;
-    hipLaunchKernelGGL(kern, dim3((unsigned)(nb <= resident ? nb : resident)), dim3(kThreads), rs16::LDS_BYTES, mvsgi::as_stream(stream), a);
+    hipLaunchKernelGGL(kern, dim3((unsigned)(nb <= resident ? nb : resident)), dim3(256), rs16::LDS_BYTES, mvsgi::as_stream(stream), a);
     return mvsgi::check_launch("mvsgi_conv3d_rs16_split");
 }
 }  // namespace

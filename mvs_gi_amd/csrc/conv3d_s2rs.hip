@@ -21,13 +21,11 @@
 
 #include <cstdlib>
 
-#ifndef MVSGI_S2RS_ST_AUX
-#define MVSGI_S2RS_ST_AUX 0     // cache policy bits of the output stores (2 = nt: measured neutral to slower)
-#endif
-
 namespace {
 
 #include "split_fmt.hpp"
+
+constexpr int kS2StAux = 0;     // cache policy bits of the output stores (2 = nt: measured neutral to slower)
 
 // LeakyReLU for slopes in [0, 1] as mul + max (plain asm max: __builtin_fmaxf first canonicalises an MFMA result with a third op)
 __device__ __forceinline__ float lrelu(const float v, const float slope) {
@@ -40,7 +38,7 @@ __device__ __forceinline__ float lrelu(const float v, const float slope) {
 // (windows and LDS-DMA pieces go through the FUNCTIONS of device_prims.hpp, window_desc / lds_dma16: in the kernel TEMPLATE below the
 // builtins' operands would be value-dependent, and hipcc's host pass then drops the kernel's stub without a diagnostic)
 __device__ __forceinline__ void s2_store16(const u32x4 v, const __amdgpu_buffer_rsrc_t dsc, const unsigned voff, const int soff) {
-    __builtin_amdgcn_raw_buffer_store_b128(v, dsc, voff, soff, MVSGI_S2RS_ST_AUX);
+    __builtin_amdgcn_raw_buffer_store_b128(v, dsc, voff, soff, kS2StAux);
 }
 template <bool F16>
 __device__ __forceinline__ u32x4 s2_pack_split(const f32x4 v, float& satm) {
@@ -55,10 +53,6 @@ template <bool F16>
 __device__ __forceinline__ f32x4 s2_mfma(const bf16x8 a, const bf16x8 b, const f32x4 c) {
     return sf_mfma16<F16>(a, b, c);
 }
-
-#ifndef MVSGI_S2RS_DMA_SPREAD
-#define MVSGI_S2RS_DMA_SPREAD 1
-#endif
 
 namespace s2 {
 constexpr int TW = 16;                         // outputs per tile (one row)
@@ -200,11 +194,11 @@ __global__ __launch_bounds__(256, (TH == 4 && NBUF == 2) ? 1 : 2) void conv3d_s2
         asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");    // window u landed; every wave is done with window u - 1
         // NBUF == 2: the window of brick u + 1 lands under this brick's MFMAs and the next wait.  Its pieces go out one per tap
         // pair (DPW == kPairs for TH == 4) instead of in a burst behind the barrier, where the workgroup's 56 requests queue up in
-        // the CU's address path in front of the MFMAs (MVSGI_S2RS_DMA_SPREAD=0 restores the burst: 559 vs 486 us per 64 frames).
+        // the CU's address path in front of the MFMAs (the burst was measured at 559 vs 486 us per 64 frames; bricks with more pieces than pairs keep it).
         // Four different issue points inside a pair for the four waves instead of one: 501 vs 493 us -- not kept
         const bool more = u + 1 < nmine;
         const auto dsc_n = window_desc(a.x, (long long)nb * frame_bytes + (((long long)(2 * nod) * Hp + 2 * noh) * Wp + 2 * now) * 64, total_bytes);
-        constexpr bool SPREAD = NBUF == 2 && MVSGI_S2RS_DMA_SPREAD && DPW <= kPairs;
+        constexpr bool SPREAD = NBUF == 2 && DPW <= kPairs;
         if constexpr (NBUF == 2 && !SPREAD)
             if (more) { _Pragma("unroll") for (int m = 0; m < DPW; ++m) lds_dma16(dsc_n, lds + (IMG - img) + (wave + 4 * m) * 1024, voff[m]); }
         // three accumulators per tile, one per product term: a tile's consecutive MFMAs then never wait for each other (with one

@@ -47,9 +47,6 @@ struct WinoArgs {
 
 #include "conv3d_wino_common.hpp"
 
-#ifndef WN_VCLAMP_A32
-#define WN_VCLAMP_A32 0     // (A/B builds: 1 = clamp the transform's sums on fp32-padded input too)
-#endif
 constexpr float kWinoActMax = 16376.f;     // fp32-padded activations are written clamped to this: the transform's sums of four stay inside fp16's range
 
 namespace wn {
@@ -246,7 +243,7 @@ __global__ __launch_bounds__(256, 1) void conv3d_wino32_kernel(WinoArgs a) {
             if constexpr (((r_ - 8) & 1) == 0) {                                                            \
                 X0 = b_ == 1 ? T[0][x_] + T[0][y_] : T[0][x_] - T[0][y_];                                   \
                 X1 = b_ == 1 ? T[1][x_] + T[1][y_] : T[1][x_] - T[1][y_];                                   \
-                if constexpr (!A32 || WN_VCLAMP_A32) {      /* (fp32-padded records arrive clamped to +-16376: their sums of four cannot leave fp16's range) */ \
+                if constexpr (!A32) {                       /* (fp32-padded records arrive clamped to +-16376: their sums of four cannot leave fp16's range) */ \
                     X0 = sf_clamp<true>(X0);                                                                \
                     X1 = sf_clamp<true>(X1);                                                                \
                     satm = sf_sat_acc(satm, X0, X1);        /* range report: a sum of four left fp16's range */ \

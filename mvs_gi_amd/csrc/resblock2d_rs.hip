@@ -61,18 +61,8 @@ __device__ __forceinline__ float lrelu(const float v, const float slope) {
     return r;
 }
 
-#ifndef MVSGI_RB_ST_AUX
-#define MVSGI_RB_ST_AUX 2     // cache policy bits of the output stores: nt (never re-read by this launch; 9.37 -> 9.22 ms per 32 frames)
-#endif
-#ifndef MVSGI_RB_EPI_OVERLAP
-#define MVSGI_RB_EPI_OVERLAP 1
-#endif
-#ifndef MVSGI_RB_DMA_SPREAD
-#define MVSGI_RB_DMA_SPREAD 2     // 0: all 10 pieces behind the barrier; 1: two per step over conv2's first five steps; 2: one per step
-#endif
-#ifndef MVSGI_RB_LD_AUX
-#define MVSGI_RB_LD_AUX 0     // cache policy bits of the window DMA (nt measured slower: the halos are re-read from L2)
-#endif
+constexpr int kRbStAux = 2;     // cache policy bits of the output stores: nt (never re-read by this launch; 9.37 -> 9.22 ms per 32 frames)
+constexpr int kRbLdAux = 0;     // cache policy bits of the window DMA (nt measured slower: the halos are re-read from L2)
 
 namespace rb {
 constexpr int PAD = 2;                        // border of the 2-D split-padded format
@@ -262,7 +252,7 @@ __global__ __launch_bounds__(256, 2) void resblock2d_rs_kernel(RbArgs a) {
     }
     // window of brick (n, oh0, ow0): origin = padded pixel (oh0, ow0) = image pixel (oh0 - 2, ow0 - 2)
 #define RB_DESC(N_, OH, OW) window_desc(a.x, (((long long)(N_) * Hp + (OH)) * Wp + (OW)) * 64, total_bytes)
-#define RB_PIECE(DSC, M) LDS_DMA16(DSC, lds + (wave + 4 * (M)) * 1024, voff[M], 0, MVSGI_RB_LD_AUX);
+#define RB_PIECE(DSC, M) LDS_DMA16(DSC, lds + (wave + 4 * (M)) * 1024, voff[M], 0, kRbLdAux);
 #define RB_STAGE(N_, OH, OW)                                                                                     \
     {                                                                                                            \
         const auto dsc_ = RB_DESC(N_, OH, OW);                                                                   \
@@ -327,7 +317,7 @@ __global__ __launch_bounds__(256, 2) void resblock2d_rs_kernel(RbArgs a) {
 #pragma unroll
         for (int k = 0; k < 8; ++k) acc[k] = b1;
         // the epilogue of a tile whose accumulation is complete (group 0: tiles 0 .. 3, after step 4) is written INTO the steps of
-        // group 1 (MVSGI_RB_EPI_OVERLAP): its ~25 vector instructions then sit between that step's MFMAs instead of behind the
+        // group 1: its ~25 vector instructions then sit between that step's MFMAs instead of behind the
         // whole convolution
         bf16x8 xres[7];                            // skip connection: window pixel (r + 2, c + 2) as an MFMA operand
 #define RB_EPI_A(K)                                                                                              \
@@ -344,21 +334,17 @@ __global__ __launch_bounds__(256, 2) void resblock2d_rs_kernel(RbArgs a) {
             *reinterpret_cast<u32x2*>(lds + (((K) & 1) ? wrbo : wrb) + (K) * TSTEP + REGION) = lo;               \
             if ((K) < 7) xres[(K) < 7 ? (K) : 0] = *reinterpret_cast<const bf16x8*>(lds + rres + (K) * TSTEP);   \
         }
-#if MVSGI_RB_EPI_OVERLAP
 #define RB_HOOK_A(ST) if ((ST) >= 5 && (ST) < 9) RB_EPI_A((ST) - 5)
-#else
-#define RB_HOOK_A(ST)
-#endif
         STAMP()
         RB_CONV(rbp, rbp, w1h, w1l, 4, RB_HOOK_A)
         STAMP()
 #pragma unroll
-        for (int k = MVSGI_RB_EPI_OVERLAP ? 4 : 0; k < 8; ++k) RB_EPI_A(k)
+        for (int k = 4; k < 8; ++k) RB_EPI_A(k)
 #undef RB_HOOK_A
 #undef RB_EPI_A
         STAMP()
         asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");             // conv1 result complete; every wave is done with the window
-        // the window of brick u + 1 lands under conv2.  Its 10 pieces per wave go out one per step of conv2 (MVSGI_RB_DMA_SPREAD):
+        // the window of brick u + 1 lands under conv2.  Its 10 pieces per wave go out one per step of conv2:
         // issued in one burst behind the barrier, the workgroup's 40 requests queue up in the CU's address path and every wave
         // sits ~2000 cycles in that segment (tools/rb_stamps.py): 8.95 ms per 32 frames in a burst, 8.70 two per step, 8.66 one
         const bool more = u + 1 < nmine;
@@ -389,31 +375,15 @@ __global__ __launch_bounds__(256, 2) void resblock2d_rs_kernel(RbArgs a) {
             /* masked lanes / rows get an offset beyond num_records (no scalar offset here: it would be added before the   */ \
             /* range check and wrap): no exec-mask region, so the store can sit between the MFMAs                          */ \
             const unsigned so_ = (okc && oh0 + r0 + 2 * (K) < a.H) ? vst + (unsigned)(2 * (K) * orow) : 0xffffff00u;      \
-            __builtin_amdgcn_raw_buffer_store_b128(o, dsc_o, so_, 0, MVSGI_RB_ST_AUX);                           \
+            __builtin_amdgcn_raw_buffer_store_b128(o, dsc_o, so_, 0, kRbStAux);                                  \
         }
-#if !MVSGI_RB_DMA_SPREAD
-        if (more) { _Pragma("unroll") for (int m = 0; m < DPW; ++m) RB_PIECE(dsc_n, m) }
-#define RB_DMAHOOK(ST)
-#elif MVSGI_RB_DMA_SPREAD == 2
 #define RB_DMAHOOK(ST)                                                                                           \
             {                                                                                                    \
                 __builtin_amdgcn_sched_barrier(0);                                                               \
                 if (more) { RB_PIECE(dsc_n, (ST)) }                                                              \
                 __builtin_amdgcn_sched_barrier(0);                                                               \
             }
-#else
-#define RB_DMAHOOK(ST)                                                                                           \
-            if ((ST) < DPW / 2) {                                                                                \
-                __builtin_amdgcn_sched_barrier(0);                                                               \
-                if (more) { RB_PIECE(dsc_n, 2 * (ST)) RB_PIECE(dsc_n, 2 * (ST) + 1) }                            \
-                __builtin_amdgcn_sched_barrier(0);                                                               \
-            }
-#endif
-#if MVSGI_RB_EPI_OVERLAP
 #define RB_HOOK_B(ST) RB_DMAHOOK(ST) if ((ST) >= 5 && (ST) < 9) RB_EPI_B((ST) - 5)
-#else
-#define RB_HOOK_B(ST) RB_DMAHOOK(ST)
-#endif
         // ---- phase B: conv2 on the 14 x 30 brick: 7 tiles per wave (columns 30, 31 of the right half are not stored) ----
 #pragma unroll
         for (int k = 0; k < 7; ++k) acc[k] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ident, xres[k], b2, 0, 0, 0);
@@ -421,7 +391,7 @@ __global__ __launch_bounds__(256, 2) void resblock2d_rs_kernel(RbArgs a) {
         RB_CONV(rbq, rbqo, w2h, w2l, 3, RB_HOOK_B)
         STAMP()
 #pragma unroll
-        for (int k = MVSGI_RB_EPI_OVERLAP ? 4 : 0; k < 7; ++k) RB_EPI_B(k)
+        for (int k = 4; k < 7; ++k) RB_EPI_B(k)
 #undef RB_HOOK_B
 #undef RB_DMAHOOK
 #undef RB_EPI_B
@@ -615,7 +585,7 @@ __global__ __launch_bounds__(256, 2) void conv2d_s2rs_kernel(C2sArgs a) {
                 const u32x2 sa = __builtin_amdgcn_permlane16_swap(hi[0], lo[0], false, false);
                 const u32x2 sb = __builtin_amdgcn_permlane16_swap(hi[1], lo[1], false, false);
                 if (okc && oh0 + 2 * wave + i < a.Ho)
-                    __builtin_amdgcn_raw_buffer_store_b128(u32x4{sa[0], sb[0], sa[1], sb[1]}, dsc_, vst, i * Wop * 64, MVSGI_RB_ST_AUX);
+                    __builtin_amdgcn_raw_buffer_store_b128(u32x4{sa[0], sb[0], sa[1], sb[1]}, dsc_, vst, i * Wop * 64, kRbStAux);
             }
         }
         n_ = nn; oh0 = noh; ow0 = now;

@@ -1,10 +1,11 @@
 #!/usr/bin/env python3
-"""isa_diff.py [-v] <tree A> <tree B> [name.hip ...] -- are the gfx950 kernels of two trees the same code?
+"""isa_diff.py [-v] [--rename OLD=NEW ...] <tree A> <tree B> [name.hip ...] -- are the gfx950 kernels of two trees the same code?
 
 Compiles every mvs_gi_amd/csrc/*.hip of both trees (or only the named ones) to device assembly with the flags of
 __graft_entry__, drops what differs between any two compiles (the __hip_cuid_<hash> symbol, .ident, .file) and compares
-the text kernel by kernel: instructions, labels and the .amdhsa_* resource block.  Needs no GPU.  Exit status 0 only
-when every kernel is identical and none was added or removed."""
+the text kernel by kernel: instructions, labels and the .amdhsa_* resource block.  --rename substitutes OLD by NEW in tree
+A's assembly first (a kernel whose mangled name changed, e.g. a template list that got shorter, then compares as the same
+kernel).  Needs no GPU.  Exit status 0 only when every kernel is identical and none was added or removed."""
 import glob
 import os
 import re
@@ -23,12 +24,14 @@ OTHER = "(outside kernels)"
 
 
 def assemble(job):
-    root, name, out = job
+    root, name, out, renames = job
     src = os.path.join(root, "mvs_gi_amd", "csrc", name)
     r = subprocess.run([HIPCC] + FLAGS + EXTRA_FLAGS.get(name, []) + [src, "-o", out], stderr=subprocess.PIPE, text=True)
     if r.returncode:
         sys.exit(f"{src}:\n{r.stderr}")
     text = re.sub(r"__hip_cuid_[0-9a-f]+", "__hip_cuid_", open(out).read())
+    for old, new in renames:
+        text = text.replace(old, new)
     return [ln for ln in text.splitlines() if not ln.lstrip().startswith((".ident", ".file"))]
 
 
@@ -52,13 +55,14 @@ def main(argv):
     if len(argv) < 2:
         sys.exit(__doc__)
     verbose = "-v" in argv
-    argv = [x for x in argv if x != "-v"]
+    renames = [tuple(argv[i + 1].split("=", 1)) for i, x in enumerate(argv) if x == "--rename"]
+    argv = [x for i, x in enumerate(argv) if x not in ("-v", "--rename") and (i == 0 or argv[i - 1] != "--rename")]
     a, b, only = os.path.abspath(argv[0]), os.path.abspath(argv[1]), set(argv[2:])
     files = [sorted(os.path.basename(p) for p in glob.glob(os.path.join(r, "mvs_gi_amd", "csrc", "*.hip"))
                     if not only or os.path.basename(p) in only) for r in (a, b)]
     with tempfile.TemporaryDirectory() as tmp, ThreadPoolExecutor(max_workers=min(16, os.cpu_count() or 1)) as ex:
-        jobs = [(r, n, os.path.join(tmp, f"{i}_{n}.s")) for i, r in enumerate((a, b)) for n in files[i]]
-        asm = dict(zip([(r, n) for r, n, _ in jobs], ex.map(assemble, jobs)))
+        jobs = [(r, n, os.path.join(tmp, f"{i}_{n}.s"), [] if i else renames) for i, r in enumerate((a, b)) for n in files[i]]
+        asm = dict(zip([(j[0], j[1]) for j in jobs], ex.map(assemble, jobs)))
     count, rest = {"identical": 0, "differs": 0, "added": 0, "removed": 0}, 0
     for n in sorted(set(files[0]) | set(files[1])):
         ka, kb = (kernels(asm.get((r, n), [])) for r in (a, b))

@@ -267,6 +267,24 @@ int mvsgi_softargmin_scaled_f32(const float* costs, const float* inv_idx, float*
                                 float* norm_costs, int B, int D, int H, int W, double scale,
                                 int OH, int OW, float post_div, int variant, mvsgi_stream_t stream);
 
+/* ---- confidence maps of the soft-argmin's softmax (an addition beyond the reference's interface) -------------------------
+ * Per output pixel of mvsgi_softargmin_scaled_f32 (same coordinate rule, output size floor(in * scale), zero-weight tap rule
+ * and fp32 weights), with v_d the blended cost of candidate d, m = max_d v_d, g_d = m - v_d, e_d = exp(-g_d), S = sum e_d,
+ * p_d = e_d / S and mu = sum p_d inv_idx[d]:
+ *   max_prob [B][1][OH][OW] fp32   max_d p_d = 1 / S
+ *   entropy  [B][1][OH][OW] fp32   -sum p_d ln p_d = ln S + (sum e_d g_d) / S, natural log; normalize_entropy != 0: divided by
+ *                                  ln D (D == 1: 0 either way)
+ *   spread   [B][1][OH][OW] fp32   sqrt(sum p_d (inv_idx[d] - mu)^2) / post_div: the unit of inv_dist / post_div
+ *   argmax   [B][1][OH][OW] int32  the lowest d with v_d == m; -1 where the float maps are NaN
+ * Any of the four outputs may be NULL (that map is neither computed for storing nor stored), not all of them.  One launch on
+ * `stream`, no atomics, no host synchronisation, no workspace: capturable.  A NaN or +inf cost under a non-zero weight, or
+ * every candidate -inf, gives NaN / -1 at that pixel; a single -inf candidate has p = 0 exactly.
+ * Returns non-zero (mvsgi_last_error()) on a non-finite or non-positive scale, OH / OW other than floor(H * scale),
+ * floor(W * scale) as computed here in double, post_div == 0, or four NULL outputs. */
+int mvsgi_confidence_f32(const float* costs, const float* inv_idx, float* max_prob, float* entropy,
+                         float* spread, int* argmax, int B, int D, int H, int W, double scale,
+                         int OH, int OW, float post_div, int normalize_entropy, mvsgi_stream_t stream);
+
 /* ---- layout helpers for the module boundary ------------------------------------------
  * [B][C][D*H*W] <-> [B][D*H*W][C]; V = D*H*W.  Used when a caller hands the regulator a
  * contiguous NCDHW tensor (e.g. produced by the reference's own cv_builder). */

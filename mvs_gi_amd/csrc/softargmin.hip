@@ -19,38 +19,7 @@ namespace {
 
 #include "device_prims.hpp"
 
-struct Axis2 {
-    int i0, i1;
-    float l0, l1;
-};
-
-__device__ __forceinline__ Axis2 axis2(int dst, int in, int scale) {
-    Axis2 a;
-    if (scale == 1) {
-        a.i0 = a.i1 = dst;
-        a.l0 = 1.f;
-        a.l1 = 0.f;
-        return a;
-    }
-    // F.interpolate(scale_factor=s) uses 1/s as the coordinate scale
-    float src = ((float)dst + 0.5f) * (1.0f / (float)scale) - 0.5f;
-    src = src < 0.f ? 0.f : src;
-    a.i0 = (int)src;
-    if (a.i0 > in - 1) a.i0 = in - 1;
-    a.i1 = a.i0 + (a.i0 < in - 1 ? 1 : 0);
-    a.l1 = src - (float)a.i0;
-    a.l0 = 1.0f - a.l1;
-    return a;
-}
-
-// The blend of the multi-pass forms (D > 32 per pixel, DMAX = 0 per row pair / band), which compute it once per pass (max,
-// sums, norm_costs).  Left to the compiler, each pass is contracted on its own (the scalar tail stores of norm_costs fused the
-// outer sum where the two passes before did not), and norm_costs were quotients of other exponentials than the sum holds:
-// the winner's exp(v' - m) was exp(-ulp(v)) instead of 1 -- 2e-3 low at |cost| ~ 3e4 -- and sum_d p_d missed 1 by the blend's
-// rounding (4e-6 at |cost| ~ 40) instead of the sum's (D + 2) 2^-24.  Every rounding is fixed here: all passes see one value.
-__device__ __forceinline__ float sa_blend(float ly0, float ly1, float lx0, float lx1, float a0, float a1, float b0, float b1) {
-    return fmaf(ly1, fmaf(lx1, b1, lx0 * b0), ly0 * fmaf(lx1, a1, lx0 * a0));
-}
+#include "softargmin_axes.hpp"
 
 // One output pixel of either thread-per-pixel kernel; axis(dst, in) is the coordinate rule (axis2 | axis2f).
 template <class Axis>
@@ -327,18 +296,6 @@ __global__ __launch_bounds__(DMAX == 32 ? 512 : 640) void softargmin_rows_kernel
 // mode = 'bilinear', align_corners = False, recompute_scale_factor = None): output size floor(in * s), source coordinate
 // max((dst + 0.5) * rs - 0.5, 0) with rs = 1 / s rounded to fp32 once on the host.  axis2() above is this for s = 1 | 2.
 // ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ Axis2 axis2f(int dst, int in, float rs) {
-    Axis2 a;
-    float src = ((float)dst + 0.5f) * rs - 0.5f;
-    src = src < 0.f ? 0.f : src;
-    a.i0 = (int)src;
-    if (a.i0 > in - 1) a.i0 = in - 1;
-    a.i1 = a.i0 + (a.i0 < in - 1 ? 1 : 0);
-    a.l1 = src - (float)a.i0;
-    a.l0 = 1.0f - a.l1;
-    return a;
-}
-
 // One thread per output pixel at any factor (fractional, down-scaling): softargmin_kernel with the float coordinate scale.
 // It is the correctness path; integer factors >= 3 take the row-band kernel below.
 __global__ __launch_bounds__(256) void softargmin_scaled_kernel(const float* __restrict__ costs, const float* __restrict__ inv_idx,

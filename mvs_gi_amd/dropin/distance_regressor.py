@@ -25,6 +25,17 @@ def regressor_forward(self, costs: Tensor):
     return H.softargmin(c, self.inv_dist_idx, scale, want, getattr(self, "post_div", 1.0))
 
 
+def regressor_confidence(self, costs: Tensor, want=H.CONFIDENCE_MAPS, normalize_entropy: bool = False, out=None) -> dict:
+    """Confidence maps of forward's softmax at forward's output resolution (hip_ops.confidence): costs [B, 1(+), D, H, W] ->
+    {name: [B, 1, OH, OW]} for max_prob, entropy, spread (in the unit of forward's inv_dist: divided by post_div) and argmax.
+    The same pre_interp / interp_scale_factor / post_div rule as forward; not part of the reference's interface."""
+    c = costs[:, 0]
+    scale = 1
+    if self.pre_interp and self.interp_scale_factor > 0:
+        scale = self.interp_scale_factor
+    return H.confidence(c, self.inv_dist_idx, scale, want, getattr(self, "post_div", 1.0), normalize_entropy, out)
+
+
 class DistanceRegressorWithFixedCandidates(nn.Module):
     def __init__(self, bf: float = 96, dist_cands: Sequence[float] = [0.5, 1, 1.5, 2, 5, 10, 20, 30, 50, 100],
                  interp_scale_factor: float = 0, pre_interp: bool = False):
@@ -47,3 +58,4 @@ class DistanceRegressorWithFixedCandidates(nn.Module):
         self.inv_dist_idx_max = float(torch.max(self.inv_dist_idx))
 
     forward = regressor_forward
+    confidence = regressor_confidence

@@ -123,7 +123,7 @@ def _patch_reference():
     rebind(r.UNetCostVolumeRegulator, forward=_reg.regulator_forward, takes_split=_reg.regulator_takes_split,
            forward_split_in=_reg.regulator_forward_split_in, __getstate__=gs)
     rebind(r.UNetDownBlk, forward=_reg.UNetDownBlk.forward, __getstate__=gs)
-    rebind(d.DistanceRegressorWithFixedCandidates, forward=_dr.regressor_forward)
+    rebind(d.DistanceRegressorWithFixedCandidates, forward=_dr.regressor_forward, confidence=_dr.regressor_confidence)
     rebind(c.BaseConvBlk3d, forward=_cm.BaseConvBlk3d.forward, __getstate__=gs)
     rebind(c.ResConvBlk3d, forward=_cm.ResConvBlk3d.forward)
     rebind(c.ResizeConv3d, forward=_cm.ResizeConv3d.forward)

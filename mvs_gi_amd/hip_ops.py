@@ -1179,6 +1179,61 @@ def softargmin(costs_bdhw, inv_idx, scale: float, want_norm_costs: bool, post_di
     return inv, pr
 
 
+CONFIDENCE_MAPS = ("max_prob", "entropy", "spread", "argmax")      # the order of mvsgi_confidence_f32's output pointers
+
+
+def confidence_shape(costs_shape, scale):
+    """(B, D, H, W), scale -> (scale as float, the maps' shape (B, 1, OH, OW)); raises on what F.interpolate would not take."""
+    scale = float(scale)
+    if not (math.isfinite(scale) and scale > 0):
+        raise ValueError(f"confidence: scale {scale} is not a finite positive factor")
+    B, _, H, W = (int(v) for v in costs_shape)
+    OH, OW = math.floor(H * scale), math.floor(W * scale)
+    if OH < 1 or OW < 1:
+        raise ValueError(f"confidence: scale {scale} gives an empty {OH} x {OW} output for {H} x {W}")
+    return scale, (B, 1, OH, OW)
+
+
+def confidence(costs_bdhw, inv_idx, scale: float, want=CONFIDENCE_MAPS, post_div: float = 1.0, normalize_entropy: bool = False,
+               out=None) -> dict:
+    """Confidence maps of the soft-argmin's softmax (include/mvsgi.h, mvsgi_confidence_f32):
+    costs [B, D, H, W], inv_idx [D] -> {name: [B, 1, OH, OW]} for the names in `want`, at softargmin()'s output resolution.
+    max_prob, entropy (natural log; divided by ln D with normalize_entropy) and spread (standard deviation of the candidates
+    under the softmax, divided by post_div like inv_dist) are fp32, argmax is int32 (-1 where the others are NaN).
+    want: a non-empty selection of CONFIDENCE_MAPS without repeats; only those maps are computed for storing and stored.
+    out: {name: tensor} for every wanted name, written in place and returned; the call then allocates nothing.  One launch on
+    costs' stream, no [B, D, OH, OW] tensor, capturable."""
+    want = (want,) if isinstance(want, str) else tuple(want)
+    if not want or len(set(want)) != len(want) or not set(want) <= set(CONFIDENCE_MAPS):
+        raise ValueError(f"confidence: want must be a non-empty selection of {CONFIDENCE_MAPS} without repeats, got {want!r}")
+    if not isinstance(costs_bdhw, torch.Tensor) or costs_bdhw.dim() != 4:
+        raise AssertionError("confidence: costs must be a [B, D, H, W] tensor")
+    scale, shape = confidence_shape(costs_bdhw.shape, scale)
+    if float(post_div) == 0.0:
+        raise ValueError("confidence: post_div must be non-zero")
+    if out is not None:
+        for n in want:
+            t = out.get(n)
+            dt = torch.int32 if n == "argmax" else torch.float32
+            if not isinstance(t, torch.Tensor):
+                raise TypeError(f"confidence: out[{n!r}] must be a tensor")
+            if t.dtype != dt:
+                raise TypeError(f"confidence: out[{n!r}]: expected {dt}, got {t.dtype}")
+            if tuple(t.shape) != shape or not t.is_contiguous() or t.device != costs_bdhw.device:
+                raise AssertionError(f"confidence: out[{n!r}] must be a contiguous {shape} tensor on {costs_bdhw.device}, got "
+                                     f"{tuple(t.shape)} on {t.device}")
+    c = _dev(costs_bdhw, "costs")
+    inv_idx = _dev(inv_idx.reshape(-1), "inv_dist_idx")
+    B, D, H, W = c.shape
+    if inv_idx.numel() != D:
+        raise AssertionError(f"{D} cost planes but {inv_idx.numel()} distance candidates")
+    if out is None:
+        out = {n: torch.empty(shape, device=c.device, dtype=torch.int32 if n == "argmax" else torch.float32) for n in want}
+    _call("mvsgi_confidence_f32", c.data_ptr(), inv_idx.data_ptr(), *(_ptr(out[n]) if n in want else None for n in CONFIDENCE_MAPS),
+          B, D, H, W, scale, shape[2], shape[3], float(post_div), int(bool(normalize_entropy)), _stream_ptr(c))
+    return {n: out[n] for n in want}
+
+
 def ncdhw_to_ndhwc(x) -> torch.Tensor:
     """contiguous [B, C, D, H, W] -> [B, D, H, W, C]."""
     x = _dev(x, "x")

@@ -48,11 +48,28 @@ def affine_instance_norms(module: torch.nn.Module) -> torch.nn.Module:
     return module
 
 
-class HotPath:
-    """feats -> inv_dist with the rig constants resident on the device."""
+def _confidence_selection(confidence):
+    """None, or the tuple of map names a path computes after the soft-argmin (hip_ops.CONFIDENCE_MAPS)."""
+    if confidence is None:
+        return None
+    want = (confidence,) if isinstance(confidence, str) else tuple(confidence)
+    if not want or len(set(want)) != len(want) or not set(want) <= set(H.CONFIDENCE_MAPS):
+        raise ValueError(f"confidence: None or a non-empty selection of {H.CONFIDENCE_MAPS} without repeats, got {confidence!r}")
+    return want
 
-    def __init__(self, cfg: PathConfig, weights, consts: Dict[str, np.ndarray], device="cuda"):
+
+class HotPath:
+    """feats -> inv_dist with the rig constants resident on the device.
+
+    With `confidence` (a selection of hip_ops.CONFIDENCE_MAPS) one more launch follows the soft-argmin on the same costs and
+    writes those maps into tensors that are allocated once per batch shape (by the first eager call: the warm-up of capture())
+    and exposed as `.confidence`, a dict that is valid until the next call.  Eager, inside the captured graph and on replay."""
+
+    def __init__(self, cfg: PathConfig, weights, consts: Dict[str, np.ndarray], device="cuda", confidence=None):
         self.cfg = cfg
+        self.confidence_maps = _confidence_selection(confidence)
+        self.confidence = None
+        self._conf_out = None
         self.device = torch.device(device)
         self.cv_builder, self.cv_regulator, self.dist_regressor = build_modules(cfg, weights, device)
         self.grids = torch.from_numpy(consts["grids"]).to(self.device)
@@ -85,7 +102,19 @@ class HotPath:
                 if not any(p is self._rig_views for p in pins):
                     pins.append(self._rig_views)
             _, g, gm, m = self._rig_views          # the same objects every call: the rig cache hits by identity
-        return self.dist_regressor(build_and_regulate(self.cv_builder, self.cv_regulator, feats, g, gm, m))
+        costs = build_and_regulate(self.cv_builder, self.cv_regulator, feats, g, gm, m)
+        out = self.dist_regressor(costs)
+        if self.confidence_maps is not None:
+            shape = tuple(out[0].shape)
+            if self._conf_out is None or tuple(next(iter(self._conf_out.values())).shape) != shape:
+                if torch.cuda.is_current_stream_capturing():
+                    raise RuntimeError("HotPath: the confidence maps of this batch shape are allocated by an eager call; capture() makes one")
+                # another batch shape: new tensors (a captured graph keeps its own alive, see capture())
+                self._conf_out = self.dist_regressor.confidence(costs, self.confidence_maps)
+            else:
+                self.dist_regressor.confidence(costs, self.confidence_maps, out=self._conf_out)
+            self.confidence = self._conf_out
+        return out
 
     # ---- hipGraph replay: the ~35 launches of one forward captured once, replayed per batch ----
     def capture(self, feats: torch.Tensor) -> None:
@@ -106,6 +135,7 @@ class HotPath:
         with torch.cuda.graph(graph, capture_error_mode="thread_local"):
             self._static_out = self(self._static_in)
         self._graph = graph
+        self._static_conf = self.confidence         # the tensors the graph writes (None without confidence maps)
 
     def replay(self, feats: Optional[torch.Tensor] = None):
         """Replay the captured forward; returns the graph's static output tensors
@@ -119,6 +149,7 @@ class HotPath:
                                  f"{self._static_in.dtype}, got {tuple(feats.shape)} {feats.dtype}; capture() again")
             self._static_in.copy_(feats, non_blocking=True)
         self._graph.replay()
+        self.confidence = self._static_conf
         return self._static_out
 
     def postprocess(self, inv_dist: torch.Tensor) -> np.ndarray:
@@ -225,11 +256,11 @@ class StreamedHotPath:
     instead of idling the chip (MI355X, G16V: two parts of 64 frames 5670 frames/s against 5570 for one part of 128 and 5490
     for one of 64).  capture() records the fork / join into ONE hipGraph; replay() is one submission per step."""
 
-    def __init__(self, cfg: PathConfig, weights, consts: Dict[str, np.ndarray], device="cuda", n_streams: int = 2):
+    def __init__(self, cfg: PathConfig, weights, consts: Dict[str, np.ndarray], device="cuda", n_streams: int = 2, confidence=None):
         if n_streams < 1:
             raise ValueError("n_streams must be >= 1")
         self.cfg, self.device = cfg, torch.device(device)
-        self.parts = [HotPath(cfg, weights, consts, device) for _ in range(n_streams)]
+        self.parts = [HotPath(cfg, weights, consts, device, confidence=confidence) for _ in range(n_streams)]
         self.streams = [torch.cuda.Stream(device=self.device) for _ in range(n_streams)]
 
     def _split(self, feats: torch.Tensor):
@@ -252,6 +283,13 @@ class StreamedHotPath:
             cur.wait_stream(st)                    # join
         return outs
 
+    @property
+    def confidence(self):
+        """With `confidence`: the parts' maps, one dict per part in frame order (valid until the next call); else None."""
+        if self.parts[0].confidence_maps is None:
+            return None
+        return [hp.confidence for hp in self.parts]
+
     def capture(self, feats: torch.Tensor) -> None:
         self._static_in = feats.clone()
         self(self._static_in)                       # warm-up: weight packing, rig constants, buffer allocation
@@ -265,6 +303,7 @@ class StreamedHotPath:
         with torch.cuda.graph(graph, capture_error_mode="thread_local"):
             self._static_out = self(self._static_in)
         self._graph = graph
+        self._static_conf = [hp.confidence for hp in self.parts]
 
     def replay(self, feats: Optional[torch.Tensor] = None):
         if getattr(self, "_graph", None) is None:
@@ -275,6 +314,8 @@ class StreamedHotPath:
                 raise ValueError(f"StreamedHotPath.replay(): captured for feats {tuple(self._static_in.shape)}, got {tuple(feats.shape)}")
             self._static_in.copy_(feats, non_blocking=True)
         self._graph.replay()
+        for hp, c in zip(self.parts, self._static_conf):
+            hp.confidence = c
         return self._static_out
 
 
@@ -293,10 +334,14 @@ class InferencePipeline:
     (the raw frames with samplers -- dropin.Reprojector.from_samplers --, the surrogate views otherwise) warped into the rig
     camera's view.  The results are `pipe.reprojection` = (xyz [1, 3, H, W], warped [1, N, 3, H, W], valid [1, N, H, W]),
     static tensors that are valid until the next call.  The rig's transforms and camera table are arguments of that launch, so
-    a captured graph holds their values: another rig is another Reprojector and a new capture()."""
+    a captured graph holds their values: another rig is another Reprojector and a new capture().
+
+    With `confidence` (a selection of hip_ops.CONFIDENCE_MAPS) the soft-argmin is followed by the launch that writes those maps
+    of its softmax (HotPath); `pipe.confidence` is the dict of static tensors [1, 1, H, W], valid until the next call, with
+    spread in the unit of the returned map (divided by bf)."""
 
     def __init__(self, cfg: PathConfig, weights, consts, device="cuda", extractor: str = "simple", samplers=None, raw_masks=None,
-                 reprojector=None):
+                 reprojector=None, confidence=None):
         """extractor: 'simple' = SimpleFeatExtraction (G16V, config29), 'sphere' = SphereEquirectFeatExtraction with the
         sphere-convolution final layer (G16VV, config103; configs/feature_extractor/sphereconv_featext.yaml).
         samplers / raw_masks: per-camera image samplers and raw-resolution masks; with both, consts["masks"] may be omitted
@@ -317,7 +362,7 @@ class InferencePipeline:
                 consts = dict(consts, masks=dropin.sample_masks(self.samplers, raw_masks).cpu().numpy())
         elif raw_masks is not None:
             raise ValueError("raw_masks need samplers")
-        self.hot = HotPath(cfg, weights, consts, device)
+        self.hot = HotPath(cfg, weights, consts, device, confidence=confidence)
         Hi, Wi = cfg.feat_hw
         Extractor = {"simple": dropin.SimpleFeatExtraction, "sphere": dropin.SphereEquirectFeatExtraction}[extractor]
         fe = Extractor(in_size=(4 * Hi, 4 * Wi), in_chs=3, chs=cfg.feat_chs, k_sz=3, layers=[5, 10], norm_type=cfg.norm_type)
@@ -331,6 +376,7 @@ class InferencePipeline:
         self.reprojector = reprojector
         self.reprojection = None
         self._reproj_out = None
+        self.confidence = None
         if reprojector is not None and reprojector.num_cams != cfg.num_cams:
             raise ValueError(f"the reprojector has {reprojector.num_cams} cameras, the rig {cfg.num_cams}")
 
@@ -346,6 +392,7 @@ class InferencePipeline:
         if g is not None and tuple(t.shape) == tuple(self._static_imgs.shape):
             self._static_imgs.copy_(t, non_blocking=True)          # the upload lands in the graph's input buffer
             g.replay()
+            self.confidence = self._static_conf
             out = self._static_inv.squeeze(0).squeeze(0).cpu().numpy()
         else:
             out = self.forward_device(t.to(self.hot.device)).squeeze(0).squeeze(0).cpu().numpy()
@@ -363,6 +410,7 @@ class InferencePipeline:
             imgs_u8 = H.resample_bilinear(imgs_u8, *self._table)   # fp32 [N, 3, H, W]: the fp32 RGB stem's input
         f = self.feature_extractor(imgs_u8)                        # [N, C, Hi, Wi], channels-last storage
         inv, _ = self.hot(f.unsqueeze(0))
+        self.confidence = self.hot.confidence
         if self.reprojector is not None:
             # the output buffers are made once (by the eager warm-up of capture(), outside the graph) and written in place
             r = self.reprojector.reproject(inv, frame, out=self._reproj_out)
@@ -392,6 +440,7 @@ class InferencePipeline:
         with torch.cuda.graph(graph, capture_error_mode="thread_local"):
             self._static_inv = self.forward_device(self._static_imgs)
         self._graph = graph
+        self._static_conf = self.confidence
 
     @torch.no_grad()
     def replay(self, imgs_u8: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -404,4 +453,5 @@ class InferencePipeline:
                                  f"{tuple(imgs_u8.shape)} {imgs_u8.dtype}; capture() again")
             self._static_imgs.copy_(imgs_u8, non_blocking=True)
         self._graph.replay()
+        self.confidence = self._static_conf
         return self._static_inv

@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define MVSGI_ABI_VERSION 8   /* 8: mvsgi_reproject_f32 (back-projection: point cloud and warped camera views), and, added later without a new number (an addition: older callers are unaffected, and the binding refuses a library that lacks a symbol it binds), mvsgi_metrics_f32, mvsgi_metrics_ws_bytes (validation metrics); 7: mvsgi_resample_bilinear_u8_f32, mvsgi_resample_bilinear_f32, mvsgi_resample_validity_u8, mvsgi_resample_u8_table_f32, mvsgi_rays_equirect_surrogate_f32 (fisheye -> surrogate-view resampler); 6: mvsgi_sweep_max_cams (masked-variance sweep for rigs of up to 8 cameras); 5: mvsgi_softargmin_scaled_f32 (soft-argmin at any interp_scale_factor); 4: mvsgi_instance_norm_f32, mvsgi_instance_norm_ws_bytes (norm_type 'instance'); 3: mvsgi_conv3d_d32_applies, mvsgi_conv3d_up2_d32_applies + MVSGI_CONV_BF16X3_D32; 2: mvsgi_saturation_flags; the symbol set of round 5 */
+#define MVSGI_ABI_VERSION 8   /* 8: mvsgi_reproject_f32 (back-projection: point cloud and warped camera views), and, added later without a new number (an addition: older callers are unaffected, and the binding refuses a library that lacks a symbol it binds), mvsgi_metrics_f32, mvsgi_metrics_ws_bytes (validation metrics), mvsgi_cloud_pack_f32, mvsgi_cloud_ws_bytes (packed point cloud); 7: mvsgi_resample_bilinear_u8_f32, mvsgi_resample_bilinear_f32, mvsgi_resample_validity_u8, mvsgi_resample_u8_table_f32, mvsgi_rays_equirect_surrogate_f32 (fisheye -> surrogate-view resampler); 6: mvsgi_sweep_max_cams (masked-variance sweep for rigs of up to 8 cameras); 5: mvsgi_softargmin_scaled_f32 (soft-argmin at any interp_scale_factor); 4: mvsgi_instance_norm_f32, mvsgi_instance_norm_ws_bytes (norm_type 'instance'); 3: mvsgi_conv3d_d32_applies, mvsgi_conv3d_up2_d32_applies + MVSGI_CONV_BF16X3_D32; 2: mvsgi_saturation_flags; the symbol set of round 5 */
 
 typedef void* mvsgi_stream_t;
 
@@ -609,6 +609,42 @@ size_t mvsgi_metrics_ws_bytes(int B, int H, int W);
 int mvsgi_metrics_f32(const float* preds, const float* target, const unsigned char* mask, int mask_kind, float lo, float hi,
                       float bf, float cmin, float cmax, float thresh, float thresh_dist, int range_scope, void* ws,
                       size_t ws_bytes, double* out, int B, int H, int W, mvsgi_stream_t stream);
+
+/* ---- packed point cloud (csrc/cloud.hip) --------------------------------------------------------------------------------
+ * The last stage behind the back-projection and the confidence maps: the prediction as a packed list of points, filtered and
+ * compacted on the device.  Not part of the reference's interface; defined as a composition of operations this library already
+ * has.  Per frame b, pixel (i, j) of the H x W map, linear index p = i * W + j (fp32, no contraction):
+ *     d = bf / inv[b][i][j]                 the IEEE single division of mvsgi_reproject_f32
+ *     xyz = rays[:, i, j] * d               the bits mvsgi_reproject_f32 writes to xyz[b][:, i, j]
+ * keep(b, p) holds iff all of (a comparison with a NaN is false)
+ *     1. i % sy == 0 && j % sx == 0
+ *     2. mask != 0                          when a mask is given: uint8 [H][W] (mask_per_frame = 0) or [B][H][W] (1)
+ *     3. d is finite && d_min <= d <= d_max (d_min > 0 drops inv = 0, negative, +-inf and NaN)
+ *     4. lo[k] <= gate_k[b][i][j] <= hi[k]  for each of the n_gates <= 4 gate planes [B][H][W] fp32
+ *     5. some camera n has valid[b][n][i][j] != 0          when require_colour
+ * colour of a kept point: warped[b][n*][0 .. C-1][i][j], n* the lowest camera index with valid set; when no camera is valid every
+ * channel is no_colour.  warped [B][N][C][H][W] fp32 and valid [B][N][H][W] uint8 as mvsgi_reproject_f32 writes them, both or
+ * neither (NULL; N and C are then ignored and C counts as 0), 1 <= N <= mvsgi_sweep_max_cams(), 1 <= C <= 4.
+ * attributes: A planes [B][H][W] fp32.  Record width R = 3 + C + A <= 16.
+ *   device, out:  points [B][capacity][R] fp32, records [x, y, z, c_0 .., a_0 ..]; the kept points of frame b in ascending p;
+ *                 counts [B][2] int32 = (written, kept), written = min(kept, capacity);
+ *                 index [B][capacity] int32, the source p of each record, or NULL.
+ *                 Rows >= written of points and index are not written; nothing but the outputs and ws is written.
+ *   host:         gates [n_gates] and attrs [A]: tables of DEVICE pointers; gate_lo / gate_hi [n_gates] fp32.  They are read by the
+ *                 call and travel in the kernels' arguments: no device copy, nothing to keep alive (as T_host of mvsgi_reproject_f32).
+ *   ws:           caller-owned device scratch of ws_bytes >= mvsgi_cloud_ws_bytes(B, H, W) bytes (0 = invalid dimensions), 16-byte
+ *                 aligned: one bit per pixel in 64-bit words (tiles of 1024 consecutive p, 16 words each), and per tile its number
+ *                 of kept pixels and its offset in the frame's list.
+ * Three launches (flags and tile counts; one exclusive scan per frame; scatter), no atomics, no waiting between workgroups, no host
+ * synchronisation: the same inputs give the same bits.  The predicate is evaluated once; the scatter reads its bits.  Every device
+ * pointer needs its element's alignment only (ws: 16 bytes).  H * W < 2^31, 1 <= B <= 65535, 1 <= capacity < 2^31, sy, sx >= 1. */
+size_t mvsgi_cloud_ws_bytes(long long B, int H, int W);
+int mvsgi_cloud_pack_f32(const float* inv, const float* rays, const unsigned char* mask, int mask_per_frame,
+                         const float* const* gates_host, const float* gate_lo_host, const float* gate_hi_host, int n_gates,
+                         const float* warped, const unsigned char* valid, int N, int C, int require_colour, float no_colour,
+                         const float* const* attrs_host, int A, float* points, int* counts, int* index, long long capacity,
+                         void* ws, size_t ws_bytes, long long B, int H, int W, int sy, int sx, float bf, float d_min, float d_max,
+                         mvsgi_stream_t stream);
 
 #ifdef __cplusplus
 }

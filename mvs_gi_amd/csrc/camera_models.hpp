@@ -18,6 +18,16 @@ __device__ __forceinline__ float transform_row(const float* t, float x, float y,
     return fmaf(t[2], z, fmaf(t[1], y, t[0] * x)) + t[3];
 }
 
+// Back-projection of one pixel (spherical_sweep_stereo.py:422, :435): d = bf / v (an IEEE single division), p = r * d.  The
+// fused back-projection (reproject.hip) and the point-cloud packer (cloud.hip) both call this, so a packed point is the
+// bits of xyz.  Returns d.
+__device__ __forceinline__ float back_project(float bf, float v, float rx, float ry, float rz, float& px, float& py, float& pz) {
+#pragma clang fp contract(off)
+    const float d = bf / v;
+    px = rx * d, py = ry * d, pz = rz * d;
+    return d;
+}
+
 struct DsParams {
     float xi, alpha, one_minus_alpha, fx, fy, cx, cy, wm1, hm1, neg_w2;
 };

@@ -86,10 +86,7 @@ __global__ __launch_bounds__(256) void reproject_kernel(const float* __restrict_
             }
         }
 #pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const float d = bf / v[k];
-            px[k] = rx[k] * d, py[k] = ry[k] * d, pz[k] = rz[k] * d;
-        }
+        for (int k = 0; k < 4; ++k) back_project(bf, v[k], rx[k], ry[k], rz[k], px[k], py[k], pz[k]);
     }
     if (xyz && cam == 0) {
         float* o = xyz + (b * 3) * HW + pix;

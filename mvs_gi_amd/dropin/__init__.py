@@ -8,6 +8,7 @@ from .feature_extractor import (BaseConvBlk2d, ResConvBlk2d, SimpleFeatExtractio
 from .image_sampler import (DoubleSphereToEquirectSampler, NoOpSampler, equirect_surrogate_rays, sample_masks,  # noqa: F401
                             stack_tables)
 from .reproject import Reprojector  # noqa: F401
+from .cloud import CloudPacker  # noqa: F401
 from .metrics import (Evaluator, MVSMetric, SSIMMetric, RMSEMetric, MAEMetric, BadPixelRatioMetric,  # noqa: F401
                       InverseMetricWrapper)
 from .install import install, uninstall  # noqa: F401

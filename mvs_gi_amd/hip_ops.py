@@ -11,6 +11,7 @@ import torch
 
 from . import _lib
 
+import ctypes
 import math
 import os
 
@@ -1147,6 +1148,155 @@ def metrics(preds, target, bf: float, cmin: float, cmax: float, valid_mask=None,
           _stream_ptr(preds))
     METRICS_EVALUATIONS += 1
     return out
+
+
+# the packed point cloud (csrc/cloud.hip), restated: tiles of 1024 consecutive pixels, 16 words of 64 bits each; at most 4 gates, 4 colour
+# channels and 16 floats per record
+CLOUD_TILE, CLOUD_WORDS_PER_TILE, CLOUD_MAX_GATES, CLOUD_MAX_CHANNELS, CLOUD_MAX_RECORD, CLOUD_MAX_BATCH = 1024, 16, 4, 4, 16, 65535
+# the default distance range: every positive finite d.  Its lower end is the smallest normal fp32, not 0: inv = +inf gives d = 0, which it drops
+# together with inv = 0 (d = inf), negative inv (d < 0) and NaN
+CLOUD_D_RANGE = (float(torch.finfo(torch.float32).tiny), float(torch.finfo(torch.float32).max))
+
+
+def _round16(n: int) -> int:
+    return -(-n // 16) * 16
+
+
+def cloud_ws_layout(B: int, H: int, W: int) -> dict:
+    """The workspace of pack_cloud(), in bytes: tiles per frame, 64-bit words per frame, the offsets of its three parts (bit words
+    [B, tiles, 16] uint64, tile counts [B, tiles] int32, tile offsets [B, tiles] int32) and the total.  Pure: no device, no library."""
+    B, H, W = int(B), int(H), int(W)
+    if not (1 <= B <= CLOUD_MAX_BATCH and H >= 1 and W >= 1 and H * W < 1 << 31):
+        raise ValueError(f"pack_cloud: unsupported shape (B {B}, H {H}, W {W})")
+    tiles = -(-(H * W) // CLOUD_TILE)
+    words = 0
+    counts = words + _round16(B * tiles * CLOUD_WORDS_PER_TILE * 8)
+    offsets = counts + _round16(B * tiles * 4)
+    return dict(tiles=tiles, words_per_frame=tiles * CLOUD_WORDS_PER_TILE, words=words, tile_counts=counts, tile_offsets=offsets,
+                total=offsets + _round16(B * tiles * 4))
+
+
+def cloud_ws(B: int, H: int, W: int, device) -> torch.Tensor:
+    """A workspace for pack_cloud() at this shape (int64; its owner keeps it: a captured graph holds its address)."""
+    n = _lib.load().mvsgi_cloud_ws_bytes(B, H, W)
+    if n == 0:
+        raise ValueError(f"pack_cloud: unsupported shape (B {B}, H {H}, W {W})")
+    return torch.empty(n // 8, device=device, dtype=torch.int64)
+
+
+def cloud_capacity(H: int, W: int, step=(1, 1)) -> int:
+    """The default capacity of pack_cloud(): the pixels the step leaves, ceil(H / sy) * ceil(W / sx)."""
+    return (-(-int(H) // int(step[0]))) * (-(-int(W) // int(step[1])))
+
+
+def _cloud_plane(t, name: str, shape, device, dtypes=(torch.float32,)) -> torch.Tensor:
+    """A tensor pack_cloud() reads or writes as it is: nothing is copied, so that a call with `ws` and `out` allocates nothing."""
+    if not isinstance(t, torch.Tensor):
+        raise TypeError(f"{name}: expected a torch.Tensor, got {type(t)}")
+    if not t.is_cuda:
+        raise RuntimeError(f"{name}: mvs_gi_amd runs on the GPU only (tensor is on {t.device}); there is no CPU fallback")
+    if t.dtype not in dtypes:
+        raise TypeError(f"{name}: expected {' or '.join(str(d) for d in dtypes)}, got {t.dtype}")
+    if device is not None and t.device != device:
+        raise AssertionError(f"{name}: on {t.device}, inv is on {device}")
+    if shape is not None and tuple(t.shape) != tuple(shape):
+        raise AssertionError(f"{name}: expected shape {list(shape)}, got {list(t.shape)}")
+    if not t.is_contiguous():
+        raise AssertionError(f"{name}: must be contiguous")
+    if t.data_ptr() % t.element_size():
+        raise AssertionError(f"{name}: must be aligned to its element size")
+    return t
+
+
+def pack_cloud(inv, rays, bf: float, *, d_range, gates=(), mask=None, step=(1, 1), warped=None, valid=None, require_colour: bool = False,
+               no_colour: float = 0.0, attrs=(), capacity=None, want_index: bool = False, ws=None, out=None) -> dict:
+    """The prediction as a packed list of points (include/mvsgi.h, "packed point cloud").
+    inv [B, H, W] (or [B, 1, H, W]) fp32, rays [3, H, W] fp32: d = bf / inv, xyz = rays * d, the bits of reproject()'s xyz.
+    A pixel p = i * W + j of frame b is kept iff i % sy == 0 and j % sx == 0, mask != 0 (uint8 / bool [H, W] or [B, H, W]), d is finite
+    and d_range[0] <= d <= d_range[1], lo <= g <= hi for every gate (g [B, H, W] fp32, lo, hi) -- at most CLOUD_MAX_GATES --, and,
+    with require_colour, some camera of valid [B, N, H, W] (bool / uint8) sees it.  warped [B, N, C, H, W] fp32 (C <= 4) and valid, as
+    reproject() returns them, give the colour: that of the lowest valid camera, no_colour when there is none.  attrs: planes [B, H, W]
+    fp32 appended to each record; R = 3 + C + A <= CLOUD_MAX_RECORD.
+    -> dict(points [B, capacity, R] fp32: the kept points of a frame in ascending p; counts [B, 2] int32 = (written, kept), written =
+    min(kept, capacity); index [B, capacity] int32, the source p, with want_index).  Rows >= written are not written.  capacity
+    defaults to cloud_capacity(H, W, step).  Three launches on inv's stream, no host synchronisation; with `ws` (cloud_ws) and `out`
+    (a dict of the outputs) given the call allocates nothing and can be captured.  Nothing is copied or converted: every tensor must
+    be contiguous and on inv's device.  There is no CPU fallback."""
+    if isinstance(inv, torch.Tensor) and inv.dim() == 4 and inv.shape[1] == 1:
+        inv = inv[:, 0]
+    inv = _cloud_plane(inv, "inv", None, None)
+    if inv.dim() != 3:
+        raise AssertionError(f"inv must be [B, H, W] or [B, 1, H, W], got {tuple(inv.shape)}")
+    B, Hh, W = (int(v) for v in inv.shape)
+    dev = inv.device
+    cloud_ws_layout(B, Hh, W)                                   # the shape's limits
+    rays = _cloud_plane(rays, "rays", (3, Hh, W), dev)
+    sy, sx = (int(v) for v in step)
+    if sy < 1 or sx < 1:
+        raise ValueError(f"step: (sy, sx) >= 1, got {tuple(step)}")
+    d_min, d_max = (float(v) for v in d_range)
+    gates = tuple(gates)
+    if len(gates) > CLOUD_MAX_GATES:
+        raise ValueError(f"pack_cloud: {len(gates)} gates (at most {CLOUD_MAX_GATES})")
+    gate_planes = [_cloud_plane(g, f"gates[{k}]", (B, Hh, W), dev) for k, (g, _, _) in enumerate(gates)]
+    mask_per_frame = 0
+    if mask is not None:
+        mask = _cloud_plane(mask, "mask", None, dev, (torch.uint8, torch.bool))
+        if tuple(mask.shape) not in ((Hh, W), (B, Hh, W)):
+            raise AssertionError(f"mask must be [{Hh}, {W}] or [{B}, {Hh}, {W}], got {list(mask.shape)}")
+        mask_per_frame = 1 if mask.dim() == 3 else 0
+    if (warped is None) != (valid is None):
+        raise ValueError("pack_cloud: warped and valid are given together (as reproject() returns them) or not at all")
+    N = C = 0
+    if warped is not None:
+        warped = _cloud_plane(warped, "warped", None, dev)
+        if warped.dim() != 5 or warped.shape[0] != B or tuple(warped.shape[3:]) != (Hh, W):
+            raise AssertionError(f"warped must be [{B}, N, C, {Hh}, {W}], got {list(warped.shape)}")
+        N, C = int(warped.shape[1]), int(warped.shape[2])
+        if not 1 <= N <= sweep_max_cams():
+            raise ValueError(f"pack_cloud: {N} cameras (1 ... {sweep_max_cams()} are supported)")
+        if not 1 <= C <= CLOUD_MAX_CHANNELS:
+            raise ValueError(f"pack_cloud: {C} colour channels (1 ... {CLOUD_MAX_CHANNELS} are supported)")
+        valid = _cloud_plane(valid, "valid", (B, N, Hh, W), dev, (torch.bool, torch.uint8))
+    elif require_colour:
+        raise ValueError("pack_cloud: require_colour needs warped and valid")
+    attrs = tuple(attrs)
+    attr_planes = [_cloud_plane(a, f"attrs[{m}]", (B, Hh, W), dev) for m, a in enumerate(attrs)]
+    R = 3 + C + len(attrs)
+    if R > CLOUD_MAX_RECORD:
+        raise ValueError(f"pack_cloud: a record of {R} floats (3 + {C} colour channels + {len(attrs)} attributes; at most {CLOUD_MAX_RECORD})")
+    capacity = cloud_capacity(Hh, W, (sy, sx)) if capacity is None else int(capacity)
+    if not 1 <= capacity < 1 << 31:
+        raise ValueError(f"capacity: 1 <= capacity < 2^31, got {capacity}")
+    shapes = {"points": ((B, capacity, R), torch.float32), "counts": ((B, 2), torch.int32)}
+    if want_index:
+        shapes["index"] = ((B, capacity), torch.int32)
+    if out is not None:
+        for k, (shape, dtype) in shapes.items():
+            if out.get(k) is not None:
+                _cloud_plane(out[k], f"out['{k}']", shape, dev, (dtype,))
+    if ws is not None:
+        if not isinstance(ws, torch.Tensor) or ws.device != dev or not ws.is_contiguous() or ws.data_ptr() % 16:
+            raise AssertionError(f"ws must be a contiguous, 16-byte aligned tensor on {dev}")
+    lib = _lib.load()
+    if ws is None:
+        ws = cloud_ws(B, Hh, W, dev)
+    elif ws.numel() * ws.element_size() < lib.mvsgi_cloud_ws_bytes(B, Hh, W):
+        raise AssertionError(f"ws holds {ws.numel() * ws.element_size()} bytes, this shape needs {lib.mvsgi_cloud_ws_bytes(B, Hh, W)} (cloud_ws)")
+    res = {}
+    for k, (shape, dtype) in shapes.items():
+        t = None if out is None else out.get(k)
+        res[k] = torch.empty(shape, device=dev, dtype=dtype) if t is None else t
+    P, F = ctypes.c_void_p, ctypes.c_float
+    gate_tab = (P * max(len(gates), 1))(*[g.data_ptr() for g in gate_planes])
+    lo_tab = (F * max(len(gates), 1))(*[float(lo) for _, lo, _ in gates])
+    hi_tab = (F * max(len(gates), 1))(*[float(hi) for _, _, hi in gates])
+    attr_tab = (P * max(len(attrs), 1))(*[a.data_ptr() for a in attr_planes])
+    _call("mvsgi_cloud_pack_f32", inv.data_ptr(), rays.data_ptr(), _ptr(mask), mask_per_frame, gate_tab, lo_tab, hi_tab, len(gates),
+          _ptr(warped), _ptr(valid), N, C, 1 if require_colour else 0, float(no_colour), attr_tab, len(attrs), res["points"].data_ptr(),
+          res["counts"].data_ptr(), _ptr(res.get("index")), capacity, ws.data_ptr(), ws.numel() * ws.element_size(), B, Hh, W, sy, sx,
+          float(bf), d_min, d_max, _stream_ptr(inv))
+    return res
 
 
 SA_AUTO, SA_PIXEL, SA_BAND = 0, 1, 2        # MVSGI_SA_* of include/mvsgi.h

@@ -5,6 +5,7 @@ inv_dist / bf post-processing.  Used by bench.py, the tests and __graft_entry__.
 """
 from __future__ import annotations
 
+import math
 from typing import Dict, Optional
 
 import numpy as np
@@ -338,15 +339,31 @@ class InferencePipeline:
 
     With `confidence` (a selection of hip_ops.CONFIDENCE_MAPS) the soft-argmin is followed by the launch that writes those maps
     of its softmax (HotPath); `pipe.confidence` is the dict of static tensors [1, 1, H, W], valid until the next call, with
-    spread in the unit of the returned map (divided by bf)."""
+    spread in the unit of the returned map (divided by bf).
+
+    With `cloud` (a dropin.CloudPacker at the output resolution, bf = 1) the last stage packs the frame's point cloud: three more
+    launches behind the back-projection, in forward_device and inside the captured graph.  Its gates and attributes are maps that
+    `confidence` selects, its colours the reprojector's warped views.  `pipe.cloud` is the dict of the packer's static tensors
+    (points, counts, index), valid until the next call; dropin.CloudPacker.to_host reads it out."""
 
     def __init__(self, cfg: PathConfig, weights, consts, device="cuda", extractor: str = "simple", samplers=None, raw_masks=None,
-                 reprojector=None, confidence=None):
+                 reprojector=None, confidence=None, cloud=None):
         """extractor: 'simple' = SimpleFeatExtraction (G16V, config29), 'sphere' = SphereEquirectFeatExtraction with the
         sphere-convolution final layer (G16VV, config103; configs/feature_extractor/sphereconv_featext.yaml).
         samplers / raw_masks: per-camera image samplers and raw-resolution masks; with both, consts["masks"] may be omitted
         (it is dropin.sample_masks(samplers, raw_masks))."""
         self.cfg = cfg
+        if cloud is not None:          # before anything touches a device
+            if cloud.colour and reprojector is None:
+                raise ValueError("cloud: the packer colours its points and there is no reprojector to warp the camera views")
+            missing = [n for n in cloud.maps if n not in (_confidence_selection(confidence) or ())]
+            if missing:
+                raise ValueError(f"cloud: the packer's gates / attributes {missing} are not among the maps confidence= selects")
+            out_hw = (math.floor(cfg.cv_hw[0] * cfg.interp_scale_factor), math.floor(cfg.cv_hw[1] * cfg.interp_scale_factor))
+            if tuple(cloud.out_shape) != out_hw:
+                raise ValueError(f"cloud: the packer's out_shape {tuple(cloud.out_shape)} is not the output's {out_hw}")
+        self.cloud_packer = cloud
+        self.cloud = None
         self.samplers = None
         if samplers is not None:
             if len(samplers) != cfg.num_cams:
@@ -393,6 +410,7 @@ class InferencePipeline:
             self._static_imgs.copy_(t, non_blocking=True)          # the upload lands in the graph's input buffer
             g.replay()
             self.confidence = self._static_conf
+            self.cloud = self._static_cloud
             out = self._static_inv.squeeze(0).squeeze(0).cpu().numpy()
         else:
             out = self.forward_device(t.to(self.hot.device)).squeeze(0).squeeze(0).cpu().numpy()
@@ -416,6 +434,11 @@ class InferencePipeline:
             r = self.reprojector.reproject(inv, frame, out=self._reproj_out)
             self._reproj_out = r
             self.reprojection = (r["xyz"], r["warped"], r["valid"])
+        if self.cloud_packer is not None:
+            # the packer's buffers are made once too (it owns them per shape) and written in place
+            colour = self.cloud_packer.colour
+            self.cloud = self.cloud_packer.pack(inv, confidence=self.confidence, warped=r["warped"] if colour else None,
+                                                valid=r["valid"] if colour else None)
         return inv
 
     # ---- hipGraph replay of the whole chain for one frame (the robot's operating point: one frame at a time) ----
@@ -441,6 +464,7 @@ class InferencePipeline:
             self._static_inv = self.forward_device(self._static_imgs)
         self._graph = graph
         self._static_conf = self.confidence
+        self._static_cloud = self.cloud
 
     @torch.no_grad()
     def replay(self, imgs_u8: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -454,4 +478,5 @@ class InferencePipeline:
             self._static_imgs.copy_(imgs_u8, non_blocking=True)
         self._graph.replay()
         self.confidence = self._static_conf
+        self.cloud = self._static_cloud
         return self._static_inv

@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define MVSGI_ABI_VERSION 8   /* 8: mvsgi_reproject_f32 (back-projection: point cloud and warped camera views), and, added later without a new number (an addition: older callers are unaffected, and the binding refuses a library that lacks a symbol it binds), mvsgi_metrics_f32, mvsgi_metrics_ws_bytes (validation metrics), mvsgi_cloud_pack_f32, mvsgi_cloud_ws_bytes (packed point cloud); 7: mvsgi_resample_bilinear_u8_f32, mvsgi_resample_bilinear_f32, mvsgi_resample_validity_u8, mvsgi_resample_u8_table_f32, mvsgi_rays_equirect_surrogate_f32 (fisheye -> surrogate-view resampler); 6: mvsgi_sweep_max_cams (masked-variance sweep for rigs of up to 8 cameras); 5: mvsgi_softargmin_scaled_f32 (soft-argmin at any interp_scale_factor); 4: mvsgi_instance_norm_f32, mvsgi_instance_norm_ws_bytes (norm_type 'instance'); 3: mvsgi_conv3d_d32_applies, mvsgi_conv3d_up2_d32_applies + MVSGI_CONV_BF16X3_D32; 2: mvsgi_saturation_flags; the symbol set of round 5 */
+#define MVSGI_ABI_VERSION 8   /* 8: mvsgi_reproject_f32 (back-projection: point cloud and warped camera views), and, added later without a new number (an addition: older callers are unaffected, and the binding refuses a library that lacks a symbol it binds), mvsgi_metrics_f32, mvsgi_metrics_ws_bytes (validation metrics), mvsgi_cloud_pack_f32, mvsgi_cloud_ws_bytes (packed point cloud), mvsgi_losses_f32, mvsgi_losses_ws_bytes (loss functions); 7: mvsgi_resample_bilinear_u8_f32, mvsgi_resample_bilinear_f32, mvsgi_resample_validity_u8, mvsgi_resample_u8_table_f32, mvsgi_rays_equirect_surrogate_f32 (fisheye -> surrogate-view resampler); 6: mvsgi_sweep_max_cams (masked-variance sweep for rigs of up to 8 cameras); 5: mvsgi_softargmin_scaled_f32 (soft-argmin at any interp_scale_factor); 4: mvsgi_instance_norm_f32, mvsgi_instance_norm_ws_bytes (norm_type 'instance'); 3: mvsgi_conv3d_d32_applies, mvsgi_conv3d_up2_d32_applies + MVSGI_CONV_BF16X3_D32; 2: mvsgi_saturation_flags; the symbol set of round 5 */
 
 typedef void* mvsgi_stream_t;
 
@@ -609,6 +609,51 @@ size_t mvsgi_metrics_ws_bytes(int B, int H, int W);
 int mvsgi_metrics_f32(const float* preds, const float* target, const unsigned char* mask, int mask_kind, float lo, float hi,
                       float bf, float cmin, float cmax, float thresh, float thresh_dist, int range_scope, void* ws,
                       size_t ws_bytes, double* out, int B, int H, int W, mvsgi_stream_t stream);
+
+/* ---- loss functions (csrc/losses.hip) -------------------------------------------------------------------------------------
+ * dsta_mvs/support/loss_function/distance_loss.py: the forward values of VolumeCrossEntropy (:21-48), MaskedSmoothL1Loss (:59-70, the
+ * shape[1] == 1 branch) and InBoundsBCEDistanceLoss (:86-105, likewise) for every frame of a batch and pooled, in one reduce and one
+ * finalise launch, without atomics: the same inputs give the same bits.  No gradients.  fp32 without contraction per element; the
+ * sums are float64, compensated (the sum of the fp32 addends to ~2^-100 relative, rounded once), the means float64.
+ * labels [B][OH][OW] fp32: the true inverse distance L.  inv_list [D] fp32, D >= 2 (read for vol and true_cost only): list = bf / dist_list as the caller's fp32
+ * division gives it, strictly decreasing (dist_list strictly increasing and positive; the caller checks, a zero bin width has no meaning).
+ *   vol        x = clamp(L, list[D-1], list[0]) (torch.clamp: a NaN stays);  bin = clamp(D - #{d: list[d] < x} - 1, 0, D - 2)
+ *              (len(list) - torch.bucketize(x, flipped list) - 1);  d = (x - list[bin]) / (list[bin+1] - list[bin]);
+ *              t[bin] = 1 - d, t[bin+1] = d, t = 0 elsewhere;  per selected element (b, c, i, j) the addend
+ *              (t - 1) * max(log1pf(-p), -100) - t * max(logf(p), -100)  (ATen's binary_cross_entropy);  vol = sum / n_vol (n_vol = 0: NaN).
+ *              p_kind MVSGI_LOSSES_P_GIVEN: p = probs[b][c][i][j], probs [B][D][OH][OW] (the regressor's norm_costs, or any probabilities);
+ *              MVSGI_LOSSES_P_FUSED: probs is the low-resolution cost volume [B][D][H][W] and p the soft-argmin's softmax at the
+ *              output pixel, as mvsgi_confidence_f32 defines it: v_c the blend of mvsgi_softargmin_scaled_f32 (same coordinate rule,
+ *              OH = floor(H * scale), OW = floor(W * scale), zero-weight-tap rule), m = max_c v_c, e_c = expf(-(m - v_c)), S = sum e_c in
+ *              order of c, p_c = e_c / S; no [B][D][OH][OW] tensor is read or written.  MVSGI_LOSSES_P_NONE: no volume loss
+ *              (columns vol and n_vol NaN); H, W and scale are read in the fused kind only.
+ *              Selection: vol_kind MVSGI_LOSSES_VOL_NONE every element; _PIXEL vol_mask [B][OH][OW] bytes, a pixel counts D times;
+ *              _VOLUME vol_mask [B][D][OH][OW] bytes.  A select: an unselected element never reaches the sum.
+ *   true_cost  optional output [B][D][OH][OW] fp32: t for every element, selected or not; null: not written.
+ *   smooth_l1  pred [B][OH][OW] fp32 (null: columns smooth_l1 and inbounds NaN): z = |pred - L|, addend z < 1 ? 0.5 * z * z : z - 0.5
+ *              over the selected pixels, / n_px.  Selection: px_kind MVSGI_LOSSES_PX_NONE every pixel; _TENSOR px_mask [B][OH][OW]
+ *              bytes; _LABEL_MAX L <= label_max (the training step masks labels above 191).
+ *   inbounds   (inbounds != 0, else NaN) in(v) = v < near_inv && v > far_inv on the raw pred and L, near_inv = fl32(1 / near_dist_threshold),
+ *              far_inv = fl32(1 / far_dist_threshold); BCELoss on {0, 1} values with its -100 clamp is 100 * #{in(pred) != in(L)} / n_px
+ *              over the selected pixels.
+ * out: [B + 1][5] float64, columns vol, smooth_l1, inbounds, n_vol, n_px.  Row b < B depends on frame b alone; row B: sums and
+ * counts added over the frames in frame order (what one call of the reference's class on the batch computes).
+ * ws: caller-owned device scratch of ws_bytes >= mvsgi_losses_ws_bytes(B, OH, OW) bytes (0 = invalid dimensions), 8-byte aligned;
+ * B < 65535.  With ws and out supplied nothing is allocated and the call can be captured into a hipGraph. */
+#define MVSGI_LOSSES_P_NONE       0
+#define MVSGI_LOSSES_P_GIVEN      1
+#define MVSGI_LOSSES_P_FUSED      2
+#define MVSGI_LOSSES_VOL_NONE     0
+#define MVSGI_LOSSES_VOL_PIXEL    1
+#define MVSGI_LOSSES_VOL_VOLUME   2
+#define MVSGI_LOSSES_PX_NONE      0
+#define MVSGI_LOSSES_PX_TENSOR    1
+#define MVSGI_LOSSES_PX_LABEL_MAX 2
+size_t mvsgi_losses_ws_bytes(int B, int OH, int OW);
+int mvsgi_losses_f32(const float* labels, const float* pred, const float* probs, int p_kind, const float* inv_list,
+                     const unsigned char* vol_mask, int vol_kind, const unsigned char* px_mask, int px_kind, float label_max,
+                     int inbounds, float near_inv, float far_inv, float* true_cost, void* ws, size_t ws_bytes, double* out,
+                     int B, int D, int H, int W, double scale, int OH, int OW, mvsgi_stream_t stream);
 
 /* ---- packed point cloud (csrc/cloud.hip) --------------------------------------------------------------------------------
  * The last stage behind the back-projection and the confidence maps: the prediction as a packed list of points, filtered and

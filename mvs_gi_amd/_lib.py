@@ -133,6 +133,9 @@ SIGNATURES = {
     "mvsgi_instance_norm_f32": (c_int, [_P] * 6 + [c_int] * 3 + [c_float, c_float, _P]),
     "mvsgi_metrics_ws_bytes": (c_size_t, [c_int] * 3),
     "mvsgi_metrics_f32": (c_int, [_P, _P, _P, c_int] + [c_float] * 7 + [c_int, _P, c_size_t, _P] + [c_int] * 3 + [_P]),
+    "mvsgi_losses_ws_bytes": (c_size_t, [c_int] * 3),
+    "mvsgi_losses_f32": (c_int, [_P, _P, _P, c_int, _P, _P, c_int, _P, c_int, c_float, c_int, c_float, c_float, _P, _P, c_size_t, _P] +
+                         [c_int] * 4 + [c_double, c_int, c_int, _P]),
     "mvsgi_cloud_ws_bytes": (c_size_t, [c_longlong, c_int, c_int]),
     "mvsgi_cloud_pack_f32": (c_int, [_P, _P, _P, c_int, _P, _P, _P, c_int, _P, _P, c_int, c_int, c_int, c_float, _P, c_int, _P, _P, _P,
                                      c_longlong, _P, c_size_t, c_longlong] + [c_int] * 4 + [c_float] * 3 + [_P]),

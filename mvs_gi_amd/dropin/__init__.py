@@ -11,4 +11,6 @@ from .reproject import Reprojector  # noqa: F401
 from .cloud import CloudPacker  # noqa: F401
 from .metrics import (Evaluator, MVSMetric, SSIMMetric, RMSEMetric, MAEMetric, BadPixelRatioMetric,  # noqa: F401
                       InverseMetricWrapper)
+from .losses import (LossEvaluator, VolumeCrossEntropy, MaskedSmoothL1Loss, InBoundsBCEDistanceLoss,  # noqa: F401
+                     NearFocusDistanceLoss)
 from .install import install, uninstall  # noqa: F401

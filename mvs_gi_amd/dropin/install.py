@@ -8,7 +8,8 @@ Two situations:
    dsta_mvs.model.cost_volume_regulator[.unet_regulator],
    dsta_mvs.model.distance_regressor[.distance_regressor],
    dsta_mvs.model.common[.common_modules], dsta_mvs.model.mvs_model.torch_only,
-   dsta_mvs.support.loss_function[.metrics]: the validation metrics, which the checkpoints pickle too),
+   dsta_mvs.support.loss_function[.metrics|.distance_loss]: the validation metrics and the loss functions, which the
+   checkpoints pickle too),
   so that checkpoints which pickle whole module objects
   (spherical_sweep_stereo.py:74; consumers api/inference_pytorch.py:87-101,
   dsta_mvs/test/utils.py:221-230) unpickle into the drop-in classes;
@@ -30,9 +31,11 @@ from . import distance_regressor as _dr
 from . import torch_only as _to
 from . import feature_extractor as _fe
 from . import metrics as _met
+from . import losses as _loss
 
 _ALIAS_FLAG = "__mvsgi_alias__"
 _METRIC_CLASSES = ["MVSMetric", "SSIMMetric", "RMSEMetric", "MAEMetric", "BadPixelRatioMetric", "InverseMetricWrapper"]
+_LOSS_CLASSES = ["VolumeCrossEntropy", "MaskedSmoothL1Loss", "InBoundsBCEDistanceLoss", "NearFocusDistanceLoss"]
 _state = {"mode": None, "saved": []}
 
 
@@ -93,6 +96,9 @@ def _install_aliases():
     _export(lf, _met, _METRIC_CLASSES)
     mods.update({"dsta_mvs.support": support, "dsta_mvs.support.loss_function": lf})
     lf.metrics = leaf("dsta_mvs.support.loss_function.metrics", _met)
+    # the loss functions (configs/base_model.yaml:83-92, configs/loss/*.yaml: dsta_mvs.support.loss_function.<Class>)
+    _export(lf, _loss, _LOSS_CLASSES)
+    lf.distance_loss = leaf("dsta_mvs.support.loss_function.distance_loss", _loss)
     root.support, support.loss_function = support, lf
     root.model = model
     model.common, model.cost_volume_builder, model.cost_volume_regulator = common, cvb, reg
@@ -153,6 +159,16 @@ def _patch_reference():
         for n in ("SSIMMetric", "RMSEMetric", "MAEMetric", "BadPixelRatioMetric"):
             rebind(getattr(lm, n), forward=_met.metric_forward, __getstate__=gs)
         rebind(lm.InverseMetricWrapper, forward=_met.inverse_forward)
+    # the loss functions' forward values: the module itself imports torch alone, its package's __init__ pulls in the metrics
+    try:
+        dl = importlib.import_module("dsta_mvs.support.loss_function.distance_loss")
+    except Exception:
+        dl = None
+    if dl is not None:
+        rebind(dl.VolumeCrossEntropy, forward=_loss.volume_forward, __getstate__=gs)
+        rebind(dl.MaskedSmoothL1Loss, forward=_loss.smooth_l1_forward, __getstate__=gs)
+        rebind(dl.InBoundsBCEDistanceLoss, forward=_loss.inbounds_forward, __getstate__=gs)
+        rebind(dl.NearFocusDistanceLoss, forward=_loss.near_focus_forward)
     _state["saved"] = saved
 
 

@@ -1150,6 +1150,152 @@ def metrics(preds, target, bf: float, cmin: float, cmax: float, valid_mask=None,
     return out
 
 
+LOSSES_COLUMNS = ("vol", "smooth_l1", "inbounds", "n_vol", "n_px")
+LOSSES_P_NONE, LOSSES_P_GIVEN, LOSSES_P_FUSED = 0, 1, 2                      # MVSGI_LOSSES_P_* of include/mvsgi.h
+LOSSES_VOL_NONE, LOSSES_VOL_PIXEL, LOSSES_VOL_VOLUME = 0, 1, 2              # MVSGI_LOSSES_VOL_*
+LOSSES_PX_NONE, LOSSES_PX_TENSOR, LOSSES_PX_LABEL_MAX = 0, 1, 2             # MVSGI_LOSSES_PX_*
+LOSSES_EVALUATIONS = 0        # calls of mvsgi_losses_f32 by this process
+# the slab of csrc/losses.hip, restated: a reduce block per 256 pixels of a frame (at most 256), 8 doubles per record
+_LOSSES_REC, _LOSSES_PIX_PER_BLOCK, _LOSSES_MAX_BLOCKS = 8, 256, 256
+
+
+def losses_ws_layout(B: int, OH: int, OW: int) -> dict:
+    """The workspace of losses(), in doubles: offsets of its two parts and the reduce blocks per frame G."""
+    G = min(max(-(-(OH * OW) // _LOSSES_PIX_PER_BLOCK), 1), _LOSSES_MAX_BLOCKS)
+    fsum = B * G * _LOSSES_REC
+    return dict(G=G, records=0, frame_sums=fsum, total=fsum + B * _LOSSES_REC)
+
+
+def losses_ws(B: int, OH: int, OW: int, device) -> torch.Tensor:
+    """A workspace for losses() at this output shape (float64; its owner keeps it: a captured graph holds its address)."""
+    n = _lib.load().mvsgi_losses_ws_bytes(B, OH, OW)
+    if n == 0:
+        raise ValueError(f"losses: unsupported shape (B {B}, OH {OH}, OW {OW})")
+    return torch.empty(n // 8, device=device, dtype=torch.float64)
+
+
+def _image(t, name: str):
+    """[B, 1, H, W] or [B, H, W] fp32 on the device -> contiguous [B, H, W]"""
+    t = _dev(t, name)
+    if t.dim() == 4 and t.shape[1] == 1:
+        t = t[:, 0]
+    if t.dim() != 3:
+        raise AssertionError(f"{name} must be [B, 1, H, W] or [B, H, W], got {tuple(t.shape)}")
+    return t
+
+
+def _byte_mask(m, name: str, shape, device):
+    if not isinstance(m, torch.Tensor):
+        raise TypeError(f"{name}: expected a torch.Tensor, got {type(m)}")
+    if m.dtype not in (torch.bool, torch.uint8):
+        raise TypeError(f"{name}: expected bool or uint8, got {m.dtype}")
+    if tuple(m.shape) != tuple(shape) or m.device != device:
+        raise AssertionError(f"{name} {tuple(m.shape)} on {m.device} must be {tuple(shape)} on {device}")
+    m = m.contiguous()
+    return m.view(torch.uint8) if m.dtype == torch.bool else m
+
+
+def _inv_list(inv_idx, device):
+    inv_idx = _dev(inv_idx.reshape(-1), "inv_dist_idx")
+    if inv_idx.numel() < 2:
+        raise ValueError(f"losses: D = {inv_idx.numel()}: the volume labels need at least two candidates")
+    if inv_idx.device != device:
+        raise AssertionError(f"inv_dist_idx is on {inv_idx.device}, the labels on {device}")
+    return inv_idx
+
+
+def losses(labels, inv_idx=None, pred=None, pred_cost=None, costs=None, scale=None, vol_mask=None, px_mask=None, label_max=None,
+           inbounds=None, true_cost=None, ws=None, out=None) -> torch.Tensor:
+    """The forward values of dsta_mvs/support/loss_function/distance_loss.py for every frame and pooled (include/mvsgi.h, "loss
+    functions") -> float64 [B + 1, 5] with LOSSES_COLUMNS, row B pooled.
+    labels [B, 1, OH, OW] or [B, OH, OW] fp32; inv_idx [D] fp32 = bf / dist_list, strictly decreasing (the caller's to check: the
+    drop-in layer raises ValueError on a list that is not); None where only the image losses are wanted.
+    vol (VolumeCrossEntropy): on pred_cost [B, D, OH, OW] (given probabilities), or on the low-resolution costs [B, D, H, W] with the
+    regressor's scale (the soft-argmin's softmax, never stored); neither: NaN.  vol_mask: [B, 1, OH, OW] (a pixel across all D) or
+    [B, D, OH, OW], bool / uint8.
+    smooth_l1 (MaskedSmoothL1Loss) and inbounds (InBoundsBCEDistanceLoss, inbounds = (near_inv, far_inv) as the fp32 thresholds) on
+    pred [B, 1, OH, OW]; no pred: NaN.  px_mask [B, 1, OH, OW] bool / uint8, or label_max (labels <= label_max), not both.
+    true_cost: an fp32 [B, D, OH, OW] tensor to receive the two-hot labels, or None.
+    Two launches on labels' stream, nothing else: with `ws` (losses_ws) and `out` given the call allocates nothing and can be
+    captured."""
+    global LOSSES_EVALUATIONS
+    labels = _image(labels, "labels")
+    B, OH, OW = (int(v) for v in labels.shape)
+    dev = labels.device
+    if inv_idx is None:
+        if pred_cost is not None or costs is not None or true_cost is not None:
+            raise ValueError("losses: the volume loss and its labels need inv_idx")
+        D = 0
+    else:
+        inv_idx = _inv_list(inv_idx, dev)
+        D = inv_idx.numel()
+    if pred is not None:
+        pred = _image(pred, "pred")
+        if tuple(pred.shape) != (B, OH, OW) or pred.device != dev:
+            raise AssertionError(f"pred {tuple(pred.shape)} on {pred.device} does not match labels {(B, OH, OW)} on {dev}")
+    if pred_cost is not None and costs is not None:
+        raise ValueError("losses: pred_cost (given probabilities) or costs (the fused softmax), not both")
+    p_kind, probs, Hh, W, sc = LOSSES_P_NONE, None, OH, OW, 1.0
+    if pred_cost is not None:
+        probs = _dev(pred_cost, "pred_cost")
+        if tuple(probs.shape) != (B, D, OH, OW) or probs.device != dev:
+            raise AssertionError(f"pred_cost {tuple(probs.shape)} on {probs.device} must be {(B, D, OH, OW)} on {dev}")
+        p_kind = LOSSES_P_GIVEN
+    elif costs is not None:
+        if not isinstance(costs, torch.Tensor) or costs.dim() != 4:
+            raise AssertionError("losses: costs must be a [B, D, H, W] tensor")
+        sc, shape = confidence_shape(costs.shape, 1.0 if scale is None else scale)
+        probs = _dev(costs, "costs")
+        if int(probs.shape[0]) != B or int(probs.shape[1]) != D or probs.device != dev:
+            raise AssertionError(f"costs {tuple(probs.shape)} on {probs.device} must be [{B}, {D}, H, W] on {dev}")
+        if shape[2:] != (OH, OW):
+            raise AssertionError(f"costs {tuple(probs.shape)} at scale {sc} give {shape[2]} x {shape[3]}, the labels are {OH} x {OW}")
+        Hh, W = int(probs.shape[2]), int(probs.shape[3])
+        p_kind = LOSSES_P_FUSED
+    vol_kind, vptr = LOSSES_VOL_NONE, None
+    if vol_mask is not None:
+        pixel = isinstance(vol_mask, torch.Tensor) and vol_mask.dim() == 4 and vol_mask.shape[1] == 1
+        vol_mask = _byte_mask(vol_mask, "vol_mask", (B, 1 if pixel else D, OH, OW), dev)
+        vol_kind, vptr = (LOSSES_VOL_PIXEL if pixel else LOSSES_VOL_VOLUME), vol_mask.data_ptr()
+    if px_mask is not None and label_max is not None:
+        raise ValueError("losses: a px_mask or a label_max, not both")
+    px_kind, pptr, hi = LOSSES_PX_NONE, None, 0.0
+    if px_mask is not None:
+        px_mask = _byte_mask(px_mask, "px_mask", (B, 1, OH, OW), dev)
+        px_kind, pptr = LOSSES_PX_TENSOR, px_mask.data_ptr()
+    elif label_max is not None:
+        px_kind, hi = LOSSES_PX_LABEL_MAX, float(label_max)
+    near, far = (0.0, 0.0) if inbounds is None else (float(inbounds[0]), float(inbounds[1]))
+    if true_cost is not None:
+        if not isinstance(true_cost, torch.Tensor) or true_cost.dtype != torch.float32 or tuple(true_cost.shape) != (B, D, OH, OW) \
+                or not true_cost.is_contiguous() or true_cost.device != dev:
+            raise AssertionError(f"true_cost must be a contiguous fp32 {(B, D, OH, OW)} tensor on {dev}")
+    if ws is None:
+        ws = losses_ws(B, OH, OW, dev)
+    elif ws.device != dev or not ws.is_contiguous():
+        raise AssertionError("ws must be a contiguous tensor on labels' device")
+    if out is None:
+        out = torch.empty((B + 1, len(LOSSES_COLUMNS)), device=dev, dtype=torch.float64)
+    elif out.dtype != torch.float64 or tuple(out.shape) != (B + 1, len(LOSSES_COLUMNS)) or not out.is_contiguous() or out.device != dev:
+        raise AssertionError(f"out must be a contiguous float64 [{B + 1}, {len(LOSSES_COLUMNS)}] tensor on {dev}")
+    _call("mvsgi_losses_f32", labels.data_ptr(), _ptr(pred), _ptr(probs), p_kind, _ptr(inv_idx), vptr, vol_kind, pptr, px_kind, hi,
+          int(inbounds is not None), near, far, _ptr(true_cost), ws.data_ptr(), ws.numel() * ws.element_size(), out.data_ptr(),
+          B, D, Hh, W, sc, OH, OW, _stream_ptr(labels))
+    LOSSES_EVALUATIONS += 1
+    return out
+
+
+def volume_labels(labels, inv_idx, out=None) -> torch.Tensor:
+    """The two-hot labels of VolumeCrossEntropy (its true_cost): labels [B, 1, OH, OW], inv_idx [D] -> fp32 [B, D, OH, OW]."""
+    lab = _image(labels, "labels")
+    inv_idx = _inv_list(inv_idx, lab.device)
+    B, OH, OW = (int(v) for v in lab.shape)
+    if out is None:
+        out = torch.empty((B, inv_idx.numel(), OH, OW), device=lab.device, dtype=torch.float32)
+    losses(lab, inv_idx, true_cost=out)
+    return out
+
+
 # the packed point cloud (csrc/cloud.hip), restated: tiles of 1024 consecutive pixels, 16 words of 64 bits each; at most 4 gates, 4 colour
 # channels and 16 floats per record
 CLOUD_TILE, CLOUD_WORDS_PER_TILE, CLOUD_MAX_GATES, CLOUD_MAX_CHANNELS, CLOUD_MAX_RECORD, CLOUD_MAX_BATCH = 1024, 16, 4, 4, 16, 65535

@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define MVSGI_ABI_VERSION 8   /* 8: mvsgi_reproject_f32 (back-projection: point cloud and warped camera views), and, added later without a new number (an addition: older callers are unaffected, and the binding refuses a library that lacks a symbol it binds), mvsgi_metrics_f32, mvsgi_metrics_ws_bytes (validation metrics), mvsgi_cloud_pack_f32, mvsgi_cloud_ws_bytes (packed point cloud), mvsgi_losses_f32, mvsgi_losses_ws_bytes (loss functions); 7: mvsgi_resample_bilinear_u8_f32, mvsgi_resample_bilinear_f32, mvsgi_resample_validity_u8, mvsgi_resample_u8_table_f32, mvsgi_rays_equirect_surrogate_f32 (fisheye -> surrogate-view resampler); 6: mvsgi_sweep_max_cams (masked-variance sweep for rigs of up to 8 cameras); 5: mvsgi_softargmin_scaled_f32 (soft-argmin at any interp_scale_factor); 4: mvsgi_instance_norm_f32, mvsgi_instance_norm_ws_bytes (norm_type 'instance'); 3: mvsgi_conv3d_d32_applies, mvsgi_conv3d_up2_d32_applies + MVSGI_CONV_BF16X3_D32; 2: mvsgi_saturation_flags; the symbol set of round 5 */
+#define MVSGI_ABI_VERSION 8   /* 8: mvsgi_reproject_f32 (back-projection: point cloud and warped camera views), and, added later without a new number (an addition: older callers are unaffected, and the binding refuses a library that lacks a symbol it binds), mvsgi_metrics_f32, mvsgi_metrics_ws_bytes (validation metrics), mvsgi_cloud_pack_f32, mvsgi_cloud_ws_bytes (packed point cloud), mvsgi_losses_f32, mvsgi_losses_ws_bytes (loss functions), mvsgi_photo_consistency_f32, mvsgi_photo_ws_bytes (photometric consistency); 7: mvsgi_resample_bilinear_u8_f32, mvsgi_resample_bilinear_f32, mvsgi_resample_validity_u8, mvsgi_resample_u8_table_f32, mvsgi_rays_equirect_surrogate_f32 (fisheye -> surrogate-view resampler); 6: mvsgi_sweep_max_cams (masked-variance sweep for rigs of up to 8 cameras); 5: mvsgi_softargmin_scaled_f32 (soft-argmin at any interp_scale_factor); 4: mvsgi_instance_norm_f32, mvsgi_instance_norm_ws_bytes (norm_type 'instance'); 3: mvsgi_conv3d_d32_applies, mvsgi_conv3d_up2_d32_applies + MVSGI_CONV_BF16X3_D32; 2: mvsgi_saturation_flags; the symbol set of round 5 */
 
 typedef void* mvsgi_stream_t;
 
@@ -690,6 +690,48 @@ int mvsgi_cloud_pack_f32(const float* inv, const float* rays, const unsigned cha
                          const float* const* attrs_host, int A, float* points, int* counts, int* index, long long capacity,
                          void* ws, size_t ws_bytes, long long B, int H, int W, int sy, int sx, float bf, float d_min, float d_max,
                          mvsgi_stream_t stream);
+
+/* ---- photometric consistency of the prediction (csrc/photo.hip) ----------------------------------------------------------------
+ * Do the cameras agree on the colour of the point a pixel's predicted distance puts in front of them?  The cost volume's own fusion
+ * rule (SphericalSweepStdMasked, dsta_mvs/model/cost_volume_builder/spherical_sweep_avg.py:92-125: the masked variance over the
+ * cameras that see a point), evaluated on the camera images at the predicted inverse distance.  Not part of the reference's
+ * interface; defined as a composition of operations this library already has.  For frame b and pixel (i, j) of the H x W map, steps
+ * 1-6 of mvsgi_reproject_f32 give valid_n and w_n[c] = warped[b][n][c][i][j] (invalid_value 0) for each camera n < N: the same
+ * functions, so the same bits; warped is never stored, and the taps of an invalid camera are not fetched.  Then in fp32, no
+ * contraction, each operation one IEEE operation, every sum over cameras or channels started at +0 and taken left to right from
+ * index 0:
+ *     1. seen_n = valid_n; with cam_masks (fp32 [N][1][Hr][Wr], the tensor sample_masks takes, the size of the images) additionally
+ *        && (the mask of camera n sampled at the same grid by the same bilinear arithmetic) > 0      (:92-102, the 4-tap rule)
+ *     2. cnt = sum_n float(seen_n);  ok = cnt > 1;  k = ok ? cnt : 1                                 (:106-111)
+ *     3. avg_c = (sum_n w_n[c] * float(seen_n)) / k                                                  (:114)
+ *     4. x_n = seen_n ? w_n[c] : avg_c;  var_c = ok ? (sum_n (x_n - avg_c) * (x_n - avg_c)) / k : 0  (:119-125)
+ *     5. photo_var = (sum_c var_c) / float(C)
+ *     6. photo_std = sqrt(photo_var)
+ *     7. a pixel is scored when ok && mask != 0 (mask: uint8 [H][W] with mask_per_frame = 0, [B][H][W] with 1, NULL: every pixel)
+ * Values of inv nobody should pass do what the chain does with them, there is no special case: 0 and NaN give coordinates no camera
+ * accepts (cnt = 0, photo_var = 0, not scored); a negative value or inf is a finite point behind the rig camera or at its centre,
+ * which another camera may see.  Occlusion is not reasoned about: a point hidden from one camera reads high.
+ *   device, out:  n_views [B][H][W] uint8 = cnt;  photo_var, photo_std [B][H][W] fp32;  mean_colour [B][C][H][W] fp32 = avg_c (0
+ *                 where cnt = 0); each may be NULL (not written); 16-byte aligned.
+ *                 table [B + 1][14] float64, or NULL: columns n (scored pixels), mean_std = sum std / n, rms = sqrt(sum var / n),
+ *                 bad = #{std > thresh} / n, coverage = n / #{mask != 0}, views_0 .. views_8 = the masked pixels with exactly k
+ *                 seen cameras; mean_std, rms and bad are NaN where n = 0.  The sums are float64, compensated (the sum of the
+ *                 fp32 addends to ~2^-100 relative, rounded once).  Row b < B depends on frame b alone; row B: sums and counts
+ *                 added over the frames in frame order.
+ *   device, in:   inv, rays, imgs (img_kind, C, Hr, Wr) as for mvsgi_reproject_f32, imgs required; inv and rays 16-byte and mask
+ *                 4-byte aligned when W % 4 == 0.
+ *   host:         T [N][16], cams [N][10] as for mvsgi_reproject_f32 (copied into the kernel's arguments by the call).
+ *   ws:           caller-owned device scratch of ws_bytes >= mvsgi_photo_ws_bytes(B, H, W) bytes (0 = invalid dimensions), 8-byte
+ *                 aligned; read with a table only (ws may be NULL without one, and the second launch is then skipped).
+ * Two launches (reduce, grid (G, B) with G a function of (H, W) alone; finalise), no atomics, no host synchronisation, no
+ * allocation: capturable, and the same inputs give the same bits.  1 <= N <= mvsgi_sweep_max_cams(); H * W < 2^31 - 2^18, B < 65535;
+ * limits of the images as for mvsgi_resample_bilinear_*. */
+size_t mvsgi_photo_ws_bytes(long long B, int H, int W);
+int mvsgi_photo_consistency_f32(const float* inv, const float* rays, const void* imgs, int img_kind, const float* cam_masks,
+                                const float* T_host, const float* cams_host, const unsigned char* mask, int mask_per_frame,
+                                float thresh, unsigned char* n_views, float* photo_var, float* photo_std, float* mean_colour,
+                                void* ws, size_t ws_bytes, double* table, long long B, int N, int C, int Hr, int Wr, int H, int W,
+                                float bf, mvsgi_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -139,6 +139,9 @@ SIGNATURES = {
     "mvsgi_cloud_ws_bytes": (c_size_t, [c_longlong, c_int, c_int]),
     "mvsgi_cloud_pack_f32": (c_int, [_P, _P, _P, c_int, _P, _P, _P, c_int, _P, _P, c_int, c_int, c_int, c_float, _P, c_int, _P, _P, _P,
                                      c_longlong, _P, c_size_t, c_longlong] + [c_int] * 4 + [c_float] * 3 + [_P]),
+    "mvsgi_photo_ws_bytes": (c_size_t, [c_longlong, c_int, c_int]),
+    "mvsgi_photo_consistency_f32": (c_int, [_P, _P, _P, c_int, _P, _P, _P, _P, c_int, c_float, _P, _P, _P, _P, _P, c_size_t, _P,
+                                            c_longlong] + [c_int] * 6 + [c_float, _P]),
 }
 
 _lib = None

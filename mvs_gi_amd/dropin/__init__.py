@@ -9,6 +9,7 @@ from .image_sampler import (DoubleSphereToEquirectSampler, NoOpSampler, equirect
                             stack_tables)
 from .reproject import Reprojector  # noqa: F401
 from .cloud import CloudPacker  # noqa: F401
+from .photo import PhotoConsistency  # noqa: F401
 from .metrics import (Evaluator, MVSMetric, SSIMMetric, RMSEMetric, MAEMetric, BadPixelRatioMetric,  # noqa: F401
                       InverseMetricWrapper)
 from .losses import (LossEvaluator, VolumeCrossEntropy, MaskedSmoothL1Loss, InBoundsBCEDistanceLoss,  # noqa: F401

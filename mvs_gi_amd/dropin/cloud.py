@@ -14,7 +14,8 @@ composition bit for bit.
 
 Gates and attributes are confidence maps, named as in hip_ops.CONFIDENCE_MAPS:
     CloudPacker(reprojector, gates={"max_prob": (0.5, inf), "spread": (-inf, 2.0)}, attrs=("max_prob",))
-`argmax` is an int map and is refused as either.
+`argmax` is an int map and is refused as either.  One more name is legal in both places: "photo_std", the photometric spread of
+dropin.PhotoConsistency (do the cameras agree on the point's colour?); its plane arrives through pack(..., photo=...).
 """
 from __future__ import annotations
 
@@ -25,10 +26,11 @@ import torch
 from .. import hip_ops as H
 
 _FLOAT_MAPS = tuple(n for n in H.CONFIDENCE_MAPS if n != "argmax")
+_PHOTO_MAPS = ("photo_std",)          # planes of dropin.PhotoConsistency, given to pack() as photo=
 
 
 class CloudPacker:
-    """packer.pack(inv, confidence=None, warped=None, valid=None, out=None) -> dict(points [B, capacity, R], counts [B, 2], index
+    """packer.pack(inv, confidence=None, warped=None, valid=None, out=None, photo=None) -> dict(points [B, capacity, R], counts [B, 2], index
     [B, capacity] with want_index); packer.to_host(result) -> list of [written_b, R] arrays.
 
     source: a dropin.Reprojector (its rays, bf and out_shape are used) or a ray table [3, H, W] (then bf: 96 for the regressor's raw
@@ -65,8 +67,8 @@ class CloudPacker:
         for name in list(gates) + list(attrs):
             if name == "argmax":
                 raise ValueError("CloudPacker: 'argmax' is an int map; gates and attributes are the fp32 maps " + ", ".join(_FLOAT_MAPS))
-            if name not in _FLOAT_MAPS:
-                raise ValueError(f"CloudPacker: unknown confidence map {name!r} (gates and attributes: {', '.join(_FLOAT_MAPS)})")
+            if name not in _FLOAT_MAPS + _PHOTO_MAPS:
+                raise ValueError(f"CloudPacker: unknown confidence map {name!r} (gates and attributes: {', '.join(_FLOAT_MAPS + _PHOTO_MAPS)})")
         if len(set(attrs)) != len(attrs):
             raise ValueError(f"CloudPacker: attrs without repeats, got {attrs}")
         if len(gates) > H.CLOUD_MAX_GATES:
@@ -107,7 +109,12 @@ class CloudPacker:
     @property
     def maps(self) -> tuple:
         """The confidence maps pack() needs, gates first."""
-        return tuple(dict.fromkeys(list(self.gates) + list(self.attrs)))
+        return tuple(n for n in dict.fromkeys(list(self.gates) + list(self.attrs)) if n not in _PHOTO_MAPS)
+
+    @property
+    def photo_maps(self) -> tuple:
+        """The planes of dropin.PhotoConsistency pack() needs (through photo=), gates first."""
+        return tuple(n for n in dict.fromkeys(list(self.gates) + list(self.attrs)) if n in _PHOTO_MAPS)
 
     def record_width(self, channels: Optional[int] = None) -> int:
         c = (self.channels if channels is None else channels) if self.colour else 0
@@ -131,8 +138,13 @@ class CloudPacker:
         """Drop every workspace and output set.  Not while a captured graph that holds their addresses is still to be replayed."""
         self._bufs = {}
 
-    def _plane(self, confidence, name: str, B: int) -> torch.Tensor:
-        if confidence is None or name not in confidence:
+    def _plane(self, confidence, name: str, B: int, photo=None) -> torch.Tensor:
+        if name in _PHOTO_MAPS:
+            if photo is None or name not in photo:
+                raise ValueError(f"CloudPacker.pack: {name!r} is a gate or an attribute of this packer and was not given (photo=, the "
+                                 "result of dropin.PhotoConsistency.evaluate)")
+            confidence = photo
+        elif confidence is None or name not in confidence:
             raise ValueError(f"CloudPacker.pack: the confidence map {name!r} is a gate or an attribute of this packer and was not given")
         t = confidence[name]
         if not isinstance(t, torch.Tensor) or t.dtype != torch.float32:
@@ -144,7 +156,7 @@ class CloudPacker:
                                  f"(or without the 1), got {tuple(confidence[name].shape)}")
         return t
 
-    def pack(self, inv, confidence=None, warped=None, valid=None, out=None) -> dict:
+    def pack(self, inv, confidence=None, warped=None, valid=None, out=None, photo=None) -> dict:
         if not isinstance(inv, torch.Tensor):
             raise TypeError(f"inv: expected a torch.Tensor, got {type(inv)}")
         if inv.dim() == 4 and inv.shape[1] == 1:
@@ -166,8 +178,8 @@ class CloudPacker:
                 raise ValueError(f"CloudPacker.pack: warped has {C} channels, this packer's records hold {self.channels}")
         elif warped is not None or valid is not None:
             raise ValueError("CloudPacker.pack: warped / valid given to a packer built with colour=False")
-        gates = [(self._plane(confidence, n, B),) + self.gates[n] for n in self.gates]
-        attrs = [self._plane(confidence, n, B) for n in self.attrs]
+        gates = [(self._plane(confidence, n, B, photo),) + self.gates[n] for n in self.gates]
+        attrs = [self._plane(confidence, n, B, photo) for n in self.attrs]
         H._cloud_plane(inv, "inv", None, None)
         ws, own = self.buffers(B, self.record_width(), inv.device)
         return H.pack_cloud(inv, self.rays, self.bf, d_range=self.d_range, gates=gates, mask=self.mask, step=self.step, warped=warped,

@@ -1296,6 +1296,111 @@ def volume_labels(labels, inv_idx, out=None) -> torch.Tensor:
     return out
 
 
+PHOTO_MAPS = ("n_views", "photo_var", "photo_std", "mean_colour")           # the order of mvsgi_photo_consistency_f32's output pointers
+PHOTO_COLUMNS = ("n", "mean_std", "rms", "bad", "coverage") + tuple(f"views_{k}" for k in range(9))
+PHOTO_OUTPUTS = PHOTO_MAPS + ("table",)
+PHOTO_EVALUATIONS = 0         # calls of mvsgi_photo_consistency_f32 by this process
+# the slab of csrc/photo.hip, restated: a reduce block per 256 quads of a frame (a quad: four consecutive pixels of a row; at most 256
+# blocks), 16 doubles per record
+_PHOTO_REC, _PHOTO_QUADS_PER_BLOCK, _PHOTO_MAX_BLOCKS = 16, 256, 256
+
+
+def photo_ws_layout(B: int, H: int, W: int) -> dict:
+    """The workspace of photo_consistency(), in doubles: offsets of its two parts and the reduce blocks per frame G (a function of
+    (H, W) alone).  Pure: no device, no library."""
+    G = min(max(-(-(H * (-(-W // 4))) // _PHOTO_QUADS_PER_BLOCK), 1), _PHOTO_MAX_BLOCKS)
+    fsum = B * G * _PHOTO_REC
+    return dict(G=G, records=0, frame_sums=fsum, total=fsum + B * _PHOTO_REC)
+
+
+def photo_ws(B: int, H: int, W: int, device) -> torch.Tensor:
+    """A workspace for photo_consistency() at this shape (float64; its owner keeps it: a captured graph holds its address)."""
+    n = _lib.load().mvsgi_photo_ws_bytes(B, H, W)
+    if n == 0:
+        raise ValueError(f"photo_consistency: unsupported shape (B {B}, H {H}, W {W})")
+    return torch.empty(n // 8, device=device, dtype=torch.float64)
+
+
+def photo_consistency(inv, rays, T, cams, bf: float, imgs, cam_masks=None, mask=None, thresh: float = 0.1, want=PHOTO_OUTPUTS, out=None,
+                      ws=None, table=None) -> dict:
+    """Photometric consistency of an inverse-distance map (include/mvsgi.h, "photometric consistency"): the
+    masked variance over the cameras that see the back-projected point, of the colours they show there -- reproject()'s valid and
+    warped put through the cost volume's fusion rule without storing them.
+    inv, rays, T, cams, bf, imgs as for reproject() (imgs uint8 [B * N, Hr, Wr, 3] or fp32 [B * N, C, Hr, Wr], required); cam_masks
+    fp32 [N, 1, Hr, Wr] (a camera also has to see the point through its mask, sampled like the image, > 0); mask uint8 / bool [H, W]
+    or [B, H, W]: the pixels the table scores; thresh: the bad-pixel threshold on photo_std.
+    want: a selection of PHOTO_OUTPUTS -- n_views uint8 [B, H, W], photo_var / photo_std fp32 [B, H, W], mean_colour fp32
+    [B, C, H, W], table float64 [B + 1, 14] with PHOTO_COLUMNS, row B pooled.  out: a dict with tensors to write in place; `table=`
+    is out["table"].  Two launches on inv's stream (one without the table), nothing else: with `out` and `ws` (photo_ws; needed with
+    the table only) given the call allocates nothing and can be captured.  There is no CPU fallback.  -> dict of the wanted outputs."""
+    global PHOTO_EVALUATIONS
+    inv = _dev(inv, "inv")
+    rays = _dev(rays, "rays")
+    if inv.dim() == 4 and inv.shape[1] == 1:
+        inv = inv.squeeze(1)
+    if inv.dim() != 3 or rays.dim() != 3 or rays.shape[0] != 3 or tuple(rays.shape[1:]) != tuple(inv.shape[1:]) or rays.device != inv.device:
+        raise AssertionError(f"inv must be [B, H, W] and rays [3, H, W] on one device, got {tuple(inv.shape)}, {tuple(rays.shape)}")
+    B, Ho, Wo = (int(v) for v in inv.shape)
+    dev = inv.device
+    T = torch.as_tensor(T)
+    cams = torch.as_tensor(cams)
+    if T.is_cuda or cams.is_cuda or T.dtype != torch.float32 or cams.dtype != torch.float32:
+        raise TypeError("T and cams are fp32 host tensors (they travel in the kernel's arguments)")
+    N = T.shape[0] if T.dim() == 3 else -1
+    if tuple(T.shape) != (N, 4, 4) or tuple(cams.shape) != (N, REPROJECT_CAM_FLOATS):
+        raise AssertionError(f"T must be [N, 4, 4] and cams [N, {REPROJECT_CAM_FLOATS}], got {tuple(T.shape)}, {tuple(cams.shape)}")
+    if not 1 <= N <= sweep_max_cams():
+        raise ValueError(f"photo_consistency: {N} cameras (1 ... {sweep_max_cams()} are supported)")
+    T, cams = T.contiguous(), cams.contiguous()
+    want = tuple(want)
+    if not want or set(want) - set(PHOTO_OUTPUTS) or len(set(want)) != len(want):
+        raise ValueError(f"want: a non-empty selection of {', '.join(repr(k) for k in PHOTO_OUTPUTS)}, got {want}")
+    imgs, u8, C, Hr, Wr = _images(imgs, "B*N", count=B * N, device=dev)
+    if cam_masks is not None:
+        cam_masks = _dev(cam_masks, "cam_masks")
+        if tuple(cam_masks.shape) != (N, 1, Hr, Wr) or cam_masks.device != dev:
+            raise AssertionError(f"cam_masks must be fp32 [{N}, 1, {Hr}, {Wr}] (the size of the images) on {dev}, got "
+                                 f"{tuple(cam_masks.shape)} on {cam_masks.device}")
+    mask_per_frame = 0
+    if mask is not None:
+        mask = _cloud_plane(mask, "mask", None, dev, (torch.uint8, torch.bool))
+        if tuple(mask.shape) not in ((Ho, Wo), (B, Ho, Wo)):
+            raise AssertionError(f"mask must be [{Ho}, {Wo}] or [{B}, {Ho}, {Wo}], got {list(mask.shape)}")
+        if Wo % 4 == 0 and mask.data_ptr() % 4:
+            raise AssertionError("mask must be 4-byte aligned when W % 4 == 0")
+        mask_per_frame = 1 if mask.dim() == 3 else 0
+    if table is not None:
+        if out is not None and out.get("table") is not None and out["table"] is not table:
+            raise ValueError("photo_consistency: table= and out['table'] are two different tensors")
+        out = dict(out or {}, table=table)
+        if "table" not in want:
+            raise ValueError("photo_consistency: a table was given but 'table' is not wanted")
+    shapes = {"n_views": ((B, Ho, Wo), torch.uint8), "photo_var": ((B, Ho, Wo), torch.float32), "photo_std": ((B, Ho, Wo), torch.float32),
+              "mean_colour": ((B, C, Ho, Wo), torch.float32), "table": ((B + 1, len(PHOTO_COLUMNS)), torch.float64)}
+    res = {}
+    for k in want:
+        shape, dtype = shapes[k]
+        t = None if out is None else out.get(k)
+        if t is None:
+            t = torch.empty(shape, device=dev, dtype=dtype)
+        elif tuple(t.shape) != shape or t.dtype != dtype or t.device != dev or not t.is_contiguous() or t.data_ptr() % 16:
+            raise AssertionError(f"out['{k}'] must be a contiguous, 16-byte aligned {dtype} {list(shape)} tensor on {dev}")
+        res[k] = t
+    ws_ptr, ws_bytes = None, 0
+    if "table" in want:
+        if ws is None:
+            ws = photo_ws(B, Ho, Wo, dev)
+        elif not isinstance(ws, torch.Tensor) or ws.device != dev or not ws.is_contiguous():
+            raise AssertionError("ws must be a contiguous tensor on inv's device")
+        ws_ptr, ws_bytes = ws.data_ptr(), ws.numel() * ws.element_size()
+    _call("mvsgi_photo_consistency_f32", inv.data_ptr(), rays.data_ptr(), imgs.data_ptr(), 0 if u8 else 1, _ptr(cam_masks), T.data_ptr(),
+          cams.data_ptr(), _ptr(mask), mask_per_frame, float(thresh), _ptr(res.get("n_views")), _ptr(res.get("photo_var")),
+          _ptr(res.get("photo_std")), _ptr(res.get("mean_colour")), ws_ptr, ws_bytes, _ptr(res.get("table")), B, N, C, Hr, Wr, Ho, Wo,
+          float(bf), _stream_ptr(inv))
+    PHOTO_EVALUATIONS += 1
+    return res
+
+
 # the packed point cloud (csrc/cloud.hip), restated: tiles of 1024 consecutive pixels, 16 words of 64 bits each; at most 4 gates, 4 colour
 # channels and 16 floats per record
 CLOUD_TILE, CLOUD_WORDS_PER_TILE, CLOUD_MAX_GATES, CLOUD_MAX_CHANNELS, CLOUD_MAX_RECORD, CLOUD_MAX_BATCH = 1024, 16, 4, 4, 16, 65535

@@ -344,10 +344,15 @@ class InferencePipeline:
     With `cloud` (a dropin.CloudPacker at the output resolution, bf = 1) the last stage packs the frame's point cloud: three more
     launches behind the back-projection, in forward_device and inside the captured graph.  Its gates and attributes are maps that
     `confidence` selects, its colours the reprojector's warped views.  `pipe.cloud` is the dict of the packer's static tensors
-    (points, counts, index), valid until the next call; dropin.CloudPacker.to_host reads it out."""
+    (points, counts, index), valid until the next call; dropin.CloudPacker.to_host reads it out.
+
+    With `photo` (a dropin.PhotoConsistency built on this pipeline's `reprojector`) one more stage follows the soft-argmin, in
+    forward_device and inside the captured graph: the photometric consistency of the frame's prediction with its own input images
+    (csrc/photo.hip, two launches).  `pipe.photo` is the dict of hip_ops.PHOTO_OUTPUTS, static tensors made by the first call and
+    valid until the next.  A `cloud` packer that names "photo_std" as a gate or an attribute takes that plane from this stage."""
 
     def __init__(self, cfg: PathConfig, weights, consts, device="cuda", extractor: str = "simple", samplers=None, raw_masks=None,
-                 reprojector=None, confidence=None, cloud=None):
+                 reprojector=None, confidence=None, cloud=None, photo=None):
         """extractor: 'simple' = SimpleFeatExtraction (G16V, config29), 'sphere' = SphereEquirectFeatExtraction with the
         sphere-convolution final layer (G16VV, config103; configs/feature_extractor/sphereconv_featext.yaml).
         samplers / raw_masks: per-camera image samplers and raw-resolution masks; with both, consts["masks"] may be omitted
@@ -362,8 +367,16 @@ class InferencePipeline:
             out_hw = (math.floor(cfg.cv_hw[0] * cfg.interp_scale_factor), math.floor(cfg.cv_hw[1] * cfg.interp_scale_factor))
             if tuple(cloud.out_shape) != out_hw:
                 raise ValueError(f"cloud: the packer's out_shape {tuple(cloud.out_shape)} is not the output's {out_hw}")
+            if getattr(cloud, "photo_maps", ()) and photo is None:
+                raise ValueError(f"cloud: the packer's gates / attributes {list(cloud.photo_maps)} need a photo= stage")
+        if photo is not None:
+            if reprojector is None or photo.reprojector is not reprojector:
+                raise ValueError("photo: the stage needs reprojector=, the Reprojector the PhotoConsistency was built on")
         self.cloud_packer = cloud
         self.cloud = None
+        self.photo_stage = photo
+        self.photo = None
+        self._photo_out = None
         self.samplers = None
         if samplers is not None:
             if len(samplers) != cfg.num_cams:
@@ -411,6 +424,7 @@ class InferencePipeline:
             g.replay()
             self.confidence = self._static_conf
             self.cloud = self._static_cloud
+            self.photo = self._static_photo
             out = self._static_inv.squeeze(0).squeeze(0).cpu().numpy()
         else:
             out = self.forward_device(t.to(self.hot.device)).squeeze(0).squeeze(0).cpu().numpy()
@@ -434,11 +448,15 @@ class InferencePipeline:
             r = self.reprojector.reproject(inv, frame, out=self._reproj_out)
             self._reproj_out = r
             self.reprojection = (r["xyz"], r["warped"], r["valid"])
+        if self.photo_stage is not None:
+            # made once like the back-projection's buffers; the workspace and the table are the stage's own
+            self.photo = self._photo_out = self.photo_stage.evaluate(inv, frame, out=self._photo_out)
         if self.cloud_packer is not None:
             # the packer's buffers are made once too (it owns them per shape) and written in place
             colour = self.cloud_packer.colour
+            more = dict(photo=self.photo) if self.photo_stage is not None else {}
             self.cloud = self.cloud_packer.pack(inv, confidence=self.confidence, warped=r["warped"] if colour else None,
-                                                valid=r["valid"] if colour else None)
+                                                valid=r["valid"] if colour else None, **more)
         return inv
 
     # ---- hipGraph replay of the whole chain for one frame (the robot's operating point: one frame at a time) ----
@@ -465,6 +483,7 @@ class InferencePipeline:
         self._graph = graph
         self._static_conf = self.confidence
         self._static_cloud = self.cloud
+        self._static_photo = self.photo
 
     @torch.no_grad()
     def replay(self, imgs_u8: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -479,4 +498,5 @@ class InferencePipeline:
         self._graph.replay()
         self.confidence = self._static_conf
         self.cloud = self._static_cloud
+        self.photo = self._static_photo
         return self._static_inv

@@ -31,6 +31,7 @@ def equirect_surrogate_rays(H_out: int, W_out: int, device="cuda") -> torch.Tens
     """Rays [3, H, W] of the pixel centres of an H x W surrogate view: u = (2j+1)/W - 1, v = (2i+1)/H - 1, lon = pi u,
     lat = pi v / 2, p = (cos lat cos lon, sin lat, -cos lat sin lon); grid_equirect(p) = (u, v)."""
     rays = torch.empty((3, int(H_out), int(W_out)), device=torch.device(device), dtype=torch.float32)
+    H._arg(rays, "rays", None)            # a CPU `device` ends here: the kernel takes device addresses only
     H._call("mvsgi_rays_equirect_surrogate_f32", rays.data_ptr(), int(H_out), int(W_out), H._stream_ptr(rays))
     return rays
 

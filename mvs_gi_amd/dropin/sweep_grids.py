@@ -16,7 +16,7 @@ from typing import Sequence
 import numpy as np
 import torch
 
-from ..hip_ops import _call, _dev, _stream_ptr
+from ..hip_ops import _arg, _call, _dev, _stream_ptr
 
 
 def _as_f32_cuda(t, device) -> torch.Tensor:
@@ -40,7 +40,8 @@ class RayMaker_UEPanorama:
         H, W = int(grid_shape[0]), int(grid_shape[1])
         N = self.dist.numel()
         rays = torch.empty((3, N, H, W), device=self.device, dtype=torch.float32)
-        _call("mvsgi_rays_panorama_f32", self.dist.data_ptr(), rays.data_ptr(), N, H, W, self.lat_range[0], self.lat_range[1], self.long_range[0],
+        _arg(rays, "rays", None)          # a CPU `device` ends here: the kernel takes device addresses only
+        _call("mvsgi_rays_panorama_f32", _arg(self.dist, "dist (the candidate distances)", rays.device, numel=N).data_ptr(), rays.data_ptr(), N, H, W, self.lat_range[0], self.lat_range[1], self.long_range[0],
               self.long_range[1], _stream_ptr(rays))
         return rays
 

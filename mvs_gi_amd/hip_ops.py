@@ -179,6 +179,48 @@ def _dev(t: torch.Tensor, name: str, dtype=torch.float32) -> torch.Tensor:
     return t
 
 
+def _arg(t, name: str, device, dtype=torch.float32, shape=None, numel=None, nbytes=None) -> torch.Tensor:
+    """A parameter or a caller-owned buffer -- scale, shift, weights in any layout, plans, `out`, `res`, the storage of a split-padded
+    activation -- checked and handed on AS IT IS: a tensor on `device` (the activation's) of `dtype` (one, or a tuple to choose
+    from), contiguous, 16-byte aligned, of the expected shape / element count / byte count (whichever the caller knows).  The
+    message names the argument.  Never copies: the hot path does not allocate, and an address a captured graph holds stays the
+    tensor's.  Attribute reads only: no synchronisation, no device query."""
+    if not isinstance(t, torch.Tensor):
+        raise TypeError(f"{name}: expected a torch.Tensor, got {type(t)}")
+    if not t.is_cuda:
+        raise RuntimeError(f"{name}: mvs_gi_amd runs on the GPU only (tensor is on {t.device}); there is no CPU fallback")
+    if device is not None and t.device != device and not (device.index is None and device.type == "cuda"):
+        raise AssertionError(f"{name}: on {t.device}, the activation is on {device}")
+    if t.dtype != dtype and (type(dtype) is not tuple or t.dtype not in dtype):
+        raise TypeError(f"{name}: expected {dtype}, got {t.dtype}")
+    if shape is not None and tuple(t.shape) != tuple(shape):
+        raise AssertionError(f"{name}: expected shape {list(shape)}, got {list(t.shape)}")
+    if numel is not None and t.numel() != numel:
+        raise AssertionError(f"{name}: expected {numel} elements, got {t.numel()} ({list(t.shape)})")
+    if nbytes is not None and t.numel() * t.element_size() != nbytes:
+        raise AssertionError(f"{name}: wrong size: expected {nbytes} bytes, got {t.numel() * t.element_size()} ({t.dtype} {list(t.shape)})")
+    if not t.is_contiguous():
+        raise AssertionError(f"{name}: must be contiguous (strides {t.stride()} of {list(t.shape)}); it is read in place, never copied")
+    if t.data_ptr() % 16:
+        raise AssertionError(f"{name}: must be 16-byte aligned (a view at an odd offset?); it is read in place, never copied")
+    return t
+
+
+def _opt(t, name: str, device, dtype=torch.float32, **kw) -> Optional[int]:
+    """_arg of an argument that may be None -> its address or None."""
+    return None if t is None else _arg(t, name, device, dtype, **kw).data_ptr()
+
+
+def _scale_shift(scale, shift, device, cout=None, suffix: str = ""):
+    """The epilogue's per-channel constants: fp32 [Cout] each -> (their addresses, Cout)."""
+    scale = _arg(scale, "scale" + suffix, device, numel=cout)
+    cout = scale.numel()
+    return scale.data_ptr(), _arg(shift, "shift" + suffix, device, numel=cout).data_ptr(), cout
+
+
+_PACKED = (torch.uint8, torch.float32)        # a packed weight whose layout the call does not tell: bytes or floats
+
+
 def _ptr(t: Optional[torch.Tensor]) -> Optional[int]:
     return None if t is None else t.data_ptr()
 
@@ -277,15 +319,14 @@ def sweep_std_valid_split(feats, grids, vmask, out: "SplitAct", fmt: str = "bf16
     if not valid_sweep_ok(feats):
         raise AssertionError(f"sweep_std_valid_split needs C == 16 and num_cams in [1, {sweep_max_cams()}], got feats {tuple(feats.shape)}")
     B, N, C, Hi, Wi = feats.shape
-    f = _feats_nhwc(feats)
     grids = _dev(grids, "grids")
     vmask = _dev(vmask, "vmask", torch.uint8)
     Bg, Ng, D, Ho, Wo, two = grids.shape
     if (Ng, two) != (N, 2) or Bg not in (1, B) or tuple(vmask.shape) != (Bg, D, Ho, Wo) or C != 16:
         raise AssertionError(f"grids {tuple(grids.shape)} / vmask {tuple(vmask.shape)} do not match feats {tuple(feats.shape)}")
-    if out.shape != (B, D, Ho, Wo, C):
-        raise AssertionError(f"split output {out.shape} does not match {(B, D, Ho, Wo, C)}")
-    _call("mvsgi_sweep_std_nhwc_valid_split_fmt", f.data_ptr(), grids.data_ptr(), vmask.data_ptr(), out.buf.data_ptr(), B, N, C, Hi, Wi, D, Ho, Wo,
+    yp = _split_ptr(out, "out", grids.device, (B, D, Ho, Wo, C))       # before the transpose of NCHW feats launches
+    f = _feats_nhwc(feats)
+    _call("mvsgi_sweep_std_nhwc_valid_split_fmt", f.data_ptr(), grids.data_ptr(), vmask.data_ptr(), yp, B, N, C, Hi, Wi, D, Ho, Wo,
           Bg, _fmt_code(fmt), _stream_ptr(f))
     out.fmt = fmt
     return out
@@ -420,19 +461,51 @@ def conv3d_v32_applies(B, Cin, Din, Hin, Win, Cout, stride=1) -> bool:
     return bool(_lib.load().mvsgi_conv3d_v32_applies(B, Cin, Din, Hin, Win, Cout, stride))
 
 
+def _split_layout_bytes(layout: int, Cout: int, Cin: int) -> int:
+    """Size of the streaming split kernel's weights in `layout` (CONV_BF16X3 | _C16 | _V32 | _D32, CONV_F16 or not: the two splits
+    share the layouts), by the library's own queries."""
+    lib = _lib.load()
+    layout &= ~CONV_F16
+    if layout == CONV_BF16X3_C16:
+        return lib.mvsgi_conv3d_packed_weight_bytes_bf16x3_c16(Cin)
+    if layout == CONV_BF16X3_V32:
+        return lib.mvsgi_conv3d_packed_weight_bytes_bf16x3_v32(Cout, Cin)
+    if layout in (CONV_BF16X3, CONV_BF16X3_D32):
+        return lib.mvsgi_conv3d_packed_weight_bytes_bf16x3(Cout, Cin)
+    raise ValueError(f"w_layout {layout} is not one of the streaming split kernel's layouts")
+
+
+def _conv3d_packed(w_packed, name: str, device, impl: int, Cout: int, Cin: int) -> Optional[int]:
+    """w_packed of conv3d, checked against the layout `impl` names -> its address or None.  A split layout (CONV_BF16X3 on channel
+    counts the split kernel takes, _C16, _V32, _D32): bytes, sized by the library's query.  CONV_MFMA, CONV_AUTO (which resolves to
+    the exact-fp32 tiled kernels or the direct one) and CONV_BF16X3 on channel counts that fall back to them: the fp32 layout of
+    pack_conv_weights, sized where that packer serves the channel counts.  CONV_DIRECT never reads it: form only."""
+    base = impl & ~CONV_F16
+    split = base in (CONV_BF16X3_C16, CONV_BF16X3_V32, CONV_BF16X3_D32) or (base == CONV_BF16X3 and Cin % 16 == 0 and Cout % 16 == 0)
+    if w_packed is None:
+        if split:
+            raise AssertionError(f"{name}: impl {impl} needs the packed weights of its layout")
+        return None
+    if split:
+        return _arg(w_packed, name, device, torch.uint8, nbytes=_split_layout_bytes(base, Cout, Cin)).data_ptr()
+    if base == CONV_DIRECT:
+        return _arg(w_packed, name, device, _PACKED).data_ptr()
+    packs = Cin % 16 == 0 and (Cout % 16 == 0 or Cout == 1)
+    return _arg(w_packed, name, device, numel=_lib.load().mvsgi_conv3d_packed_weight_floats(Cout, Cin) if packs else None).data_ptr()
+
+
 def conv3d(x, w_oidhw, w_packed, scale, shift, res=None, stride=1, neg_slope=0.01, impl=CONV_AUTO, out=None):
     """x [B, D, H, W, Cin] -> y [B, Do, Ho, Wo, Cout] = act(conv(x) * scale + shift (+ res));
     act(v) = v if v > 0 else v * neg_slope (1.0 = no activation)."""
     x = _dev(x, "x")
     B, Din, Hin, Win, Cin = x.shape
-    Cout = scale.numel()
+    dev = x.device
+    sc, sh, Cout = _scale_shift(scale, shift, dev)
     Do, Ho, Wo = (Din - 1) // stride + 1, (Hin - 1) // stride + 1, (Win - 1) // stride + 1
-    if res is not None:
-        res = _dev(res, "res")
-        if tuple(res.shape) != (B, Do, Ho, Wo, Cout):
-            raise AssertionError(f"residual {tuple(res.shape)} does not match output {(B, Do, Ho, Wo, Cout)}")
-    y = out if out is not None else torch.empty((B, Do, Ho, Wo, Cout), device=x.device, dtype=torch.float32)
-    _call("mvsgi_conv3d_f32", x.data_ptr(), _ptr(w_oidhw), _ptr(w_packed), scale.data_ptr(), shift.data_ptr(), _ptr(res), y.data_ptr(), B, Cin, Din,
+    shp = (B, Do, Ho, Wo, Cout)
+    y = torch.empty(shp, device=dev, dtype=torch.float32) if out is None else _arg(out, "out", dev, shape=shp)
+    _call("mvsgi_conv3d_f32", x.data_ptr(), _opt(w_oidhw, "w_oidhw", dev, shape=(Cout, Cin, 3, 3, 3)),
+          _conv3d_packed(w_packed, "w_packed", dev, impl, Cout, Cin), sc, sh, _opt(res, "res", dev, shape=shp), y.data_ptr(), B, Cin, Din,
           Hin, Win, Cout, stride, float(neg_slope), impl, _stream_ptr(x))
     return y
 
@@ -442,14 +515,12 @@ def conv3d_up2(x, w_packed_b3, scale, shift, res=None, neg_slope=0.01, out=None,
     w_layout: CONV_BF16X3 (pack_conv_weights_bf16x3) or CONV_BF16X3_C16 (pack_conv_weights_bf16x3_c16, Cout == 16)."""
     x = _dev(x, "x")
     B, Dl, Hl, Wl, Cin = x.shape
-    Cout = scale.numel()
+    dev = x.device
+    sc, sh, Cout = _scale_shift(scale, shift, dev)
     shp = (B, 2 * Dl, 2 * Hl, 2 * Wl, Cout)
-    if res is not None:
-        res = _dev(res, "res")
-        if tuple(res.shape) != shp:
-            raise AssertionError(f"residual {tuple(res.shape)} does not match output {shp}")
-    y = out if out is not None else torch.empty(shp, device=x.device, dtype=torch.float32)
-    _call("mvsgi_conv3d_up2_f32", x.data_ptr(), _ptr(w_packed_b3), w_layout, scale.data_ptr(), shift.data_ptr(), _ptr(res), y.data_ptr(), B, Cin, Dl,
+    wp = _arg(w_packed_b3, "w_packed_b3", dev, torch.uint8, nbytes=_split_layout_bytes(w_layout, Cout, Cin))
+    y = torch.empty(shp, device=dev, dtype=torch.float32) if out is None else _arg(out, "out", dev, shape=shp)
+    _call("mvsgi_conv3d_up2_f32", x.data_ptr(), wp.data_ptr(), w_layout, sc, sh, _opt(res, "res", dev, shape=shp), y.data_ptr(), B, Cin, Dl,
           Hl, Wl, Cout, float(neg_slope), _stream_ptr(x))
     return y
 
@@ -458,15 +529,13 @@ def conv3d_up2_out_split(x, w_packed_b3, scale, shift, out: "SplitAct", res=None
     """conv3d_up2 with the result written split-padded into `out` (B, 2Dl, 2Hl, 2Wl, Cout)."""
     x = _dev(x, "x")
     B, Dl, Hl, Wl, Cin = x.shape
-    Cout = scale.numel()
-    if out.shape != (B, 2 * Dl, 2 * Hl, 2 * Wl, Cout):
-        raise AssertionError(f"split output {out.shape} does not match {(B, 2 * Dl, 2 * Hl, 2 * Wl, Cout)}")
-    if res is not None:
-        res = _dev(res, "res")
-        if tuple(res.shape) != out.shape:
-            raise AssertionError(f"residual {tuple(res.shape)} does not match output {out.shape}")
-    _call("mvsgi_conv3d_up2_f32_out_split", x.data_ptr(), _ptr(w_packed_b3), w_layout, scale.data_ptr(), shift.data_ptr(), _ptr(res),
-          out.buf.data_ptr(), B, Cin, Dl, Hl, Wl, Cout, float(neg_slope), _stream_ptr(x))
+    dev = x.device
+    sc, sh, Cout = _scale_shift(scale, shift, dev)
+    shp = (B, 2 * Dl, 2 * Hl, 2 * Wl, Cout)
+    yp = _split_ptr(out, "out", dev, shp)
+    wp = _arg(w_packed_b3, "w_packed_b3", dev, torch.uint8, nbytes=_split_layout_bytes(w_layout, Cout, Cin))
+    _call("mvsgi_conv3d_up2_f32_out_split", x.data_ptr(), wp.data_ptr(), w_layout, sc, sh, _opt(res, "res", dev, shape=shp),
+          yp, B, Cin, Dl, Hl, Wl, Cout, float(neg_slope), _stream_ptr(x))
     out.fmt = "f16" if w_layout & CONV_F16 else "bf16"
     return out
 
@@ -499,16 +568,22 @@ def conv3d_up2_poly_plan(w_oidhw: torch.Tensor, D: int, H: int, W: int, fmt: str
     return (plan, unscale) if fmt == "f16" else plan
 
 
+def _poly_plan_ptr(plan, device, x: "SplitAct") -> int:
+    """The polyphase plan for x's (low-resolution) geometry, on the device, sized by the library's query -> its address."""
+    return _arg(plan, "plan", device, torch.uint8, nbytes=_lib.load().mvsgi_conv3d_up2_poly_plan_bytes(x.D, x.H, x.W)).data_ptr()
+
+
 def conv3d_up2_poly(x: "SplitAct", plan: torch.Tensor, scale, shift, neg_slope=0.01, out=None) -> torch.Tensor:
     """act(conv(trilinear_x2(x)) * scale + shift) for Cin = 32, Cout = 16 in polyphase form: x split-padded (low resolution)
     -> fp32 [B, 2D, 2H, 2W, 16]."""
-    if x.C != 32 or scale.numel() != 16:
+    xp = _split_ptr(x, "x")
+    dev = x.buf.device
+    if x.C != 32:
         raise AssertionError("conv3d_up2_poly is the 32 -> 16 kernel")
+    sc, sh, _ = _scale_shift(scale, shift, dev, 16)
     shp = (x.B, 2 * x.D, 2 * x.H, 2 * x.W, 16)
-    y = out if out is not None else torch.empty(shp, device=x.buf.device, dtype=torch.float32)
-    if tuple(y.shape) != shp or not y.is_contiguous():
-        raise AssertionError(f"output {tuple(y.shape)} does not match {shp}")
-    _call("mvsgi_conv3d_up2_poly_fmt", x.buf.data_ptr(), plan.data_ptr(), scale.data_ptr(), shift.data_ptr(), y.data_ptr(), 0, x.B, x.D, x.H, x.W,
+    y = torch.empty(shp, device=dev, dtype=torch.float32) if out is None else _arg(out, "out", dev, shape=shp)
+    _call("mvsgi_conv3d_up2_poly_fmt", xp, _poly_plan_ptr(plan, dev, x), sc, sh, y.data_ptr(), 0, x.B, x.D, x.H, x.W,
           float(neg_slope), _fmt_code(x.fmt), _stream_ptr(x.buf))
     return y
 
@@ -528,16 +603,21 @@ def conv3d_up2_poly_split(x: "SplitAct", plan: torch.Tensor, scale, shift, out: 
     the main kernel: the Winograd form where conv3d_up2_poly_wino_pays(), else the direct kernel; `direct` (or MVSGI_POLY_WINO=0)
     keeps the direct kernel, `wino` forces the Winograd form (an error where it does not apply).  `out.rec == "f32"` (set by the
     caller): the Winograd form writes fp32 records for conv3d_head_split instead of pairs -- an error where that form cannot run."""
-    if x.C != 32 or scale.numel() != 16 or out.shape != (x.B, 2 * x.D, 2 * x.H, 2 * x.W, 16):
-        raise AssertionError(f"conv3d_up2_poly_split: input {x.shape}, output {out.shape}")
+    xp = _split_ptr(x, "x")
+    dev = x.buf.device
+    if x.C != 32:
+        raise AssertionError(f"conv3d_up2_poly_split: input {x.shape}: the 32 -> 16 kernel")
+    yp = _split_ptr(out, "out", dev, (x.B, 2 * x.D, 2 * x.H, 2 * x.W, 16))
+    sc, sh, _ = _scale_shift(scale, shift, dev, 16)
+    pp = _poly_plan_ptr(plan, dev, x)
     if out.rec == "f32":          # the caller asked for fp32 records (SplitAct.rec): only the Winograd form writes them
         if x.fmt != "f16" or direct or not POLY_WINO:
             raise AssertionError(f"conv3d_up2_poly_split: fp32 records need the fp16 split's Winograd form (input holds {x.fmt} pieces, direct={direct})")
-        _call("mvsgi_conv3d_up2_poly_rec32", x.buf.data_ptr(), plan.data_ptr(), scale.data_ptr(), shift.data_ptr(), out.buf.data_ptr(),
+        _call("mvsgi_conv3d_up2_poly_rec32", xp, pp, sc, sh, yp,
               x.B, x.D, x.H, x.W, float(neg_slope), _stream_ptr(x.buf))
         out.fmt = x.fmt
         return out
-    _call("mvsgi_conv3d_up2_poly_fmt", x.buf.data_ptr(), plan.data_ptr(), scale.data_ptr(), shift.data_ptr(), out.buf.data_ptr(),
+    _call("mvsgi_conv3d_up2_poly_fmt", xp, pp, sc, sh, yp,
           5 if wino else (3 if (direct or not POLY_WINO) else 1), x.B, x.D, x.H, x.W, float(neg_slope), _fmt_code(x.fmt), _stream_ptr(x.buf))
     out.fmt = x.fmt
     return out
@@ -578,11 +658,13 @@ def conv3d_head_split(x: "SplitAct", w_packed, scale: float, shift: float, neg_s
         raise AssertionError(f"conv3d_head_split(f16={f16}) on a split-padded buffer holding {x.fmt} pieces")
     if x.rec == "f32" and not f16:
         raise AssertionError("conv3d_head_split: fp32 records are read in the fp16 split only")
-    y = out if out is not None else torch.empty((x.B, x.D, x.H, x.W, 1), device=x.buf.device, dtype=torch.float32)
-    if tuple(y.shape) != (x.B, x.D, x.H, x.W, 1) or not y.is_contiguous():
-        raise AssertionError(f"head output {tuple(y.shape)} does not match {(x.B, x.D, x.H, x.W, 1)}")
+    xp = _split_ptr(x, "x")
+    dev = x.buf.device
+    shp = (x.B, x.D, x.H, x.W, 1)
+    y = torch.empty(shp, device=dev, dtype=torch.float32) if out is None else _arg(out, "out", dev, shape=shp)
+    wp = _arg(w_packed, "w_packed", dev, torch.uint8, nbytes=_lib.load().mvsgi_conv3d_head_split_packed_weight_bytes(x.C))
     _call("mvsgi_conv3d_head_rec32_f16" if x.rec == "f32" else ("mvsgi_conv3d_head_split_f16" if f16 else "mvsgi_conv3d_head_split"),
-          x.buf.data_ptr(), w_packed.data_ptr(), float(scale),
+          xp, wp.data_ptr(), float(scale),
           float(shift), y.data_ptr(), x.B, x.C, x.D, x.H, x.W, float(neg_slope), _stream_ptr(x.buf))
     return y
 
@@ -621,6 +703,8 @@ class SplitAct:
         self.rec = "pairs"
         if buf is None:
             buf = torch.zeros((self.B, self.D + 2, self.H + 2, self.W + 2, self.C), device=device, dtype=torch.int32)
+        else:         # caller-owned storage (a batch slice buf[:B] / buf[i:j] of a larger buffer qualifies): checked like any other buffer
+            _arg(buf, "buf", torch.device(device), torch.int32, shape=(self.B, self.D + 2, self.H + 2, self.W + 2, self.C))
         self.buf = buf
 
     @property
@@ -632,13 +716,22 @@ class SplitAct:
         return self.buf.device
 
 
+def _split_ptr(s, name: str, device=None, shape=None) -> int:
+    """A split-padded activation a kernel reads or writes in place: a SplitAct whose storage still is the int32, contiguous, 16-byte
+    aligned [B, D + 2, H + 2, W + 2, C] device tensor its geometry says (`buf` is an attribute: it can be replaced after the
+    constructor's check), on `device` and of the logical `shape` where given -> the storage's address."""
+    if not isinstance(s, SplitAct):
+        raise TypeError(f"{name}: expected a SplitAct, got {type(s)}")
+    if shape is not None and s.shape != tuple(shape):
+        raise AssertionError(f"{name}: split-padded buffer {s.shape} does not match {tuple(shape)}")
+    return _arg(s.buf, f"{name}.buf", device, torch.int32, shape=(s.B, s.D + 2, s.H + 2, s.W + 2, s.C)).data_ptr()
+
+
 def act_to_split(x_ndhwc: torch.Tensor, out: Optional[SplitAct] = None, fmt: str = "bf16") -> SplitAct:
     x = _dev(x_ndhwc, "x")
     B, D, Hh, W, C = x.shape
     y = out if out is not None else SplitAct(B, D, Hh, W, C, x.device)
-    if y.shape != (B, D, Hh, W, C):
-        raise AssertionError(f"split buffer {y.shape} does not match {tuple(x.shape)}")
-    _call("mvsgi_act_f32_to_split_fmt", x.data_ptr(), y.buf.data_ptr(), B, C, D, Hh, W, _fmt_code(fmt), _stream_ptr(x))
+    _call("mvsgi_act_f32_to_split_fmt", x.data_ptr(), _split_ptr(y, "out", x.device, (B, D, Hh, W, C)), B, C, D, Hh, W, _fmt_code(fmt), _stream_ptr(x))
     y.fmt = fmt
     return y
 
@@ -646,8 +739,9 @@ def act_to_split(x_ndhwc: torch.Tensor, out: Optional[SplitAct] = None, fmt: str
 def act_from_split(x: SplitAct, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     if x.rec != "pairs":
         raise AssertionError("act_from_split reads (hi | lo) pairs; this buffer holds fp32 records")
-    y = out if out is not None else torch.empty(x.shape, device=x.buf.device, dtype=torch.float32)
-    _call("mvsgi_act_split_to_f32_fmt", x.buf.data_ptr(), y.data_ptr(), x.B, x.C, x.D, x.H, x.W, _fmt_code(x.fmt), _stream_ptr(x.buf))
+    xp = _split_ptr(x, "x")
+    y = torch.empty(x.shape, device=x.buf.device, dtype=torch.float32) if out is None else _arg(out, "out", x.buf.device, shape=x.shape)
+    _call("mvsgi_act_split_to_f32_fmt", xp, y.data_ptr(), x.B, x.C, x.D, x.H, x.W, _fmt_code(x.fmt), _stream_ptr(x.buf))
     return y
 
 
@@ -674,21 +768,24 @@ def conv3d_rs(x: SplitAct, w_packed_rs, scale, shift, res: Optional[SplitAct] = 
               out=None, out_f32: bool = False):
     """Register-stationary split-bf16 conv (Cin = Cout = 32, stride 1) on split-padded activations.  `out_f32`: the
     result is a plain fp32 [B, D, H, W, 32] tensor instead of a SplitAct (hand-over to an fp32-reading kernel)."""
-    Cout = scale.numel()
+    xp = _split_ptr(x, "x")
+    dev = x.buf.device
+    sc, sh, Cout = _scale_shift(scale, shift, dev)
+    shp = (x.B, x.D, x.H, x.W, Cout)
     if out_f32:
-        y = out if out is not None else torch.empty((x.B, x.D, x.H, x.W, Cout), device=x.buf.device, dtype=torch.float32)
+        y = torch.empty(shp, device=dev, dtype=torch.float32) if out is None else _arg(out, "out", dev, shape=shp)
         yp = y.data_ptr()
-        if tuple(y.shape) != (x.B, x.D, x.H, x.W, Cout) or not y.is_contiguous():
-            raise AssertionError(f"fp32 output {tuple(y.shape)} does not match {(x.B, x.D, x.H, x.W, Cout)}")
     else:
-        y = out if out is not None else SplitAct(x.B, x.D, x.H, x.W, Cout, x.buf.device)
-        yp = y.buf.data_ptr()
-        if y.shape != (x.B, x.D, x.H, x.W, Cout):
-            raise AssertionError(f"split output {y.shape} does not match {(x.B, x.D, x.H, x.W, Cout)}")
-    if res is not None and (res.shape != (x.B, x.D, x.H, x.W, Cout) or res.fmt != x.fmt):
+        y = out if out is not None else SplitAct(x.B, x.D, x.H, x.W, Cout, dev)
+        yp = _split_ptr(y, "out", dev, shp)
+    rp = None if res is None else _split_ptr(res, "res", dev, shp)
+    if res is not None and res.fmt != x.fmt:
         raise AssertionError(f"residual {res.shape} ({res.fmt}) does not match the output ({x.fmt})")
-    _call("mvsgi_conv3d_rs_split_fmt", x.buf.data_ptr(), w_packed_rs.data_ptr(), scale.data_ptr(), shift.data_ptr(),
-          None if res is None else res.buf.data_ptr(), yp, int(out_f32), x.B, x.C, x.D, x.H, x.W, Cout, float(neg_slope), _fmt_code(x.fmt),
+    nb = _lib.load().mvsgi_conv3d_rs_packed_weight_bytes(Cout, x.C)
+    if not nb:
+        raise AssertionError(f"conv3d_rs: no register-stationary kernel for {x.C} -> {Cout} channels")
+    _call("mvsgi_conv3d_rs_split_fmt", xp, _arg(w_packed_rs, "w_packed_rs", dev, torch.uint8, nbytes=nb).data_ptr(), sc, sh,
+          rp, yp, int(out_f32), x.B, x.C, x.D, x.H, x.W, Cout, float(neg_slope), _fmt_code(x.fmt),
           _stream_ptr(x.buf))
     if not out_f32:
         y.fmt = x.fmt
@@ -742,22 +839,21 @@ def conv3d_wino(x: SplitAct, w_packed, scale, shift, res: Optional[SplitAct] = N
     lib = _lib.load()
     if x.fmt not in ("f16", "f32p") or x.C != 32:
         raise AssertionError(f"conv3d_wino: needs a 32-channel input in the fp16 split or fp32-padded (got {x.C}, {x.fmt})")
+    xp = _split_ptr(x, "x")
+    dev = x.buf.device
     if out_f32:
-        y = out if out is not None else torch.empty(x.shape, device=x.buf.device, dtype=torch.float32)
-        if tuple(y.shape) != x.shape or not y.is_contiguous() or y.dtype != torch.float32:
-            raise AssertionError(f"fp32 output {tuple(y.shape)} does not match {x.shape}")
+        y = torch.empty(x.shape, device=dev, dtype=torch.float32) if out is None else _arg(out, "out", dev, shape=x.shape)
         yp = y.data_ptr()
     else:
-        y = out if out is not None else SplitAct(x.B, x.D, x.H, x.W, 32, x.buf.device)
-        if y.shape != x.shape:
-            raise AssertionError(f"split output {y.shape} does not match {x.shape}")
-        yp = y.buf.data_ptr()
-    if res is not None and (res.shape != x.shape or res.fmt != x.fmt):
+        y = out if out is not None else SplitAct(x.B, x.D, x.H, x.W, 32, dev)
+        yp = _split_ptr(y, "out", dev, x.shape)
+    rp = None if res is None else _split_ptr(res, "res", dev, x.shape)
+    if res is not None and res.fmt != x.fmt:
         raise AssertionError(f"residual {res.shape} ({res.fmt}) does not match the input ({x.fmt})")
-    if w_packed.numel() != lib.mvsgi_conv3d_wino32_packed_weight_bytes():
-        raise AssertionError("conv3d_wino: packed weights of the wrong size")
-    _call("mvsgi_conv3d_wino32_f16", x.buf.data_ptr(), w_packed.data_ptr(), scale.data_ptr(), shift.data_ptr(),
-          None if res is None else res.buf.data_ptr(), yp, int(out_f32), int(x.fmt == "f32p"), x.B, x.D, x.H, x.W, float(neg_slope),
+    wp = _arg(w_packed, "w_packed", dev, torch.uint8, nbytes=lib.mvsgi_conv3d_wino32_packed_weight_bytes())
+    sc, sh, _ = _scale_shift(scale, shift, dev, 32)
+    _call("mvsgi_conv3d_wino32_f16", xp, wp.data_ptr(), sc, sh,
+          rp, yp, int(out_f32), int(x.fmt == "f32p"), x.B, x.D, x.H, x.W, float(neg_slope),
           _stream_ptr(x.buf))
     if not out_f32:
         y.fmt = x.fmt
@@ -769,13 +865,13 @@ def conv3d_out_split(x, w_packed_b3, scale, shift, out: "SplitAct", res=None, st
     pack_conv_weights_f16x3 (scale carrying the unscale) and the output in the fp16 split."""
     x = _dev(x, "x")
     B, Din, Hin, Win, Cin = x.shape
-    Cout = scale.numel()
+    dev = x.device
+    sc, sh, Cout = _scale_shift(scale, shift, dev)
     Do, Ho, Wo = (Din - 1) // stride + 1, (Hin - 1) // stride + 1, (Win - 1) // stride + 1
-    if out.shape != (B, Do, Ho, Wo, Cout):
-        raise AssertionError(f"split output {out.shape} does not match {(B, Do, Ho, Wo, Cout)}")
-    if res is not None:
-        res = _dev(res, "res")
-    _call("mvsgi_conv3d_f32_out_split_fmt", x.data_ptr(), w_packed_b3.data_ptr(), scale.data_ptr(), shift.data_ptr(), _ptr(res), out.buf.data_ptr(),
+    shp = (B, Do, Ho, Wo, Cout)
+    yp = _split_ptr(out, "out", dev, shp)
+    wp = _arg(w_packed_b3, "w_packed_b3", dev, torch.uint8, nbytes=_split_layout_bytes(CONV_BF16X3, Cout, Cin))
+    _call("mvsgi_conv3d_f32_out_split_fmt", x.data_ptr(), wp.data_ptr(), sc, sh, _opt(res, "res", dev, shape=shp), yp,
           B, Cin, Din, Hin, Win, Cout, stride, float(neg_slope), _fmt_code(fmt), _stream_ptr(x))
     out.fmt = fmt
     return out
@@ -784,17 +880,21 @@ def conv3d_out_split(x, w_packed_b3, scale, shift, out: "SplitAct", res=None, st
 def conv3d_rs16(x: "SplitAct", w_packed_rs, scale, shift, neg_slope=0.01, out=None, out_split: Optional["SplitAct"] = None):
     """Register-stationary 16 -> 16 conv (post_vol) on a split-padded volume -> fp32 [B, D, H, W, 16], or (out_split) a
     split-padded volume of the same geometry (the hand-over to conv3d_s2rs)."""
-    if x.C != 16 or scale.numel() != 16:
+    xp = _split_ptr(x, "x")
+    dev = x.buf.device
+    if x.C != 16:
         raise AssertionError("conv3d_rs16 is the 16 -> 16 kernel")
+    sc, sh, _ = _scale_shift(scale, shift, dev, 16)
+    wp = _arg(w_packed_rs, "w_packed_rs", dev, torch.uint8, nbytes=_lib.load().mvsgi_conv3d_rs_packed_weight_bytes(16, 16)).data_ptr()
     if out_split is not None:
-        if out_split.shape != x.shape or out_split.buf.data_ptr() == x.buf.data_ptr():
+        if _split_ptr(out_split, "out_split", dev, x.shape) == xp:
             raise AssertionError(f"split output {out_split.shape} must match the input {x.shape} and be another buffer")
-        _call("mvsgi_conv3d_rs16_split_fmt", x.buf.data_ptr(), w_packed_rs.data_ptr(), scale.data_ptr(), shift.data_ptr(), out_split.buf.data_ptr(),
+        _call("mvsgi_conv3d_rs16_split_fmt", xp, wp, sc, sh, out_split.buf.data_ptr(),
               1, x.B, x.D, x.H, x.W, float(neg_slope), _fmt_code(x.fmt), _stream_ptr(x.buf))
         out_split.fmt = x.fmt
         return out_split
-    y = out if out is not None else torch.empty((x.B, x.D, x.H, x.W, 16), device=x.buf.device, dtype=torch.float32)
-    _call("mvsgi_conv3d_rs16_split_fmt", x.buf.data_ptr(), w_packed_rs.data_ptr(), scale.data_ptr(), shift.data_ptr(), y.data_ptr(), 0, x.B, x.D,
+    y = torch.empty(x.shape, device=dev, dtype=torch.float32) if out is None else _arg(out, "out", dev, shape=x.shape)
+    _call("mvsgi_conv3d_rs16_split_fmt", xp, wp, sc, sh, y.data_ptr(), 0, x.B, x.D,
           x.H, x.W, float(neg_slope), _fmt_code(x.fmt), _stream_ptr(x.buf))
     return y
 
@@ -827,9 +927,13 @@ def conv3d_s2rs(x: "SplitAct", w_packed, shift, out: "SplitAct", neg_slope=0.01,
     """16 -> 32 channel 3x3x3 stride-2 conv + scale / shift + LeakyReLU, split-padded in and out (LDS-DMA staging).
     `out_f32p` (fp16 split): the output is fp32-padded (plain fp32 records, fmt 'f32p') for a Winograd-form level 0 behind it."""
     Do, Ho, Wo = (x.D - 1) // 2 + 1, (x.H - 1) // 2 + 1, (x.W - 1) // 2 + 1
-    if x.C != 16 or out.shape != (x.B, Do, Ho, Wo, 32) or shift.numel() != 32:
-        raise AssertionError(f"conv3d_s2rs: input {x.shape} -> output {out.shape}, expected {(x.B, Do, Ho, Wo, 32)}")
-    _call("mvsgi_conv3d_s2rs_out_fmt", x.buf.data_ptr(), w_packed.data_ptr(), shift.data_ptr(), out.buf.data_ptr(), x.B, x.D, x.H, x.W,
+    xp = _split_ptr(x, "x")
+    dev = x.buf.device
+    if x.C != 16:
+        raise AssertionError(f"conv3d_s2rs: input {x.shape}: the 16 -> 32 kernel")
+    yp = _split_ptr(out, "out", dev, (x.B, Do, Ho, Wo, 32))
+    wp = _arg(w_packed, "w_packed", dev, torch.uint8, nbytes=_lib.load().mvsgi_conv3d_s2rs_packed_weight_bytes())
+    _call("mvsgi_conv3d_s2rs_out_fmt", xp, wp.data_ptr(), _arg(shift, "shift", dev, numel=32).data_ptr(), yp, x.B, x.D, x.H, x.W,
           float(neg_slope), float(unscale), _fmt_code(x.fmt), int(out_f32p), _stream_ptr(x.buf))
     out.fmt = "f32p" if out_f32p else x.fmt
     return out
@@ -888,20 +992,35 @@ def conv2d(x, w_oihw, w_packed, scale, shift, res=None, stride=1, neg_slope=0.01
             B, Cin, Hin, Win = x.shape
         else:
             B, Hin, Win, Cin = x.shape
-    Cout, k = scale.numel(), int(w_oihw.shape[-1])
+    dev = x.device
+    sc, sh, Cout = _scale_shift(scale, shift, dev)
+    if not isinstance(w_oihw, torch.Tensor) or w_oihw.dim() != 4:
+        raise TypeError(f"w_oihw: expected a [Cout, Cin, k, k] tensor, got {getattr(w_oihw, 'shape', type(w_oihw))}")
+    k = int(w_oihw.shape[-1])
+    wo = _arg(w_oihw, "w_oihw", dev, shape=(Cout, Cin, k, k)).data_ptr()
     pad = k // 2
     Ho, Wo = (Hin + 2 * pad - k) // stride + 1, (Win + 2 * pad - k) // stride + 1
-    if res is not None:
-        res = _dev(res, "res")
-        if tuple(res.shape) != (B, Ho, Wo, Cout):
-            raise AssertionError(f"residual {tuple(res.shape)} does not match output {(B, Ho, Wo, Cout)}")
+    wp = None
+    if w_packed is not None:
+        lib = _lib.load()
+        # the layouts conv2d's impl names (include/mvsgi.h, K2-2D); with AUTO / DIRECT on fp32 input nothing reads w_packed: form only
+        if impl == CONV_BF16X3 and k == 3 and Cin % 16 == 0 and Cout % 16 == 0:
+            wp = _arg(w_packed, "w_packed", dev, torch.uint8, nbytes=lib.mvsgi_conv2d_packed_weight_bytes_bf16x3(Cout, Cin))
+        elif impl == CONV_MFMA and k == 3 and Cin % 16 == 0 and Cout in (16, 32):
+            wp = _arg(w_packed, "w_packed", dev, numel=lib.mvsgi_conv2d_packed_weight_floats(Cout, Cin))
+        elif layout == 2:
+            wp = _arg(w_packed, "w_packed", dev, torch.uint8, nbytes=lib.mvsgi_conv2d_stem_packed_weight_bytes())
+        else:
+            wp = _arg(w_packed, "w_packed", dev, _PACKED)
+        wp = wp.data_ptr()
+    rp = _opt(res, "res", dev, shape=(B, Ho, Wo, Cout))
     if out_split is not None:
-        _check_split2d(out_split, B, Ho, Wo, x.device)
-        _call("mvsgi_conv2d_f32_out_split2d", x.data_ptr(), _ptr(w_oihw), _ptr(w_packed), scale.data_ptr(), shift.data_ptr(), _ptr(res),
+        _check_split2d(out_split, B, Ho, Wo, dev)
+        _call("mvsgi_conv2d_f32_out_split2d", x.data_ptr(), wo, wp, sc, sh, rp,
               out_split.data_ptr(), B, Cin, Hin, Win, Cout, k, stride, float(neg_slope), impl, layout, _stream_ptr(x))
         return out_split
-    y = torch.empty((B, Ho, Wo, Cout), device=x.device, dtype=torch.float32)
-    _call("mvsgi_conv2d_f32", x.data_ptr(), _ptr(w_oihw), _ptr(w_packed), scale.data_ptr(), shift.data_ptr(), _ptr(res), y.data_ptr(), B, Cin, Hin,
+    y = torch.empty((B, Ho, Wo, Cout), device=dev, dtype=torch.float32)
+    _call("mvsgi_conv2d_f32", x.data_ptr(), wo, wp, sc, sh, rp, y.data_ptr(), B, Cin, Hin,
           Win, Cout, k, stride, float(neg_slope), impl, layout, _stream_ptr(x))
     return y
 
@@ -1056,18 +1175,14 @@ def instance_norm(x, res=None, gamma=None, beta=None, eps: float = 1e-5, neg_slo
         res = _dev(res, "res")
         if tuple(res.shape) != tuple(x.shape):
             raise AssertionError(f"residual {tuple(res.shape)} does not match {tuple(x.shape)}")
-    for t, name in ((gamma, "gamma"), (beta, "beta")):
-        if t is not None and (t.numel() != C or not t.is_cuda or t.dtype != torch.float32 or not t.is_contiguous()):
-            raise AssertionError(f"{name} must be a contiguous fp32 [{C}] device tensor")
+    gp, bp = _opt(gamma, "gamma", x.device, numel=C), _opt(beta, "beta", x.device, numel=C)
     if out is None:
         out = torch.empty_like(x)
-    elif out.data_ptr() != x.data_ptr():
-        out = _dev(out, "out")
-        if tuple(out.shape) != tuple(x.shape) or out.data_ptr() % 16:
-            raise AssertionError(f"out {tuple(out.shape)} does not match {tuple(x.shape)}")
+    elif not (isinstance(out, torch.Tensor) and out.data_ptr() == x.data_ptr() and out.is_contiguous() and out.shape == x.shape):
+        _arg(out, "out", x.device, shape=x.shape)       # written in place: a copy (what _dev makes of awkward strides) would take the result with it
     nbytes = lib.mvsgi_instance_norm_ws_bytes(B, S, C)
     ws = torch.empty(max(int(nbytes), 16), device=x.device, dtype=torch.uint8)
-    _call("mvsgi_instance_norm_f32", x.data_ptr(), _ptr(res), _ptr(gamma), _ptr(beta), out.data_ptr(), ws.data_ptr(), B, S, C, float(eps),
+    _call("mvsgi_instance_norm_f32", x.data_ptr(), _ptr(res), gp, bp, out.data_ptr(), ws.data_ptr(), B, S, C, float(eps),
           float(neg_slope), _stream_ptr(x))
     return out
 
@@ -1682,20 +1797,16 @@ def deform_conv2d(x_nhwc, offset, w_packed, scale, shift, kernel_size, stride=(1
     offset = _dev(offset, "offset")
     N, Hh, W, Cin = x.shape
     Kh, Kw = kernel_size
-    Cout = scale.numel()
+    dev = x.device
+    sc, sh, Cout = _scale_shift(scale, shift, dev)
     Ho = (Hh + 2 * padding[0] - (dilation[0] * (Kh - 1) + 1)) // stride[0] + 1
     Wo = (W + 2 * padding[1] - (dilation[1] * (Kw - 1) + 1)) // stride[1] + 1
     if offset.dim() != 4 or tuple(offset.shape[1:]) != (2 * Kh * Kw, Ho, Wo) or offset.shape[0] not in (1, N):
         raise AssertionError(f"offset {tuple(offset.shape)} does not match [1|{N}, {2 * Kh * Kw}, {Ho}, {Wo}]")
-    if tuple(w_packed.shape) != (Kh * Kw, Cin, Cout):
-        raise AssertionError(f"w_packed {tuple(w_packed.shape)} does not match {(Kh * Kw, Cin, Cout)}")
-    if res is not None:
-        res = _dev(res, "res")
-        if tuple(res.shape) != (N, Ho, Wo, Cout):
-            raise AssertionError(f"residual {tuple(res.shape)} does not match output {(N, Ho, Wo, Cout)}")
-    y = torch.empty((N, Ho, Wo, Cout), device=x.device, dtype=torch.float32)
-    _call("mvsgi_deform_conv2d_f32", x.data_ptr(), offset.data_ptr(), int(offset.shape[0] == N and N > 1), w_packed.data_ptr(), scale.data_ptr(),
-          shift.data_ptr(), _ptr(res), y.data_ptr(), N, Cin, Hh, W, Cout, Kh, Kw, stride[0], stride[1], padding[0], padding[1], dilation[0],
+    wp = _arg(w_packed, "w_packed", dev, shape=(Kh * Kw, Cin, Cout))
+    y = torch.empty((N, Ho, Wo, Cout), device=dev, dtype=torch.float32)
+    _call("mvsgi_deform_conv2d_f32", x.data_ptr(), offset.data_ptr(), int(offset.shape[0] == N and N > 1), wp.data_ptr(), sc,
+          sh, _opt(res, "res", dev, shape=(N, Ho, Wo, Cout)), y.data_ptr(), N, Cin, Hh, W, Cout, Kh, Kw, stride[0], stride[1], padding[0], padding[1], dilation[0],
           dilation[1], float(neg_slope), _stream_ptr(x))
     return y
 
@@ -1707,9 +1818,22 @@ def split2d_buffer(N: int, H: int, W: int, device) -> torch.Tensor:
     return torch.zeros((N, H + 4, W + 4, 64), device=device, dtype=torch.uint8)
 
 
-def _check_split2d(t: torch.Tensor, N: int, H: int, W: int, device) -> None:
-    if t.dtype != torch.uint8 or tuple(t.shape) != (N, H + 4, W + 4, 64) or not t.is_contiguous() or t.device != device:
-        raise AssertionError(f"split-padded 2-D buffer {tuple(t.shape)} {t.dtype} {t.device} does not match {(N, H + 4, W + 4, 64)} uint8 on {device}")
+def _check_split2d(t: torch.Tensor, N: int, H: int, W: int, device, name: str = "out_split") -> None:
+    """A caller-owned 2-D split-padded buffer (split2d_buffer) for N images of H x W pixels."""
+    _arg(t, name, device, torch.uint8, shape=(N, H + 4, W + 4, 64))
+
+
+def _split2d_dims(x_split, name: str):
+    """A 2-D split-padded input, checked -> (N, H, W)."""
+    if not isinstance(x_split, torch.Tensor) or x_split.dim() != 4:
+        raise TypeError(f"{name}: expected a [N, H + 4, W + 4, 64] uint8 tensor, got {getattr(x_split, 'shape', type(x_split))}")
+    N, Hp, Wp, _ = x_split.shape
+    _arg(x_split, name, None, torch.uint8, shape=(N, Hp, Wp, 64))
+    return N, Hp - 4, Wp - 4
+
+
+def _rs2d_packed(wp, name: str, device) -> int:
+    return _arg(wp, name, device, torch.uint8, nbytes=_lib.load().mvsgi_resblock2d_split_packed_weight_bytes()).data_ptr()
 
 
 def f32_to_split2d(x_nhwc: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -1719,16 +1843,15 @@ def f32_to_split2d(x_nhwc: torch.Tensor, out: Optional[torch.Tensor] = None) -> 
         raise AssertionError(f"the 2-D split-padded format holds 16 channels, got {tuple(x.shape)}")
     if out is None:
         out = split2d_buffer(N, Hh, W, x.device)
-    _check_split2d(out, N, Hh, W, x.device)
+    _check_split2d(out, N, Hh, W, x.device, "out")
     _call("mvsgi_f32_to_split2d", x.data_ptr(), out.data_ptr(), N, Hh, W, _stream_ptr(x))
     return out
 
 
 def split2d_to_f32(x_split: torch.Tensor) -> torch.Tensor:
-    N, Hp, Wp, _ = x_split.shape
-    _check_split2d(x_split, N, Hp - 4, Wp - 4, x_split.device)
-    y = torch.empty((N, Hp - 4, Wp - 4, 16), device=x_split.device, dtype=torch.float32)
-    _call("mvsgi_split2d_to_f32", x_split.data_ptr(), y.data_ptr(), N, Hp - 4, Wp - 4, _stream_ptr(x_split))
+    N, Hh, W = _split2d_dims(x_split, "x_split")
+    y = torch.empty((N, Hh, W, 16), device=x_split.device, dtype=torch.float32)
+    _call("mvsgi_split2d_to_f32", x_split.data_ptr(), y.data_ptr(), N, Hh, W, _stream_ptr(x_split))
     return y
 
 
@@ -1748,30 +1871,26 @@ def resblock2d_split(x_split, wp1, shift1, wp2, shift2, neg_slope=0.01, out_spli
     """Fused 16 -> 16 residual block on a 2-D split-padded input [N, H + 4, W + 4, 64] uint8 (wp1 / wp2 carry the scales).
     out_split: the split-padded buffer that receives the output (returned); None: the output is a plain fp32 [N, H, W, 16]
     tensor."""
-    N, Hp, Wp, _ = x_split.shape
-    Hh, W = Hp - 4, Wp - 4
-    _check_split2d(x_split, N, Hh, W, x_split.device)
-    if shift1.numel() != 16 or shift2.numel() != 16:
-        raise AssertionError("resblock2d_split is the 16-channel block")
+    N, Hh, W = _split2d_dims(x_split, "x_split")
+    dev = x_split.device
     if out_split is not None:
-        _check_split2d(out_split, N, Hh, W, x_split.device)
+        _check_split2d(out_split, N, Hh, W, dev)
         y = out_split
     else:
-        y = torch.empty((N, Hh, W, 16), device=x_split.device, dtype=torch.float32)
-    _call("mvsgi_resblock2d_split", x_split.data_ptr(), wp1.data_ptr(), shift1.data_ptr(), wp2.data_ptr(), shift2.data_ptr(), y.data_ptr(),
+        y = torch.empty((N, Hh, W, 16), device=dev, dtype=torch.float32)
+    _call("mvsgi_resblock2d_split", x_split.data_ptr(), _rs2d_packed(wp1, "wp1", dev), _arg(shift1, "shift1", dev, numel=16).data_ptr(),
+          _rs2d_packed(wp2, "wp2", dev), _arg(shift2, "shift2", dev, numel=16).data_ptr(), y.data_ptr(),
           int(out_split is not None), N, Hh, W, float(neg_slope), _stream_ptr(x_split))
     return y
 
 
 def conv2d_s2_split(x_split, w_packed, shift, out_split, neg_slope=0.01) -> torch.Tensor:
     """16 -> 16 channel 3x3 stride-2 layer on 2-D split-padded activations (weights from pack_resblock2d_split_weights)."""
-    N, Hp, Wp, _ = x_split.shape
-    Hh, W = Hp - 4, Wp - 4
-    _check_split2d(x_split, N, Hh, W, x_split.device)
-    _check_split2d(out_split, N, (Hh - 1) // 2 + 1, (W - 1) // 2 + 1, x_split.device)
-    if shift.numel() != 16:
-        raise AssertionError("conv2d_s2_split is the 16-channel layer")
-    _call("mvsgi_conv2d_s2_split", x_split.data_ptr(), w_packed.data_ptr(), shift.data_ptr(), out_split.data_ptr(), N, Hh, W, float(neg_slope),
+    N, Hh, W = _split2d_dims(x_split, "x_split")
+    dev = x_split.device
+    _check_split2d(out_split, N, (Hh - 1) // 2 + 1, (W - 1) // 2 + 1, dev)
+    _call("mvsgi_conv2d_s2_split", x_split.data_ptr(), _rs2d_packed(w_packed, "w_packed", dev), _arg(shift, "shift", dev, numel=16).data_ptr(),
+          out_split.data_ptr(), N, Hh, W, float(neg_slope),
           _stream_ptr(x_split))
     return out_split
 
@@ -1780,9 +1899,13 @@ def resblock2d(x_nhwc, wp1, scale1, shift1, wp2, scale2, shift2, neg_slope=0.01)
     """Fused 16 -> 16 residual block (two 3x3 convs + BN + LeakyReLU + skip): x [N, H, W, 16] -> y, same shape."""
     x = _dev(x_nhwc, "x")
     N, Hh, W, C = x.shape
-    if C != 16 or scale1.numel() != 16 or scale2.numel() != 16:
+    if C != 16:
         raise AssertionError(f"resblock2d is the 16-channel block, got x {tuple(x.shape)}")
+    dev = x.device
+    nb = _lib.load().mvsgi_conv2d_packed_weight_bytes_bf16x3(16, 16)
+    p1, p2 = (_arg(w, n, dev, torch.uint8, nbytes=nb).data_ptr() for w, n in ((wp1, "wp1"), (wp2, "wp2")))
+    (sc1, sh1, _), (sc2, sh2, _) = _scale_shift(scale1, shift1, dev, 16, "1"), _scale_shift(scale2, shift2, dev, 16, "2")
     y = torch.empty_like(x)
-    _call("mvsgi_resblock2d_f32", x.data_ptr(), wp1.data_ptr(), scale1.data_ptr(), shift1.data_ptr(), wp2.data_ptr(), scale2.data_ptr(),
-          shift2.data_ptr(), y.data_ptr(), N, Hh, W, float(neg_slope), _stream_ptr(x))
+    _call("mvsgi_resblock2d_f32", x.data_ptr(), p1, sc1, sh1, p2, sc2,
+          sh2, y.data_ptr(), N, Hh, W, float(neg_slope), _stream_ptr(x))
     return y

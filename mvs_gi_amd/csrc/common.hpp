@@ -46,6 +46,9 @@ inline hipStream_t as_stream(mvsgi_stream_t s) { return reinterpret_cast<hipStre
 
 inline long long cdiv(long long a, long long b) { return (a + b - 1) / b; }
 
+// p is a multiple of a (a power of two); a null pointer is aligned
+inline bool aligned(const void* p, unsigned a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
+
 // cameras of a rig: one validity bit per camera in a byte (csrc/sweep.hip); mvsgi_sweep_max_cams() and the size of the
 // back-projection's camera table (csrc/reproject.hip)
 constexpr int kMaxCams = 8;

@@ -53,15 +53,8 @@ __global__ __launch_bounds__(256) void confidence_kernel(const float* __restrict
     const Axis2 ay = axis2f(oy, H, rs), ax = axis2f(ox, W, rs);
     const long long HW = (long long)H * W;
     const float* cb = costs + (long long)b * D * HW;
-    const long long o00 = (long long)ay.i0 * W + ax.i0, o01 = (long long)ay.i0 * W + ax.i1;
-    const long long o10 = (long long)ay.i1 * W + ax.i0, o11 = (long long)ay.i1 * W + ax.i1;
-    // a tap under a weight of exactly 0 is not blended, as in softargmin_pixel()
-    const bool x1 = ax.l1 == 0.f, y1 = ay.l1 == 0.f;
-    auto sample = [&](int d) {
-        const float* p = cb + d * HW;
-        const float p01 = x1 ? 0.f : p[o01], p10 = y1 ? 0.f : p[o10], p11 = (x1 || y1) ? 0.f : p[o11];
-        return sa_blend(ay.l0, ay.l1, ax.l0, ax.l1, p[o00], p01, p10, p11);
-    };
+    const Taps taps = sa_taps(ay, ax, W);
+    auto sample = [&](int d) { return sa_sample(cb + d * HW, ay, ax, taps); };
 
     float m = -INFINITY, V = 0.f, mu;
     int k = 0;

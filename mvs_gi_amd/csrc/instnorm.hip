@@ -222,7 +222,7 @@ __global__ __launch_bounds__(kThreads) void instnorm_apply(const float* x, const
     }
 }
 
-inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+using mvsgi::aligned;
 
 int check_dims(const char* what, int B, int S, int C) {
     MVSGI_REQUIRE(B > 0 && C > 0, "%s: non-positive dimension (B %d, C %d)", what, B, C);
@@ -246,7 +246,7 @@ extern "C" int mvsgi_instance_norm_f32(const float* x, const float* res, const f
     const char* what = "mvsgi_instance_norm_f32";
     MVSGI_REQUIRE(x && y && ws, "%s: null pointer (x, y and ws are required)", what);
     if (check_dims(what, B, S, C)) return 1;
-    MVSGI_REQUIRE(aligned16(x) && aligned16(y) && aligned16(ws) && (!res || aligned16(res)),
+    MVSGI_REQUIRE(aligned(x, 16) && aligned(y, 16) && aligned(ws, 16) && (!res || aligned(res, 16)),
                   "%s: x, res, y and ws must be 16-byte aligned", what);
     MVSGI_REQUIRE(eps >= 0.f, "%s: eps = %g must be >= 0", what, (double)eps);
     const Chunking k = chunking(S, C);

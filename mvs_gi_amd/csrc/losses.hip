@@ -8,24 +8,21 @@
 //                         either read (pred_cost, FUSED = false) or are those of the soft-argmin's softmax at that pixel, from
 //                         the low-resolution costs by csrc/confidence.hip's expressions (sa_blend, max, expf(-(m - v)), the sum in
 //                         order of d, e / S): no [B, D, OH, OW] tensor is read or written.  D <= 16 and D <= 32 gather the blended
-//                         candidates once into registers; larger D walks them again per pass.  A thread keeps the sums of the
-//                         cross-entropy and smooth-L1 addends as compensated float64 pairs and the counts as integers; wave
-//                         reduction by shuffles, block reduction through LDS, one record of kRec doubles per block.  G depends on
-//                         OH * OW alone: frame b's records, and with them row b, do not depend on B.
-//   2. losses_finalise    grid B + 1: block b sums frame b's G records in index order -> row b; block B sums every frame the same
-//                         way (one thread per frame) and then the frames' sums in frame order -> the pooled row.
-// No atomics, no allocation, no host synchronisation: the same inputs give the same bits on every run.
+//                         candidates once into registers; larger D walks them again per pass.  The thread's record: the sums of
+//                         the cross-entropy and smooth-L1 addends (pairs), the two counts and the in-bounds mismatches.
+//   2. losses_finalise    frame_finalise with WriteRow's formulas.
+// The table's scheme -- records, slab, merge order, finalise -- is csrc/frame_reduce.hpp's; G = ceil(OH * OW / 256), at most 256.
 #include "common.hpp"
 
 #include <cmath>
 
 namespace {
 
+#include "frame_reduce.hpp"
 #include "softargmin_axes.hpp"
 
-constexpr int kThreads = 256;
-constexpr int kWaves = kThreads / 64;
-constexpr int kMaxReduceBlocks = 256;     // records per frame (what losses_finalise sums in order)
+using mvsgi::aligned;
+constexpr int kMaxReduceBlocks = 256;     // records per frame (what frame_finalise sums in order)
 constexpr int kRec = 8;                   // doubles per record
 constexpr int kCols = 5;                  // vol, smooth_l1, inbounds, n_vol, n_px
 
@@ -36,48 +33,15 @@ struct Params {
     float hi, near_inv, far_inv, rs;
 };
 
-// The slab, in doubles: [B][G][kRec] records | [B][kRec] frame sums (written and read by the pooled row's block)
-struct Layout {
-    int G;
-    size_t rec, fsum, total;
+struct RecMerge {
+    __device__ __forceinline__ void operator()(double* a, const double* b) const {
+        sum_merge(a[F_VH], a[F_VL], b[F_VH], b[F_VL]);
+        sum_merge(a[F_SH], a[F_SL], b[F_SH], b[F_SL]);
+        a[F_NV] += b[F_NV];
+        a[F_NP] += b[F_NP];
+        a[F_MM] += b[F_MM];
+    }
 };
-
-inline Layout layout(int B, int OH, int OW) {
-    Layout l;
-    const long long g = mvsgi::cdiv((long long)OH * OW, kThreads);
-    l.G = (int)(g < 1 ? 1 : g > kMaxReduceBlocks ? kMaxReduceBlocks : g);
-    l.rec = 0;
-    l.fsum = l.rec + (size_t)B * l.G * kRec;
-    l.total = l.fsum + (size_t)B * kRec;
-    return l;
-}
-
-// torch.clamp: min(max(t, lo), hi), a NaN stays a NaN
-__device__ __forceinline__ float clamp_nan(float t, float lo, float hi) { return t != t ? t : fminf(fmaxf(t, lo), hi); }
-
-// (h, l) += x with the rounding error of h + x kept in l (Knuth's two-sum; h stays the plain running sum)
-__device__ __forceinline__ void sum_add(double& h, double& l, double x) {
-    const double t = h + x;
-    const double bp = t - h;
-    l += (h - (t - bp)) + (x - bp);
-    h = t;
-}
-__device__ __forceinline__ void sum_merge(double& h, double& l, double bh, double bl) {
-    sum_add(h, l, bh);
-    l += bl;
-}
-// the pair's value; an infinite or NaN sum leaves a NaN in l, the sum is then h
-__device__ __forceinline__ double sum_value(double h, double l) { return l - l == 0.0 ? h + l : h; }
-
-__device__ __forceinline__ double shfl_down(double v, int off) { return __shfl_down(v, off, 64); }
-
-__device__ __forceinline__ void rec_merge(double* a, const double* b) {
-    sum_merge(a[F_VH], a[F_VL], b[F_VH], b[F_VL]);
-    sum_merge(a[F_SH], a[F_SL], b[F_SH], b[F_SL]);
-    a[F_NV] += b[F_NV];
-    a[F_NP] += b[F_NP];
-    a[F_MM] += b[F_MM];
-}
 
 // ATen's binary_cross_entropy per element: std::max(log, -100) keeps a NaN
 __device__ __forceinline__ float bce(float t, float p) {
@@ -102,7 +66,6 @@ __global__ __launch_bounds__(kThreads) void losses_reduce(const float* __restric
                                                           const float* __restrict__ inv_list, const unsigned char* __restrict__ vol_mask,
                                                           const unsigned char* __restrict__ px_mask, float* __restrict__ true_cost,
                                                           double* __restrict__ recs, int npix, Params k) {
-    __shared__ double red[kWaves][kRec];
     const int t = threadIdx.x, b = blockIdx.y, G = gridDim.x, D = k.D;
     const long long fbase = (long long)b * npix;            // the frame in a [B][OH][OW] tensor
     const long long vbase = (long long)b * D * npix;        // the frame in a [B][D][OH][OW] tensor
@@ -157,14 +120,8 @@ __global__ __launch_bounds__(kThreads) void losses_reduce(const float* __restric
             const Axis2 ay = axis2f(oy, k.H, k.rs), ax = axis2f(ox, k.W, k.rs);
             const long long HW = (long long)k.H * k.W;
             const float* cb = costs + (long long)b * D * HW;
-            const long long o00 = (long long)ay.i0 * k.W + ax.i0, o01 = (long long)ay.i0 * k.W + ax.i1;
-            const long long o10 = (long long)ay.i1 * k.W + ax.i0, o11 = (long long)ay.i1 * k.W + ax.i1;
-            const bool x1 = ax.l1 == 0.f, y1 = ay.l1 == 0.f;
-            auto sample = [&](int d) {
-                const float* p = cb + d * HW;
-                const float p01 = x1 ? 0.f : p[o01], p10 = y1 ? 0.f : p[o10], p11 = (x1 || y1) ? 0.f : p[o11];
-                return sa_blend(ay.l0, ay.l1, ax.l0, ax.l1, p[o00], p01, p10, p11);
-            };
+            const Taps taps = sa_taps(ay, ax, k.W);
+            auto sample = [&](int d) { return sa_sample(cb + d * HW, ay, ax, taps); };
             float m = -INFINITY, S = 0.f;
             if constexpr (DMAX > 0) {
                 float v[DMAX];
@@ -195,72 +152,29 @@ __global__ __launch_bounds__(kThreads) void losses_reduce(const float* __restric
     double r[kRec];
     r[F_VH] = a.vh, r[F_VL] = a.vl, r[F_SH] = a.sh, r[F_SL] = a.sl;
     r[F_NV] = (double)a.nv, r[F_NP] = (double)a.np, r[F_MM] = (double)a.mm, r[F_PAD] = 0.0;
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-        double o[kRec];
-#pragma unroll
-        for (int j = 0; j < kRec; ++j) o[j] = shfl_down(r[j], off);
-        rec_merge(r, o);
-    }
-    if ((t & 63) == 0) {
-#pragma unroll
-        for (int j = 0; j < kRec; ++j) red[t >> 6][j] = r[j];
-    }
-    __syncthreads();
-    if (t == 0) {
-        for (int w = 1; w < kWaves; ++w) rec_merge(r, red[w]);
-        double* out = recs + ((long long)b * G + blockIdx.x) * kRec;
-#pragma unroll
-        for (int j = 0; j < kRec; ++j) out[j] = r[j];
-    }
+    block_reduce_store<kRec>(r, recs, b, G, RecMerge());
 }
 
-// count records from src, in index order -> x
-__device__ __forceinline__ void sum_records(const double* src, int count, double* x) {
-#pragma unroll
-    for (int j = 0; j < kRec; ++j) x[j] = 0.0;
-    for (int g = 0; g < count; ++g) rec_merge(x, src + (long long)g * kRec);
-}
-
-__device__ __forceinline__ void write_row(const double* x, double* row, int have_vol, int have_pred, int inbounds) {
-    const double nan = __builtin_nan("");
-    row[0] = have_vol ? sum_value(x[F_VH], x[F_VL]) / x[F_NV] : nan;
-    row[1] = have_pred ? sum_value(x[F_SH], x[F_SL]) / x[F_NP] : nan;
-    row[2] = have_pred && inbounds ? 100.0 * x[F_MM] / x[F_NP] : nan;
-    row[3] = have_vol ? x[F_NV] : nan;
-    row[4] = x[F_NP];
-}
-
-__global__ __launch_bounds__(kThreads) void losses_finalise(const double* recs, double* fsum,
-                                                            double* __restrict__ out, int B, int G, int have_vol, int have_pred,
-                                                            int inbounds) {
-    const int t = threadIdx.x, b = blockIdx.x;
-    double x[kRec];
-    if (b < B) {
-        if (t == 0) {
-            sum_records(recs + (long long)b * G * kRec, G, x);
-            write_row(x, out + (long long)b * kCols, have_vol, have_pred, inbounds);
-        }
-        return;
+struct WriteRow {
+    __device__ __forceinline__ void operator()(const double* x, double* row, int have_vol, int have_pred, int inbounds) const {
+        const double nan = __builtin_nan("");
+        row[0] = have_vol ? sum_value(x[F_VH], x[F_VL]) / x[F_NV] : nan;
+        row[1] = have_pred ? sum_value(x[F_SH], x[F_SL]) / x[F_NP] : nan;
+        row[2] = have_pred && inbounds ? 100.0 * x[F_MM] / x[F_NP] : nan;
+        row[3] = have_vol ? x[F_NV] : nan;
+        row[4] = x[F_NP];
     }
-    // the pooled row: every frame's sum as its own block computes it, then the frames in frame order
-    for (int f = t; f < B; f += kThreads) {
-        sum_records(recs + (long long)f * G * kRec, G, x);
-#pragma unroll
-        for (int j = 0; j < kRec; ++j) fsum[(long long)f * kRec + j] = x[j];
-    }
-    __syncthreads();
-    if (t == 0) {
-        sum_records(fsum, B, x);
-        write_row(x, out + (long long)B * kCols, have_vol, have_pred, inbounds);
-    }
+};
+
+__global__ __launch_bounds__(kThreads) void losses_finalise(const double* recs, double* fsum, double* __restrict__ out, int B, int G,
+                                                            int have_vol, int have_pred, int inbounds) {
+    frame_finalise<kRec, kCols>(recs, fsum, out, B, G, RecMerge(), WriteRow(), have_vol, have_pred, inbounds);
 }
 
-inline bool aligned(const void* p, unsigned a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
+// a reduce block per kThreads pixels of a frame
+inline FrameSlab layout(int B, int OH, int OW) { return frame_slab(B, (long long)OH * OW, kThreads, kMaxReduceBlocks, kRec); }
 
-bool dims_ok(int B, int OH, int OW) {
-    return B >= 1 && OH >= 1 && OW >= 1 && B < 65535 && (long long)OH * OW < (1ll << 31) - (long long)kMaxReduceBlocks * kThreads;
-}
+bool dims_ok(int B, int OH, int OW) { return frame_dims_ok(B, OH, OW, (long long)kMaxReduceBlocks * kThreads); }
 
 }  // namespace
 
@@ -300,7 +214,7 @@ extern "C" int mvsgi_losses_f32(const float* labels, const float* pred, const fl
                       "%s: caller's output %d x %d is not floor(%d x %d * %g) = %g x %g", what, OH, OW, H, W, scale, oh, ow);
         rs = (float)(1.0 / scale);
     }
-    const Layout l = layout(B, OH, OW);
+    const FrameSlab l = layout(B, OH, OW);
     MVSGI_REQUIRE(ws_bytes >= l.total * sizeof(double), "%s: workspace of %zu bytes is too small (mvsgi_losses_ws_bytes: %zu)", what,
                   ws_bytes, l.total * sizeof(double));
     MVSGI_REQUIRE(aligned(ws, 8) && aligned(out, 8), "%s: ws and out must be 8-byte aligned", what);

@@ -6,11 +6,9 @@
 //   1. metrics_reduce     grid (G, B): one flat pass over a frame's preds / target / mask in quads of 16 bytes (4 of the mask), the
 //                         last H * W % 4 pixels one by one; both forms from one load.  A frame is a flat run: W % 4 needs no
 //                         row tail, and where H * W % 4 != 0 the frames that start off a 16-byte boundary use the same quads
-//                         through 4-byte aligned loads.  A thread
-//                         keeps S2 = sum e^2 and S1 = sum |e| as compensated float64 pairs (two-sum: the pair holds the sum
-//                         of its fp32 addends to ~2^-100), the counts as integers and the four extrema as fp32; wave reduction by
-//                         shuffles, block reduction through LDS, one record of kRec doubles per block into the slab.  G depends on
-//                         H * W alone, so frame b's record set, and with it frame b's row, does not depend on B.
+//                         through 4-byte aligned loads.  The thread's record, per form: S2 = sum e^2 and S1 = sum |e| (pairs: a
+//                         pair holds the sum of its fp32 addends to ~2^-100), the two counts and the four extrema (fp32 in the
+//                         thread, merged by NaN-sticky min / max).
 //   2. metrics_finalise   grid B: sums frame b's G records in index order -> the frame's sums (slab) and the reduction columns of
 //                         row b; c1 / c2 of the SSIM from the frame's extrema, or from those of every record of the launch
 //                         (extrema do not depend on an order).
@@ -20,13 +18,15 @@
 //                         by 32 consecutive lanes): a half-wave always touches consecutive addresses, no bank is hit twice.
 //   4. metrics_last       grid B + 1: block b sums frame b's tile sums (fixed order); block B the pooled row from the frames' sums
 //                         in frame order.
-// No atomics, no allocation, no host synchronisation: the same inputs give the same bits on every run.
+// The records, the slab's first two parts and the merge order are csrc/frame_reduce.hpp's (G = ceil(H * W / 4096), at most 64); the
+// two finalising kernels are this file's own: they carry two forms, the extrema and the SSIM tiles.
 #include "common.hpp"
 
 namespace {
 
-constexpr int kThreads = 256;
-constexpr int kWaves = kThreads / 64;
+#include "frame_reduce.hpp"
+
+using mvsgi::aligned;
 constexpr int kMaxReduceBlocks = 64;      // records per frame (what metrics_finalise sums in order)
 constexpr int kPixPerBlock = 4096;        // a reduce block covers at least this many pixels, while there are fewer than the cap
 constexpr int kFields = 10;               // per form: S2 hi, S2 lo, S1 hi, S1 lo, NB, n, minP, maxP, minT, maxT
@@ -51,30 +51,24 @@ struct Gauss {
     double w[kTaps];
 };
 
-// The slab, in doubles: [B][G][kRec] records | [B][kRec] frame sums | [B][2 forms][c1, c2] | [2 forms][B][T] tile sums
-struct Layout {
-    int G, tx, ty, T;
-    size_t rec, fsum, consts, tiles, total;
+// The slab, in doubles: FrameSlab's two parts | [B][2 forms][c1, c2] | [2 forms][B][T] tile sums
+struct Layout : FrameSlab {
+    int tx, ty, T;
+    size_t consts, tiles;
 };
 
 inline Layout layout(int B, int H, int W) {
     Layout l;
-    const long long npix = (long long)H * W;
-    long long g = mvsgi::cdiv(npix, kPixPerBlock);
-    l.G = (int)(g < 1 ? 1 : g > kMaxReduceBlocks ? kMaxReduceBlocks : g);
+    // a reduce block per kPixPerBlock pixels of a frame
+    static_cast<FrameSlab&>(l) = frame_slab(B, (long long)H * W, kPixPerBlock, kMaxReduceBlocks, kRec);
     l.ty = H >= kTaps && W >= kTaps ? (int)mvsgi::cdiv(H - kTaps + 1, kTileH) : 0;
     l.tx = H >= kTaps && W >= kTaps ? (int)mvsgi::cdiv(W - kTaps + 1, kTileW) : 0;
     l.T = l.tx * l.ty;
-    l.rec = 0;
-    l.fsum = l.rec + (size_t)B * l.G * kRec;
-    l.consts = l.fsum + (size_t)B * kRec;
+    l.consts = l.total;
     l.tiles = l.consts + (size_t)B * 4;
     l.total = l.tiles + (size_t)2 * B * l.T;
     return l;
 }
-
-// torch.clamp: min(max(t, lo), hi), a NaN stays a NaN
-__device__ __forceinline__ float clamp_nan(float t, float lo, float hi) { return t != t ? t : fminf(fmaxf(t, lo), hi); }
 
 // MVSMetric.clamp_and_scale (form 0), behind InverseMetricWrapper's 1 / x (form 1)
 __device__ __forceinline__ void scaled(int form, float p, float t, const Params& k, float& P, float& T) {
@@ -91,20 +85,6 @@ __device__ __forceinline__ float min_nan(float m, float v) { return (v < m || v 
 __device__ __forceinline__ float max_nan(float m, float v) { return (v > m || v != v) ? v : m; }
 __device__ __forceinline__ double dmin_nan(double m, double v) { return (v < m || v != v) ? v : m; }
 __device__ __forceinline__ double dmax_nan(double m, double v) { return (v > m || v != v) ? v : m; }
-
-// (h, l) += x with the rounding error of h + x kept in l (Knuth's two-sum; h stays the plain running sum)
-__device__ __forceinline__ void sum_add(double& h, double& l, double x) {
-    const double t = h + x;
-    const double bp = t - h;
-    l += (h - (t - bp)) + (x - bp);
-    h = t;
-}
-__device__ __forceinline__ void sum_merge(double& h, double& l, double bh, double bl) {
-    sum_add(h, l, bh);
-    l += bl;
-}
-// the pair's value; an infinite or NaN sum leaves a NaN in l, the sum is then h
-__device__ __forceinline__ double sum_value(double h, double l) { return l - l == 0.0 ? h + l : h; }
 
 struct Acc {
     double s2h[2], s2l[2], s1h[2], s1l[2];
@@ -134,39 +114,29 @@ __device__ __forceinline__ void pixel(Acc& a, float p, float t, unsigned m, cons
     a.n += v ? 1u : 0u;
 }
 
-__device__ __forceinline__ double shfl_down(double v, int off) { return __shfl_down(v, off, 64); }
+// the fields of one form: x (op)= y
+__device__ __forceinline__ void form_merge(double* x, const double* y) {
+    sum_merge(x[F_S2H], x[F_S2L], y[F_S2H], y[F_S2L]);
+    sum_merge(x[F_S1H], x[F_S1L], y[F_S1H], y[F_S1L]);
+    x[F_NB] += y[F_NB];
+    x[F_N] += y[F_N];
+    x[F_MINP] = dmin_nan(x[F_MINP], y[F_MINP]);
+    x[F_MAXP] = dmax_nan(x[F_MAXP], y[F_MAXP]);
+    x[F_MINT] = dmin_nan(x[F_MINT], y[F_MINT]);
+    x[F_MAXT] = dmax_nan(x[F_MAXT], y[F_MAXT]);
+}
 
 // field j of record a (op)= field j of record b
-__device__ __forceinline__ void rec_merge(double* a, const double* b) {
+struct RecMerge {
+    __device__ __forceinline__ void operator()(double* a, const double* b) const {
 #pragma unroll
-    for (int f = 0; f < 2; ++f) {
-        double* x = a + f * kFields;
-        const double* y = b + f * kFields;
-        sum_merge(x[F_S2H], x[F_S2L], y[F_S2H], y[F_S2L]);
-        sum_merge(x[F_S1H], x[F_S1L], y[F_S1H], y[F_S1L]);
-        x[F_NB] += y[F_NB];
-        x[F_N] += y[F_N];
-        x[F_MINP] = dmin_nan(x[F_MINP], y[F_MINP]);
-        x[F_MAXP] = dmax_nan(x[F_MAXP], y[F_MAXP]);
-        x[F_MINT] = dmin_nan(x[F_MINT], y[F_MINT]);
-        x[F_MAXT] = dmax_nan(x[F_MAXT], y[F_MAXT]);
+        for (int f = 0; f < 2; ++f) form_merge(a + f * kFields, b + f * kFields);
     }
-}
-
-__device__ __forceinline__ void rec_init(double* r) {
-#pragma unroll
-    for (int f = 0; f < 2; ++f) {
-        double* x = r + f * kFields;
-        x[F_S2H] = x[F_S2L] = x[F_S1H] = x[F_S1L] = x[F_NB] = x[F_N] = 0.0;
-        x[F_MINP] = x[F_MINT] = __builtin_inf();
-        x[F_MAXP] = x[F_MAXT] = -__builtin_inf();
-    }
-}
+};
 
 __global__ __launch_bounds__(kThreads) void metrics_reduce(const float* __restrict__ preds, const float* __restrict__ target,
                                                            const unsigned char* __restrict__ mask, double* __restrict__ recs,
                                                            int npix, Params k) {
-    __shared__ double red[kWaves][kRec];
     const int t = threadIdx.x, b = blockIdx.y, G = gridDim.x;
     const long long base = (long long)b * npix;
     const float* pb = preds + base;
@@ -215,43 +185,16 @@ __global__ __launch_bounds__(kThreads) void metrics_reduce(const float* __restri
         x[F_MINT] = (double)a.mnT[f];
         x[F_MAXT] = (double)a.mxT[f];
     }
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-        double o[kRec];
-#pragma unroll
-        for (int j = 0; j < kRec; ++j) o[j] = shfl_down(r[j], off);
-        rec_merge(r, o);
-    }
-    if ((t & 63) == 0) {
-#pragma unroll
-        for (int j = 0; j < kRec; ++j) red[t >> 6][j] = r[j];
-    }
-    __syncthreads();
-    if (t == 0) {
-        for (int w = 1; w < kWaves; ++w) rec_merge(r, red[w]);
-        double* out = recs + ((long long)b * G + blockIdx.x) * kRec;
-#pragma unroll
-        for (int j = 0; j < kRec; ++j) out[j] = r[j];
-    }
+    block_reduce_store<kRec>(r, recs, b, G, RecMerge());
 }
 
 // threads 0 and 1 (form f): count records of kRec doubles from src, in index order -> dst[f * kFields ...]
-__device__ __forceinline__ void sum_records(const double* __restrict__ src, int count, double* dst, int f) {
+__device__ __forceinline__ void sum_form(const double* __restrict__ src, int count, double* dst, int f) {
     double x[kFields];
     x[F_S2H] = x[F_S2L] = x[F_S1H] = x[F_S1L] = x[F_NB] = x[F_N] = 0.0;
     x[F_MINP] = x[F_MINT] = __builtin_inf();
     x[F_MAXP] = x[F_MAXT] = -__builtin_inf();
-    for (int g = 0; g < count; ++g) {
-        const double* y = src + (long long)g * kRec + f * kFields;
-        sum_merge(x[F_S2H], x[F_S2L], y[F_S2H], y[F_S2L]);
-        sum_merge(x[F_S1H], x[F_S1L], y[F_S1H], y[F_S1L]);
-        x[F_NB] += y[F_NB];
-        x[F_N] += y[F_N];
-        x[F_MINP] = dmin_nan(x[F_MINP], y[F_MINP]);
-        x[F_MAXP] = dmax_nan(x[F_MAXP], y[F_MAXP]);
-        x[F_MINT] = dmin_nan(x[F_MINT], y[F_MINT]);
-        x[F_MAXT] = dmax_nan(x[F_MAXT], y[F_MAXT]);
-    }
+    sum_records<kRec>(src, count, x, [f](double* a, const double* rec) { form_merge(a, rec + f * kFields); });
 #pragma unroll
     for (int j = 0; j < kFields; ++j) dst[f * kFields + j] = x[j];
 }
@@ -272,7 +215,7 @@ __global__ __launch_bounds__(kThreads) void metrics_finalise(const double* __res
     __shared__ double ext[kWaves][8];
     const int t = threadIdx.x, b = blockIdx.x;
     if (t < 2) {
-        sum_records(recs + (long long)b * G * kRec, G, sh, t);
+        sum_form(recs + (long long)b * G * kRec, G, sh, t);
         for (int j = 0; j < kFields; ++j) fsum[(long long)b * kRec + t * kFields + j] = sh[t * kFields + j];
         write_row(sh + t * kFields, out + (long long)b * 9, t, mask_kind, (double)npix);
     }
@@ -409,7 +352,7 @@ __global__ __launch_bounds__(kThreads) void metrics_last(const double* __restric
     const bool pooled = b == B;
     double* row = out + (long long)b * 9;
     if (pooled && t < 2) {
-        sum_records(fsum, B, sh, t);
+        sum_form(fsum, B, sh, t);
         write_row(sh + t * kFields, row, t, mask_kind, (double)npix);      // the reference's H * W under the pooled count, literally
     }
     // frame b: the mean of its map; pooled: the mean of the frames' means, all of them over the same number of windows
@@ -424,11 +367,7 @@ __global__ __launch_bounds__(kThreads) void metrics_last(const double* __restric
     }
 }
 
-inline bool aligned(const void* p, unsigned a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
-
-bool dims_ok(int B, int H, int W) {
-    return B >= 1 && H >= 1 && W >= 1 && B < 65535 && (long long)H * W < (1ll << 31) - 4 * (long long)kMaxReduceBlocks * kThreads;
-}
+bool dims_ok(int B, int H, int W) { return frame_dims_ok(B, H, W, 4ll * kMaxReduceBlocks * kThreads); }
 
 }  // namespace
 

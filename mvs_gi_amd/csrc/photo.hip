@@ -12,24 +12,22 @@
 //                         channel, one pass over the cameras fetches the samples into registers (taps set up again from the kept
 //                         coordinates: eight floats of tap state per camera and pixel would not fit beside them), the mean and the
 //                         deviations are taken from those registers: every tap is fetched once.  The quads of a frame are strided
-//                         over G blocks, G a function of (H, W) alone, so frame b's records, and with them row b, do not depend on B.
-//                         With a table: compensated float64 sums of std and var and the counts, wave reduction by shuffles, block
-//                         reduction through LDS, one record of kRec doubles per block.
-//   2. photo_finalise     grid B + 1: block b sums frame b's G records in index order -> row b; block B sums every frame the same
-//                         way (one thread per frame, kept in the slab) and then the frames' sums in frame order -> the pooled row.
-// No atomics, no allocation, no host synchronisation: the same inputs give the same bits on every run.
+//                         over G blocks.  With a table, the thread's record: the sums of std and var (pairs), the bad, scored and
+//                         masked counts and the histogram of views.
+//   2. photo_finalise     frame_finalise with WriteRow's formulas (with a table only).
+// The table's scheme -- records, slab, merge order, finalise -- is csrc/frame_reduce.hpp's; G = ceil(quads / 256), at most 256.
 #include "common.hpp"
 
 namespace {
 
 #include "camera_models.hpp"
+#include "frame_reduce.hpp"
 #include "sampling.hpp"
 
+using mvsgi::aligned;
 using mvsgi::kMaxCams;
 constexpr int kCamFloats = 10;            // host camera table row, as mvsgi_reproject_f32's
-constexpr int kThreads = 256;
-constexpr int kWaves = kThreads / 64;
-constexpr int kMaxReduceBlocks = 256;     // records per frame (what photo_finalise sums in order)
+constexpr int kMaxReduceBlocks = 256;     // records per frame (what frame_finalise sums in order)
 constexpr int kViews = kMaxCams + 1;      // histogram bins: 0 .. 8 seen cameras
 constexpr int kRec = 7 + kViews;          // doubles per record
 constexpr int kCols = 5 + kViews;         // n, mean_std, rms, bad, coverage, views_0 .. views_8
@@ -57,44 +55,14 @@ struct PhotoOut {
     double* recs;
 };
 
-// The slab, in doubles: [B][G][kRec] records | [B][kRec] frame sums (written and read by the pooled row's block)
-struct Layout {
-    int G;
-    size_t rec, fsum, total;
-};
-
-inline Layout layout(long long B, int H, int W) {
-    Layout l;
-    const long long g = mvsgi::cdiv((long long)H * ((W + 3) / 4), kThreads);
-    l.G = (int)(g < 1 ? 1 : g > kMaxReduceBlocks ? kMaxReduceBlocks : g);
-    l.rec = 0;
-    l.fsum = l.rec + (size_t)B * l.G * kRec;
-    l.total = l.fsum + (size_t)B * kRec;
-    return l;
-}
-
-// (h, l) += x with the rounding error of h + x kept in l (Knuth's two-sum; h stays the plain running sum)
-__device__ __forceinline__ void sum_add(double& h, double& l, double x) {
-    const double t = h + x;
-    const double bp = t - h;
-    l += (h - (t - bp)) + (x - bp);
-    h = t;
-}
-__device__ __forceinline__ void sum_merge(double& h, double& l, double bh, double bl) {
-    sum_add(h, l, bh);
-    l += bl;
-}
-// the pair's value; an infinite or NaN sum leaves a NaN in l, the sum is then h
-__device__ __forceinline__ double sum_value(double h, double l) { return l - l == 0.0 ? h + l : h; }
-
-__device__ __forceinline__ double shfl_down(double v, int off) { return __shfl_down(v, off, 64); }
-
-__device__ __forceinline__ void rec_merge(double* a, const double* b) {
-    sum_merge(a[F_SH], a[F_SL], b[F_SH], b[F_SL]);
-    sum_merge(a[F_VH], a[F_VL], b[F_VH], b[F_VL]);
+struct RecMerge {
+    __device__ __forceinline__ void operator()(double* a, const double* b) const {
+        sum_merge(a[F_SH], a[F_SL], b[F_SH], b[F_SL]);
+        sum_merge(a[F_VH], a[F_VL], b[F_VH], b[F_VL]);
 #pragma unroll
-    for (int j = F_NB; j < kRec; ++j) a[j] += b[j];
-}
+        for (int j = F_NB; j < kRec; ++j) a[j] += b[j];
+    }
+};
 
 // IN: layout of the camera images.  VEC: W % 4 == 0; otherwise element-wise with a row tail.  NT: cameras held in registers, N <= NT.
 template <int IN, bool VEC, int NT>
@@ -104,7 +72,6 @@ __global__ __launch_bounds__(kThreads) void photo_reduce(const float* __restrict
                                                          float bf, float thresh, float pi_f) {
 #pragma clang fp contract(off)
     __shared__ float lut[IN == U8HWC3 ? 256 : 1];
-    __shared__ double red[kWaves][kRec];
     stage_u8_table<IN>(lut);
     const int t = threadIdx.x, G = gridDim.x;
     const long long b = blockIdx.y;
@@ -318,74 +285,33 @@ __global__ __launch_bounds__(kThreads) void photo_reduce(const float* __restrict
     r[F_NB] = (double)nbad, r[F_N] = (double)nsc, r[F_NM] = (double)nmask;
 #pragma unroll
     for (int h = 0; h < kViews; ++h) r[F_V0 + h] = (double)hist[h];
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-        double x[kRec];
-#pragma unroll
-        for (int j = 0; j < kRec; ++j) x[j] = shfl_down(r[j], off);
-        rec_merge(r, x);
-    }
-    if ((t & 63) == 0) {
-#pragma unroll
-        for (int j = 0; j < kRec; ++j) red[t >> 6][j] = r[j];
-    }
-    __syncthreads();
-    if (t == 0) {
-        for (int w = 1; w < kWaves; ++w) rec_merge(r, red[w]);
-        double* out = o.recs + (b * G + blockIdx.x) * kRec;
-#pragma unroll
-        for (int j = 0; j < kRec; ++j) out[j] = r[j];
-    }
+    block_reduce_store<kRec>(r, o.recs, b, G, RecMerge());
 }
 
-// count records from src, in index order -> x
-__device__ __forceinline__ void sum_records(const double* src, int count, double* x) {
+struct WriteRow {
+    __device__ __forceinline__ void operator()(const double* x, double* row) const {
+        const double n = x[F_N];
+        const double nan = __builtin_nan("");
+        row[0] = n;
+        row[1] = n > 0.0 ? sum_value(x[F_SH], x[F_SL]) / n : nan;
+        row[2] = n > 0.0 ? sqrt(sum_value(x[F_VH], x[F_VL]) / n) : nan;
+        row[3] = n > 0.0 ? x[F_NB] / n : nan;
+        row[4] = n / x[F_NM];
 #pragma unroll
-    for (int j = 0; j < kRec; ++j) x[j] = 0.0;
-    for (int g = 0; g < count; ++g) rec_merge(x, src + (long long)g * kRec);
-}
-
-__device__ __forceinline__ void write_row(const double* x, double* row) {
-    const double n = x[F_N];
-    const double nan = __builtin_nan("");
-    row[0] = n;
-    row[1] = n > 0.0 ? sum_value(x[F_SH], x[F_SL]) / n : nan;
-    row[2] = n > 0.0 ? sqrt(sum_value(x[F_VH], x[F_VL]) / n) : nan;
-    row[3] = n > 0.0 ? x[F_NB] / n : nan;
-    row[4] = n / x[F_NM];
-#pragma unroll
-    for (int h = 0; h < kViews; ++h) row[5 + h] = x[F_V0 + h];
-}
+        for (int h = 0; h < kViews; ++h) row[5 + h] = x[F_V0 + h];
+    }
+};
 
 __global__ __launch_bounds__(kThreads) void photo_finalise(const double* recs, double* fsum, double* __restrict__ out, int B, int G) {
-    const int t = threadIdx.x, b = blockIdx.x;
-    double x[kRec];
-    if (b < B) {
-        if (t == 0) {
-            sum_records(recs + (long long)b * G * kRec, G, x);
-            write_row(x, out + (long long)b * kCols);
-        }
-        return;
-    }
-    // the pooled row: every frame's sum as its own block computes it, then the frames in frame order
-    for (int f = t; f < B; f += kThreads) {
-        sum_records(recs + (long long)f * G * kRec, G, x);
-#pragma unroll
-        for (int j = 0; j < kRec; ++j) fsum[(long long)f * kRec + j] = x[j];
-    }
-    __syncthreads();
-    if (t == 0) {
-        sum_records(fsum, B, x);
-        write_row(x, out + (long long)B * kCols);
-    }
+    frame_finalise<kRec, kCols>(recs, fsum, out, B, G, RecMerge(), WriteRow());
 }
 
-inline bool aligned(const void* p, unsigned a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
-
-bool dims_ok(long long B, int H, int W) {
-    return B >= 1 && H >= 1 && W >= 1 && B < 65535 &&
-           (long long)H * W < (1ll << 31) - 4ll * kMaxReduceBlocks * kThreads;
+// a reduce block per kThreads quads of a frame (a quad: four consecutive pixels of a row, a thread's unit of work)
+inline FrameSlab layout(long long B, int H, int W) {
+    return frame_slab(B, (long long)H * ((W + 3) / 4), kThreads, kMaxReduceBlocks, kRec);
 }
+
+bool dims_ok(long long B, int H, int W) { return frame_dims_ok(B, H, W, 4ll * kMaxReduceBlocks * kThreads); }
 
 }  // namespace
 
@@ -438,7 +364,7 @@ extern "C" int mvsgi_photo_consistency_f32(const float* inv, const float* rays, 
         MVSGI_REQUIRE(aligned(inv, 16) && aligned(rays, 16), "%s: inv and rays must be 16-byte aligned when W %% 4 == 0", what);
         MVSGI_REQUIRE(aligned(mask, 4), "%s: mask must be 4-byte aligned when W %% 4 == 0", what);
     }
-    const Layout l = layout(B, H, W);
+    const FrameSlab l = layout(B, H, W);
     double* slab = nullptr;
     if (table) {
         MVSGI_REQUIRE(ws, "%s: null pointer (the table needs ws)", what);

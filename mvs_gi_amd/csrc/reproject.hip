@@ -179,7 +179,7 @@ __global__ __launch_bounds__(256) void reproject_kernel(const float* __restrict_
     }
 }
 
-inline bool aligned16(const void* p) { return (uintptr_t)p % 16 == 0; }
+using mvsgi::aligned;
 
 }  // namespace
 
@@ -221,10 +221,10 @@ extern "C" int mvsgi_reproject_f32(const float* inv, const float* rays, const vo
             c.ds = make_ds_params(t[1], t[2], t[3], t[4], t[5], t[6], (int)t[8] + 1, (int)t[9] + 1, t[7]);
         }
     }
-    MVSGI_REQUIRE(aligned16(xyz) && aligned16(warped) && aligned16(valid) && aligned16(grid),
+    MVSGI_REQUIRE(aligned(xyz, 16) && aligned(warped, 16) && aligned(valid, 16) && aligned(grid, 16),
                   "%s: outputs must be 16-byte aligned", what);
     const bool vec = W % 4 == 0;
-    if (vec) MVSGI_REQUIRE(aligned16(inv) && aligned16(rays), "%s: inv and rays must be 16-byte aligned when W %% 4 == 0", what);
+    if (vec) MVSGI_REQUIRE(aligned(inv, 16) && aligned(rays, 16), "%s: inv and rays must be 16-byte aligned when W %% 4 == 0", what);
     ReprojDims s{B, N, C, Hr, Wr, H, W, (W + 3) / 4};
     const long long nb = mvsgi::cdiv(B * H * s.Wq, 256);
     MVSGI_REQUIRE(nb < (1ll << 31), "%s: %lld blocks (B * H * W too large for one launch)", what, nb);

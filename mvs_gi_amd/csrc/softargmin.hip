@@ -31,17 +31,11 @@ __device__ __forceinline__ void softargmin_pixel(const float* __restrict__ costs
     const Axis2 ay = axis(oy, H), ax = axis(ox, W);
     const long long HW = (long long)H * W;
     const float* cb = costs + (long long)b * D * HW;
-    const long long o00 = (long long)ay.i0 * W + ax.i0, o01 = (long long)ay.i0 * W + ax.i1;
-    const long long o10 = (long long)ay.i1 * W + ax.i0, o11 = (long long)ay.i1 * W + ax.i1;
-
-    // A tap under a weight of exactly 0 is not blended: it enters the expression as 0, whatever it holds.  Every pixel at scale 1
-    // and the centre-aligned pixels of an odd factor have such a tap (l1 == 0, i1 = i0 + 1), and 0 * c would turn a -inf or NaN
-    // cost of the NEIGHBOURING pixel into a NaN here.  Finite costs give the same bits as before (0 * c = 0 * 0).
-    const bool x1 = ax.l1 == 0.f, y1 = ay.l1 == 0.f;
+    const Taps taps = sa_taps(ay, ax, W);
+    // this file is compiled with contraction on: the expression below, as the compiler contracts it, is what defines the bits
     auto sample = [&](int d) {
-        const float* p = cb + d * HW;
-        const float p01 = x1 ? 0.f : p[o01], p10 = y1 ? 0.f : p[o10], p11 = (x1 || y1) ? 0.f : p[o11];
-        return ay.l0 * (ax.l0 * p[o00] + ax.l1 * p01) + ay.l1 * (ax.l0 * p10 + ax.l1 * p11);
+        const TapValues v = sa_fetch(cb + d * HW, taps);
+        return ay.l0 * (ax.l0 * v.p00 + ax.l1 * v.p01) + ay.l1 * (ax.l0 * v.p10 + ax.l1 * v.p11);
     };
 
     if (D <= 32) {
@@ -73,11 +67,8 @@ __device__ __forceinline__ void softargmin_pixel(const float* __restrict__ costs
         }
         return;
     }
-    auto sample_mp = [&](int d) {                // the same taps; one rounding order for all three passes, see sa_blend()
-        const float* p = cb + d * HW;
-        const float p01 = x1 ? 0.f : p[o01], p10 = y1 ? 0.f : p[o10], p11 = (x1 || y1) ? 0.f : p[o11];
-        return sa_blend(ay.l0, ay.l1, ax.l0, ax.l1, p[o00], p01, p10, p11);
-    };
+    // the same taps; one rounding order for all three passes, see sa_blend()
+    auto sample_mp = [&](int d) { return sa_sample(cb + d * HW, ay, ax, taps); };
     float m = -INFINITY;
     for (int d = 0; d < D; ++d) m = fmaxf(m, sample_mp(d));
     float s = 0.f, t = 0.f;

@@ -1,5 +1,6 @@
-// The coordinate rule and the blend that csrc/softargmin.hip (upsample + softmax + expectation) and csrc/confidence.hip (the
-// confidence maps of the same softmax) share: one definition, so that both blend the same value of a candidate at a pixel.
+// The coordinate rule, the taps of a pixel and the blend that csrc/softargmin.hip (upsample + softmax + expectation),
+// csrc/confidence.hip (the confidence maps of the same softmax) and csrc/losses.hip (the cross-entropy on it) share: one
+// definition, so that all of them blend the same value of a candidate at a pixel.
 // Include inside the translation unit's anonymous namespace (behind common.hpp), as device_prims.hpp is.
 #pragma once
 
@@ -49,4 +50,39 @@ __device__ __forceinline__ Axis2 axis2f(int dst, int in, float rs) {
     a.l1 = src - (float)a.i0;
     a.l0 = 1.0f - a.l1;
     return a;
+}
+
+// The taps of an output pixel inside a candidate's [H][W] plane.  A tap under a weight of exactly 0 is not blended: it enters the
+// expression as 0, whatever it holds.  Every pixel at scale 1 and the centre-aligned pixels of an odd factor have such a tap
+// (l1 == 0, i1 = i0 + 1), and 0 * c would turn a -inf or NaN cost of the NEIGHBOURING pixel into a NaN here.  Finite costs give
+// the same bits either way (0 * c = 0 * 0).
+struct Taps {
+    long long o00, o01, o10, o11;
+    bool x1, y1;                                 // the right column's / the lower row's weight is 0
+};
+
+__device__ __forceinline__ Taps sa_taps(const Axis2& ay, const Axis2& ax, int W) {
+    Taps t;
+    t.o00 = (long long)ay.i0 * W + ax.i0, t.o01 = (long long)ay.i0 * W + ax.i1;
+    t.o10 = (long long)ay.i1 * W + ax.i0, t.o11 = (long long)ay.i1 * W + ax.i1;
+    t.x1 = ax.l1 == 0.f, t.y1 = ay.l1 == 0.f;
+    return t;
+}
+
+struct TapValues {
+    float p00, p01, p10, p11;
+};
+
+// the four taps of the candidate whose plane is p
+__device__ __forceinline__ TapValues sa_fetch(const float* p, const Taps& t) {
+    TapValues v;
+    v.p01 = t.x1 ? 0.f : p[t.o01], v.p10 = t.y1 ? 0.f : p[t.o10], v.p11 = (t.x1 || t.y1) ? 0.f : p[t.o11];
+    v.p00 = p[t.o00];
+    return v;
+}
+
+// the candidate's value at the pixel, by sa_blend
+__device__ __forceinline__ float sa_sample(const float* p, const Axis2& ay, const Axis2& ax, const Taps& t) {
+    const TapValues v = sa_fetch(p, t);
+    return sa_blend(ay.l0, ay.l1, ax.l0, ax.l1, v.p00, v.p01, v.p10, v.p11);
 }

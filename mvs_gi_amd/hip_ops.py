@@ -1187,6 +1187,22 @@ def instance_norm(x, res=None, gamma=None, beta=None, eps: float = 1e-5, neg_slo
     return out
 
 
+def _slab_layout(B: int, units: int, units_per_block: int, max_blocks: int, rec: int) -> dict:
+    """The slab of csrc/frame_reduce.hpp, restated, in doubles: [B][G][rec] records | [B][rec] frame sums; a reduce block per
+    units_per_block units of a frame, at least one and at most max_blocks."""
+    G = min(max(-(-units // units_per_block), 1), max_blocks)
+    fsum = B * G * rec
+    return dict(G=G, records=0, frame_sums=fsum, total=fsum + B * rec)
+
+
+def _ws(symbol: str, label: str, dims: dict, device, dtype) -> torch.Tensor:
+    """A workspace of the size the library's `symbol` gives for dims (8-byte elements; 0 bytes: the shape is not supported)."""
+    n = getattr(_lib.load(), symbol)(*dims.values())
+    if n == 0:
+        raise ValueError(f"{label}: unsupported shape ({', '.join(f'{k} {v}' for k, v in dims.items())})")
+    return torch.empty(n // 8, device=device, dtype=dtype)
+
+
 METRICS_COLUMNS = ("rmse", "mae", "bad", "ssim", "rmse_dist", "mae_dist", "bad_dist", "ssim_dist", "n")
 METRICS_MASK_NONE, METRICS_MASK_TENSOR, METRICS_MASK_RANGE = 0, 1, 2        # MVSGI_METRICS_MASK_* of include/mvsgi.h
 METRICS_RANGE_SCOPES = {"frame": 0, "batch": 1}                              # MVSGI_METRICS_RANGE_*
@@ -1198,21 +1214,16 @@ _METRICS_REC, _METRICS_PIX_PER_BLOCK, _METRICS_MAX_BLOCKS, _METRICS_TILE = 20, 4
 
 def metrics_ws_layout(B: int, H: int, W: int) -> dict:
     """The workspace of metrics(), in doubles: offsets of its four parts, reduce blocks per frame G, SSIM tiles per frame T."""
-    G = min(max(-(-(H * W) // _METRICS_PIX_PER_BLOCK), 1), _METRICS_MAX_BLOCKS)
+    slab = _slab_layout(B, H * W, _METRICS_PIX_PER_BLOCK, _METRICS_MAX_BLOCKS, _METRICS_REC)
     T = (-(-(H - 10) // _METRICS_TILE[0])) * (-(-(W - 10) // _METRICS_TILE[1])) if H >= 11 and W >= 11 else 0
-    rec = 0
-    fsum = rec + B * G * _METRICS_REC
-    consts = fsum + B * _METRICS_REC
+    consts = slab["total"]
     tiles = consts + B * 4
-    return dict(G=G, T=T, records=rec, frame_sums=fsum, consts=consts, tiles=tiles, total=tiles + 2 * B * T)
+    return dict(slab, T=T, consts=consts, tiles=tiles, total=tiles + 2 * B * T)
 
 
 def metrics_ws(B: int, H: int, W: int, device) -> torch.Tensor:
     """A workspace for metrics() at this shape (float64; its owner keeps it: a captured graph holds its address)."""
-    n = _lib.load().mvsgi_metrics_ws_bytes(B, H, W)
-    if n == 0:
-        raise ValueError(f"metrics: unsupported shape (B {B}, H {H}, W {W})")
-    return torch.empty(n // 8, device=device, dtype=torch.float64)
+    return _ws("mvsgi_metrics_ws_bytes", "metrics", dict(B=B, H=H, W=W), device, torch.float64)
 
 
 def metrics(preds, target, bf: float, cmin: float, cmax: float, valid_mask=None, label_range=None, thresh: float = 0.1,
@@ -1222,14 +1233,10 @@ def metrics(preds, target, bf: float, cmin: float, cmax: float, valid_mask=None,
     valid_mask: [B, 1, H, W] bool / uint8, or label_range = (lo, hi) on the raw target, or neither.  At most four launches on
     preds' stream, nothing else: with `ws` (metrics_ws) and `out` given the call allocates nothing and can be captured."""
     global METRICS_EVALUATIONS
-    preds = _dev(preds, "preds")
-    target = _dev(target, "target")
-    if preds.dim() == 4 and preds.shape[1] == 1:
-        preds = preds[:, 0]
-    if target.dim() == 4 and target.shape[1] == 1:
-        target = target[:, 0]
-    if preds.dim() != 3 or tuple(target.shape) != tuple(preds.shape):
-        raise AssertionError(f"preds and target must both be [B, 1, H, W] or [B, H, W], got {tuple(preds.shape)} and {tuple(target.shape)}")
+    preds = _image(preds, "preds")
+    target = _image(target, "target")
+    if tuple(target.shape) != tuple(preds.shape):
+        raise AssertionError(f"target {tuple(target.shape)} does not match preds {tuple(preds.shape)}")
     B, Hh, W = (int(v) for v in preds.shape)
     if valid_mask is not None and label_range is not None:
         raise ValueError("metrics: a valid_mask or a label_range, not both")
@@ -1276,17 +1283,12 @@ _LOSSES_REC, _LOSSES_PIX_PER_BLOCK, _LOSSES_MAX_BLOCKS = 8, 256, 256
 
 def losses_ws_layout(B: int, OH: int, OW: int) -> dict:
     """The workspace of losses(), in doubles: offsets of its two parts and the reduce blocks per frame G."""
-    G = min(max(-(-(OH * OW) // _LOSSES_PIX_PER_BLOCK), 1), _LOSSES_MAX_BLOCKS)
-    fsum = B * G * _LOSSES_REC
-    return dict(G=G, records=0, frame_sums=fsum, total=fsum + B * _LOSSES_REC)
+    return _slab_layout(B, OH * OW, _LOSSES_PIX_PER_BLOCK, _LOSSES_MAX_BLOCKS, _LOSSES_REC)
 
 
 def losses_ws(B: int, OH: int, OW: int, device) -> torch.Tensor:
     """A workspace for losses() at this output shape (float64; its owner keeps it: a captured graph holds its address)."""
-    n = _lib.load().mvsgi_losses_ws_bytes(B, OH, OW)
-    if n == 0:
-        raise ValueError(f"losses: unsupported shape (B {B}, OH {OH}, OW {OW})")
-    return torch.empty(n // 8, device=device, dtype=torch.float64)
+    return _ws("mvsgi_losses_ws_bytes", "losses", dict(B=B, OH=OH, OW=OW), device, torch.float64)
 
 
 def _image(t, name: str):
@@ -1423,17 +1425,12 @@ _PHOTO_REC, _PHOTO_QUADS_PER_BLOCK, _PHOTO_MAX_BLOCKS = 16, 256, 256
 def photo_ws_layout(B: int, H: int, W: int) -> dict:
     """The workspace of photo_consistency(), in doubles: offsets of its two parts and the reduce blocks per frame G (a function of
     (H, W) alone).  Pure: no device, no library."""
-    G = min(max(-(-(H * (-(-W // 4))) // _PHOTO_QUADS_PER_BLOCK), 1), _PHOTO_MAX_BLOCKS)
-    fsum = B * G * _PHOTO_REC
-    return dict(G=G, records=0, frame_sums=fsum, total=fsum + B * _PHOTO_REC)
+    return _slab_layout(B, H * (-(-W // 4)), _PHOTO_QUADS_PER_BLOCK, _PHOTO_MAX_BLOCKS, _PHOTO_REC)
 
 
 def photo_ws(B: int, H: int, W: int, device) -> torch.Tensor:
     """A workspace for photo_consistency() at this shape (float64; its owner keeps it: a captured graph holds its address)."""
-    n = _lib.load().mvsgi_photo_ws_bytes(B, H, W)
-    if n == 0:
-        raise ValueError(f"photo_consistency: unsupported shape (B {B}, H {H}, W {W})")
-    return torch.empty(n // 8, device=device, dtype=torch.float64)
+    return _ws("mvsgi_photo_ws_bytes", "photo_consistency", dict(B=B, H=H, W=W), device, torch.float64)
 
 
 def photo_consistency(inv, rays, T, cams, bf: float, imgs, cam_masks=None, mask=None, thresh: float = 0.1, want=PHOTO_OUTPUTS, out=None,
@@ -1544,10 +1541,7 @@ def cloud_ws_layout(B: int, H: int, W: int) -> dict:
 
 def cloud_ws(B: int, H: int, W: int, device) -> torch.Tensor:
     """A workspace for pack_cloud() at this shape (int64; its owner keeps it: a captured graph holds its address)."""
-    n = _lib.load().mvsgi_cloud_ws_bytes(B, H, W)
-    if n == 0:
-        raise ValueError(f"pack_cloud: unsupported shape (B {B}, H {H}, W {W})")
-    return torch.empty(n // 8, device=device, dtype=torch.int64)
+    return _ws("mvsgi_cloud_ws_bytes", "pack_cloud", dict(B=B, H=H, W=W), device, torch.int64)
 
 
 def cloud_capacity(H: int, W: int, step=(1, 1)) -> int:

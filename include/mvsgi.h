@@ -732,6 +732,53 @@ int mvsgi_photo_consistency_f32(const float* inv, const float* rays, const void*
                                 float thresh, unsigned char* n_views, float* photo_var, float* photo_std, float* mean_colour,
                                 void* ws, size_t ws_bytes, double* table, long long B, int N, int C, int Hr, int Wr, int H, int W,
                                 float bf, mvsgi_stream_t stream);
+/* The same with one more input: cam_seen [B][N][H][W] bytes, or NULL.  Step 1 becomes seen_n = valid_n && (the camera-mask rule) &&
+ * cam_seen[b][n][i][j] != 0: what mvsgi_visibility_f32 writes to `visible` makes the fusion rule skip the cameras a nearer surface hides
+ * the point from.  4-byte aligned when W % 4 == 0.  With NULL this is mvsgi_photo_consistency_f32 (the same kernels, the same bits), and
+ * so is an all-ones plane in its values. */
+int mvsgi_photo_consistency_seen_f32(const float* inv, const float* rays, const void* imgs, int img_kind, const float* cam_masks,
+                                     const float* T_host, const float* cams_host, const unsigned char* mask, int mask_per_frame,
+                                     float thresh, unsigned char* n_views, float* photo_var, float* photo_std, float* mean_colour,
+                                     void* ws, size_t ws_bytes, double* table, long long B, int N, int C, int Hr, int Wr, int H, int W,
+                                     float bf, const unsigned char* cam_seen, mvsgi_stream_t stream);
+
+/* ---- camera range images and visibility (csrc/visibility.hip) ---------------------------------------------------------------------
+ * The predicted surface forward-rendered into each camera, the nearest point kept per cell of the camera's own Hz x Wz buffer (a
+ * z-buffer), and per pixel and camera whether the pixel's own point is the one the camera sees there.  Not part of the reference's
+ * interface; defined as a composition of operations this library already has.  All arithmetic is fp32, no contraction, one IEEE
+ * operation per written operation.  For frame b, pixel (i, j) of the H x W map and camera n < N <= mvsgi_sweep_max_cams():
+ *     1. steps 1-5 of mvsgi_reproject_f32 (the same functions, so the same bits): v = inv[b][i][j], d = bf / v, p = rays[:, i, j] * d,
+ *        q = T_n p, (g, in_fov) the camera's projection of q, valid_n = in_fov && |gx| <= 1 && |gy| <= 1
+ *     2. live = 0 < v <= FLT_MAX && d <= FLT_MAX   (a NaN, zero, negative or infinite v is not live, nor a v so small that d
+ *        overflows; v = +inf would give d = 0, the rig camera's own centre)
+ *     3. r2 = (qx * qx + qy * qy) + qz * qz    the squared range from camera n; no square root
+ *     4. cell: cx = clamp(int(floorf(((gx + 1) * float(Wz)) * 0.5f)), 0, Wz - 1), cy likewise with gy and Hz
+ *     5. splat, iff live && valid_n && mask != 0 (mask: uint8 [H][W] with mask_per_frame = 0, [B][H][W] with 1, NULL: every pixel):
+ *        z2[b][n][cy][cx] = min(z2[b][n][cy][cx], r2), the buffer starting at +inf.  With footprint = 2 instead into the four cells
+ *        (clamp(x0 + dx, 0, Wz - 1), clamp(y0 + dy, 0, Hz - 1)), dx, dy in {0, 1}, x0 = floorf(((gx + 1) * float(Wz) - 1) * 0.5f), y0
+ *        likewise (cells that coincide after the clamp are harmless).  Longitude does not wrap: the footprint clamps at the edge.
+ *     6. test, in a later launch and always at the cell of step 4: visible_n = live && valid_n && r2 <= z2[b][n][cy][cx] * k2, with
+ *        k2 = fp32((1 + tol)^2) rounded once from double by the caller.  A pixel the mask excluded is not splatted but is tested.
+ *     7. n_visible = sum_n visible_n
+ *     8. range = sqrtf(z2) (+inf in an empty cell)
+ * When a point is splatted r2 is >= +0 and not a NaN (a NaN q is not valid), so its bit pattern orders like an unsigned integer and
+ * +inf is the fill value: the minimum is an atomic minimum on the unsigned pattern, independent of the order of arrival.  The same
+ * inputs give the same bits in every run, and a captured launch replays the eager bits.  A cell holds the minimum over everything that
+ * lands in it, so a slanted surface reads nearer than its own points: tol is the caller's answer.  An empty cell
+ * occludes nothing.
+ *   device:  inv, rays as for mvsgi_reproject_f32 (16-byte aligned when W % 4 == 0); mask 4-byte aligned when W % 4 == 0;
+ *            z2 [B][N][Hz][Wz] fp32, 16-byte aligned: written by mvsgi_camera_range_f32 (every cell), read by mvsgi_visibility_f32;
+ *            visible [B][N][H][W] uint8 (0 / 1), n_visible [B][H][W] uint8, range [B][N][Hz][Wz] fp32: each may be NULL (not all), 16-byte
+ *            aligned.
+ *   host:    T [N][16], cams [N][10] as for mvsgi_reproject_f32 (copied into the kernels' arguments by the call).
+ * mvsgi_camera_range_f32: two launches (fill, splat); mvsgi_visibility_f32: one launch for visible / n_visible and one for range.  No
+ * host synchronisation, no allocation: capturable.  H * W < 2^31, Hz * Wz < 2^31, Hz, Wz <= 2^24, 1 <= k2 < inf, footprint 1 or 2. */
+int mvsgi_camera_range_f32(const float* inv, const float* rays, const float* T_host, const float* cams_host, const unsigned char* mask,
+                           int mask_per_frame, int footprint, float* z2, long long B, int N, int H, int W, int Hz, int Wz, float bf,
+                           mvsgi_stream_t stream);
+int mvsgi_visibility_f32(const float* inv, const float* rays, const float* T_host, const float* cams_host, const float* z2, float k2,
+                         unsigned char* visible, unsigned char* n_visible, float* range, long long B, int N, int H, int W, int Hz,
+                         int Wz, float bf, mvsgi_stream_t stream);
 
 #ifdef __cplusplus
 }

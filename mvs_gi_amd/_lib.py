@@ -142,6 +142,10 @@ SIGNATURES = {
     "mvsgi_photo_ws_bytes": (c_size_t, [c_longlong, c_int, c_int]),
     "mvsgi_photo_consistency_f32": (c_int, [_P, _P, _P, c_int, _P, _P, _P, _P, c_int, c_float, _P, _P, _P, _P, _P, c_size_t, _P,
                                             c_longlong] + [c_int] * 6 + [c_float, _P]),
+    "mvsgi_photo_consistency_seen_f32": (c_int, [_P, _P, _P, c_int, _P, _P, _P, _P, c_int, c_float, _P, _P, _P, _P, _P, c_size_t, _P,
+                                                 c_longlong] + [c_int] * 6 + [c_float, _P, _P]),
+    "mvsgi_camera_range_f32": (c_int, [_P] * 5 + [c_int, c_int, _P, c_longlong] + [c_int] * 5 + [c_float, _P]),
+    "mvsgi_visibility_f32": (c_int, [_P] * 5 + [c_float, _P, _P, _P, c_longlong] + [c_int] * 5 + [c_float, _P]),
 }
 
 _lib = None

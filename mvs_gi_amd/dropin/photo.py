@@ -16,8 +16,9 @@ needs no labels.  Not part of the reference's interface (install() does not serv
 this package already has (include/mvsgi.h, "photometric consistency"), which PhotoConsistency.evaluate_chain
 executes in torch and tests/test_gpu_photo.py compares bit for bit.
 
-Occlusion is not reasoned about: a point hidden from one camera but inside its field of view reads high.  The rig's baseline bounds
-how often that happens.
+Occlusion is not reasoned about by this stage alone: a point hidden from one camera but inside its field of view reads high.  The
+rig's baseline bounds how often that happens.  PhotoConsistency(..., visibility=dropin.Visibility(...)) keeps
+the cameras a nearer predicted surface hides the point from out of the fusion.
 """
 from __future__ import annotations
 
@@ -33,12 +34,13 @@ class PhotoConsistency:
     reprojector: the dropin.Reprojector of the rig at the map's resolution (its rays, transforms, camera table and bf are used);
     cam_masks: fp32 [N, 1, Hr, Wr] (or [1, N, 1, Hr, Wr], as sample_masks takes them), the size of the images: a camera sees a point
     only where its mask, sampled like its image, is > 0; mask: uint8 / bool [H, W] or [B, H, W], the pixels the table scores; thresh:
-    the table's bad-pixel threshold on photo_std.
+    the table's bad-pixel threshold on photo_std; visibility: a dropin.Visibility built on the same reprojector -- a camera then also
+    has to see the point (its `visible`, evaluated first, or the cam_seen= plane handed to evaluate()).
 
     The evaluator owns one workspace and one table per (B, H, W, device), made at the first evaluation of that shape and never
     replaced: a captured graph holds their addresses.  A table returned without `out` is valid until the next evaluation at its shape."""
 
-    def __init__(self, reprojector, cam_masks=None, mask=None, thresh: float = 0.1):
+    def __init__(self, reprojector, cam_masks=None, mask=None, thresh: float = 0.1, visibility=None):
         for a in ("rays", "T", "cams", "bf", "out_shape", "num_cams", "reproject"):
             if not hasattr(reprojector, a):
                 raise TypeError(f"PhotoConsistency: expected a dropin.Reprojector, got {type(reprojector)}")
@@ -65,7 +67,11 @@ class PhotoConsistency:
         self.thresh = float(thresh)
         if self.thresh != self.thresh:
             raise ValueError("PhotoConsistency: thresh must not be a NaN")
+        if visibility is not None and getattr(visibility, "reprojector", None) is not reprojector:
+            raise ValueError("PhotoConsistency: visibility= must be a dropin.Visibility built on the same reprojector")
+        self.visibility = visibility
         self._bufs = {}          # (B, H, W, device) -> (workspace, table): made at first use, NEVER replaced (a captured graph holds them)
+        self._seen = {}          # (B, H, W, device) -> the visibility stage's `visible`, likewise
 
     def buffers(self, B: int, device) -> tuple:
         Hh, W = self.out_shape
@@ -79,12 +85,21 @@ class PhotoConsistency:
     def release(self) -> None:
         """Drop every workspace and table.  Not while a captured graph that holds their addresses is still to be replayed."""
         self._bufs = {}
+        self._seen = {}
 
-    def evaluate(self, inv, imgs, want=H.PHOTO_OUTPUTS, out=None) -> dict:
+    def evaluate(self, inv, imgs, want=H.PHOTO_OUTPUTS, out=None, cam_seen=None) -> dict:
+        """cam_seen: bool / uint8 [B, N, H, W], the cameras that may see each pixel (a Visibility's `visible`); None with a
+        visibility= stage: that stage is evaluated first, into a buffer this evaluator owns."""
         rp = self.reprojector
         inv = rp._inv(inv)
         imgs = rp._imgs(imgs, inv.shape[0])
         want = tuple(want)
+        if cam_seen is None and self.visibility is not None:
+            H._dev(inv, "inv")
+            key = (int(inv.shape[0]),) + self.out_shape + (inv.device,)
+            got = self.visibility.evaluate(inv, want=("visible",), out=self._seen.get(key))
+            self._seen[key] = {"visible": got["visible"]}
+            cam_seen = got["visible"]
         ws = None
         if "table" in want:
             H._dev(inv, "inv")
@@ -92,9 +107,9 @@ class PhotoConsistency:
             if out is None or out.get("table") is None:
                 out = dict(out or {}, table=table)
         return H.photo_consistency(inv, rp.rays, rp.T, rp.cams, rp.bf, imgs, cam_masks=self.cam_masks, mask=self.mask, thresh=self.thresh,
-                                   want=want, out=out, ws=ws)
+                                   want=want, out=out, ws=ws, cam_seen=cam_seen)
 
-    def evaluate_chain(self, inv, imgs, want=H.PHOTO_OUTPUTS) -> dict:
+    def evaluate_chain(self, inv, imgs, want=H.PHOTO_OUTPUTS, cam_seen=None) -> dict:
         """The definition of evaluate(), executed: Reprojector.reproject()'s valid and warped (and, with camera masks, its grid
         through hip_ops.resample_bilinear), then the fusion rule in torch, one operation per line, sums over cameras and channels
         started at zero and taken in index order.  The planes are the bits evaluate() returns, but for photo_std, where torch's
@@ -113,6 +128,10 @@ class PhotoConsistency:
         if self.cam_masks is not None:
             m = H.resample_bilinear(self.cam_masks.repeat(B, 1, 1, 1), r["grid"].view(B * N, Ho, Wo, 2), r["valid"].view(B * N, Ho, Wo))
             seen = seen & (m.view(B, N, Ho, Wo) > 0)
+        if cam_seen is None and self.visibility is not None:
+            cam_seen = self.visibility.evaluate_chain(inv, want=("visible",))["visible"]
+        if cam_seen is not None:
+            seen = seen & (cam_seen != 0)
         C = int(w.shape[2])
         seen_f = seen.to(torch.float32)
         cnt = torch.zeros((B, Ho, Wo), device=inv.device, dtype=torch.float32)

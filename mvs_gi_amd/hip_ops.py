@@ -1434,13 +1434,15 @@ def photo_ws(B: int, H: int, W: int, device) -> torch.Tensor:
 
 
 def photo_consistency(inv, rays, T, cams, bf: float, imgs, cam_masks=None, mask=None, thresh: float = 0.1, want=PHOTO_OUTPUTS, out=None,
-                      ws=None, table=None) -> dict:
+                      ws=None, table=None, cam_seen=None) -> dict:
     """Photometric consistency of an inverse-distance map (include/mvsgi.h, "photometric consistency"): the
     masked variance over the cameras that see the back-projected point, of the colours they show there -- reproject()'s valid and
     warped put through the cost volume's fusion rule without storing them.
     inv, rays, T, cams, bf, imgs as for reproject() (imgs uint8 [B * N, Hr, Wr, 3] or fp32 [B * N, C, Hr, Wr], required); cam_masks
     fp32 [N, 1, Hr, Wr] (a camera also has to see the point through its mask, sampled like the image, > 0); mask uint8 / bool [H, W]
-    or [B, H, W]: the pixels the table scores; thresh: the bad-pixel threshold on photo_std.
+    or [B, H, W]: the pixels the table scores; thresh: the bad-pixel threshold on photo_std; cam_seen bool / uint8 [B, N, H, W], read in
+    place: a camera sees a pixel only where it is set -- visibility()'s `visible` keeps the cameras a nearer surface hides the point from
+    out of the fusion (mvsgi_photo_consistency_seen_f32; None: the entry point without it).
     want: a selection of PHOTO_OUTPUTS -- n_views uint8 [B, H, W], photo_var / photo_std fp32 [B, H, W], mean_colour fp32
     [B, C, H, W], table float64 [B + 1, 14] with PHOTO_COLUMNS, row B pooled.  out: a dict with tensors to write in place; `table=`
     is out["table"].  Two launches on inv's stream (one without the table), nothing else: with `out` and `ws` (photo_ws; needed with
@@ -1481,6 +1483,10 @@ def photo_consistency(inv, rays, T, cams, bf: float, imgs, cam_masks=None, mask=
         if Wo % 4 == 0 and mask.data_ptr() % 4:
             raise AssertionError("mask must be 4-byte aligned when W % 4 == 0")
         mask_per_frame = 1 if mask.dim() == 3 else 0
+    if cam_seen is not None:
+        cam_seen = _cloud_plane(cam_seen, "cam_seen", (B, N, Ho, Wo), dev, (torch.uint8, torch.bool))
+        if Wo % 4 == 0 and cam_seen.data_ptr() % 4:
+            raise AssertionError("cam_seen must be 4-byte aligned when W % 4 == 0")
     if table is not None:
         if out is not None and out.get("table") is not None and out["table"] is not table:
             raise ValueError("photo_consistency: table= and out['table'] are two different tensors")
@@ -1505,11 +1511,119 @@ def photo_consistency(inv, rays, T, cams, bf: float, imgs, cam_masks=None, mask=
         elif not isinstance(ws, torch.Tensor) or ws.device != dev or not ws.is_contiguous():
             raise AssertionError("ws must be a contiguous tensor on inv's device")
         ws_ptr, ws_bytes = ws.data_ptr(), ws.numel() * ws.element_size()
-    _call("mvsgi_photo_consistency_f32", inv.data_ptr(), rays.data_ptr(), imgs.data_ptr(), 0 if u8 else 1, _ptr(cam_masks), T.data_ptr(),
-          cams.data_ptr(), _ptr(mask), mask_per_frame, float(thresh), _ptr(res.get("n_views")), _ptr(res.get("photo_var")),
-          _ptr(res.get("photo_std")), _ptr(res.get("mean_colour")), ws_ptr, ws_bytes, _ptr(res.get("table")), B, N, C, Hr, Wr, Ho, Wo,
-          float(bf), _stream_ptr(inv))
+    args = (inv.data_ptr(), rays.data_ptr(), imgs.data_ptr(), 0 if u8 else 1, _ptr(cam_masks), T.data_ptr(), cams.data_ptr(), _ptr(mask),
+            mask_per_frame, float(thresh), _ptr(res.get("n_views")), _ptr(res.get("photo_var")), _ptr(res.get("photo_std")),
+            _ptr(res.get("mean_colour")), ws_ptr, ws_bytes, _ptr(res.get("table")), B, N, C, Hr, Wr, Ho, Wo, float(bf))
+    if cam_seen is None:
+        _call("mvsgi_photo_consistency_f32", *args, _stream_ptr(inv))
+    else:
+        _call("mvsgi_photo_consistency_seen_f32", *args, cam_seen.data_ptr(), _stream_ptr(inv))
     PHOTO_EVALUATIONS += 1
+    return res
+
+
+# ---- camera range images and visibility (csrc/visibility.hip; include/mvsgi.h, "camera range images and visibility") ----
+VISIBILITY_OUTPUTS = ("visible", "n_visible", "range")                     # the order of mvsgi_visibility_f32's output pointers
+VISIBILITY_TOL = 0.02
+
+
+def visibility_k2(tol: float) -> float:
+    """(1 + tol)^2 in double: the factor of the visibility test, which the call rounds to fp32 once."""
+    tol = float(tol)
+    if not 0.0 <= tol < float("inf"):
+        raise ValueError(f"tol: 0 <= tol < inf, got {tol}")
+    return (1.0 + tol) * (1.0 + tol)
+
+
+def _view_args(who: str, inv, rays, T, cams):
+    """inv, rays, T and cams as reproject() takes them -> (inv [B, H, W], rays, T, cams, B, H, W, N)"""
+    inv = _dev(inv, "inv")
+    rays = _dev(rays, "rays")
+    if inv.dim() == 4 and inv.shape[1] == 1:
+        inv = inv.squeeze(1)
+    if inv.dim() != 3 or rays.dim() != 3 or rays.shape[0] != 3 or tuple(rays.shape[1:]) != tuple(inv.shape[1:]) or rays.device != inv.device:
+        raise AssertionError(f"inv must be [B, H, W] and rays [3, H, W] on one device, got {tuple(inv.shape)}, {tuple(rays.shape)}")
+    T = torch.as_tensor(T)
+    cams = torch.as_tensor(cams)
+    if T.is_cuda or cams.is_cuda or T.dtype != torch.float32 or cams.dtype != torch.float32:
+        raise TypeError("T and cams are fp32 host tensors (they travel in the kernel's arguments)")
+    N = T.shape[0] if T.dim() == 3 else -1
+    if tuple(T.shape) != (N, 4, 4) or tuple(cams.shape) != (N, REPROJECT_CAM_FLOATS):
+        raise AssertionError(f"T must be [N, 4, 4] and cams [N, {REPROJECT_CAM_FLOATS}], got {tuple(T.shape)}, {tuple(cams.shape)}")
+    if not 1 <= N <= sweep_max_cams():
+        raise ValueError(f"{who}: {N} cameras (1 ... {sweep_max_cams()} are supported)")
+    B, Ho, Wo = (int(v) for v in inv.shape)
+    return inv, rays, T.contiguous(), cams.contiguous(), B, Ho, Wo, N
+
+
+def _zshape(zshape):
+    try:
+        Hz, Wz = (int(v) for v in zshape)
+    except (TypeError, ValueError):
+        raise ValueError(f"zshape: (Hz, Wz), got {zshape!r}") from None
+    if not (1 <= Hz <= 1 << 24 and 1 <= Wz <= 1 << 24 and Hz * Wz < 1 << 31):
+        raise ValueError(f"zshape: 1 <= Hz, Wz <= 2^24 and Hz * Wz < 2^31, got {(Hz, Wz)}")
+    return Hz, Wz
+
+
+def camera_range(inv, rays, T, cams, bf: float, zshape, mask=None, footprint: int = 1, out=None) -> torch.Tensor:
+    """The prediction forward-rendered into every camera: z2 [B, N, Hz, Wz] fp32, per cell of camera n's buffer the smallest squared
+    range (from that camera) of the back-projected points that land in it, +inf in an empty cell (include/mvsgi.h, "camera range
+    images and visibility").  inv, rays, T, cams, bf as for reproject(); zshape = (Hz, Wz); mask uint8 / bool
+    [H, W] or [B, H, W], read in place: the pixels that are rendered; footprint 1 (the nearest cell) or 2 (the four cells around the
+    point); out: the tensor to write.  Two launches on inv's stream (fill, splat); the minimum is an integer atomic on the bit pattern,
+    independent of the order of arrival: the same inputs give the same bits.  With `out` the call allocates nothing and can be
+    captured.  There is no CPU fallback."""
+    inv, rays, T, cams, B, Ho, Wo, N = _view_args("camera_range", inv, rays, T, cams)
+    dev = inv.device
+    Hz, Wz = _zshape(zshape)
+    if footprint not in (1, 2):
+        raise ValueError(f"footprint: 1 or 2, got {footprint!r}")
+    mask_per_frame = 0
+    if mask is not None:
+        mask = _cloud_plane(mask, "mask", None, dev, (torch.uint8, torch.bool))
+        if tuple(mask.shape) not in ((Ho, Wo), (B, Ho, Wo)):
+            raise AssertionError(f"mask must be [{Ho}, {Wo}] or [{B}, {Ho}, {Wo}], got {list(mask.shape)}")
+        if Wo % 4 == 0 and mask.data_ptr() % 4:
+            raise AssertionError("mask must be 4-byte aligned when W % 4 == 0")
+        mask_per_frame = 1 if mask.dim() == 3 else 0
+    if out is None:
+        out = torch.empty((B, N, Hz, Wz), device=dev, dtype=torch.float32)
+    else:
+        _arg(out, "out", dev, shape=(B, N, Hz, Wz))
+    _call("mvsgi_camera_range_f32", inv.data_ptr(), rays.data_ptr(), T.data_ptr(), cams.data_ptr(), _ptr(mask), mask_per_frame,
+          int(footprint), out.data_ptr(), B, N, Ho, Wo, Hz, Wz, float(bf), _stream_ptr(inv))
+    return out
+
+
+def visibility(inv, rays, T, cams, bf: float, z2, tol: float = VISIBILITY_TOL, want=VISIBILITY_OUTPUTS, out=None) -> dict:
+    """Which cameras see each pixel's point: visible [B, N, H, W] bool = live & valid_n & (r2 <= z2[cell] * fp32((1 + tol)^2)) at the
+    nearest cell of camera_range()'s z2 [B, N, Hz, Wz]; n_visible [B, H, W] uint8, their number; range [B, N, Hz, Wz] fp32 = sqrt(z2),
+    the cameras' range images (+inf in an empty cell).  inv, rays, T, cams, bf as for camera_range(); want: a selection of
+    VISIBILITY_OUTPUTS; out: a dict with tensors to write in place.  One launch for visible / n_visible, one for range, on inv's stream;
+    with `out` the call allocates nothing and can be captured.  There is no CPU fallback.  -> dict of the wanted outputs."""
+    inv, rays, T, cams, B, Ho, Wo, N = _view_args("visibility", inv, rays, T, cams)
+    dev = inv.device
+    z2 = _arg(z2, "z2", dev)
+    if z2.dim() != 4 or tuple(z2.shape[:2]) != (B, N):
+        raise AssertionError(f"z2 must be [{B}, {N}, Hz, Wz], got {list(z2.shape)}")
+    Hz, Wz = _zshape(z2.shape[2:])
+    k2 = visibility_k2(tol)
+    want = tuple(want)
+    if not want or set(want) - set(VISIBILITY_OUTPUTS) or len(set(want)) != len(want):
+        raise ValueError(f"want: a non-empty selection of {', '.join(repr(k) for k in VISIBILITY_OUTPUTS)}, got {want}")
+    shapes = {"visible": ((B, N, Ho, Wo), torch.bool), "n_visible": ((B, Ho, Wo), torch.uint8), "range": ((B, N, Hz, Wz), torch.float32)}
+    res = {}
+    for k in want:
+        shape, dtype = shapes[k]
+        t = None if out is None else out.get(k)
+        if t is None:
+            t = torch.empty(shape, device=dev, dtype=dtype)
+        elif tuple(t.shape) != shape or t.dtype != dtype or t.device != dev or not t.is_contiguous() or t.data_ptr() % 16:
+            raise AssertionError(f"out['{k}'] must be a contiguous, 16-byte aligned {dtype} {list(shape)} tensor on {dev}")
+        res[k] = t
+    _call("mvsgi_visibility_f32", inv.data_ptr(), rays.data_ptr(), T.data_ptr(), cams.data_ptr(), z2.data_ptr(), k2,
+          _ptr(res.get("visible")), _ptr(res.get("n_visible")), _ptr(res.get("range")), B, N, Ho, Wo, Hz, Wz, float(bf), _stream_ptr(inv))
     return res
 
 

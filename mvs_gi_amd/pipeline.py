@@ -349,10 +349,17 @@ class InferencePipeline:
     With `photo` (a dropin.PhotoConsistency built on this pipeline's `reprojector`) one more stage follows the soft-argmin, in
     forward_device and inside the captured graph: the photometric consistency of the frame's prediction with its own input images
     (csrc/photo.hip, two launches).  `pipe.photo` is the dict of hip_ops.PHOTO_OUTPUTS, static tensors made by the first call and
-    valid until the next.  A `cloud` packer that names "photo_std" as a gate or an attribute takes that plane from this stage."""
+    valid until the next.  A `cloud` packer that names "photo_std" as a gate or an attribute takes that plane from this stage.
+
+    With `visibility` (a dropin.Visibility built on this pipeline's `reprojector`) the range images and the visibility of the frame's
+    prediction follow the soft-argmin, ahead of `photo` and `cloud`, in forward_device and inside the captured graph
+    (csrc/visibility.hip, four launches).  `pipe.visibility` is the dict of dropin.Visibility.OUTPUTS, static tensors made by the first
+    call and valid until the next.  A `photo` stage built with this Visibility fuses the cameras that see the point only, and the
+    `cloud` packer takes `visible` where it took the back-projection's `valid`: the colour of the lowest camera that sees the point.
+    Without it every launch and every result is what it was."""
 
     def __init__(self, cfg: PathConfig, weights, consts, device="cuda", extractor: str = "simple", samplers=None, raw_masks=None,
-                 reprojector=None, confidence=None, cloud=None, photo=None):
+                 reprojector=None, confidence=None, cloud=None, photo=None, visibility=None):
         """extractor: 'simple' = SimpleFeatExtraction (G16V, config29), 'sphere' = SphereEquirectFeatExtraction with the
         sphere-convolution final layer (G16VV, config103; configs/feature_extractor/sphereconv_featext.yaml).
         samplers / raw_masks: per-camera image samplers and raw-resolution masks; with both, consts["masks"] may be omitted
@@ -372,6 +379,16 @@ class InferencePipeline:
         if photo is not None:
             if reprojector is None or photo.reprojector is not reprojector:
                 raise ValueError("photo: the stage needs reprojector=, the Reprojector the PhotoConsistency was built on")
+        if visibility is not None:
+            if reprojector is None or getattr(visibility, "reprojector", None) is not reprojector:
+                raise ValueError("visibility: the stage needs reprojector=, the Reprojector the Visibility was built on")
+            if photo is not None and getattr(photo, "visibility", None) not in (None, visibility):
+                raise ValueError("visibility: the photo= stage was built with another Visibility")
+        elif photo is not None and getattr(photo, "visibility", None) is not None:
+            raise ValueError("photo: the stage was built with a Visibility; pass it as visibility= too")
+        self.visibility_stage = visibility
+        self.visibility = None
+        self._vis_out = None
         self.cloud_packer = cloud
         self.cloud = None
         self.photo_stage = photo
@@ -425,6 +442,7 @@ class InferencePipeline:
             self.confidence = self._static_conf
             self.cloud = self._static_cloud
             self.photo = self._static_photo
+            self.visibility = self._static_vis
             out = self._static_inv.squeeze(0).squeeze(0).cpu().numpy()
         else:
             out = self.forward_device(t.to(self.hot.device)).squeeze(0).squeeze(0).cpu().numpy()
@@ -448,15 +466,21 @@ class InferencePipeline:
             r = self.reprojector.reproject(inv, frame, out=self._reproj_out)
             self._reproj_out = r
             self.reprojection = (r["xyz"], r["warped"], r["valid"])
+        seen = None
+        if self.visibility_stage is not None:
+            # made once like the back-projection's buffers; the range buffer is the stage's own
+            self.visibility = self._vis_out = self.visibility_stage.evaluate(inv, out=self._vis_out)
+            seen = self.visibility["visible"]
         if self.photo_stage is not None:
             # made once like the back-projection's buffers; the workspace and the table are the stage's own
-            self.photo = self._photo_out = self.photo_stage.evaluate(inv, frame, out=self._photo_out)
+            more = dict(cam_seen=seen) if seen is not None and self.photo_stage.visibility is not None else {}
+            self.photo = self._photo_out = self.photo_stage.evaluate(inv, frame, out=self._photo_out, **more)
         if self.cloud_packer is not None:
             # the packer's buffers are made once too (it owns them per shape) and written in place
             colour = self.cloud_packer.colour
             more = dict(photo=self.photo) if self.photo_stage is not None else {}
             self.cloud = self.cloud_packer.pack(inv, confidence=self.confidence, warped=r["warped"] if colour else None,
-                                                valid=r["valid"] if colour else None, **more)
+                                                valid=(r["valid"] if seen is None else seen) if colour else None, **more)
         return inv
 
     # ---- hipGraph replay of the whole chain for one frame (the robot's operating point: one frame at a time) ----
@@ -484,6 +508,7 @@ class InferencePipeline:
         self._static_conf = self.confidence
         self._static_cloud = self.cloud
         self._static_photo = self.photo
+        self._static_vis = self.visibility
 
     @torch.no_grad()
     def replay(self, imgs_u8: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -499,4 +524,5 @@ class InferencePipeline:
         self.confidence = self._static_conf
         self.cloud = self._static_cloud
         self.photo = self._static_photo
+        self.visibility = self._static_vis
         return self._static_inv

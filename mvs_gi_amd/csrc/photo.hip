@@ -2,8 +2,10 @@
 // dsta_mvs/model/cost_volume_builder/spherical_sweep_avg.py:92-125: the masked variance over the cameras that see a point) applied
 // to the colours the cameras show at the back-projected point, per pixel and as per-frame scores.  The definition is in
 // include/mvsgi.h (section "photometric consistency") and DESIGN.md 19; steps 1-6 are reproject.hip's (the same functions of
-// camera_models.hpp and sampling.hpp), so valid_n and w_n[c] are the bits of mvsgi_reproject_f32's valid and warped, which are never
-// stored here.  This file is compiled with contraction off.
+// view_rig.hpp -- the rig, its host loop, a point's way into a camera, the byte quads read; the quad's points are its text, kept in
+// photo_reduce.inc for the row-tail instances' sake -- and sampling.hpp), so
+// valid_n and w_n[c] are the bits of mvsgi_reproject_f32's valid and warped, which are never stored here.  This file is compiled with
+// contraction off.
 //
 //   1. photo_reduce<IN, VEC, NT>  grid (G, B): a thread owns four consecutive pixels of a row (16-byte loads of inv and the ray
 //                         planes, 16-byte stores of the fp32 planes, 4-byte stores of n_views; rows whose length is no multiple of
@@ -22,29 +24,19 @@
 
 namespace {
 
-#include "camera_models.hpp"
 #include "frame_reduce.hpp"
 #include "sampling.hpp"
+#include "view_rig.hpp"
 
 using mvsgi::aligned;
 using mvsgi::kMaxCams;
-constexpr int kCamFloats = 10;            // host camera table row, as mvsgi_reproject_f32's
 constexpr int kMaxReduceBlocks = 256;     // records per frame (what frame_finalise sums in order)
 constexpr int kViews = kMaxCams + 1;      // histogram bins: 0 .. 8 seen cameras
 constexpr int kRec = 7 + kViews;          // doubles per record
 constexpr int kCols = 5 + kViews;         // n, mean_std, rms, bad, coverage, views_0 .. views_8
 
 enum { F_SH, F_SL, F_VH, F_VL, F_NB, F_N, F_NM, F_V0 };
-enum PhotoModel { DOUBLE_SPHERE = 0, EQUIRECT = 1 };
 
-struct PhotoCam {
-    float T[12];                          // rows 0..2 of the 4 x 4 transform, row-major
-    DsParams ds;                          // read when model == DOUBLE_SPHERE
-    int model, pad;
-};
-struct PhotoRig {
-    PhotoCam cam[kMaxCams];
-};
 struct PhotoDims {
     int N, C, Hr, Wr, H, W;
     int Wq;                               // threads per output row: ceil(W / 4)
@@ -107,8 +99,7 @@ int photo_consistency(const char* what, const float* inv, const float* rays, con
                       mvsgi_stream_t stream) {
     MVSGI_REQUIRE(inv && rays && imgs && T_host && cams_host, "%s: null pointer (inv, rays, imgs, T and cams are required)", what);
     MVSGI_REQUIRE(n_views || photo_var || photo_std || mean_colour || table, "%s: null pointer (every output is NULL)", what);
-    MVSGI_REQUIRE(N >= 1 && N <= kMaxCams, "%s: N = %d cameras (need 1 <= N <= %d)", what, N, kMaxCams);
-    MVSGI_REQUIRE(B >= 1 && H >= 1 && W >= 1, "%s: non-positive dimension (B = %lld, H = %d, W = %d)", what, B, H, W);
+    if (check_view_dims(what, B, N, H, W)) return 1;
     MVSGI_REQUIRE(img_kind == U8HWC3 || img_kind == F32CHW, "%s: unknown image kind %d (0 = uint8 HWC3, 1 = fp32 CHW)", what, img_kind);
     MVSGI_REQUIRE(C >= 1, "%s: C = %d channels (need C >= 1)", what, C);
     MVSGI_REQUIRE(img_kind != U8HWC3 || C == 3, "%s: uint8 images have C = 3 channels, got C = %d", what, C);
@@ -118,31 +109,14 @@ int photo_consistency(const char* what, const float* inv, const float* rays, con
     MVSGI_REQUIRE(dims_ok(B, H, W), "%s: map %d x %d or batch %lld too large (H * W < 2^31 - 2^18, B < 65535)", what, H, W, B);
     MVSGI_REQUIRE(mask_per_frame == 0 || mask_per_frame == 1, "%s: mask_per_frame = %d (0: [H][W], 1: [B][H][W])", what, mask_per_frame);
     MVSGI_REQUIRE(thresh == thresh, "%s: thresh is a NaN", what);
-    PhotoRig rig;
-    memset(&rig, 0, sizeof(rig));
-    for (int k = 0; k < N; ++k) {
-        const float* t = cams_host + k * kCamFloats;
-        PhotoCam& c = rig.cam[k];
-        MVSGI_REQUIRE(t[0] == (float)DOUBLE_SPHERE || t[0] == (float)EQUIRECT,
-                      "%s: camera %d: unknown model id %g (0 = double sphere, 1 = equirectangular)", what, k, (double)t[0]);
-        c.model = (int)t[0];
-        memcpy(c.T, T_host + k * 16, sizeof(c.T));
-        if (c.model == DOUBLE_SPHERE) {
-            // calib_h - 1 and calib_w - 1 of an integer shape: whole numbers a float holds exactly, so the casts below are exact
-            auto size_m1 = [](float v) { return v >= 1.0f && v < 16777216.0f && v == truncf(v); };
-            MVSGI_REQUIRE(size_m1(t[8]) && size_m1(t[9]), "%s: camera %d: calib shape (%g, %g) (need calib > 1)", what, k,
-                          (double)t[8] + 1.0, (double)t[9] + 1.0);
-            c.ds = make_ds_params(t[1], t[2], t[3], t[4], t[5], t[6], (int)t[8] + 1, (int)t[9] + 1, t[7]);
-        }
-    }
+    ViewRig rig;
+    if (load_view_rig(what, T_host, cams_host, N, rig)) return 1;
     MVSGI_REQUIRE(aligned(n_views, 16) && aligned(photo_var, 16) && aligned(photo_std, 16) && aligned(mean_colour, 16),
                   "%s: outputs must be 16-byte aligned", what);
     MVSGI_REQUIRE(aligned(cam_masks, 4) && (img_kind == U8HWC3 || aligned(imgs, 4)), "%s: fp32 images and masks must be 4-byte aligned", what);
     const bool vec = W % 4 == 0;
-    if (vec) {
-        MVSGI_REQUIRE(aligned(inv, 16) && aligned(rays, 16), "%s: inv and rays must be 16-byte aligned when W %% 4 == 0", what);
-        MVSGI_REQUIRE(aligned(mask, 4) && aligned(cam_seen, 4), "%s: mask and cam_seen must be 4-byte aligned when W %% 4 == 0", what);
-    }
+    if (check_quad_loads(what, inv, rays, W)) return 1;
+    if (vec) MVSGI_REQUIRE(aligned(mask, 4) && aligned(cam_seen, 4), "%s: mask and cam_seen must be 4-byte aligned when W %% 4 == 0", what);
     const FrameSlab l = layout(B, H, W);
     double* slab = nullptr;
     if (table) {

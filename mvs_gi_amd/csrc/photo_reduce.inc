@@ -9,13 +9,13 @@ template <int IN, bool VEC, int NT>
 #if MVSGI_PHOTO_SEEN
 __global__ __launch_bounds__(kThreads) void photo_reduce_seen(const float* __restrict__ inv, const float* __restrict__ rays,
                                                               const void* __restrict__ imgs, const float* __restrict__ cam_masks,
-                                                              const unsigned char* __restrict__ mask, PhotoOut o, PhotoRig rig,
+                                                              const unsigned char* __restrict__ mask, PhotoOut o, ViewRig rig,
                                                               PhotoDims s, float bf, float thresh, float pi_f,
                                                               const unsigned char* __restrict__ cam_seen) {
 #else
 __global__ __launch_bounds__(kThreads) void photo_reduce(const float* __restrict__ inv, const float* __restrict__ rays,
                                                          const void* __restrict__ imgs, const float* __restrict__ cam_masks,
-                                                         const unsigned char* __restrict__ mask, PhotoOut o, PhotoRig rig, PhotoDims s,
+                                                         const unsigned char* __restrict__ mask, PhotoOut o, ViewRig rig, PhotoDims s,
                                                          float bf, float thresh, float pi_f) {
 #endif
 #pragma clang fp contract(off)
@@ -40,7 +40,8 @@ __global__ __launch_bounds__(kThreads) void photo_reduce(const float* __restrict
         const int n = VEC ? 4 : min(4, s.W - j);                          // pixels of this thread inside the row
         const long long pix = (long long)i * s.W + j;                     // first pixel of this thread inside a plane
 
-        // steps 1, 2 of the back-projection: d = bf / v, p = r * d
+        // steps 1, 2 of the back-projection: d = bf / v, p = r * d.  The text of view_rig.hpp's quad_points, kept here: called as that
+        // function the row-tail instances of this kernel came out as other, slower code (DESIGN.md 20); so is n_views' store below
         float px[4], py[4], pz[4];
         {
             float v[4], rx[4], ry[4], rz[4];
@@ -72,30 +73,15 @@ __global__ __launch_bounds__(kThreads) void photo_reduce(const float* __restrict
 #pragma unroll
         for (int cam = 0; cam < NT; ++cam) {
             if (cam < s.N) {
-                const PhotoCam& c = rig.cam[cam];
+                const ViewCam& c = rig.cam[cam];
 #if MVSGI_PHOTO_SEEN
-                unsigned sw = 0u;                                         // cam_seen of the thread's four pixels, a byte each
-                {
-                    const unsigned char* sb = cam_seen + (b * s.N + cam) * HW + pix;
-                    if (VEC) {
-                        sw = *reinterpret_cast<const unsigned*>(sb);
-                    } else {
-#pragma unroll
-                        for (int k = 0; k < 4; ++k)
-                            if (k < n) sw |= (unsigned)sb[k] << (8 * k);
-                    }
-                }
+                // cam_seen of the thread's four pixels, a byte each
+                const unsigned sw = load_byte_quad<VEC>(cam_seen + (b * s.N + cam) * HW + pix, n);
 #endif
 #pragma unroll
                 for (int k = 0; k < 4; ++k) {
-                    const float x = transform_row(c.T, px[k], py[k], pz[k]);
-                    const float y = transform_row(c.T + 4, px[k], py[k], pz[k]);
-                    const float z = transform_row(c.T + 8, px[k], py[k], pz[k]);
-                    bool in_fov = true;
-                    if (c.model == DOUBLE_SPHERE)
-                        in_fov = project_double_sphere(c.ds, x, y, z, gx[cam][k], gy[cam][k]);
-                    else
-                        project_equirect(x, y, z, pi_f, gx[cam][k], gy[cam][k]);
+                    float x, y, z;
+                    const bool in_fov = camera_view(c, px[k], py[k], pz[k], pi_f, x, y, z, gx[cam][k], gy[cam][k]);
                     const bool ok = grid_valid(in_fov, gx[cam][k], gy[cam][k]) && k < n;
                     bool sn = ok;
                     if (ok && cam_masks) {                                // an invalid camera's taps are not fetched
@@ -216,16 +202,7 @@ __global__ __launch_bounds__(kThreads) void photo_reduce(const float* __restrict
         // step 7: the scores
         if (o.recs) {
             unsigned mw = 0x01010101u;
-            if (mb) {
-                if (VEC) {
-                    mw = *reinterpret_cast<const unsigned*>(mb + pix);
-                } else {
-                    mw = 0u;
-#pragma unroll
-                    for (int k = 0; k < 4; ++k)
-                        if (k < n) mw |= (unsigned)mb[pix + k] << (8 * k);
-                }
-            }
+            if (mb) mw = load_byte_quad<VEC>(mb + pix, n);
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
                 const bool masked = k < n && ((mw >> (8 * k)) & 0xffu) != 0u;

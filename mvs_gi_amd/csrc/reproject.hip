@@ -17,26 +17,16 @@
 // 16-byte stores per plane; rows whose length is no multiple of four take the element-wise form of the same thread shape.
 // The camera table and the transforms are kernel arguments (by value, N <= 8): nothing rig-constant is loaded from memory.
 // The threads of camera 0 write xyz.  The taps of an invalid pixel are never fetched.
+//
+// The rig argument and the host loop that fills it, the thread's quad (its place, its loads, its points), a point's way into a
+// camera and the four validity bytes stored as one word are view_rig.hpp's, which photo.hip and visibility.hip call as well.
 #include "common.hpp"
 
 namespace {
 
-#include "camera_models.hpp"
 #include "sampling.hpp"
+#include "view_rig.hpp"
 
-using mvsgi::kMaxCams;
-constexpr int kCamFloats = 10;       // host camera table row: model, xi, alpha, fx, fy, cx, cy, w2, calib_h - 1, calib_w - 1
-
-enum ReprojModel { DOUBLE_SPHERE = 0, EQUIRECT = 1 };
-
-struct ReprojCam {
-    float T[12];                                                    // rows 0..2 of the 4 x 4 transform, row-major
-    DsParams ds;                                                    // read when model == DOUBLE_SPHERE
-    int model, pad;
-};
-struct ReprojRig {
-    ReprojCam cam[kMaxCams];
-};
 struct ReprojDims {
     long long B;      // frames
     int N, C, Hr, Wr, H, W;
@@ -48,46 +38,23 @@ template <int IN, bool VEC>
 __global__ __launch_bounds__(256) void reproject_kernel(const float* __restrict__ inv, const float* __restrict__ rays,
                                                         const void* __restrict__ imgs, float* __restrict__ xyz,
                                                         float* __restrict__ warped, unsigned char* __restrict__ valid,
-                                                        float* __restrict__ grid, ReprojRig rig, ReprojDims s, float bf,
+                                                        float* __restrict__ grid, ViewRig rig, ReprojDims s, float bf,
                                                         float invalid_value, float pi_f, int per_cam) {
 #pragma clang fp contract(off)
     __shared__ float lut[IN == U8HWC3 ? 256 : 1];
     stage_u8_table<IN>(lut);
     const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
     if (idx >= s.B * s.H * s.Wq) return;
-    const int j = (int)(idx % s.Wq) * 4;
-    const long long row = idx / s.Wq;
-    const int i = (int)(row % s.H);
-    const long long b = row / s.H;
+    const Quad t = quad_at<VEC>(idx, s.H, s.W, s.Wq);
+    const long long b = t.b;
+    const int n = t.n;
     const int cam = (int)blockIdx.y;
-    const int n = VEC ? 4 : min(4, s.W - j);                            // pixels of this thread inside the row
     const long long HW = (long long)s.H * s.W;
-    const long long pix = (long long)i * s.W + j;                       // first pixel of this thread inside a plane
+    const long long pix = t.pix(s.W);                                   // first pixel of this thread inside a plane
 
     // steps 1, 2: d = bf / v, p = r * d  (spherical_sweep_stereo.py:422, :435)
-    float v[4], px[4], py[4], pz[4];
-    {
-        float rx[4], ry[4], rz[4];
-        if (VEC) {
-            const f32x4 v4 = *reinterpret_cast<const f32x4*>(inv + b * HW + pix);
-            const f32x4 x4 = *reinterpret_cast<const f32x4*>(rays + pix);
-            const f32x4 y4 = *reinterpret_cast<const f32x4*>(rays + HW + pix);
-            const f32x4 z4 = *reinterpret_cast<const f32x4*>(rays + 2 * HW + pix);
-#pragma unroll
-            for (int k = 0; k < 4; ++k) v[k] = v4[k], rx[k] = x4[k], ry[k] = y4[k], rz[k] = z4[k];
-        } else {
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const bool in = k < n;
-                v[k] = in ? inv[b * HW + pix + k] : 1.0f;
-                rx[k] = in ? rays[pix + k] : 0.0f;
-                ry[k] = in ? rays[HW + pix + k] : 0.0f;
-                rz[k] = in ? rays[2 * HW + pix + k] : 0.0f;
-            }
-        }
-#pragma unroll
-        for (int k = 0; k < 4; ++k) back_project(bf, v[k], rx[k], ry[k], rz[k], px[k], py[k], pz[k]);
-    }
+    float px[4], py[4], pz[4];
+    quad_points<VEC>(inv + b * HW, rays, HW, pix, n, bf, px, py, pz);
     if (xyz && cam == 0) {
         float* o = xyz + (b * 3) * HW + pix;
         if (VEC) {
@@ -102,23 +69,13 @@ __global__ __launch_bounds__(256) void reproject_kernel(const float* __restrict_
     }
     if (!per_cam) return;
 
-    const ReprojCam& c = rig.cam[cam];
+    const ViewCam& c = rig.cam[cam];
     float gx[4], gy[4];
     bool ok[4];
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
-        // step 3: transform_row, once per coordinate
-        const float x = transform_row(c.T, px[k], py[k], pz[k]);
-        const float y = transform_row(c.T + 4, px[k], py[k], pz[k]);
-        const float z = transform_row(c.T + 8, px[k], py[k], pz[k]);
-        // step 4: the camera's projection
-        bool in_fov = true;
-        if (c.model == DOUBLE_SPHERE)
-            in_fov = project_double_sphere(c.ds, x, y, z, gx[k], gy[k]);
-        else
-            project_equirect(x, y, z, pi_f, gx[k], gy[k]);
-        // step 5: grid_valid
-        ok[k] = grid_valid(in_fov, gx[k], gy[k]);
+        float x, y, z;                                                  // steps 3-5
+        ok[k] = grid_valid(camera_view(c, px[k], py[k], pz[k], pi_f, x, y, z, gx[k], gy[k]), gx[k], gy[k]);
     }
 
     const long long m = b * s.N + cam;                                  // image and per-camera plane of this thread
@@ -134,14 +91,8 @@ __global__ __launch_bounds__(256) void reproject_kernel(const float* __restrict_
         }
     }
     if (valid) {
-        unsigned char* o = valid + m * HW + pix;
-        if (VEC) {
-            *reinterpret_cast<unsigned*>(o) = (ok[0] ? 1u : 0u) | (ok[1] ? 0x100u : 0u) | (ok[2] ? 0x10000u : 0u) | (ok[3] ? 0x1000000u : 0u);
-        } else {
-#pragma unroll
-            for (int k = 0; k < 4; ++k)
-                if (k < n) o[k] = ok[k] ? 1 : 0;
-        }
+        store_byte_quad<VEC>(valid + m * HW + pix, n,
+                             (ok[0] ? 1u : 0u) | (ok[1] ? 0x100u : 0u) | (ok[2] ? 0x10000u : 0u) | (ok[3] ? 0x1000000u : 0u));
     }
     if (IN == NO_IMAGES) return;
 
@@ -190,8 +141,7 @@ extern "C" int mvsgi_reproject_f32(const float* inv, const float* rays, const vo
     const char* what = "mvsgi_reproject_f32";
     MVSGI_REQUIRE(inv && rays && T_host && cams_host, "%s: null pointer (inv, rays, T and cams are required)", what);
     MVSGI_REQUIRE(xyz || warped || valid || grid, "%s: null pointer (every output is NULL)", what);
-    MVSGI_REQUIRE(N >= 1 && N <= kMaxCams, "%s: N = %d cameras (need 1 <= N <= %d)", what, N, kMaxCams);
-    MVSGI_REQUIRE(B >= 1 && H >= 1 && W >= 1, "%s: non-positive dimension (B = %lld, H = %d, W = %d)", what, B, H, W);
+    if (check_view_dims(what, B, N, H, W)) return 1;
     MVSGI_REQUIRE(!warped || imgs, "%s: warped without imgs", what);
     MVSGI_REQUIRE(!imgs || warped, "%s: imgs without warped (imgs may be NULL exactly when warped is NULL)", what);
     int in = NO_IMAGES;
@@ -204,27 +154,12 @@ extern "C" int mvsgi_reproject_f32(const float* inv, const float* rays, const vo
         if (check_tap_offsets(what, "image", in, Hr, Wr)) return 1;
     }
     MVSGI_REQUIRE((long long)H * W < (1ll << 31) && B < (1ll << 31), "%s: map %d x %d or batch %lld too large", what, H, W, B);
-    ReprojRig rig;
-    memset(&rig, 0, sizeof(rig));
-    for (int k = 0; k < N; ++k) {
-        const float* t = cams_host + k * kCamFloats;
-        ReprojCam& c = rig.cam[k];
-        MVSGI_REQUIRE(t[0] == (float)DOUBLE_SPHERE || t[0] == (float)EQUIRECT,
-                      "%s: camera %d: unknown model id %g (0 = double sphere, 1 = equirectangular)", what, k, (double)t[0]);
-        c.model = (int)t[0];
-        memcpy(c.T, T_host + k * 16, sizeof(c.T));
-        if (c.model == DOUBLE_SPHERE) {
-            // calib_h - 1 and calib_w - 1 of an integer shape: whole numbers a float holds exactly, so the casts below are exact
-            auto size_m1 = [](float v) { return v >= 1.0f && v < 16777216.0f && v == truncf(v); };
-            MVSGI_REQUIRE(size_m1(t[8]) && size_m1(t[9]), "%s: camera %d: calib shape (%g, %g) (need calib > 1)", what, k,
-                          (double)t[8] + 1.0, (double)t[9] + 1.0);
-            c.ds = make_ds_params(t[1], t[2], t[3], t[4], t[5], t[6], (int)t[8] + 1, (int)t[9] + 1, t[7]);
-        }
-    }
+    ViewRig rig;
+    if (load_view_rig(what, T_host, cams_host, N, rig)) return 1;
     MVSGI_REQUIRE(aligned(xyz, 16) && aligned(warped, 16) && aligned(valid, 16) && aligned(grid, 16),
                   "%s: outputs must be 16-byte aligned", what);
     const bool vec = W % 4 == 0;
-    if (vec) MVSGI_REQUIRE(aligned(inv, 16) && aligned(rays, 16), "%s: inv and rays must be 16-byte aligned when W %% 4 == 0", what);
+    if (check_quad_loads(what, inv, rays, W)) return 1;
     ReprojDims s{B, N, C, Hr, Wr, H, W, (W + 3) / 4};
     const long long nb = mvsgi::cdiv(B * H * s.Wq, 256);
     MVSGI_REQUIRE(nb < (1ll << 31), "%s: %lld blocks (B * H * W too large for one launch)", what, nb);

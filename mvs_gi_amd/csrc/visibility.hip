@@ -1,8 +1,9 @@
 // Camera range images and visibility of the predicted inverse distance: the predicted surface forward-rendered into every camera,
 // the nearest point kept per cell (a z-buffer), and per pixel and camera whether the pixel's own point is that nearest one.  The
 // definition is in include/mvsgi.h (section "camera range images and visibility") and DESIGN.md 20; steps 1-5 are reproject.hip's
-// (the same functions of camera_models.hpp), so q, the grid and valid_n are the bits of mvsgi_reproject_f32.  This file is compiled
-// with contraction off.
+// (the same functions of view_rig.hpp: the rig and its host loop, the thread's quad and its points, a point's way into a camera, the
+// byte quads), so q, the grid and valid_n are the bits of mvsgi_reproject_f32.  The `live` rule and the squared range are this
+// file's.  This file is compiled with contraction off.
 //
 //   1. fill_kernel          z2 = +inf (0x7f800000), 16 bytes per thread with an element-wise tail.
 //   2. range_splat_kernel   reproject_kernel's thread shape: a thread owns four consecutive pixels of a row for one camera
@@ -24,24 +25,12 @@
 
 namespace {
 
-#include "camera_models.hpp"
 #include "device_prims.hpp"
+#include "view_rig.hpp"
 
 using mvsgi::aligned;
-using mvsgi::kMaxCams;
-constexpr int kCamFloats = 10;            // host camera table row, as mvsgi_reproject_f32's
 constexpr unsigned kInfBits = 0x7f800000u;
 
-enum VisModel { DOUBLE_SPHERE = 0, EQUIRECT = 1 };
-
-struct VisCam {
-    float T[12];                          // rows 0..2 of the 4 x 4 transform, row-major
-    DsParams ds;                          // read when model == DOUBLE_SPHERE
-    int model, pad;
-};
-struct VisRig {
-    VisCam cam[kMaxCams];
-};
 struct VisDims {
     long long B;                          // frames
     int N, H, W;
@@ -50,50 +39,24 @@ struct VisDims {
     int mask_per_frame, footprint;
 };
 
-// steps 1, 2 of the back-projection for a thread's four pixels, and the definition's step 2: live = 0 < v <= FLT_MAX && d <= FLT_MAX
-// (a NaN compares false; v = +inf would give d = 0, the rig camera's own centre); a lane past the row's end is not live
+// the points of the thread's quad (view_rig.hpp) and the definition's step 2: live = 0 < v <= FLT_MAX && d <= FLT_MAX (a NaN compares
+// false; v = +inf would give d = 0, the rig camera's own centre); a lane past the row's end is not live
 template <bool VEC>
-__device__ __forceinline__ void quad_points(const float* __restrict__ inv, const float* __restrict__ rays, long long HW, long long pix,
+__device__ __forceinline__ void live_points(const float* __restrict__ inv, const float* __restrict__ rays, long long HW, long long pix,
                                             int n, float bf, bool (&live)[4], float (&px)[4], float (&py)[4], float (&pz)[4]) {
 #pragma clang fp contract(off)
-    float v[4], rx[4], ry[4], rz[4];
-    if (VEC) {
-        const f32x4 v4 = *reinterpret_cast<const f32x4*>(inv + pix);
-        const f32x4 x4 = *reinterpret_cast<const f32x4*>(rays + pix);
-        const f32x4 y4 = *reinterpret_cast<const f32x4*>(rays + HW + pix);
-        const f32x4 z4 = *reinterpret_cast<const f32x4*>(rays + 2 * HW + pix);
-#pragma unroll
-        for (int k = 0; k < 4; ++k) v[k] = v4[k], rx[k] = x4[k], ry[k] = y4[k], rz[k] = z4[k];
-    } else {
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const bool in = k < n;
-            v[k] = in ? inv[pix + k] : 1.0f;
-            rx[k] = in ? rays[pix + k] : 0.0f;
-            ry[k] = in ? rays[HW + pix + k] : 0.0f;
-            rz[k] = in ? rays[2 * HW + pix + k] : 0.0f;
-        }
-    }
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const float d = back_project(bf, v[k], rx[k], ry[k], rz[k], px[k], py[k], pz[k]);
-        live[k] = k < n && v[k] > 0.0f && v[k] <= FLT_MAX && d <= FLT_MAX;
-    }
+    quad_points<VEC>(inv, rays, HW, pix, n, bf, px, py, pz,
+                     [&](int k, float v, float d) { live[k] = k < n && v > 0.0f && v <= FLT_MAX && d <= FLT_MAX; });
 }
 
-// steps 3-5 of the back-projection and the definition's step 3: the grid coordinates, the squared range; returns valid_n
-__device__ __forceinline__ bool camera_view(const VisCam& c, float px, float py, float pz, float pi_f, float& gx, float& gy, float& r2) {
+// steps 3, 4 of the back-projection (view_rig.hpp) and the definition's step 3: the grid coordinates, the squared range; returns in_fov,
+// and valid_n is the caller's grid_valid of it (applied there, the kernels are the code they were)
+__device__ __forceinline__ bool view_range(const ViewCam& c, float px, float py, float pz, float pi_f, float& gx, float& gy, float& r2) {
 #pragma clang fp contract(off)
-    const float x = transform_row(c.T, px, py, pz);
-    const float y = transform_row(c.T + 4, px, py, pz);
-    const float z = transform_row(c.T + 8, px, py, pz);
-    bool in_fov = true;
-    if (c.model == DOUBLE_SPHERE)
-        in_fov = project_double_sphere(c.ds, x, y, z, gx, gy);
-    else
-        project_equirect(x, y, z, pi_f, gx, gy);
+    float x, y, z;
+    const bool in_fov = camera_view(c, px, py, pz, pi_f, x, y, z, gx, gy);
     r2 = (x * x + y * y) + z * z;
-    return grid_valid(in_fov, gx, gy);
+    return in_fov;
 }
 
 __device__ __forceinline__ int clamp_cell(float f, int n) { return min(max((int)f, 0), n - 1); }
@@ -119,56 +82,43 @@ __global__ __launch_bounds__(256) void fill_kernel(unsigned* __restrict__ z2, lo
     }
 }
 
-// a thread's place in the map: reproject_kernel's
-struct Quad {
+// a thread's place in the map: view_rig.hpp's split behind the bounds check, in the form these kernels had it (a bool and the pixel
+// offset; with the check and the offset in the kernels their row-tail instances came out as other, slower code: DESIGN.md 20)
+struct VisQuad {
     long long b, pix;
     int n;
 };
 template <bool VEC>
-__device__ __forceinline__ bool quad_of_thread(const VisDims& s, Quad& q) {
+__device__ __forceinline__ bool quad_of_thread(const VisDims& s, VisQuad& q) {
     const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
     if (idx >= s.B * s.H * s.Wq) return false;
-    const int j = (int)(idx % s.Wq) * 4;
-    const long long row = idx / s.Wq;
-    const int i = (int)(row % s.H);
-    q.b = row / s.H;
-    q.n = VEC ? 4 : min(4, s.W - j);
-    q.pix = (long long)i * s.W + j;
+    const Quad t = quad_at<VEC>(idx, s.H, s.W, s.Wq);
+    q.b = t.b, q.n = t.n, q.pix = t.pix(s.W);
     return true;
 }
 
 template <bool VEC>
 __global__ __launch_bounds__(256) void range_splat_kernel(const float* __restrict__ inv, const float* __restrict__ rays,
-                                                          const unsigned char* __restrict__ mask, unsigned* __restrict__ z2, VisRig rig,
+                                                          const unsigned char* __restrict__ mask, unsigned* __restrict__ z2, ViewRig rig,
                                                           VisDims s, float bf, float pi_f) {
 #pragma clang fp contract(off)
-    Quad t;
+    VisQuad t;
     if (!quad_of_thread<VEC>(s, t)) return;
     const int cam = (int)blockIdx.y;
     const long long HW = (long long)s.H * s.W;
     bool live[4];
     float px[4], py[4], pz[4];
-    quad_points<VEC>(inv + t.b * HW, rays, HW, t.pix, t.n, bf, live, px, py, pz);
+    live_points<VEC>(inv + t.b * HW, rays, HW, t.pix, t.n, bf, live, px, py, pz);
 
     unsigned mw = 0x01010101u;
-    if (mask) {
-        const unsigned char* mb = mask + (s.mask_per_frame ? t.b * HW : 0) + t.pix;
-        if (VEC) {
-            mw = *reinterpret_cast<const unsigned*>(mb);
-        } else {
-            mw = 0u;
-#pragma unroll
-            for (int k = 0; k < 4; ++k)
-                if (k < t.n) mw |= (unsigned)mb[k] << (8 * k);
-        }
-    }
-    const VisCam& c = rig.cam[cam];
+    if (mask) mw = load_byte_quad<VEC>(mask + (s.mask_per_frame ? t.b * HW : 0) + t.pix, t.n);
+    const ViewCam& c = rig.cam[cam];
     unsigned* plane = z2 + ((t.b * s.N + cam) * s.Hz) * (long long)s.Wz;
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
         if (!live[k] || ((mw >> (8 * k)) & 0xffu) == 0u) continue;
         float gx, gy, r2;
-        if (!camera_view(c, px[k], py[k], pz[k], pi_f, gx, gy, r2)) continue;
+        if (!grid_valid(view_range(c, px[k], py[k], pz[k], pi_f, gx, gy, r2), gx, gy)) continue;
         const unsigned bits = __float_as_uint(r2);
         if (s.footprint == 1) {
             atomicMin(plane + (long long)nearest_cell(gy, s.Hz) * s.Wz + nearest_cell(gx, s.Wz), bits);
@@ -188,53 +138,35 @@ __global__ __launch_bounds__(256) void range_splat_kernel(const float* __restric
 template <bool VEC, bool LOOP>
 __global__ __launch_bounds__(256) void visibility_kernel(const float* __restrict__ inv, const float* __restrict__ rays,
                                                          const float* __restrict__ z2, unsigned char* __restrict__ visible,
-                                                         unsigned char* __restrict__ n_visible, VisRig rig, VisDims s, float bf, float k2,
+                                                         unsigned char* __restrict__ n_visible, ViewRig rig, VisDims s, float bf, float k2,
                                                          float pi_f) {
 #pragma clang fp contract(off)
-    Quad t;
+    VisQuad t;
     if (!quad_of_thread<VEC>(s, t)) return;
     const long long HW = (long long)s.H * s.W;
     bool live[4];
     float px[4], py[4], pz[4];
-    quad_points<VEC>(inv + t.b * HW, rays, HW, t.pix, t.n, bf, live, px, py, pz);
+    live_points<VEC>(inv + t.b * HW, rays, HW, t.pix, t.n, bf, live, px, py, pz);
 
     unsigned count = 0;                                                   // byte k: the cameras that see pixel k (at most 8)
     const int cam0 = LOOP ? 0 : (int)blockIdx.y, cam1 = LOOP ? s.N : cam0 + 1;
 #pragma unroll 1
     for (int cam = cam0; cam < cam1; ++cam) {
-        const VisCam& c = rig.cam[cam];
+        const ViewCam& c = rig.cam[cam];
         const float* plane = z2 + ((t.b * s.N + cam) * s.Hz) * (long long)s.Wz;
         unsigned word = 0;
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
             if (!live[k]) continue;
             float gx, gy, r2;
-            if (!camera_view(c, px[k], py[k], pz[k], pi_f, gx, gy, r2)) continue;
+            if (!grid_valid(view_range(c, px[k], py[k], pz[k], pi_f, gx, gy, r2), gx, gy)) continue;
             const float z = plane[(long long)nearest_cell(gy, s.Hz) * s.Wz + nearest_cell(gx, s.Wz)];
             word |= (r2 <= z * k2 ? 1u : 0u) << (8 * k);
         }
         count += word;
-        if (visible) {
-            unsigned char* o = visible + (t.b * s.N + cam) * HW + t.pix;
-            if (VEC) {
-                *reinterpret_cast<unsigned*>(o) = word;
-            } else {
-#pragma unroll
-                for (int k = 0; k < 4; ++k)
-                    if (k < t.n) o[k] = (unsigned char)((word >> (8 * k)) & 0xffu);
-            }
-        }
+        if (visible) store_byte_quad<VEC>(visible + (t.b * s.N + cam) * HW + t.pix, t.n, word);
     }
-    if (LOOP) {
-        unsigned char* o = n_visible + t.b * HW + t.pix;
-        if (VEC) {
-            *reinterpret_cast<unsigned*>(o) = count;
-        } else {
-#pragma unroll
-            for (int k = 0; k < 4; ++k)
-                if (k < t.n) o[k] = (unsigned char)((count >> (8 * k)) & 0xffu);
-        }
-    }
+    if (LOOP) store_byte_quad<VEC>(n_visible + t.b * HW + t.pix, t.n, count);
 }
 
 __global__ __launch_bounds__(256) void range_kernel(const float* __restrict__ z2, float* __restrict__ range, long long count) {
@@ -249,10 +181,9 @@ __global__ __launch_bounds__(256) void range_kernel(const float* __restrict__ z2
 
 // the checks and the rig both entry points share; 0 on success
 int vis_setup(const char* what, const float* inv, const float* rays, const float* T_host, const float* cams_host, long long B, int N,
-              int H, int W, int Hz, int Wz, VisRig& rig, long long& cells) {
+              int H, int W, int Hz, int Wz, ViewRig& rig, long long& cells) {
     MVSGI_REQUIRE(inv && rays && T_host && cams_host, "%s: null pointer (inv, rays, T and cams are required)", what);
-    MVSGI_REQUIRE(N >= 1 && N <= kMaxCams, "%s: N = %d cameras (need 1 <= N <= %d)", what, N, kMaxCams);
-    MVSGI_REQUIRE(B >= 1 && H >= 1 && W >= 1, "%s: non-positive dimension (B = %lld, H = %d, W = %d)", what, B, H, W);
+    if (check_view_dims(what, B, N, H, W)) return 1;
     MVSGI_REQUIRE(Hz >= 1 && Wz >= 1, "%s: non-positive dimension (buffer %d x %d)", what, Hz, Wz);
     MVSGI_REQUIRE(Hz <= (1 << 24) && Wz <= (1 << 24), "%s: buffer %d x %d: a side above 2^24 is no exact float", what, Hz, Wz);
     MVSGI_REQUIRE((long long)H * W < (1ll << 31) && (long long)Hz * Wz < (1ll << 31) && B < (1ll << 31),
@@ -262,23 +193,7 @@ int vis_setup(const char* what, const float* inv, const float* rays, const float
     MVSGI_REQUIRE(B * N <= ((1ll << 41) - 1) / plane, "%s: B * N * Hz * Wz = %lld * %lld cells is too large for one launch (< 2^41)", what,
                   B * N, plane);
     cells = B * N * plane;
-    memset(&rig, 0, sizeof(rig));
-    for (int k = 0; k < N; ++k) {
-        const float* t = cams_host + k * kCamFloats;
-        VisCam& c = rig.cam[k];
-        MVSGI_REQUIRE(t[0] == (float)DOUBLE_SPHERE || t[0] == (float)EQUIRECT,
-                      "%s: camera %d: unknown model id %g (0 = double sphere, 1 = equirectangular)", what, k, (double)t[0]);
-        c.model = (int)t[0];
-        memcpy(c.T, T_host + k * 16, sizeof(c.T));
-        if (c.model == DOUBLE_SPHERE) {
-            // calib_h - 1 and calib_w - 1 of an integer shape: whole numbers a float holds exactly, so the casts below are exact
-            auto size_m1 = [](float v) { return v >= 1.0f && v < 16777216.0f && v == truncf(v); };
-            MVSGI_REQUIRE(size_m1(t[8]) && size_m1(t[9]), "%s: camera %d: calib shape (%g, %g) (need calib > 1)", what, k,
-                          (double)t[8] + 1.0, (double)t[9] + 1.0);
-            c.ds = make_ds_params(t[1], t[2], t[3], t[4], t[5], t[6], (int)t[8] + 1, (int)t[9] + 1, t[7]);
-        }
-    }
-    if (W % 4 == 0) MVSGI_REQUIRE(aligned(inv, 16) && aligned(rays, 16), "%s: inv and rays must be 16-byte aligned when W %% 4 == 0", what);
+    if (load_view_rig(what, T_host, cams_host, N, rig) || check_quad_loads(what, inv, rays, W)) return 1;
     MVSGI_REQUIRE(mvsgi::cdiv(B * H * ((W + 3) / 4), 256) < (1ll << 31), "%s: B * H * W too large for one launch", what);
     return 0;
 }
@@ -289,7 +204,7 @@ extern "C" int mvsgi_camera_range_f32(const float* inv, const float* rays, const
                                       const unsigned char* mask, int mask_per_frame, int footprint, float* z2, long long B, int N, int H,
                                       int W, int Hz, int Wz, float bf, mvsgi_stream_t stream) {
     const char* what = "mvsgi_camera_range_f32";
-    VisRig rig;
+    ViewRig rig;
     long long cells = 0;
     if (vis_setup(what, inv, rays, T_host, cams_host, B, N, H, W, Hz, Wz, rig, cells)) return 1;
     MVSGI_REQUIRE(z2, "%s: null pointer (z2)", what);
@@ -315,7 +230,7 @@ extern "C" int mvsgi_visibility_f32(const float* inv, const float* rays, const f
                                     float k2, unsigned char* visible, unsigned char* n_visible, float* range, long long B, int N, int H,
                                     int W, int Hz, int Wz, float bf, mvsgi_stream_t stream) {
     const char* what = "mvsgi_visibility_f32";
-    VisRig rig;
+    ViewRig rig;
     long long cells = 0;
     if (vis_setup(what, inv, rays, T_host, cams_host, B, N, H, W, Hz, Wz, rig, cells)) return 1;
     MVSGI_REQUIRE(z2, "%s: null pointer (z2)", what);

@@ -1107,21 +1107,14 @@ def resample_bilinear(imgs, grid, valid, invalid_value: float = 0.0, out=None) -
 REPROJECT_CAM_FLOATS = 10     # camera table row: model id (0 double sphere, 1 equirectangular), xi, alpha, fx, fy, cx, cy, w2, calib_h - 1, calib_w - 1
 
 
-def reproject(inv, rays, T, cams, bf: float, imgs=None, invalid_value: float = 0.0, want=("xyz", "warped", "valid"), out=None) -> dict:
-    """Back-projection of an inverse-distance map (spherical_sweep_stereo.py:417-471; include/mvsgi.h: mvsgi_reproject_f32):
-    d = bf / inv, xyz = rays * d, each camera's projection of T[n] xyz, its validity and the camera images sampled there.
-    inv [B, H, W] (or [B, 1, H, W]) fp32 on the device; rays [3, H, W] fp32 on the device; T [N, 4, 4] and cams
-    [N, REPROJECT_CAM_FLOATS] host tensors (fp32); imgs uint8 [B * N, Hr, Wr, 3] or fp32 [B * N, C, Hr, Wr] on the device,
-    needed exactly when "warped" is wanted.  want: the outputs to compute, of "xyz" [B, 3, H, W], "warped" [B, N, C, H, W],
-    "valid" [B, N, H, W] bool and "grid" [B, N, H, W, 2]; out: a dict with tensors to write in place (graph capture).
-    One launch on inv's stream; there is no CPU fallback.  -> dict of the wanted outputs."""
+def _view_args(who: str, inv, rays, T, cams):
+    """inv, rays, T and cams as reproject() takes them -> (inv [B, H, W], rays, T, cams, B, H, W, N)"""
     inv = _dev(inv, "inv")
     rays = _dev(rays, "rays")
     if inv.dim() == 4 and inv.shape[1] == 1:
         inv = inv.squeeze(1)
     if inv.dim() != 3 or rays.dim() != 3 or rays.shape[0] != 3 or tuple(rays.shape[1:]) != tuple(inv.shape[1:]) or rays.device != inv.device:
         raise AssertionError(f"inv must be [B, H, W] and rays [3, H, W] on one device, got {tuple(inv.shape)}, {tuple(rays.shape)}")
-    B, Ho, Wo = inv.shape
     T = torch.as_tensor(T)
     cams = torch.as_tensor(cams)
     if T.is_cuda or cams.is_cuda or T.dtype != torch.float32 or cams.dtype != torch.float32:
@@ -1130,28 +1123,64 @@ def reproject(inv, rays, T, cams, bf: float, imgs=None, invalid_value: float = 0
     if tuple(T.shape) != (N, 4, 4) or tuple(cams.shape) != (N, REPROJECT_CAM_FLOATS):
         raise AssertionError(f"T must be [N, 4, 4] and cams [N, {REPROJECT_CAM_FLOATS}], got {tuple(T.shape)}, {tuple(cams.shape)}")
     if not 1 <= N <= sweep_max_cams():
-        raise ValueError(f"reproject: {N} cameras (1 ... {sweep_max_cams()} are supported)")
-    T, cams = T.contiguous(), cams.contiguous()
+        raise ValueError(f"{who}: {N} cameras (1 ... {sweep_max_cams()} are supported)")
+    B, Ho, Wo = (int(v) for v in inv.shape)
+    return inv, rays, T.contiguous(), cams.contiguous(), B, Ho, Wo, N
+
+
+def _pixel_mask(mask, B: int, Ho: int, Wo: int, dev):
+    """A pixel mask uint8 / bool [H, W] or [B, H, W], read in place -> (mask, mask_per_frame); (None, 0) without one"""
+    if mask is None:
+        return None, 0
+    mask = _cloud_plane(mask, "mask", None, dev, (torch.uint8, torch.bool))
+    if tuple(mask.shape) not in ((Ho, Wo), (B, Ho, Wo)):
+        raise AssertionError(f"mask must be [{Ho}, {Wo}] or [{B}, {Ho}, {Wo}], got {list(mask.shape)}")
+    if Wo % 4 == 0 and mask.data_ptr() % 4:
+        raise AssertionError("mask must be 4-byte aligned when W % 4 == 0")
+    return mask, 1 if mask.dim() == 3 else 0
+
+
+def _wanted(want, names) -> tuple:
+    """want as a tuple, checked to be a selection of names.  Apart from _outputs(): some shapes there come from arguments that are
+    checked after the selection (the images' channels)"""
     want = tuple(want)
-    if not want or set(want) - {"xyz", "warped", "valid", "grid"} or len(set(want)) != len(want):
-        raise ValueError(f"want: a non-empty selection of 'xyz', 'warped', 'valid', 'grid', got {want}")
+    if not want or set(want) - set(names) or len(set(want)) != len(want):
+        raise ValueError(f"want: a non-empty selection of {', '.join(repr(k) for k in names)}, got {want}")
+    return want
+
+
+def _outputs(want, out, dev, shapes: dict) -> dict:
+    """The wanted outputs, each out[k] where the caller gave one (checked against shapes[k] = (shape, dtype)), else a new tensor"""
+    res = {}
+    for k in want:
+        shape, dtype = shapes[k]
+        t = None if out is None else out.get(k)
+        if t is None:
+            t = torch.empty(shape, device=dev, dtype=dtype)
+        elif tuple(t.shape) != shape or t.dtype != dtype or t.device != dev or not t.is_contiguous() or t.data_ptr() % 16:
+            raise AssertionError(f"out['{k}'] must be a contiguous, 16-byte aligned {dtype} {list(shape)} tensor on {dev}")
+        res[k] = t
+    return res
+
+
+def reproject(inv, rays, T, cams, bf: float, imgs=None, invalid_value: float = 0.0, want=("xyz", "warped", "valid"), out=None) -> dict:
+    """Back-projection of an inverse-distance map (spherical_sweep_stereo.py:417-471; include/mvsgi.h: mvsgi_reproject_f32):
+    d = bf / inv, xyz = rays * d, each camera's projection of T[n] xyz, its validity and the camera images sampled there.
+    inv [B, H, W] (or [B, 1, H, W]) fp32 on the device; rays [3, H, W] fp32 on the device; T [N, 4, 4] and cams
+    [N, REPROJECT_CAM_FLOATS] host tensors (fp32); imgs uint8 [B * N, Hr, Wr, 3] or fp32 [B * N, C, Hr, Wr] on the device,
+    needed exactly when "warped" is wanted.  want: the outputs to compute, of "xyz" [B, 3, H, W], "warped" [B, N, C, H, W],
+    "valid" [B, N, H, W] bool and "grid" [B, N, H, W, 2]; out: a dict with tensors to write in place (graph capture).
+    One launch on inv's stream; there is no CPU fallback.  -> dict of the wanted outputs."""
+    inv, rays, T, cams, B, Ho, Wo, N = _view_args("reproject", inv, rays, T, cams)
+    want = _wanted(want, ("xyz", "warped", "valid", "grid"))
     kind, C, Hr, Wr = 0, 0, 0, 0
     if "warped" in want:
         imgs, u8, C, Hr, Wr = _images(imgs, "B*N", count=B * N, device=inv.device)
         kind = 0 if u8 else 1
     elif imgs is not None:
         raise ValueError("reproject: imgs given but 'warped' is not wanted")
-    shapes = {"xyz": ((B, 3, Ho, Wo), torch.float32), "warped": ((B, N, C, Ho, Wo), torch.float32),
-              "valid": ((B, N, Ho, Wo), torch.bool), "grid": ((B, N, Ho, Wo, 2), torch.float32)}
-    res = {}
-    for k in want:
-        shape, dtype = shapes[k]
-        t = None if out is None else out.get(k)
-        if t is None:
-            t = torch.empty(shape, device=inv.device, dtype=dtype)
-        elif tuple(t.shape) != shape or t.dtype != dtype or t.device != inv.device or not t.is_contiguous() or t.data_ptr() % 16:
-            raise AssertionError(f"out['{k}'] must be a contiguous, 16-byte aligned {dtype} {list(shape)} tensor on {inv.device}")
-        res[k] = t
+    res = _outputs(want, out, inv.device, {"xyz": ((B, 3, Ho, Wo), torch.float32), "warped": ((B, N, C, Ho, Wo), torch.float32),
+                                           "valid": ((B, N, Ho, Wo), torch.bool), "grid": ((B, N, Ho, Wo, 2), torch.float32)})
     _call("mvsgi_reproject_f32", inv.data_ptr(), rays.data_ptr(), _ptr(imgs) if "warped" in want else None, kind, T.data_ptr(),
           cams.data_ptr(), _ptr(res.get("xyz")), _ptr(res.get("warped")), _ptr(res.get("valid")), _ptr(res.get("grid")), B, N, C, Hr, Wr,
           Ho, Wo, float(bf), float(invalid_value), _stream_ptr(inv))
@@ -1448,41 +1477,16 @@ def photo_consistency(inv, rays, T, cams, bf: float, imgs, cam_masks=None, mask=
     is out["table"].  Two launches on inv's stream (one without the table), nothing else: with `out` and `ws` (photo_ws; needed with
     the table only) given the call allocates nothing and can be captured.  There is no CPU fallback.  -> dict of the wanted outputs."""
     global PHOTO_EVALUATIONS
-    inv = _dev(inv, "inv")
-    rays = _dev(rays, "rays")
-    if inv.dim() == 4 and inv.shape[1] == 1:
-        inv = inv.squeeze(1)
-    if inv.dim() != 3 or rays.dim() != 3 or rays.shape[0] != 3 or tuple(rays.shape[1:]) != tuple(inv.shape[1:]) or rays.device != inv.device:
-        raise AssertionError(f"inv must be [B, H, W] and rays [3, H, W] on one device, got {tuple(inv.shape)}, {tuple(rays.shape)}")
-    B, Ho, Wo = (int(v) for v in inv.shape)
+    inv, rays, T, cams, B, Ho, Wo, N = _view_args("photo_consistency", inv, rays, T, cams)
     dev = inv.device
-    T = torch.as_tensor(T)
-    cams = torch.as_tensor(cams)
-    if T.is_cuda or cams.is_cuda or T.dtype != torch.float32 or cams.dtype != torch.float32:
-        raise TypeError("T and cams are fp32 host tensors (they travel in the kernel's arguments)")
-    N = T.shape[0] if T.dim() == 3 else -1
-    if tuple(T.shape) != (N, 4, 4) or tuple(cams.shape) != (N, REPROJECT_CAM_FLOATS):
-        raise AssertionError(f"T must be [N, 4, 4] and cams [N, {REPROJECT_CAM_FLOATS}], got {tuple(T.shape)}, {tuple(cams.shape)}")
-    if not 1 <= N <= sweep_max_cams():
-        raise ValueError(f"photo_consistency: {N} cameras (1 ... {sweep_max_cams()} are supported)")
-    T, cams = T.contiguous(), cams.contiguous()
-    want = tuple(want)
-    if not want or set(want) - set(PHOTO_OUTPUTS) or len(set(want)) != len(want):
-        raise ValueError(f"want: a non-empty selection of {', '.join(repr(k) for k in PHOTO_OUTPUTS)}, got {want}")
+    want = _wanted(want, PHOTO_OUTPUTS)
     imgs, u8, C, Hr, Wr = _images(imgs, "B*N", count=B * N, device=dev)
     if cam_masks is not None:
         cam_masks = _dev(cam_masks, "cam_masks")
         if tuple(cam_masks.shape) != (N, 1, Hr, Wr) or cam_masks.device != dev:
             raise AssertionError(f"cam_masks must be fp32 [{N}, 1, {Hr}, {Wr}] (the size of the images) on {dev}, got "
                                  f"{tuple(cam_masks.shape)} on {cam_masks.device}")
-    mask_per_frame = 0
-    if mask is not None:
-        mask = _cloud_plane(mask, "mask", None, dev, (torch.uint8, torch.bool))
-        if tuple(mask.shape) not in ((Ho, Wo), (B, Ho, Wo)):
-            raise AssertionError(f"mask must be [{Ho}, {Wo}] or [{B}, {Ho}, {Wo}], got {list(mask.shape)}")
-        if Wo % 4 == 0 and mask.data_ptr() % 4:
-            raise AssertionError("mask must be 4-byte aligned when W % 4 == 0")
-        mask_per_frame = 1 if mask.dim() == 3 else 0
+    mask, mask_per_frame = _pixel_mask(mask, B, Ho, Wo, dev)
     if cam_seen is not None:
         cam_seen = _cloud_plane(cam_seen, "cam_seen", (B, N, Ho, Wo), dev, (torch.uint8, torch.bool))
         if Wo % 4 == 0 and cam_seen.data_ptr() % 4:
@@ -1493,17 +1497,9 @@ def photo_consistency(inv, rays, T, cams, bf: float, imgs, cam_masks=None, mask=
         out = dict(out or {}, table=table)
         if "table" not in want:
             raise ValueError("photo_consistency: a table was given but 'table' is not wanted")
-    shapes = {"n_views": ((B, Ho, Wo), torch.uint8), "photo_var": ((B, Ho, Wo), torch.float32), "photo_std": ((B, Ho, Wo), torch.float32),
-              "mean_colour": ((B, C, Ho, Wo), torch.float32), "table": ((B + 1, len(PHOTO_COLUMNS)), torch.float64)}
-    res = {}
-    for k in want:
-        shape, dtype = shapes[k]
-        t = None if out is None else out.get(k)
-        if t is None:
-            t = torch.empty(shape, device=dev, dtype=dtype)
-        elif tuple(t.shape) != shape or t.dtype != dtype or t.device != dev or not t.is_contiguous() or t.data_ptr() % 16:
-            raise AssertionError(f"out['{k}'] must be a contiguous, 16-byte aligned {dtype} {list(shape)} tensor on {dev}")
-        res[k] = t
+    res = _outputs(want, out, dev, {"n_views": ((B, Ho, Wo), torch.uint8), "photo_var": ((B, Ho, Wo), torch.float32),
+                                    "photo_std": ((B, Ho, Wo), torch.float32), "mean_colour": ((B, C, Ho, Wo), torch.float32),
+                                    "table": ((B + 1, len(PHOTO_COLUMNS)), torch.float64)})
     ws_ptr, ws_bytes = None, 0
     if "table" in want:
         if ws is None:
@@ -1535,27 +1531,6 @@ def visibility_k2(tol: float) -> float:
     return (1.0 + tol) * (1.0 + tol)
 
 
-def _view_args(who: str, inv, rays, T, cams):
-    """inv, rays, T and cams as reproject() takes them -> (inv [B, H, W], rays, T, cams, B, H, W, N)"""
-    inv = _dev(inv, "inv")
-    rays = _dev(rays, "rays")
-    if inv.dim() == 4 and inv.shape[1] == 1:
-        inv = inv.squeeze(1)
-    if inv.dim() != 3 or rays.dim() != 3 or rays.shape[0] != 3 or tuple(rays.shape[1:]) != tuple(inv.shape[1:]) or rays.device != inv.device:
-        raise AssertionError(f"inv must be [B, H, W] and rays [3, H, W] on one device, got {tuple(inv.shape)}, {tuple(rays.shape)}")
-    T = torch.as_tensor(T)
-    cams = torch.as_tensor(cams)
-    if T.is_cuda or cams.is_cuda or T.dtype != torch.float32 or cams.dtype != torch.float32:
-        raise TypeError("T and cams are fp32 host tensors (they travel in the kernel's arguments)")
-    N = T.shape[0] if T.dim() == 3 else -1
-    if tuple(T.shape) != (N, 4, 4) or tuple(cams.shape) != (N, REPROJECT_CAM_FLOATS):
-        raise AssertionError(f"T must be [N, 4, 4] and cams [N, {REPROJECT_CAM_FLOATS}], got {tuple(T.shape)}, {tuple(cams.shape)}")
-    if not 1 <= N <= sweep_max_cams():
-        raise ValueError(f"{who}: {N} cameras (1 ... {sweep_max_cams()} are supported)")
-    B, Ho, Wo = (int(v) for v in inv.shape)
-    return inv, rays, T.contiguous(), cams.contiguous(), B, Ho, Wo, N
-
-
 def _zshape(zshape):
     try:
         Hz, Wz = (int(v) for v in zshape)
@@ -1579,14 +1554,7 @@ def camera_range(inv, rays, T, cams, bf: float, zshape, mask=None, footprint: in
     Hz, Wz = _zshape(zshape)
     if footprint not in (1, 2):
         raise ValueError(f"footprint: 1 or 2, got {footprint!r}")
-    mask_per_frame = 0
-    if mask is not None:
-        mask = _cloud_plane(mask, "mask", None, dev, (torch.uint8, torch.bool))
-        if tuple(mask.shape) not in ((Ho, Wo), (B, Ho, Wo)):
-            raise AssertionError(f"mask must be [{Ho}, {Wo}] or [{B}, {Ho}, {Wo}], got {list(mask.shape)}")
-        if Wo % 4 == 0 and mask.data_ptr() % 4:
-            raise AssertionError("mask must be 4-byte aligned when W % 4 == 0")
-        mask_per_frame = 1 if mask.dim() == 3 else 0
+    mask, mask_per_frame = _pixel_mask(mask, B, Ho, Wo, dev)
     if out is None:
         out = torch.empty((B, N, Hz, Wz), device=dev, dtype=torch.float32)
     else:
@@ -1609,19 +1577,9 @@ def visibility(inv, rays, T, cams, bf: float, z2, tol: float = VISIBILITY_TOL, w
         raise AssertionError(f"z2 must be [{B}, {N}, Hz, Wz], got {list(z2.shape)}")
     Hz, Wz = _zshape(z2.shape[2:])
     k2 = visibility_k2(tol)
-    want = tuple(want)
-    if not want or set(want) - set(VISIBILITY_OUTPUTS) or len(set(want)) != len(want):
-        raise ValueError(f"want: a non-empty selection of {', '.join(repr(k) for k in VISIBILITY_OUTPUTS)}, got {want}")
-    shapes = {"visible": ((B, N, Ho, Wo), torch.bool), "n_visible": ((B, Ho, Wo), torch.uint8), "range": ((B, N, Hz, Wz), torch.float32)}
-    res = {}
-    for k in want:
-        shape, dtype = shapes[k]
-        t = None if out is None else out.get(k)
-        if t is None:
-            t = torch.empty(shape, device=dev, dtype=dtype)
-        elif tuple(t.shape) != shape or t.dtype != dtype or t.device != dev or not t.is_contiguous() or t.data_ptr() % 16:
-            raise AssertionError(f"out['{k}'] must be a contiguous, 16-byte aligned {dtype} {list(shape)} tensor on {dev}")
-        res[k] = t
+    want = _wanted(want, VISIBILITY_OUTPUTS)
+    res = _outputs(want, out, dev, {"visible": ((B, N, Ho, Wo), torch.bool), "n_visible": ((B, Ho, Wo), torch.uint8),
+                                    "range": ((B, N, Hz, Wz), torch.float32)})
     _call("mvsgi_visibility_f32", inv.data_ptr(), rays.data_ptr(), T.data_ptr(), cams.data_ptr(), z2.data_ptr(), k2,
           _ptr(res.get("visible")), _ptr(res.get("n_visible")), _ptr(res.get("range")), B, N, Ho, Wo, Hz, Wz, float(bf), _stream_ptr(inv))
     return res

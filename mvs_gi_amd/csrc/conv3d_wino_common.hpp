@@ -1,7 +1,14 @@
-// Shared by the Winograd-form kernels (csrc/conv3d_wino.hip: K2w, the level-0 residual convs; csrc/conv3d_wino_up2.hip: K3w, the
-// polyphase ResizeConv3d): mixed-precision fma helpers on fp16 pairs, the split of a value pair, and the inline-asm MFMA forms that
-// keep the weights in the accumulator half of the register file.  Include inside the translation unit's anonymous namespace, behind
-// split_fmt.hpp.
+// The plane march of the Winograd-form kernels (csrc/conv3d_wino.hip: K2w, the level-0 residual convs; csrc/conv3d_wino_up2.hip: K3w,
+// the polyphase ResizeConv3d), once: mixed-precision fma helpers on fp16 pairs and the split of a value pair; the LDS image geometry;
+// a wave's role, its resident weights, its fragment reads and DMA plan; the transform's pieces; the MFMA slot table and the inline-asm
+// MFMA forms that keep the weights in the accumulator half of the register file; the exchange through A^T; the XCD share of the unit
+// space; the weight packing's rules.  A kernel keeps what is its own: ring sizes and LDS budget (namespace wn / wu), what sits between
+// w-pass and split, its staging requests (*_DMA_ISSUE, *_RES_DMA, *_DPIECE), its epilogue, *_STEP / *_FINISH with their wait counts, its
+// prologue, unit loop and output addressing.  The macros use the kernels' names for a wave's state (a, lds, tid, lane, wv .. osg of
+// WN_LANE / WN_ROLE, wh, wl, rd0, rd1, raw, T, X0, X1, L0, L1, vh, vl, Y, frame_bytes, total_bytes, Wp, DEPTH, ZB) and are macros, not
+// functions, because the kernels' assembly follows the spelling: a unit is one basic block of `if constexpr` pieces around asm
+// statements, and even in the prologue an inline function or another statement order gives another schedule.
+// Include inside the translation unit's anonymous namespace, behind split_fmt.hpp.
 #pragma once
 
 // fp32 <- f16 half of a dword through the mixed-precision fma (one instruction where widen + add are two or three)
@@ -53,6 +60,156 @@ __device__ __forceinline__ void split_pair(float v0, float v1, unsigned& hi, uns
     hi = sf_cvt_pk<true>(v0, v1);
     lo = sf_cvt_pk<true>(mix_sub_lo(v0, hi), mix_sub_hi(v1, hi));
 }
+// the same under MODE.FP16_OVFL: the conversions saturate by themselves
+__device__ __forceinline__ void split_pair_ovfl(float v0, float v1, unsigned& hi, unsigned& lo, float& satm) {
+    satm = sf_sat_acc(satm, v0, v1);         // range report (csrc/split_fmt.hpp): on the unclamped values
+    hi = sf_cvt_pk<true>(v0, v1);
+    lo = sf_cvt_pk<true>(mix_sub_lo(v0, hi), mix_sub_hi(v1, hi));
+}
+
+namespace wino {
+// LDS image of one input plane of a unit: 4 rows x 34 columns x 8 sixteen-byte pieces per voxel, as TWO sub-images: the pieces read by
+// the even channel groups (kg = 0, 2) and those read by the odd ones, SUB slots apart (a multiple of 16); inside a sub-image even and
+// odd columns apart, 5 slots per voxel (its 4 pieces + 1 pad).  ds_read_b128 is serviced in the lane groups {0-3, 12-15, 20-27},
+// {4-11, 16-19, 28-31}, ... (MI355X_MICROARCH.md, LDS): tiles n = 0-3, 12-15 of one channel group with tiles 4-11 of the next.  The two
+// read the same slot of their own sub-image's records, so a group walks 16 same-parity columns with stride 5, odd: all 16
+// sixteen-byte units of the 256-byte bank row (a single image with 9 slots per voxel is conflict-free for 16 CONSECUTIVE lanes and
+// two-way conflicted under the real groups: 8 LDS cycles per read instead of 4).  The staging side stays pieces of 128-byte records.
+constexpr int HALF = 17, PITCH = 5, RPITCH = 9;   // slots per voxel: plane sub-images | residual records (8 pieces + 1 pad)
+constexpr int NVOX = 4 * 2 * HALF;                // 136 voxels of a plane region
+constexpr int SUB = (NVOX * PITCH + 15) / 16 * 16;    // 688
+constexpr int PLANE_SLOTS = 2 * SUB;              // 1376
+constexpr int NDMA = 22, DPW = 6;                 // 1 KiB pieces per plane; per wave (waves 2, 3 aim their sixth at a dummy KiB)
+constexpr int PLANE_LDS = NDMA * 1024;            // 22,528
+constexpr int RD2 = 16;                           // from a lane's first piece to its second (hi -> lo, or fp32 channels 0-3 -> 4-7)
+// residual (K3w: correction) records of one output plane of a unit: 2 rows x 32 voxels at the 9-slot pitch (the epilogue's 8-byte reads
+// walk them with stride 18 slots: two-way conflicts at worst), 576 slots in 9 one-KiB pieces; a ring of three images (a unit's last
+// plane is requested a step early)
+constexpr int RDPW = 3, RES_LDS = 4 * RDPW * 1024, NRES = 3;
+constexpr unsigned NOREC = 0xffffff00u;           // a request offset beyond every descriptor's num_records: the DMA writes zeros
+static_assert(PLANE_SLOTS <= NDMA * 64, "DMA pieces cover the image");
+}  // namespace wino
+
+// A wave's role.  Wave wv owns row a = wv of the 4 x 4 transform space; lane (tile n, channel group kg).  B^T row a has two non-zeros:
+// t = x[i0] + sgn * x[i1].  After the exchange the wave finishes output voxel (pa, q) of every tile, A^T's sign osg.  (Two macros: the
+// kernels' tensor sizes are formed between them, and the order of these statements decides hipcc's schedule of the prologue.)
+#define WN_LANE()                                                                                           \
+    const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);                                                \
+    const int n = lane & 15, kg = lane >> 4;
+#define WN_ROLE()                                                                                           \
+    const int i0 = wv == 0 ? 0 : (wv == 2 ? 2 : 1);                                                         \
+    const int i1 = wv == 0 ? 2 : (wv == 1 ? 2 : (wv == 2 ? 1 : 3));                                         \
+    const float sgn = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(wv == 1 ? 0x3f800000 : 0xbf800000)); \
+    const int pa = wv & 1, q = wv >> 1;                                                                     \
+    const float osg = pa ? -1.f : 1.f;
+
+// Resident weights: the wave's 4 (b) x 3 (kd) x 2 (cout tiles) x (hi, lo) fragments from fragment row ROW of wp
+// ([row][b 4][kd 3][cout tile 2][hi | lo][64 lanes] sixteen-byte fragments), pinned to the accumulator file for the whole launch.
+#define WN_WEIGHTS(ROW)                                                                                     \
+    u32x4 wh[4][3][2], wl[4][3][2];                                                                         \
+    _Pragma("unroll") for (int b = 0; b < 4; ++b)                                                           \
+        _Pragma("unroll") for (int kd = 0; kd < 3; ++kd)                                                    \
+            _Pragma("unroll") for (int c = 0; c < 2; ++c) {                                                 \
+                const u32x4* p_ = a.wp + ((long long)(((((ROW) * 4 + b) * 3 + kd) * 2 + c) * 2)) * 64 + lane; \
+                wh[b][kd][c] = p_[0];                                                                       \
+                wl[b][kd][c] = p_[64];                                                                      \
+            }                                                                                               \
+    _Pragma("unroll") for (int b = 0; b < 4; ++b)                                                           \
+        _Pragma("unroll") for (int kd = 0; kd < 3; ++kd)                                                    \
+            _Pragma("unroll") for (int c = 0; c < 2; ++c) asm volatile("" : "+a"(wh[b][kd][c]), "+a"(wl[b][kd][c]));
+
+// fragment reads: a lane's first piece (fp16 pairs: hi, slice kg >> 1, channel half kg & 1; fp32 records: channels 8 kg .. 8 kg + 3, the
+// second piece RD2 on) of column 2 n in patch row I, image 0
+#define WN_FRAG_RD(I) (((kg & 1) * SUB + ((I) * 2 * HALF + n) * PITCH + (kg >> 1) * 2) * 16)
+// DMA plan of a plane image: piece m = wv + 4 k fills slots [64 m, 64 m + 64); voff[k] = the request offset of this lane's slot from
+// the patch origin.  Piece c of a record: fp32 records (A32) -- even groups read pieces 0, 1 | 4, 5, odd ones 2, 3 | 6, 7; fp16 pairs --
+// [slice][hi | lo][channels 0-7 | 8-15]: even groups read the "0-7" pieces (0, 2 | 4, 6), odd ones the "8-15" pieces (1, 3 | 5, 7)
+#define WN_PLANE_PLAN(A32)                                                                                  \
+    unsigned voff[DPW];                                                                                     \
+    _Pragma("unroll") for (int k = 0; k < DPW; ++k) {                                                       \
+        const int m = wv + 4 * k;                                                                           \
+        const int sl = m * 64 + lane;                                                                       \
+        const int sub = sl >= SUB ? 1 : 0, rem = sl - sub * SUB;                                            \
+        const int vox = rem / PITCH, c = rem - vox * PITCH;                                                 \
+        const int row = vox / (2 * HALF), rr = vox - row * (2 * HALF);                                      \
+        const int par = rr / HALF, idx = rr - par * HALF;                                                   \
+        const int piece = (A32) ? (c >> 1) * 4 + sub * 2 + (c & 1) : c * 2 + sub;                           \
+        voff[k] = (m < NDMA && sl < PLANE_SLOTS && vox < NVOX && c < 4) ? (unsigned)((row * Wp + 2 * idx + par) * 128 + piece * 16) : NOREC; \
+    }
+// request K of this lane into a residual / correction image: slot -> voxel (row vox >> 5, column vox & 31) and piece of its record;
+// slots with vox >= 64 or piece == 8 are pads
+#define WN_RES_SLOT(K)                                                                                      \
+    const int sl = (wv + 4 * (K)) * 64 + lane;                                                              \
+    const int vox = sl / RPITCH, piece = sl - vox * RPITCH;
+// The XCD share of the unit space: workgroups are dealt to the 8 XCDs round-robin; XCD x owns the contiguous eighth [lo, lo + cnt) of
+// the T units and its workgroups walk it side by side, so that the units sharing patch rows -- tile rows r and r + 1, groups_w ids
+// apart -- are read through ONE L2 at about the same time (the plain walk blockIdx + k * G fetched every shared row from HBM twice:
+// 1313 MB per launch against 840 MB of tensors, K2w)
+__device__ __forceinline__ void wino_xcd_share(int T, int x, int& lo, int& cnt) {
+    const int q8 = T >> 3, r8 = T & 7;
+    lo = x < r8 ? x * (q8 + 1) : r8 * (q8 + 1) + (x - r8) * q8;
+    cnt = q8 + (x < r8 ? 1 : 0);
+}
+
+// descriptor whose base is the patch origin of unit U (padded rows 2 r .., columns 32 c ..); no records past the workgroup's last unit:
+// requests through it write zeros
+#define WN_DESC(U, LIVE)                                                                                    \
+    ({                                                                                                      \
+        const int c_ = (U) % a.groups_w, t_ = (U) / a.groups_w;                                             \
+        const int r_ = t_ % a.tiles_h, b_ = t_ / a.tiles_h;                                                 \
+        const long long off_ = (LIVE) ? b_ * frame_bytes + ((long long)(2 * r_) * Wp + 32 * c_) * 128 : 0;  \
+        const long long left_ = total_bytes - off_;                                                         \
+        window_desc(a.x + off_, 0, left_, LIVE);                                                            \
+    })
+// the raw patches of the plane in image BUF_: [patch row i0 | i1][column][first | second piece]
+#define WN_READ(BUF_)                                                                                       \
+    {                                                                                                       \
+        const unsigned char* im_ = lds + (BUF_) * PLANE_LDS;                                                \
+        _Pragma("unroll") for (int j_ = 0; j_ < 4; ++j_) {                                                  \
+            const int o_ = (((j_ & 1) * HALF + (j_ >> 1)) * PITCH) * 16;                                    \
+            raw[0][j_][0] = *reinterpret_cast<const u32x4*>(im_ + rd0 + o_);                                \
+            raw[0][j_][1] = *reinterpret_cast<const u32x4*>(im_ + rd0 + o_ + RD2);                          \
+            raw[1][j_][0] = *reinterpret_cast<const u32x4*>(im_ + rd1 + o_);                                \
+            raw[1][j_][1] = *reinterpret_cast<const u32x4*>(im_ + rd1 + o_ + RD2);                          \
+        }                                                                                                   \
+    }
+
+// The transform raw -> V[VN] (all four b of this wave's a; split; B-operand layout: lane (tile n, kg) holds channels 8 kg .. 8 kg + 7)
+// goes piece by piece, each sized to ride behind one MFMA: M = 0 .. 71 -> channel pair d = M / 18 and, within it, 8 pieces of the h-pass
+// (one (column j, half) each), then per b one piece of the w-pass (+ what the kernel does to X0, X1) and one of the split; piece 16
+// closes the last b.  A kernel's *_TPIECE is that frame around the pieces below.
+// h-pass of fp16 pairs, piece R: three dependent mixed-precision fmas.  ONE asm statement per chain: hipcc pads every VGPR an asm
+// statement defines against a use by the very next instruction (it must assume a partial-register write), 4 cycles per pad, and only
+// its own instructions count as distance
+#define WN_HPASS(R, J, D)                                                                                   \
+    if constexpr (((R) & 1) == 0) {                                                                         \
+        asm("v_fma_mix_f32 %0, %1, 1.0, %2 op_sel:[0,0,0] op_sel_hi:[1,0,1]\n\t"                            \
+            "v_fma_mix_f32 %0, %3, %5, %0 op_sel:[0,0,0] op_sel_hi:[1,0,0]\n\t"                             \
+            "v_fma_mix_f32 %0, %4, %5, %0 op_sel:[0,0,0] op_sel_hi:[1,0,0]"                                  \
+            : "=&v"(T[0][J]) : "v"(raw[0][J][0][D]), "v"(raw[0][J][1][D]), "v"(raw[1][J][0][D]), "v"(raw[1][J][1][D]), "s"(sgn)); \
+    } else {                                                                                                \
+        asm("v_fma_mix_f32 %0, %1, 1.0, %2 op_sel:[1,0,1] op_sel_hi:[1,0,1]\n\t"                            \
+            "v_fma_mix_f32 %0, %3, %5, %0 op_sel:[1,0,0] op_sel_hi:[1,0,0]\n\t"                             \
+            "v_fma_mix_f32 %0, %4, %5, %0 op_sel:[1,0,0] op_sel_hi:[1,0,0]"                                  \
+            : "=&v"(T[1][J]) : "v"(raw[0][J][0][D]), "v"(raw[0][J][1][D]), "v"(raw[1][J][0][D]), "v"(raw[1][J][1][D]), "s"(sgn)); \
+    }
+// w-pass of column b = B: row b of B^T on the h-pass of the channel pair
+#define WN_WPASS(B)                                                                                         \
+    {                                                                                                       \
+        constexpr int x_ = (B) == 0 ? 0 : ((B) == 2 ? 2 : 1), y_ = (B) == 0 ? 2 : ((B) == 1 ? 2 : ((B) == 2 ? 1 : 3)); \
+        X0 = (B) == 1 ? T[0][x_] + T[0][y_] : T[0][x_] - T[0][y_];                                          \
+        X1 = (B) == 1 ? T[1][x_] + T[1][y_] : T[1][x_] - T[1][y_];                                          \
+    }
+// the split of (X0, X1): the hi halves now, the lo halves one piece later (not right behind the asm that made them)
+#define WN_SPLIT_HI(VN, B, D)                                                                               \
+    {                                                                                                       \
+        const unsigned h_ = sf_cvt_pk<true>(X0, X1);                                                        \
+        vh[VN][B][D] = h_;                                                                                  \
+        asm("v_fma_mix_f32 %0, %2, -1.0, %3 op_sel:[0,0,0] op_sel_hi:[1,0,0]\n\t"                           \
+            "v_fma_mix_f32 %1, %2, -1.0, %4 op_sel:[1,0,0] op_sel_hi:[1,0,0]"                                \
+            : "=&v"(L0), "=&v"(L1) : "v"(h_), "v"(X0), "v"(X1));                                            \
+    }
+#define WN_SPLIT_LO(VN, B, D) vl[VN][B][D] = sf_cvt_pk<true>(L0, L1);
 
 // The MFMAs are inline asm so that the weights can be pinned to the accumulator half of the register file ("a"); the output
 // accumulators and the transformed activations are ordinary registers.  hipcc pads no hazards around asm: the step ends in WN_PAD
@@ -64,4 +221,73 @@ __device__ __forceinline__ void split_pair(float v0, float v1, unsigned& hi, uns
 #define WN_MFA(ACC, WREG, XREG) asm volatile("v_mfma_f32_16x16x32_f16 %0, %1, %2, %0" : "+a"(ACC) : "a"(WREG), "v"(XREG));
 #define WN_MFA0(ACC, WREG, XREG) asm volatile("v_mfma_f32_16x16x32_f16 %0, %1, %2, 0" : "+a"(ACC) : "a"(WREG), "v"(XREG));
 #define WN_PAD() asm volatile("s_nop 15\n\ts_nop 7" ::: "memory");
+// The MFMA of slot M = 0 .. 71 of plane step P (term-major inside a depth tap: the three products of an accumulator are 8 MFMAs apart;
+// the accumulators finished in this step first).  Open output planes: P + 1 in slot SI, P in slot SM, P - 1 in slot SF; V of plane P in
+// vh / vl[VB].  Depth taps that fall on the zero border have no MFMAs: kd = 2 of plane 0 (output plane -1), kd = 0 of plane DEPTH - 1
+// (output plane DEPTH); an output plane's first contribution starts its accumulators (C = 0).
+#define WN_SLOT_MFMA(M, P, SI, SM, SF, VB)                                                                  \
+    {                                                                                                       \
+        constexpr int g_ = (M) / 24, w_ = (M) % 24, tm_ = w_ / 8, b_ = (w_ % 8) / 2, c_ = w_ % 2;           \
+        constexpr int kd_ = 2 - g_, s_ = g_ == 0 ? (SF) : (g_ == 1 ? (SM) : (SI));                          \
+        constexpr bool live_ = !(g_ == 0 && (P) == 0) && !(g_ == 2 && (P) == DEPTH - 1);                    \
+        constexpr bool first_ = tm_ == 0 && (g_ == 2 || (g_ == 1 && (P) == 0));                             \
+        if constexpr (live_) {                                                                              \
+            if constexpr (s_ >= 1) {                                                                        \
+                if constexpr (first_) { WN_MFA0(Y[s_][b_][c_], wl[b_][kd_][c_], vh[VB][b_]) }               \
+                else if constexpr (tm_ == 0) { WN_MFA(Y[s_][b_][c_], wl[b_][kd_][c_], vh[VB][b_]) }         \
+                else if constexpr (tm_ == 1) { WN_MFA(Y[s_][b_][c_], wh[b_][kd_][c_], vl[VB][b_]) }         \
+                else { WN_MFA(Y[s_][b_][c_], wh[b_][kd_][c_], vh[VB][b_]) }                                 \
+            } else {                                                                                        \
+                if constexpr (first_) { WN_MF0(Y[s_][b_][c_], wl[b_][kd_][c_], vh[VB][b_]) }                \
+                else if constexpr (tm_ == 0) { WN_MF(Y[s_][b_][c_], wl[b_][kd_][c_], vh[VB][b_]) }          \
+                else if constexpr (tm_ == 1) { WN_MF(Y[s_][b_][c_], wh[b_][kd_][c_], vl[VB][b_]) }          \
+                else { WN_MF(Y[s_][b_][c_], wh[b_][kd_][c_], vh[VB][b_]) }                                  \
+            }                                                                                               \
+        }                                                                                                   \
+    }
+// F(M .. M + 7, ...) and F(0 .. 71, ...): the slots of a step, the transform pieces of a prologue
+#define WN_REP8(F, M, ...)                                                                                  \
+    F(M, __VA_ARGS__) F(M + 1, __VA_ARGS__) F(M + 2, __VA_ARGS__) F(M + 3, __VA_ARGS__)                     \
+    F(M + 4, __VA_ARGS__) F(M + 5, __VA_ARGS__) F(M + 6, __VA_ARGS__) F(M + 7, __VA_ARGS__)
+#define WN_REP72(F, ...)                                                                                    \
+    WN_REP8(F, 0, __VA_ARGS__) WN_REP8(F, 8, __VA_ARGS__) WN_REP8(F, 16, __VA_ARGS__) WN_REP8(F, 24, __VA_ARGS__) WN_REP8(F, 32, __VA_ARGS__) \
+    WN_REP8(F, 40, __VA_ARGS__) WN_REP8(F, 48, __VA_ARGS__) WN_REP8(F, 56, __VA_ARGS__) WN_REP8(F, 64, __VA_ARGS__)
+// plane step P of a kernel's STEP macro (P a compile-time constant: a unit is ONE basic block -- hipcc re-homes asm-tied accumulators at
+// block boundaries, behind the back of the hazards it cannot see): slots follow the plane mod 3, the V pair the plane mod 2
+#define WN_STEPP(STEP, P) STEP(P, ((P) + 1) % 3, (P) % 3, ((P) + 2) % 3, (P) & 1)
 
+// the finished accumulators of slot SF leave through A^T: over b inside the wave, over a across the waves (LDS exchange image ZIMG)
+#define WN_OUT_WRITE(SF, ZIMG)                                                                              \
+    _Pragma("unroll") for (int c_ = 0; c_ < 2; ++c_) {                                                      \
+        f32x4 y0_ = Y[SF][0][c_], y1_ = Y[SF][1][c_], y2_ = Y[SF][2][c_], y3_ = Y[SF][3][c_];               \
+        if constexpr ((SF) >= 1) {      /* out of the accumulator file WHOLE (element-wise reads of an asm "+a" vector gave stale values, hipcc 7.2) */ \
+            asm volatile("" : "+v"(y0_), "+v"(y1_), "+v"(y2_), "+v"(y3_));                                  \
+        }                                                                                                   \
+        const f32x4 z0_ = (y0_ + y1_) + y2_;                                                                \
+        const f32x4 z1_ = (y1_ - y2_) - y3_;                                                                \
+        *reinterpret_cast<f32x4*>(lds + ZB + (ZIMG) * 16384 + ((wv * 2 + 0) * 2 + c_) * 1024 + lane * 16) = z0_; \
+        *reinterpret_cast<f32x4*>(lds + ZB + (ZIMG) * 16384 + ((wv * 2 + 1) * 2 + c_) * 1024 + lane * 16) = z1_; \
+    }
+// ... after which wave (pa, q) reads what it needs for its output voxel of every tile: t = zz_[c][0] + osg * (zz_[c][1] + zz_[c][2])
+#define WN_EXCHANGE_READS(ZIMG)                                                                             \
+    f32x4 zz_[2][3];                                                                                        \
+    _Pragma("unroll") for (int c_ = 0; c_ < 2; ++c_)                                                        \
+        _Pragma("unroll") for (int k_ = 0; k_ < 3; ++k_)                                                    \
+            zz_[c_][k_] = *reinterpret_cast<const f32x4*>(lds + ZB + (ZIMG) * 16384 + (((pa + k_) * 2 + q) * 2 + c_) * 1024 + lane * 16);
+
+// ---- weight packing: U = G g G^T per (cout, cin, kd), pre-scaled per cout by a power of two so that max |U| lies in (512, 1024],
+// split, in the MFMA's A-operand order [a][b][kd][cout tile][hi | lo][lane = (cin group) * 16 + cout][8 cins] ----
+#define WINO_G {{1., 0., 0.}, {0.5, 0.5, 0.5}, {0.5, -0.5, 0.5}, {0., 0., 1.}}
+// k such that amax * 2^k lies in (512, 1024], from frexp's amax = m * 2^e, m in [0.5, 1); clamped to +-100
+template <typename F>
+__host__ __device__ __forceinline__ int wino_prescale_exp(F m, int e) {
+    const int k = m == (F)0.5 ? 11 - e : 10 - e;
+    return k < -100 ? -100 : (k > 100 ? 100 : k);
+}
+// U[ab = a * 4 + b][kd][co][ci]'s hi and lo parts to their half-words of the packed weights wp
+__host__ __device__ __forceinline__ void wino_weight_store(unsigned short* wp, int ab, int kd, int co, int ci, unsigned short hi, unsigned short lo) {
+    const long long frag = (((long long)ab * 3 + kd) * 2 + (co >> 4)) * 2;
+    const int lane = (ci >> 3) * 16 + (co & 15);
+    wp[((frag + 0) * 64 + lane) * 8 + (ci & 7)] = hi;
+    wp[((frag + 1) * 64 + lane) * 8 + (ci & 7)] = lo;
+}

@@ -86,6 +86,23 @@ inline int persistent_geometry(K kern, int threads, size_t lds_bytes, int max_wg
     out = g;
     return 0;
 }
+// The persistent grid for nb units: what is resident on the device, rounded down to a multiple of 8 (at least 8) -- each workgroup
+// walks the units blockIdx.x + k * gridDim.x, which stay on its XCD's contiguous run of the index space (xcd_remap); the unit walk
+// needs gridDim.x % 8 == 0 or gridDim.x == nb (CU counts of whole-XCD devices are multiples of 8).
+inline unsigned persistent_grid(const PersistentGeom& geo, long long nb) {
+    long long resident = ((long long)geo.cus * geo.wgs_per_cu) / 8 * 8;
+    if (resident < 8) resident = 8;
+    return (unsigned)(nb <= resident ? nb : resident);
+}
+// The launch tail of a persistent kernel that takes its arguments as one struct: geometry, grid, launch, check.
+template <class K, class A>
+inline int launch_persistent(K kern, int threads, size_t lds_bytes, int max_wgs_per_cu, PersistentGeom (&cache)[kMaxDevices],
+                             const char* what, long long nb, hipStream_t st, const A& args) {
+    PersistentGeom geo;
+    if (persistent_geometry(kern, threads, lds_bytes, max_wgs_per_cu, cache, what, geo)) return 1;
+    hipLaunchKernelGGL(kern, dim3(persistent_grid(geo, nb)), dim3((unsigned)threads), lds_bytes, st, args);
+    return check_launch(what);
+}
 
 // CU count of the current device (cached per device ordinal; 256 when it cannot be read: MI355X)
 inline int device_cus() {

@@ -1441,11 +1441,8 @@ int launch_bf16x3(ConvArgs a, hipStream_t st) {
         }
     }
 #endif
-    // persistent grid (a multiple of 8 unless it covers every unit once): each workgroup walks the
-    // units blockIdx.x + k*gridDim.x, which stay on its XCD's contiguous run of the index space
-    // (the unit walk needs gridDim.x % 8 == 0 or gridDim.x == total: CU counts of whole-XCD devices are multiples of 8)
-    const long long resident = ((long long)geo.cus * geo.wgs_per_cu) / 8 * 8 > 0 ? ((long long)geo.cus * geo.wgs_per_cu) / 8 * 8 : 8;
-    const unsigned grid = (unsigned)(nb <= resident ? nb : resident);
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(512), lds_bytes, st, a);
+    // (the geometry was needed above, for the border split, and this launcher's two messages differ: the tail's parts, not
+    // mvsgi::launch_persistent)
+    hipLaunchKernelGGL(kern, dim3(mvsgi::persistent_grid(geo, nb)), dim3(512), lds_bytes, st, a);
     return mvsgi::check_launch("mvsgi_conv3d_f32(bf16x3)");
 }

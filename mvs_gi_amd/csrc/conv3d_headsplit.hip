@@ -54,15 +54,7 @@ __global__ void head_split_pack_kernel(const float* __restrict__ w, bf16x8* __re
     for (int j = 0; j < 8; ++j) {
         const float v = tap < 27 ? w[(cs * 16 + 8 * (kg & 1) + j) * 27 + tap] : 0.f;
         unsigned short h, l;
-        if (f16) {
-            const _Float16 hh = (_Float16)v;
-            h = __builtin_bit_cast(unsigned short, hh);
-            l = __builtin_bit_cast(unsigned short, (_Float16)(v - (float)hh));
-        } else {
-            const __bf16 hh = (__bf16)v;
-            h = __builtin_bit_cast(unsigned short, hh);
-            l = __builtin_bit_cast(unsigned short, (__bf16)(v - (float)hh));
-        }
+        sf_split_weight(v, f16, h, l);
         a1[j] = h;
         a2[j] = kg < 2 ? l : (unsigned short)0;
     }

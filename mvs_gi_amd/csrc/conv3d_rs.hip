@@ -890,14 +890,10 @@ extern "C" int mvsgi_conv3d_rs_split_fmt(const void* x, const void* w_packed_rs,
     }
 #endif
     static mvsgi::PersistentGeom geo_cache[4][mvsgi::kMaxDevices] = {};
-    mvsgi::PersistentGeom geo;
     void (*kern)(RsArgs) = fmt ? (y_is_f32 ? conv3d_rs32_kernel<1, true> : conv3d_rs32_kernel<0, true>)
                                : (y_is_f32 ? conv3d_rs32_kernel<1, false> : conv3d_rs32_kernel<0, false>);
-    if (mvsgi::persistent_geometry(kern, 256, rs::LDS_BYTES, 1, geo_cache[(y_is_f32 ? 1 : 0) + (fmt ? 2 : 0)], "mvsgi_conv3d_rs_split", geo)) return 1;
-    const long long resident = (long long)geo.cus / 8 * 8 > 0 ? (long long)geo.cus / 8 * 8 : 8;
-    hipLaunchKernelGGL(kern, dim3((unsigned)(nb <= resident ? nb : resident)), dim3(256), rs::LDS_BYTES,
-                       mvsgi::as_stream(stream), a);
-    return mvsgi::check_launch("mvsgi_conv3d_rs_split");
+    return mvsgi::launch_persistent(kern, 256, rs::LDS_BYTES, 1, geo_cache[(y_is_f32 ? 1 : 0) + (fmt ? 2 : 0)], "mvsgi_conv3d_rs_split", nb,
+                                    mvsgi::as_stream(stream), a);
 }
 extern "C" int mvsgi_conv3d_rs_split(const void* x, const void* w_packed_rs, const float* scale, const float* shift,
                                      const void* res, void* y, int y_is_f32, int B, int Cin, int D, int H, int W, int Cout,
@@ -997,14 +993,10 @@ int rs16_run(const void* x, const void* w_packed_rs, const float* scale, const f
     MVSGI_SAT_WORDS(sat_words_);
     a.sat = sat_words_;
     static mvsgi::PersistentGeom geo_cache[4][mvsgi::kMaxDevices] = {};
-    mvsgi::PersistentGeom geo;
     void (*kern)(Rs16Args) = fmt ? (y_is_split ? conv3d_rs16_kernel<true, true> : conv3d_rs16_kernel<false, true>)
                                  : (y_is_split ? conv3d_rs16_kernel<true, false> : conv3d_rs16_kernel<false, false>);
-    if (mvsgi::persistent_geometry(kern, 256, rs16::LDS_BYTES, 1, geo_cache[(y_is_split ? 1 : 0) + (fmt ? 2 : 0)], "mvsgi_conv3d_rs16_split", geo))
-        return 1;
-    const long long resident = (long long)geo.cus / 8 * 8 > 0 ? (long long)geo.cus / 8 * 8 : 8;
-    hipLaunchKernelGGL(kern, dim3((unsigned)(nb <= resident ? nb : resident)), dim3(256), rs16::LDS_BYTES, mvsgi::as_stream(stream), a);
-    return mvsgi::check_launch("mvsgi_conv3d_rs16_split");
+    return mvsgi::launch_persistent(kern, 256, rs16::LDS_BYTES, 1, geo_cache[(y_is_split ? 1 : 0) + (fmt ? 2 : 0)], "mvsgi_conv3d_rs16_split", nb,
+                                    mvsgi::as_stream(stream), a);
 }
 }  // namespace
 

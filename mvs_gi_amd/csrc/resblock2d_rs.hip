@@ -31,35 +31,7 @@
 
 namespace {
 
-#include "device_prims.hpp"
-
-__device__ __forceinline__ void split4(const f32x4 x, u32x2& hi, u32x2& lo) {
-#pragma unroll
-    for (int p = 0; p < 2; ++p) {
-        const f32x2 v = {x[2 * p], x[2 * p + 1]};
-        const unsigned hb = __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2));
-        const f32x2 hf = {__builtin_bit_cast(float, hb << 16), __builtin_bit_cast(float, hb & 0xffff0000u)};
-        hi[p] = hb;
-        lo[p] = __builtin_bit_cast(unsigned, __builtin_convertvector(v - hf, bf16x2));
-    }
-}
-__device__ __forceinline__ f32x4 join4(const u32x2 hi, const u32x2 lo) {
-    f32x4 r;
-#pragma unroll
-    for (int p = 0; p < 2; ++p) {
-        r[2 * p] = __builtin_bit_cast(float, hi[p] << 16) + __builtin_bit_cast(float, lo[p] << 16);
-        r[2 * p + 1] = __builtin_bit_cast(float, hi[p] & 0xffff0000u) + __builtin_bit_cast(float, lo[p] & 0xffff0000u);
-    }
-    return r;
-}
-
-// LeakyReLU for slopes in [0, 1] as mul + max (plain asm max: __builtin_fmaxf first canonicalises an MFMA result with a third op)
-__device__ __forceinline__ float lrelu(const float v, const float slope) {
-    const float m = v * slope;
-    float r;
-    asm("v_max_f32 %0, %1, %2" : "=v"(r) : "v"(v), "v"(m));
-    return r;
-}
+#include "presplit_common.hpp"     // this file is the bf16 split throughout: sf_split4<false> / sf_join4<false>, ps_pack_split<false>
 
 constexpr int kRbStAux = 2;     // cache policy bits of the output stores: nt (never re-read by this launch; 9.37 -> 9.22 ms per 32 frames)
 constexpr int kRbLdAux = 0;     // cache policy bits of the window DMA (nt measured slower: the halos are re-read from L2)
@@ -69,13 +41,12 @@ constexpr int PAD = 2;                        // border of the 2-D split-padded 
 constexpr int TOH = 14, TOW = 30;             // output brick
 constexpr int RH = TOH + 2, RW = TOW + 2;     // conv1 region 16 x 32 = 32 MFMA tiles of 16 pixels
 constexpr int IH = TOH + 4, IW = TOW + 4;     // input window 18 x 34
-constexpr int NPX = IH * IW;                  // 612 pixels
-constexpr int PIECES = (NPX + 31) / 32;       // 20 DMA pieces of 32 pixels x 32 B per region
-constexpr int REGION = PIECES * 1024;         // 20,480: HI region, then the LO region
-constexpr int IMGA = 2 * REGION;              // 40,960: the window
+using Win = PsPieces<IH * IW>;                // 612 pixels: 20 DMA pieces per region, 10 per wave
+constexpr int NPX = Win::NPX, DPW = Win::DPW;
+constexpr int REGION = Win::REGION;           // 20,480: HI region, then the LO region
+constexpr int IMGA = Win::IMG;                // 40,960: the window
 constexpr int IMGB = REGION + NPX * 32;       // 40,064: the conv1 result (LO region at the same distance)
 constexpr int LDS_BYTES = IMGA + IMGB;        // 81,024: two workgroups per CU
-constexpr int DPW = 2 * PIECES / 4;           // 10 pieces per wave
 static_assert(2 * LDS_BYTES <= 160 * 1024, "two workgroups per CU");
 static_assert(REGION + 7 * 2 * IW * 32 < 65536, "a wave's tiles are 16-bit immediates from its base addresses");
 }  // namespace rb
@@ -96,8 +67,8 @@ __global__ void f32_to_split2d_kernel(const float* __restrict__ x, unsigned char
     const float* src = x + (((long long)b * H + h) * W + w) * 16 + g * 8;
     const f32x4 a0 = *reinterpret_cast<const f32x4*>(src), a1 = *reinterpret_cast<const f32x4*>(src + 4);
     u32x2 h0, l0, h1, l1;
-    split4(a0, h0, l0);
-    split4(a1, h1, l1);
+    sf_split4<false>(a0, h0, l0);
+    sf_split4<false>(a1, h1, l1);
     unsigned char* dst = y + (((long long)b * (H + 2 * rb::PAD) + h + rb::PAD) * (W + 2 * rb::PAD) + w + rb::PAD) * 64 + g * 16;
     *reinterpret_cast<u32x4*>(dst) = u32x4{h0[0], h0[1], h1[0], h1[1]};
     *reinterpret_cast<u32x4*>(dst + 32) = u32x4{l0[0], l0[1], l1[0], l1[1]};
@@ -116,34 +87,18 @@ __global__ void split2d_to_f32_kernel(const unsigned char* __restrict__ x, float
     const unsigned char* src = x + (((long long)b * (H + 2 * rb::PAD) + h + rb::PAD) * (W + 2 * rb::PAD) + w + rb::PAD) * 64 + g * 16;
     const u32x4 hi = *reinterpret_cast<const u32x4*>(src), lo = *reinterpret_cast<const u32x4*>(src + 32);
     float* dst = y + (((long long)b * H + h) * W + w) * 16 + g * 8;
-    *reinterpret_cast<f32x4*>(dst) = join4(u32x2{hi[0], hi[1]}, u32x2{lo[0], lo[1]});
-    *reinterpret_cast<f32x4*>(dst + 4) = join4(u32x2{hi[2], hi[3]}, u32x2{lo[2], lo[3]});
+    *reinterpret_cast<f32x4*>(dst) = sf_join4<false>(u32x2{hi[0], hi[1]}, u32x2{lo[0], lo[1]});
+    *reinterpret_cast<f32x4*>(dst + 4) = sf_join4<false>(u32x2{hi[2], hi[3]}, u32x2{lo[2], lo[3]});
 }
 
-// [Cout 16][Cin 16][3][3] x scale[Cout] -> [5 pairs][hi | lo][64 lanes][8 bf16]
-//   lane = (kg << 4) | i holds scale[i] * W[cout = i][cin = (kg & 1) * 8 + j][tap = 2 p + (kg >> 1)]  (tap 9 of pair 4: zeros)
-// The BatchNorm scale is folded into the weights here (fp32 product, then hi | lo) and the shift is the accumulators' initial
-// value: the epilogues have no scale / shift arithmetic left.
-__global__ void rb_pack_weights_kernel(const float* __restrict__ w, const float* __restrict__ scale, bf16x8* __restrict__ wp) {
-    const int idx = blockIdx.x * 64 + threadIdx.x;
-    if (idx >= 5 * 64) return;
-    const int lane = idx & 63, p = idx >> 6;
-    const int kg = lane >> 4, co = lane & 15, ci = (kg & 1) * 8, tap = 2 * p + (kg >> 1);
-    bf16x8 hi, lo;
-    for (int j = 0; j < 8; ++j) {
-        const float v = tap < 9 ? w[(co * 16 + ci + j) * 9 + tap] * scale[co] : 0.f;
-        const __bf16 h = (__bf16)v;
-        hi[j] = h;
-        lo[j] = (__bf16)(v - (float)h);
-    }
-    wp[(p * 2) * 64 + lane] = hi;
-    wp[(p * 2 + 1) * 64 + lane] = lo;
-}
+// [Cout 16][Cin 16][3][3] x scale[Cout] -> [5 pairs][hi | lo][64 lanes][8 bf16]: the shared packer, one cout tile (instantiated
+// here, not at its first use: the kernels below keep their place in the code object)
+template __global__ void ps_pack_weights_kernel<9>(const float* __restrict__, const float* __restrict__, bf16x8* __restrict__, int, bool);
 
 struct RbArgs {
     const unsigned char* x;    // 2-D split-padded [N][H+4][W+4][64]
     unsigned char* y;          // the same geometry, or (OUTF32) plain fp32 [N][H][W][16]
-    const bf16x8* wp1;         // rb_pack_weights_kernel (scale folded in)
+    const bf16x8* wp1;         // ps_pack_weights_kernel<9>: [5 pairs][hi | lo][64 lanes][8 bf16], scale folded in
     const bf16x8* wp2;
     const float* shift1;
     const float* shift2;
@@ -169,11 +124,7 @@ __global__ __launch_bounds__(256, 2) void resblock2d_rs_kernel(RbArgs a) {
     const long long total_bytes = (long long)a.N * Hp * Wp * 64;
     const long long out_bytes = OUTF32 ? (long long)a.N * a.H * a.W * 64 : total_bytes;
     const int orow = (OUTF32 ? a.W : Wp) * 64;                       // bytes per output row
-    const int total = a.total_units, G = gridDim.x;
-    // bricks of this workgroup: logical ids remap(blockIdx) + k * (G / 8) -- XCD x walks a contiguous eighth of the bricks
-    const int nmine = (total - (int)blockIdx.x + G - 1) / G;
-    const int id0 = G == total ? (int)blockIdx.x : xcd_remap((int)blockIdx.x, total);
-    const int idstep = G == total ? 0 : G >> 3;
+    PS_WALK(a.total_units, nmine, id0, idstep)
 
     // ---- both weight sets, resident ----
     bf16x8 w1h[5], w1l[5], w2h[5], w2l[5];
@@ -201,8 +152,7 @@ __global__ __launch_bounds__(256, 2) void resblock2d_rs_kernel(RbArgs a) {
     int rbp[5], rbq[5], rbqo[5];  // window / conv1-result image (even, odd tiles; its base does not fit the 16-bit immediates)
 #pragma unroll
     for (int p = 0; p < 5; ++p) {
-        const int tA = 2 * p, tB = 2 * p + 1 < 9 ? 2 * p + 1 : 2 * p;
-        const int t = (kg >> 1) ? tB : tA;
+        PS_PAIR_TAP(t, p, kg, 9)
         const int v = (r0 + t / 3) * IW + 16 * hf + col + t % 3;
         rbp[p] = v * 32 + (kg & 1) * 16;
         rbq[p] = IMGA + v * 32 + (((kg & 1) ^ ((v >> 2) & 1)) << 4);
@@ -215,18 +165,12 @@ __global__ __launch_bounds__(256, 2) void resblock2d_rs_kernel(RbArgs a) {
     const int wrb = IMGA + wv0 * 32 + ((((kg >> 1) ^ ((wv0 >> 2) & 1)) << 4) | ((kg & 1) << 3));
     const int wrbo = wrb ^ 16;
     constexpr int TSTEP = 2 * IW * 32;          // bytes between a wave's consecutive tiles (two rows)
-    // ---- DMA plan: piece q = wave + 4 m fills LDS bytes [q * 1024, +1024) of the window: 32 pixels x 2 chunks of one region ----
+    // ---- DMA plan: piece q = wave + 4 m fills LDS bytes [q * 1024, +1024) of the window ----
     unsigned voff[DPW];
 #pragma unroll
-    for (int m = 0; m < DPW; ++m) {
-        const int q = wave + 4 * m;
-        const int region = q >= PIECES ? 1 : 0, j = q - region * PIECES;
-        const int v = 32 * j + (lane >> 1), chunk = lane & 1;
-        const int wy = v / IW, wx = v - wy * IW;
-        voff[m] = v < NPX ? (unsigned)((wy * Wp + wx) * 64 + region * 32 + chunk * 16) : 0xffffff00u;   // beyond num_records: zeros
-    }
+    for (int m = 0; m < DPW; ++m) voff[m] = ps_window_voff<IH, IW>(wave + 4 * m, lane, Wp);
     // ---- output: lane offset from the brick's first output pixel, tile k = + 2 k * orow (scalar) ----
-    //      split: lanes kg and kg ^ 1 trade halves, kg even stores hi / lo of channels 8 (kg >> 1) .. + 7 (16 bytes)
+    //      split: the 16-byte chunk ps_pack_split leaves in this lane
     const unsigned vst = (unsigned)(r0 * orow + (16 * hf + col) * 64 + (OUTF32 ? kg * 16 : (kg & 1) * 32 + (kg >> 1) * 16));
 
     // brick order: an image is cut into PATCHES of patch x patch bricks, ids run patch by patch (ragged patches at the right /
@@ -325,7 +269,7 @@ __global__ __launch_bounds__(256, 2) void resblock2d_rs_kernel(RbArgs a) {
             f32x4 v = acc[K];                                                                                    \
             _Pragma("unroll") for (int e = 0; e < 4; ++e) v[e] = lrelu(v[e], a.neg_slope);                       \
             u32x2 hi, lo;                                                                                        \
-            split4(v, hi, lo);                                                                                   \
+            sf_split4<false>(v, hi, lo);                                                                         \
             if (edge) {                                                                                          \
                 const int gh = oh0 - 1 + r0 + 2 * (K), gw = ow0 - 1 + 16 * hf + col;                             \
                 if (!(gh >= 0 && gh < a.H && gw >= 0 && gw < a.W)) hi = lo = u32x2{0u, 0u};                      \
@@ -363,15 +307,8 @@ __global__ __launch_bounds__(256, 2) void resblock2d_rs_kernel(RbArgs a) {
             f32x4 v = acc[K];                                                                                    \
             _Pragma("unroll") for (int e = 0; e < 4; ++e) v[e] = lrelu(v[e], a.neg_slope);                       \
             u32x4 o;                                                                                             \
-            if constexpr (OUTF32) {                                                                              \
-                o = __builtin_bit_cast(u32x4, v);                                                                \
-            } else {                                                                                             \
-                u32x2 hi, lo;                                                                                    \
-                split4(v, hi, lo);                                                                               \
-                const u32x2 sa = __builtin_amdgcn_permlane16_swap(hi[0], lo[0], false, false);                   \
-                const u32x2 sb = __builtin_amdgcn_permlane16_swap(hi[1], lo[1], false, false);                   \
-                o = u32x4{sa[0], sb[0], sa[1], sb[1]};                                                           \
-            }                                                                                                    \
+            if constexpr (OUTF32) o = __builtin_bit_cast(u32x4, v);                                              \
+            else o = ps_pack_split<false>(v);                                                                    \
             /* masked lanes / rows get an offset beyond num_records (no scalar offset here: it would be added before the   */ \
             /* range check and wrap): no exec-mask region, so the store can sit between the MFMAs                          */ \
             const unsigned so_ = (okc && oh0 + r0 + 2 * (K) < a.H) ? vst + (unsigned)(2 * (K) * orow) : 0xffffff00u;      \
@@ -407,20 +344,14 @@ __global__ __launch_bounds__(256, 2) void resblock2d_rs_kernel(RbArgs a) {
 }
 
 template <bool OUTF32>
-int rb_launch(const RbArgs& a, hipStream_t st, const char* what) {
+int rb_launch(RbArgs a, hipStream_t st, const char* what) {
     static mvsgi::PersistentGeom geo_cache[mvsgi::kMaxDevices] = {};
-    mvsgi::PersistentGeom geo;
-    if (mvsgi::persistent_geometry(resblock2d_rs_kernel<OUTF32>, 256, rb::LDS_BYTES, 2, geo_cache, what, geo)) return 1;
-    long long resident = ((long long)geo.cus * geo.wgs_per_cu) / 8 * 8;
-    if (resident < 8) resident = 8;
-    const long long nb = a.total_units;
 #ifdef MVSGI_RS_STAMPS
-    RbArgs a2 = a;
     {   // MVSGI_STAMP=1: record; =2: print the stamps of the previous launch
         static unsigned long long* dbgbuf = nullptr;
         const char* e_ = getenv("MVSGI_STAMP");
         if (e_ && !dbgbuf) { (void)hipMalloc(&dbgbuf, 4 * 256 * 8); (void)hipMemset(dbgbuf, 0, 4 * 256 * 8); }
-        a2.dbg = e_ ? dbgbuf : nullptr;
+        a.dbg = e_ ? dbgbuf : nullptr;
         if (e_ && atoi(e_) == 2 && dbgbuf) {
             static unsigned long long h[4 * 256];
             (void)hipDeviceSynchronize();
@@ -432,32 +363,26 @@ int rb_launch(const RbArgs& a, hipStream_t st, const char* what) {
             }
         }
     }
-    hipLaunchKernelGGL(resblock2d_rs_kernel<OUTF32>, dim3((unsigned)(nb <= resident ? nb : resident)), dim3(256), rb::LDS_BYTES, st, a2);
-#else
-    hipLaunchKernelGGL(resblock2d_rs_kernel<OUTF32>, dim3((unsigned)(nb <= resident ? nb : resident)), dim3(256), rb::LDS_BYTES, st, a);
 #endif
-    return mvsgi::check_launch(what);
+    return mvsgi::launch_persistent(resblock2d_rs_kernel<OUTF32>, 256, rb::LDS_BYTES, 2, geo_cache, what, a.total_units, st, a);
 }
 
 // ---------------------------------------------------------------------------------------------
 // The extractor's stride-2 layer between its two runs of residual blocks (BaseConvBlk2d 16 -> 16, 3x3, stride 2, padding 1 +
-// BatchNorm + LeakyReLU; simple_feature_extractor.py:60-66) on the same format: the 3-D kernel of csrc/conv3d_s2rs.hip in two
-// dimensions.  A brick = 8 output rows x 16 columns, its window 17 x 33 input pixels, de-interleaved into even and odd columns by
-// the DMA's per-lane source addresses (a tile's 16 outputs then read unit-stride pixels for every tap); double-buffered windows
-// (72 KB: two workgroups per CU), one DMA piece in front of each MFMA group; wave w owns output rows 2 w, 2 w + 1; weights in
-// rb_pack_weights_kernel's order (scale folded in), shift = the accumulators' start value.  The layer is HBM-bound (reads the
-// full-resolution tensor once): with it the last block of the first run hands on split activations instead of fp32.
+// BatchNorm + LeakyReLU; simple_feature_extractor.py:60-66) on the same format: K2g's scheme (csrc/conv3d_s2rs.hip) on one plane,
+// with the stride-2 window, the walk and the split epilogue of presplit_common.hpp.  A brick = 8 output rows x 16 columns, its
+// window 17 x 33 input pixels (PsS2Window<1, 17>: de-interleaved into even and odd columns); double-buffered windows (72 KB: two
+// workgroups per CU), one DMA piece in front of each MFMA group; wave w owns output rows 2 w, 2 w + 1; the block's weight order
+// (scale folded in), shift = the accumulators' start value.  The layer is HBM-bound (reads the full-resolution tensor once): with
+// it the last block of the first run hands on split activations instead of fp32.
 // ---------------------------------------------------------------------------------------------
 namespace c2s {
-constexpr int TH = 8, TW = 16;                 // output brick
-constexpr int IHt = 2 * TH + 1, IW = 2 * TW + 1;   // window 17 x 33
-constexpr int NPX = IHt * IW;                  // 561
-constexpr int PIECES = (NPX + 31) / 32;        // 18 per region
-constexpr int REGION = PIECES * 1024;
-constexpr int IMG = 2 * REGION;                // 36,864
+constexpr int TH = 8;                          // output rows of a brick
+using Win = PsS2Window<1, 2 * TH + 1>;         // 17 x 33 = 561 pixels: 18 pieces per region, 9 per wave
+constexpr int TW = Win::TW, IW = Win::IW, IHt = Win::IHt, DPW = Win::DPW, REGION = Win::REGION;
+constexpr int IMG = Win::IMG;                  // 36,864
 constexpr int LDS_BYTES = 2 * IMG;
-constexpr int DPW = 2 * PIECES / 4;            // 9 pieces per wave
-static_assert(2 * PIECES % 4 == 0 && 2 * LDS_BYTES <= 160 * 1024, "geometry");
+static_assert(2 * LDS_BYTES <= 160 * 1024, "two workgroups per CU");
 }  // namespace c2s
 
 struct C2sArgs {
@@ -478,10 +403,7 @@ __global__ __launch_bounds__(256, 2) void conv2d_s2rs_kernel(C2sArgs a) {
     const int col = lane & 15, kg = lane >> 4;
     const int Hp = a.H + 2 * rb::PAD, Wp = a.W + 2 * rb::PAD, Hop = a.Ho + 2 * rb::PAD, Wop = a.Wo + 2 * rb::PAD;
     const long long total_bytes = (long long)a.N * Hp * Wp * 64, ototal_bytes = (long long)a.N * Hop * Wop * 64;
-    const int total = a.total_units, G = gridDim.x;
-    const int nmine = (total - (int)blockIdx.x + G - 1) / G;
-    const int id0 = G == total ? (int)blockIdx.x : xcd_remap((int)blockIdx.x, total);
-    const int idstep = G == total ? 0 : G >> 3;
+    PS_WALK(a.total_units, nmine, id0, idstep)
 
     bf16x8 wh[5], wl[5];
 #pragma unroll
@@ -495,21 +417,13 @@ __global__ __launch_bounds__(256, 2) void conv2d_s2rs_kernel(C2sArgs a) {
     int rbp[5];
 #pragma unroll
     for (int p = 0; p < 5; ++p) {
-        const int tA = 2 * p, tB = 2 * p + 1 < 9 ? 2 * p + 1 : 2 * p;
-        const int t = (kg >> 1) ? tB : tA;
+        PS_PAIR_TAP(t, p, kg, 9)
         const int kh = t / 3, kw = t % 3;
-        rbp[p] = ((4 * wave + kh) * IW + (kw & 1) * (TW + 1) + col + (kw >> 1)) * 32 + (kg & 1) * 16;
+        rbp[p] = ((4 * wave + kh) * IW + PS_S2_SLOT(Win, kw, col)) * 32 + (kg & 1) * 16;
     }
     unsigned voff[DPW];
 #pragma unroll
-    for (int m = 0; m < DPW; ++m) {
-        const int q = wave + 4 * m;
-        const int region = q >= PIECES ? 1 : 0, j = q - region * PIECES;
-        const int v = 32 * j + (lane >> 1), chunk = lane & 1;
-        const int row = v / IW, e = v - row * IW;
-        const int c = e <= TW ? 2 * e : 2 * (e - TW - 1) + 1;
-        voff[m] = v < NPX ? (unsigned)((row * Wp + c) * 64 + region * 32 + chunk * 16) : 0xffffff00u;
-    }
+    for (int m = 0; m < DPW; ++m) voff[m] = Win::voff(wave + 4 * m, lane, Hp, Wp);
     const unsigned vst = (unsigned)((2 * wave * Wop + col) * 64 + (kg & 1) * 32 + (kg >> 1) * 16);
 
 #define C2S_DECODE(ID, N_, OH, OW)                               \
@@ -527,7 +441,7 @@ __global__ __launch_bounds__(256, 2) void conv2d_s2rs_kernel(C2sArgs a) {
     {
         const auto d0_ = C2S_DESC(n_, oh0, ow0);
 #pragma unroll
-        for (int m = 0; m < DPW; ++m) lds_dma16(d0_, lds + (wave + 4 * m) * 1024, voff[m]);
+        for (int m = 0; m < DPW; ++m) ps_dma_piece(d0_, lds, wave, m, voff[m]);
     }
     for (int u = 0; u < nmine; ++u) {
         int nn, noh, now;
@@ -554,7 +468,7 @@ __global__ __launch_bounds__(256, 2) void conv2d_s2rs_kernel(C2sArgs a) {
 #define C2S_DMA(K)                                                                                               \
     if ((K) < DPW) {                                                                                             \
         __builtin_amdgcn_sched_barrier(0);                                                                       \
-        if (more) lds_dma16(dsc_n, lds + (IMG - img) + (wave + 4 * (K)) * 1024, voff[K]);                        \
+        if (more) ps_dma_piece(dsc_n, lds + (IMG - img), wave, (K), voff[K]);                                    \
         __builtin_amdgcn_sched_barrier(0);                                                                       \
     }
         C2S_READ(0, 0)
@@ -580,12 +494,8 @@ __global__ __launch_bounds__(256, 2) void conv2d_s2rs_kernel(C2sArgs a) {
                 f32x4 v = acc[i] + (acc1[i] + acc2[i]);
 #pragma unroll
                 for (int e = 0; e < 4; ++e) v[e] = lrelu(v[e], a.neg_slope);
-                u32x2 hi, lo;
-                split4(v, hi, lo);
-                const u32x2 sa = __builtin_amdgcn_permlane16_swap(hi[0], lo[0], false, false);
-                const u32x2 sb = __builtin_amdgcn_permlane16_swap(hi[1], lo[1], false, false);
-                if (okc && oh0 + 2 * wave + i < a.Ho)
-                    __builtin_amdgcn_raw_buffer_store_b128(u32x4{sa[0], sb[0], sa[1], sb[1]}, dsc_, vst, i * Wop * 64, kRbStAux);
+                const u32x4 o = ps_pack_split<false>(v);
+                if (okc && oh0 + 2 * wave + i < a.Ho) __builtin_amdgcn_raw_buffer_store_b128(o, dsc_, vst, i * Wop * 64, kRbStAux);
             }
         }
         n_ = nn; oh0 = noh; ow0 = now;
@@ -618,13 +528,8 @@ extern "C" int mvsgi_conv2d_s2_split(const void* x_split, const void* w_packed, 
     MVSGI_REQUIRE(nb < (1ll << 31), "mvsgi_conv2d_s2_split: too many bricks");
     a.total_units = (int)nb;
     static mvsgi::PersistentGeom geo_cache[mvsgi::kMaxDevices] = {};
-    mvsgi::PersistentGeom geo;
-    if (mvsgi::persistent_geometry(conv2d_s2rs_kernel, 256, c2s::LDS_BYTES, 2, geo_cache, "mvsgi_conv2d_s2_split", geo)) return 1;
-    long long resident = ((long long)geo.cus * geo.wgs_per_cu) / 8 * 8;
-    if (resident < 8) resident = 8;
-    hipLaunchKernelGGL(conv2d_s2rs_kernel, dim3((unsigned)(nb <= resident ? nb : resident)), dim3(256), c2s::LDS_BYTES,
-                       mvsgi::as_stream(stream), a);
-    return mvsgi::check_launch("mvsgi_conv2d_s2_split");
+    return mvsgi::launch_persistent(conv2d_s2rs_kernel, 256, c2s::LDS_BYTES, 2, geo_cache, "mvsgi_conv2d_s2_split", nb,
+                                    mvsgi::as_stream(stream), a);
 }
 
 extern "C" size_t mvsgi_split2d_bytes(int N, int H, int W) {
@@ -656,7 +561,8 @@ extern "C" size_t mvsgi_resblock2d_split_packed_weight_bytes(void) { return (siz
 
 extern "C" int mvsgi_resblock2d_split_pack_weights(const float* w_oihw, const float* scale, void* w_packed, mvsgi_stream_t stream) {
     MVSGI_REQUIRE(w_oihw && scale && w_packed, "mvsgi_resblock2d_split_pack_weights: null pointer");
-    hipLaunchKernelGGL(rb_pack_weights_kernel, dim3(5), dim3(64), 0, mvsgi::as_stream(stream), w_oihw, scale, static_cast<bf16x8*>(w_packed));
+    hipLaunchKernelGGL(ps_pack_weights_kernel<9>, dim3(5), dim3(64), 0, mvsgi::as_stream(stream), w_oihw, scale, static_cast<bf16x8*>(w_packed),
+                       1, false);
     return mvsgi::check_launch("mvsgi_resblock2d_split_pack_weights");
 }
 

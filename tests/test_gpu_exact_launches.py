@@ -9,6 +9,9 @@ float64 reference, the same comparison (exact_cases.assert_exact: np.array_equal
     E.WALK_VARIANT_IDS): units >= 2 R + r;
   - the split cost head marches the whole depth in one block (E.HEAD_MARCH_SHAPES: nd = 1).
 
+The weight packers these launches depend on (csrc/presplit_common.hpp, csrc/conv3d_headsplit.hip) are compared byte for byte with
+their lane rules, written once here.
+
 A float64 reference of such batches is affordable because frames of a batch are independent: every case is built, and its
 conditions (a)-(c) asserted, on E.FRAMES distinct frames which the kernel sees B times in an irregular order (E.frame_index:
 neighbouring frames always differ, no period), and the reference is expanded by the same index; the residual is drawn for all B
@@ -312,6 +315,67 @@ def test_head_split_whole_depth_march(shape, regime, kind):
             xs.fmt, xs.rec = "f16", "f32"
         y = H.conv3d_head_split(xs, wp, scale * un, shift, neg_slope=c.slope, f16=True)
     E.assert_exact(_np(y), _want(c), _lsb(c), f"cost head, {kind}")
+
+
+# ------------------------------------------------------------------------------------------------ weight packers, byte for byte
+def _split_bits(v, fmt):
+    """(hi, lo) bit patterns of csrc/split_fmt.hpp:sf_split_weight with torch's round-to-nearest casts on the CPU: hi = cast(v),
+    lo = cast(v - hi)."""
+    dt = E.SPLIT_DT[fmt]
+    hi = v.to(dt)
+    return hi.view(torch.int16), (v - hi.float()).to(dt).view(torch.int16)
+
+
+def _pair_lane_rule(w, scale, fmt):
+    """The lane rule of csrc/presplit_common.hpp:ps_pack_weights_kernel, written once: [cout tile][pair p][hi | lo][64 lanes][8], lane =
+    (kg << 4) | i holds scale[co] * W[co = 16 ct + i][cin = 8 (kg & 1) + j][tap = 2 p + (kg >> 1)], zeros past the last tap."""
+    co, taps = w.shape[0], w[0, 0].numel()
+    pairs = (taps + 1) // 2
+    v = w.float().reshape(co, 16, taps) * scale.float().reshape(co, 1, 1)                 # the fp32 product
+    v = torch.nn.functional.pad(v, (0, 2 * pairs - taps))
+    x = torch.stack(_split_bits(v, fmt)).reshape(2, co // 16, 16, 2, 8, pairs, 2)         # [hi | lo][ct][i][kg & 1][j][p][kg >> 1]
+    return x.permute(1, 5, 0, 6, 3, 2, 4).contiguous().view(torch.uint8).flatten()        # [ct][p][hi | lo][kg >> 1][kg & 1][i][j]
+
+
+def _head_lane_rule(w, fmt):
+    """csrc/conv3d_headsplit.hip:head_split_pack_kernel: [Cin / 16][tap tile tt][A1 | A2][64 lanes][8], lane = (kg << 4) | i, tap =
+    16 tt + i (zeros from tap 27); A1 = hi(W[16 cs + 8 (kg & 1) + j][tap]) for every kg, A2 = lo of the same for kg < 2, else zeros."""
+    cin = w.shape[1]
+    v = torch.nn.functional.pad(w.float().reshape(cin, 27), (0, 5))
+    h, l = (t.reshape(cin // 16, 2, 8, 2, 16).permute(0, 3, 1, 4, 2) for t in _split_bits(v, fmt))   # [cs][tt][kg & 1][i][j]
+    a1, a2 = torch.cat((h, h), dim=2), torch.cat((l, torch.zeros_like(l)), dim=2)                    # [cs][tt][kg][i][j]
+    return torch.stack((a1, a2), dim=2).contiguous().view(torch.uint8).flatten()
+
+
+def _same_bytes(got, want, what):
+    got = got.cpu()
+    assert got.shape == want.shape, (what, got.shape, want.shape)
+    bad = (got != want).nonzero().flatten()
+    assert bad.numel() == 0, f"{what}: {bad.numel()} of {want.numel()} bytes differ, first at {int(bad[0])}"
+
+
+def test_weight_packers_byte_for_byte():
+    """pack_resblock2d_split_weights (9 taps, one cout tile, bf16), pack_conv_weights_s2rs (27 taps, two cout tiles, both splits, with
+    the prescale it returns) and pack_head_split_weights[_f16] (its own A1 | A2 rule) against the lane rules above: every byte, no
+    tolerance.  Wide integers (lo != 0) times a per-channel scale that is an odd multiple of 1/8: the products are exact in fp32 and
+    need both roundings of the split."""
+    rng = np.random.default_rng(2207)
+    w2, s2 = E.wide(rng, (16, 16, 3, 3), "bf16", 1.0), (E.narrow(rng, (16,), 7) + 0.5) / 4
+    _same_bytes(H.pack_resblock2d_split_weights(_g(w2), _g(s2)), _pair_lane_rule(w2, s2, "bf16"), "resblock2d split packer")
+    for fmt in FMTS:
+        w3, s3 = E.wide(rng, (32, 16, 3, 3, 3), fmt, 1.0), (E.narrow(rng, (32,), 7) + 0.5) / 4
+        if fmt == "bf16":
+            wp, up = H.pack_conv_weights_s2rs(_g(w3), _g(s3)), 1.0
+        else:
+            wp, up, un = H.pack_conv_weights_s2rs(_g(w3), _g(s3), "f16")
+            assert up * un == 1.0
+        _same_bytes(wp, _pair_lane_rule(w3, s3.float() * up, fmt), f"s2rs packer, {fmt}")
+        wh = E.wide(rng, (1, 32, 3, 3, 3), fmt, 1.0)
+        if fmt == "bf16":
+            hp, un = H.pack_head_split_weights(_g(wh)), 1.0
+        else:
+            hp, un = H.pack_head_split_weights_f16(_g(wh))
+        _same_bytes(hp, _head_lane_rule(wh.float() * (1.0 / un), fmt), f"head packer, {fmt}")
 
 
 # ------------------------------------------------------------------------------------------------ coverage of conv3d_variants.inc

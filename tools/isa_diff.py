@@ -2,7 +2,8 @@
 """isa_diff.py [-v] [--rename OLD=NEW ...] <tree A> <tree B> [name.hip ...] -- are the gfx950 kernels of two trees the same code?
 
 Compiles every mvs_gi_amd/csrc/*.hip of both trees (or only the named ones) to device assembly with the flags of
-__graft_entry__, drops what differs between any two compiles (the __hip_cuid_<hash> symbol, .ident, .file) and compares
+__graft_entry__, drops what differs between any two compiles (the __hip_cuid_<hash> symbol, .ident, .file) and the
+function ordinal in local labels (a kernel's position in its unit, which changes when a neighbour is added or removed), and compares
 the text kernel by kernel: instructions, labels and the .amdhsa_* resource block.  --rename substitutes OLD by NEW in tree
 A's assembly first (a kernel whose mangled name changed, e.g. a template list that got shorter, then compares as the same
 kernel).  Needs no GPU.  Exit status 0 only when every kernel is identical and none was added or removed."""
@@ -30,21 +31,28 @@ def assemble(job):
     if r.returncode:
         sys.exit(f"{src}:\n{r.stderr}")
     text = re.sub(r"__hip_cuid_[0-9a-f]+", "__hip_cuid_", open(out).read())
+    # local labels carry the function's ordinal within the unit (.LBB<n>_<block>, .Lfunc_end<n>): a kernel added, removed or moved in
+    # front of another renumbers it without changing its code
+    text = re.sub(r"(\.LBB|\bBB)\d+_(\d+)", r"\1_\2", re.sub(r"\bLfunc_(begin|end)\d+", r"Lfunc_\1", text))
     for old, new in renames:
         text = text.replace(old, new)
     return [ln for ln in text.splitlines() if not ln.lstrip().startswith((".ident", ".file"))]
 
 
 def kernels(lines):
-    """{kernel symbol: its lines, from its .type line to the next kernel's}; what precedes the first kernel and the
-    metadata note behind the last one go under OTHER."""
+    """{kernel symbol: its lines, from the directives in front of its .type line (.section, .globl, .p2align: they name this
+    kernel, not the one before it) to the next kernel's}; what precedes the first kernel and the metadata note behind the last
+    one go under OTHER."""
     names = {ln.split()[1] for ln in lines if ln.lstrip().startswith(".amdhsa_kernel ")}
     out, cur = {OTHER: []}, OTHER
     for ln in lines:
         m = re.match(r"\s*\.type\s+(\S+),@function", ln)
         if m and m.group(1) in names:
+            head = []
+            while out[cur] and out[cur][-1].lstrip().startswith((".section", ".globl", ".weak", ".protected", ".hidden", ".p2align")):
+                head.insert(0, out[cur].pop())
             cur = m.group(1)
-            out[cur] = []
+            out[cur] = head
         elif ln.lstrip().startswith(".amdgpu_metadata") or re.match(r"\s*\.type\s+\S+,@object", ln):
             cur = OTHER
         out[cur].append(ln)

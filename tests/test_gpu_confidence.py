@@ -204,9 +204,10 @@ def test_regressor_confidence_dropin(arena):
     assert tuple(inv.shape) == tuple(dr.confidence(costs)["argmax"].shape)
 
 
-def test_regressor_confidence_on_an_unpickled_reference_regressor(arena, golden_dir):
+def test_regressor_confidence_on_an_unpickled_reference_regressor(arena, golden_dir, request):
     import mvs_gi_amd
     assert mvs_gi_amd.install() in ("alias", "patch")
+    request.addfinalizer(mvs_gi_amd.dropin.uninstall)       # the host tests of install() start from a process without the aliases
     hp = torch.load(os.path.join(golden_dir, "pickled_modules_tiny.pt"), weights_only=False)["hyper_parameters"]
     z = np.load(os.path.join(golden_dir, "pickled_modules_tiny_io.npz"))
     dr = hp["dist_regressor"].eval().to(DEV)

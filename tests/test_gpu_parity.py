@@ -858,9 +858,10 @@ def test_precision_check_prefers_the_bf16_split_outside_fp16_range():
         H.set_conv_mode(old)
 
 
-def test_unpickled_reference_modules_run_on_hip(golden_dir):
+def test_unpickled_reference_modules_run_on_hip(golden_dir, request):
     import mvs_gi_amd
     assert mvs_gi_amd.install() in ("alias", "patch")
+    request.addfinalizer(mvs_gi_amd.dropin.uninstall)       # the host tests of install() start from a process without the aliases
     hp = torch.load(os.path.join(golden_dir, "pickled_modules_tiny.pt"), weights_only=False)["hyper_parameters"]
     z = _load(golden_dir, "pickled_modules_tiny_io")
     cvb, reg, dr = (hp[k].eval().to(DEV) for k in ("cv_builder", "cv_regulator", "dist_regressor"))
@@ -1615,7 +1616,8 @@ def test_split_padded_format_round_trip_and_border():
 
 
 @pytest.mark.parametrize("shape", [(1, 2, 4, 16), (1, 4, 8, 32), (2, 5, 7, 37), (3, 3, 9, 16), (1, 8, 12, 48),
-                                   (4, 9, 30, 70)])      # 800 ragged bricks on <= 256 workgroups: the steady-state walk (n > 1 per workgroup)
+                                   (4, 9, 30, 70),       # 800 ragged bricks on <= 256 workgroups: the steady-state walk (n > 1 per workgroup)
+                                   (2, 1, 1, 4), (2, 2, 1, 8)])      # the deepest levels of a stage_factor=1 / keep_last_chs regulator: axes of length 1
 @pytest.mark.parametrize("res,slope,out_f32", [(True, 0.01, False), (False, 0.01, True), (True, 0.0, True), (False, 1.0, False)])
 def test_conv3d_rs_vs_oracle(shape, res, slope, out_f32):
     """Register-stationary 32 -> 32 conv on split-padded activations against the CPU oracle's conv block on the SAME
@@ -1642,7 +1644,9 @@ def test_conv3d_rs_vs_oracle(shape, res, slope, out_f32):
             assert int(sl.abs().max()) == 0
 
 
-@pytest.mark.parametrize("shape", [(1, 16, 32, 8, 16, 16, 2), (2, 16, 32, 7, 9, 13, 2), (1, 32, 32, 4, 6, 10, 1), (1, 16, 16, 5, 9, 11, 1)])
+@pytest.mark.parametrize("shape", [(1, 16, 32, 8, 16, 16, 2), (2, 16, 32, 7, 9, 13, 2), (1, 32, 32, 4, 6, 10, 1), (1, 16, 16, 5, 9, 11, 1),
+                                   # stride 2 at Cin 32 / 48: the first conv of a deeper 32 -> 32 level, of a (48, 32) regulator
+                                   (2, 32, 32, 7, 9, 13, 2), (2, 32, 32, 2, 2, 8, 2), (2, 48, 32, 5, 7, 19, 2)])
 def test_streaming_conv_split_padded_output_is_the_split_of_its_fp32_output(shape):
     B, cin, cout, d, h, w, s = shape
     rng = np.random.default_rng(11)

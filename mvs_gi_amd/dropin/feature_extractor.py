@@ -256,10 +256,26 @@ def _split_chain_forward(self, xin: Tensor, with_final: bool = True) -> Optional
     return y                                         # channels-last fp32
 
 
+def _images_in(self, x: Tensor) -> Tensor:
+    """The stem's input: NCHW fp32 images as they are, or uint8 [M, H, W, in_chs] camera images.  The 5x5 stride-2 3 -> 16 stem
+    has kernels that read the bytes and convert on the way in; in front of any other stem (another chs or in_chs) the images are
+    converted as the reference does (api/inference_class.py:104-107), with torch ops a hipGraph capture records, and the stem
+    reads fp32 NCHW."""
+    if x.dtype != torch.uint8:
+        return H._dev(x, "imgs")
+    L = lower_conv2d_block(self.first)
+    if x.dim() != 4 or x.shape[-1] != L.cin:
+        raise TypeError(f"imgs: expected uint8 [M, H, W, {L.cin}], got {tuple(x.shape)}")
+    if (L.k, L.stride, L.cin, L.cout) == (5, 2, 3, 16):
+        return x
+    return H._dev(x.permute(0, 3, 1, 2).float() / 255.0, "imgs")
+
+
 def extractor_forward(self, x: Tensor) -> Tensor:
     """simple_feature_extractor.py:81-84.  The RGB stem reads the caller's NCHW fp32 images directly, or
-    uint8 [M, H, W, 3] camera images (converted /255 in the kernel, api/inference_class.py:104-107)."""
-    xin = x if x.dtype == torch.uint8 else H._dev(x, "imgs")
+    uint8 [M, H, W, in_chs] camera images (converted /255 in the 3 -> 16 stem's kernel, in front of any other stem:
+    api/inference_class.py:104-107)."""
+    xin = _images_in(self, x)
     out = _split_chain_forward(self, xin)
     if out is not None:
         return _nchw_view(out)
@@ -448,7 +464,7 @@ class SphereConvBlk(nn.Module):
 
 def sphere_extractor_forward(self, x: Tensor) -> Tensor:
     """SphereEquirectFeatExtraction.forward (feature_extractor/sphere_feature_extractor.py:80-83)."""
-    xin = x if x.dtype == torch.uint8 else H._dev(x, "imgs")
+    xin = _images_in(self, x)
     y = _split_chain_forward(self, xin, with_final=False)
     if y is None:
         y = lower_conv2d_block(self.first).run(xin, in_nchw=True)

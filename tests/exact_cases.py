@@ -464,6 +464,15 @@ POLY_WINO_SHAPES = [(1, 8, 2, 32), (3, 8, 6, 32)]
 HEAD_F32_SHAPES = [(2, 16, 5, 7, 9, False), (2, 64, 5, 7, 9, True)]          # the fp32 LDS-tiled cost head behind H.conv3d at Cout = 1
 HEAD_SHAPES = [(1, 16, 1, 1, 1), (1, 16, 3, 5, 7), (1, 32, 4, 9, 33)]
 CONV2D_SHAPES = [(2, 16, 16, 20, 36, 1, True), (1, 16, 16, 33, 47, 1, False), (2, 16, 16, 24, 40, 2, False)]
+# channel counts whose Cout / 16 leaves a remainder against the two-tile templates of the split kernel (3 under D2_N32 and its
+# stride-2 form, 5 under D2_N64), and 16 -> 32; the fp32 MFMA kernel takes the rows with Cout in (16, 32), out_split those with 16
+CONV2D_WIDE_SHAPES = [(1, 32, 32, 9, 21, 2, False), (1, 48, 48, 9, 21, 1, True), (1, 48, 48, 10, 22, 2, False), (1, 80, 80, 5, 19, 1, False),
+                      (1, 16, 32, 9, 21, 1, False)]
+# (B, Cin, Cout, H, W, stride, res, k, NCHW input): the direct kernel alone -- a Cout % 4 != 0 tail group, k of 1, 5 and 7, and the
+# generic NCHW stem (in_chs of 1 and 4)
+CONV2D_DIRECT_ROWS = [(2, 6, 6, 9, 13, 1, True, 3, False), (1, 8, 8, 9, 13, 2, False, 3, False), (1, 16, 16, 9, 13, 1, True, 1, False),
+                      (1, 16, 16, 9, 13, 1, True, 5, False), (1, 16, 16, 9, 13, 1, True, 7, False), (2, 1, 16, 11, 14, 2, False, 5, True),
+                      (2, 4, 16, 11, 14, 2, False, 5, True)]
 RESBLOCK2D_SHAPES = [(1, 1, 1), (2, 15, 31), (1, 9, 100)]
 S2_2D_SHAPES = [(1, 2, 2), (3, 17, 33)]
 
@@ -524,12 +533,16 @@ def _table():
         for rg in REGIMES:
             add("conv3d_up2_poly_wino", f"{(B, d, h, w)}-{rg}", fmt="f16", regime=rg, slope=_slope(i), seed=1100 + i, up2=True, poly=True, polywino=True,
                 bound=F16_MAX, **_c3(B, 32, 16, d, h, w))
-    for i, (B, ci, co, h, w, s, res) in enumerate(CONV2D_SHAPES):
+    for i, (B, ci, co, h, w, s, res) in enumerate(CONV2D_SHAPES + CONV2D_WIDE_SHAPES):
         for rg in REGIMES:
             add("conv2d_f32", f"{(B, ci, co, h, w, s)}-{rg}", fmt="f32", regime=rg, slope=_slope(i), seed=1200 + i, **_c2(B, ci, co, h, w, s, res))
             add("conv2d_bf16", f"{(B, ci, co, h, w, s)}-{rg}", fmt="bf16", regime=rg, slope=_slope(i + 1), seed=1300 + i, **_c2(B, ci, co, h, w, s, res))
     for rg in REGIMES:
         add("conv2d_stem_f32", f"(2, 3, 16, 30, 52, 2)-{rg}", fmt="f32", regime=rg, slope=0.25, seed=1400, k=5, **_c2(2, 3, 16, 30, 52, 2))
+    for i, (B, ci, co, h, w, s, res, k, nchw) in enumerate(CONV2D_DIRECT_ROWS):
+        for rg in REGIMES:
+            add("conv2d_direct", f"{(B, ci, co, h, w, s)}-k{k}-{'nchw' if nchw else 'nhwc'}-{rg}", fmt="f32", regime=rg, slope=_slope(i), seed=1600 + i,
+                k=k, **_c2(B, ci, co, h, w, s, res))
     for i, (B, h, w) in enumerate(S2_2D_SHAPES):
         for rg in REGIMES:
             add("conv2d_s2_split", f"{(B, h, w)}-{rg}", fmt="bf16", regime=rg, slope=_slope(i), seed=1500 + i, fold_scale=True, **_c2(B, 16, 16, h, w, 2))

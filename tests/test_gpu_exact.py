@@ -20,8 +20,11 @@ Winograd 32->32              H.conv3d_wino, act32 on/off, out_f32 on/off, res   
 polyphase ResizeConv3d       H.conv3d_up2_poly, H.conv3d_up2_poly_split direct       POLY_SHAPES, both splits
                              on/off; Winograd form (wino=True)                       POLY_WINO_SHAPES (fp16 split)
 cost head                    H.conv3d_head_split, bf16 and f16=True                  HEAD_SHAPES
-2-D conv                     H.conv2d direct, fp32 MFMA, bf16x3, out_split,          CONV2D_SHAPES (stride 1 and 2); 5x5 stem on float NCHW
-                             5x5 stem (in_nchw)
+2-D conv                     H.conv2d direct, fp32 MFMA, bf16x3, out_split,          CONV2D_SHAPES (stride 1 and 2); 5x5 stem on float NCHW;
+                             5x5 stem (in_nchw)                                      CONV2D_WIDE_SHAPES (32, 48, 80 channels, 16 -> 32: fp32 MFMA
+                                                                                     at Cout 16 | 32, out_split at Cout 16)
+2-D conv, direct kernel      H.conv2d impl CONV_AUTO where only the direct kernel    CONV2D_DIRECT_ROWS (Cout 6 and 8, k of 1 | 5 | 7, NCHW input
+                             serves                                                  of 1 and 4 channels)
 2-D residual block           H.resblock2d, H.resblock2d_split (both outputs)         RESBLOCK2D_SHAPES x three regimes (w2_wide: conv2's lo weights)
 2-D stride-2 on split input  H.conv2d_s2_split                                       S2_2D_SHAPES
 deformable conv              H.deform_conv2d, quad-lane and generic kernel           DEFORM_ROWS, shared and per-image offset field
@@ -406,7 +409,10 @@ def test_conv2d_fp32_direct_and_mfma(name):
     y = H.conv2d(xg, wg, None, sc, sh, res=rg, stride=c.stride, neg_slope=c.slope, impl=H.CONV_DIRECT)
     E.assert_exact(_np(y), _want(c), _lsb(c), "direct")
     wpf = H.pack_conv2d_weights_f32(wg)
-    assert wpf is not None and H.conv2d_variant(Cin, Cout, 3, c.stride, H.CONV_MFMA).startswith("conv3d_mfma_kernel<")
+    assert (wpf is not None) == (Cout in (16, 32))       # the fp32 MFMA kernel's channel counts (every 16 -> 16 row runs it)
+    if wpf is None:
+        return
+    assert H.conv2d_variant(Cin, Cout, 3, c.stride, H.CONV_MFMA).startswith("conv3d_mfma_kernel<")
     y = H.conv2d(xg, wg, wpf, sc, sh, res=rg, stride=c.stride, neg_slope=c.slope, impl=H.CONV_MFMA)
     E.assert_exact(_np(y), _want(c), _lsb(c), "fp32 MFMA")
 
@@ -420,6 +426,8 @@ def test_conv2d_bf16x3_and_split_output(name):
     wp = H.pack_conv2d_weights_bf16x3(wg)
     y = H.conv2d(xg, wg, wp, sc, sh, res=rg, stride=c.stride, neg_slope=c.slope, impl=H.CONV_BF16X3)
     E.assert_exact(_np(y), _want(c), _lsb(c), "bf16x3")
+    if Cout != 16:                                       # the 2-D split-padded format holds 16 channels
+        return
     ys = H.conv2d(xg, wg, wp, sc, sh, res=rg, stride=c.stride, neg_slope=c.slope, impl=H.CONV_BF16X3,
                   out_split=H.split2d_buffer(B, *c.ref.shape[2:], xg.device))
     E.assert_exact(_np(H.split2d_to_f32(ys)), _want(c, "bf16"), _lsb(c), "split output")
@@ -432,6 +440,19 @@ def test_conv2d_stem_5x5_float_nchw(name):
     assert H.conv2d_variant(3, 16, 5, 2, H.CONV_AUTO, True).startswith("conv2d_direct_kernel<")
     y = H.conv2d(_g(c.x), _g(c.w), None, _g(c.scale), _g(c.shift), stride=2, neg_slope=c.slope, in_nchw=True)
     E.assert_exact(_np(y), _want(c), _lsb(c), "5x5 stem")
+
+
+@pytest.mark.parametrize("name", E.ids("conv2d_direct"))
+def test_conv2d_direct_odd_channels_kernel_sizes_and_nchw(name):
+    """conv2d_direct_kernel<4> where nothing else serves: Cout of 6 (a tail group of two channels) and 8, k of 1, 5 and 7 on 16
+    channels, and the generic NCHW stem on 1 and 4 input channels."""
+    c = E.case("conv2d_direct", name)
+    B, Cin, Cout, Hh, W = _dims(c)
+    k, nchw = int(c.w.shape[-1]), "-nchw-" in name
+    assert H.conv2d_variant(Cin, Cout, k, c.stride, H.CONV_AUTO, nchw).startswith("conv2d_direct_kernel<")
+    xg = _g(c.x) if nchw else _cl(c.x)
+    y = H.conv2d(xg, _g(c.w), None, _g(c.scale), _g(c.shift), res=_cl(c.r), stride=c.stride, neg_slope=c.slope, in_nchw=nchw)
+    E.assert_exact(_np(y), _want(c), _lsb(c), f"direct k = {k}")
 
 
 @pytest.mark.parametrize("name", E.ids("conv2d_s2_split"))

@@ -1096,7 +1096,10 @@ def test_bench_self_launches_its_ranks():
 
 # ------------------------------------------------------------------------------ feature extractor (§8(f) rank 1)
 @pytest.mark.parametrize("shape", [(2, 16, 16, 20, 36, 1, True), (1, 16, 16, 33, 47, 1, False), (2, 16, 16, 24, 40, 2, False),
-                                   (1, 32, 32, 17, 30, 1, True), (1, 16, 64, 16, 32, 2, False), (1, 64, 64, 12, 20, 1, True)])
+                                   (1, 32, 32, 17, 30, 1, True), (1, 16, 64, 16, 32, 2, False), (1, 64, 64, 12, 20, 1, True),
+                                   # the channel / stride rows of exact_cases.CONV2D_WIDE_SHAPES: Cout / 16 of 3 and 5 against the two-tile templates
+                                   (1, 32, 32, 9, 21, 2, False), (1, 48, 48, 9, 21, 1, True), (1, 48, 48, 10, 22, 2, False),
+                                   (1, 80, 80, 5, 19, 1, False), (1, 16, 32, 9, 21, 1, False)])
 def test_conv2d_bf16x3_and_direct_vs_aten(shape):
     B, Cin, Cout, Hh, W, stride, res = shape
     rng = np.random.default_rng(sum(shape))

@@ -780,6 +780,57 @@ int mvsgi_visibility_f32(const float* inv, const float* rays, const float* T_hos
                          unsigned char* visible, unsigned char* n_visible, float* range, long long B, int N, int H, int W, int Hz,
                          int Wz, float bf, mvsgi_stream_t stream);
 
+/* ---- temporal fusion (csrc/temporal.hip) ------------------------------------------------------------------------------------------
+ * The previous fused prediction of a sequence, warped to the rig's new pose and fused with the new measurement: a z-buffer that carries
+ * its source pixel, then a per-pixel gated Kalman update.  Not part of the reference's interface; defined as a composition of
+ * operations this library already has.  All arithmetic is fp32, no contraction, one IEEE operation per written operation; the steps
+ * shared with mvsgi_reproject_f32 and mvsgi_camera_range_f32 are the same functions, so the same bits.  B independent sequences, one
+ * step per call; frame b, H x W maps of the rig camera (an equirectangular panorama, rays as mvsgi_rays_panorama_f32 makes them).
+ * Stage A, splat (mvsgi_temporal_splat_f32), source pixel (i, j), s = i * W + j:
+ *     1. v = prev_inv[b][i][j], d = bf / v, p = rays[:, i, j] * d                      (steps 1, 2 of mvsgi_reproject_f32)
+ *     2. live = prev_age[b][i][j] != 0 && 0 < v <= FLT_MAX && d <= FLT_MAX             (mvsgi_camera_range_f32's rule and the age)
+ *     3. q = T_b p (rows 0..2 of T[b], the row rule of mvsgi_transform_points_f32); r2 = (qx * qx + qy * qy) + qz * qz; the point is
+ *        rejected unless 0 < r2 <= FLT_MAX (a NaN compares false)
+ *     4. (gx, gy) = the equirectangular projection of q (mvsgi_grid_equirect_f32); u = gx * au + bu, w = gy * av + bv, each a multiply
+ *        then an add; cx = int(floorf(u)), cy = int(floorf(w)); with wrap != 0: cx += W when cx < 0, cx -= W when cx >= W, once each;
+ *        rejected unless 0 <= cx < W && 0 <= cy < H (decided on the floats, so a NaN or a value no int holds is rejected too).
+ *        au = pi * W / (long1 - long0), bu = -long0 * W / (long1 - long0), av = (pi / 2) * H / (lat1 - lat0),
+ *        bv = (pi / 2 - lat0) * H / (lat1 - lat0) of the rig camera's ranges, float64 on the host, rounded once: the inverse of the
+ *        panorama's ray table (lon = theta, lat = phi - pi / 2), so at T = identity a live pixel lands in its own cell.
+ *     5. key = (uint64(bits(r2)) << 32) | uint32(s);  zkey[b][cy][cx] = min(zkey[b][cy][cx], key), the buffer starting at
+ *        EMPTY = 0x7F800000FFFFFFFF (+inf over the largest index).  The nearest source wins a cell, on equal r2 the lower index.  r2 is
+ *        positive and finite, so its pattern orders like an unsigned integer, and an integer minimum does not depend on the order of
+ *        arrival: every run and every captured replay give the same bits.
+ * Stage B, resolve and fuse (mvsgi_temporal_fuse_f32), target pixel t:
+ *     1. key = zkey[b][t]; r2 = float(bits(key >> 32)); s = min(key & 0xffffffff, H * W - 1) (< H * W by construction, clamped all the same)
+ *     2. warped_inv = bf / sqrtf(r2); ratio = warped_inv / prev_inv[b][s]; g = ratio * ratio; var_w = prev_var[b][s] * (g * g) + q_var
+ *        (along the ray d inv' / d inv = (inv' / inv)^2; the cosine between the old and the new ray is dropped: an approximation)
+ *     3. prior = key != EMPTY && 0 <= var_w <= FLT_MAX
+ *     4. m = cur_inv[b][t]; sd = cur_std ? cur_std[b][t] : meas_std; var_m = sd * sd
+ *     5. meas = 0 < m <= FLT_MAX && 0 < var_m <= FLT_MAX
+ *     6. neither:            fused = m (as it is), var = +inf, age = 0
+ *        prior only:         fused = warped_inv, var = var_w, age = prev_age[b][s]           (not confirmed: not incremented)
+ *        meas only:          fused = m, var = var_m, age = 1
+ *        both: e = m - warped_inv, S = var_w + var_m; they agree iff e * e <= gate2 * S, then K = var_w / S,
+ *                            fused = warped_inv + K * e, var = var_w - K * var_w, age = min(prev_age[b][s] + 1, 255)
+ *        both, disagreeing:  fused = m, var = var_m, age = 1                                 (the measurement restarts the pixel)
+ *     7. optional: warped_inv (0 in an empty cell), warped_var = var_w (+inf in an empty cell), src = s as int32 (-1 in an empty cell;
+ *        a source index above 2^31 - 1 reads negative)
+ *   device:  prev_inv, prev_var, cur_inv, cur_std [B][H][W] fp32; prev_age, age [B][H][W] uint8; rays [3][H][W]; T [B][16] fp32 row-major
+ *            4 x 4, READ FROM DEVICE MEMORY by the splat (it changes every step; a captured launch sees the value of the replay);
+ *            zkey [B][H][W] uint64; fused, var, warped_inv, warped_var fp32, src int32 [B][H][W].  Everything 16-byte aligned.  The
+ *            outputs of the fuse may each be NULL (not all); none may alias prev_* (stage B gathers the state at s).
+ *   host:    bf; au, bu, av, bv, wrap as above; gate2 = fp32(gate^2) > 0, q_var >= 0, meas_std > 0 (read when cur_std is NULL).
+ * mvsgi_temporal_splat_f32: two launches (fill, splat); mvsgi_temporal_fuse_f32: one.  No host synchronisation, no allocation:
+ * capturable.  H * W < 2^32 and B * ceil(H * ceil(W / 4) / 256) < 2^31. */
+int mvsgi_temporal_splat_f32(const float* prev_inv, const unsigned char* prev_age, const float* rays, const float* T,
+                             unsigned long long* zkey, long long B, int H, int W, float bf, float au, float bu, float av, float bv,
+                             int wrap, mvsgi_stream_t stream);
+int mvsgi_temporal_fuse_f32(const unsigned long long* zkey, const float* prev_inv, const float* prev_var,
+                            const unsigned char* prev_age, const float* cur_inv, const float* cur_std, float meas_std, float* fused,
+                            float* var, unsigned char* age, float* warped_inv, float* warped_var, int* src, long long B, int H, int W,
+                            float bf, float gate2, float q_var, mvsgi_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

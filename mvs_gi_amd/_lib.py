@@ -146,6 +146,8 @@ SIGNATURES = {
                                                  c_longlong] + [c_int] * 6 + [c_float, _P, _P]),
     "mvsgi_camera_range_f32": (c_int, [_P] * 5 + [c_int, c_int, _P, c_longlong] + [c_int] * 5 + [c_float, _P]),
     "mvsgi_visibility_f32": (c_int, [_P] * 5 + [c_float, _P, _P, _P, c_longlong] + [c_int] * 5 + [c_float, _P]),
+    "mvsgi_temporal_splat_f32": (c_int, [_P] * 5 + [c_longlong, c_int, c_int] + [c_float] * 5 + [c_int, _P]),
+    "mvsgi_temporal_fuse_f32": (c_int, [_P] * 6 + [c_float] + [_P] * 6 + [c_longlong, c_int, c_int] + [c_float] * 3 + [_P]),
 }
 
 _lib = None

@@ -95,10 +95,13 @@ class Reprojector:
         self.T = compose_transforms(poses, R_raw)
         self._T_dev = None               # reproject_chain's device copy, made at its first call
         Ho, Wo = self.out_shape
+        # the ranges the rays were made from (TemporalFusion inverts them in closed form); None with a caller's ray table
+        self.long_range = self.lat_range = None
         if rays is None:
             if long_range is None or lat_range is None:
                 raise ValueError("Reprojector: long_range and lat_range of the rig camera, or a ray table")
             rm = RayMaker_UEPanorama(np.ones(1, np.float32), long_range, lat_range, device=self.device)
+            self.long_range, self.lat_range = rm.long_range, rm.lat_range
             rays = rm.make_rays_for_candidates(self.out_shape).view(3, Ho, Wo)
         else:
             rays = torch.as_tensor(rays).to(device=self.device, dtype=torch.float32).contiguous()

@@ -1585,6 +1585,144 @@ def visibility(inv, rays, T, cams, bf: float, z2, tol: float = VISIBILITY_TOL, w
     return res
 
 
+# ---- temporal fusion (csrc/temporal.hip; include/mvsgi.h, "temporal fusion") ----
+TEMPORAL_OUTPUTS = ("fused", "var", "age", "warped_inv", "warped_var", "src")   # the order of mvsgi_temporal_fuse_f32's output pointers
+TEMPORAL_EMPTY = 0x7F800000FFFFFFFF                                             # an empty cell of zkey: +inf over the largest source index
+TEMPORAL_GATE = 3.0
+
+
+def temporal_affine(long_range, lat_range, shape) -> tuple:
+    """(au, bu, av, bv, wrap) of a rig panorama of `shape` = (H, W) with these ranges in radians, in float64 (the calls round each to
+    fp32 once): column = floor(gx * au + bu), row = floor(gy * av + bv) of an equirectangular grid coordinate, the inverse of
+    RayMaker_UEPanorama's ray table; wrap: the longitude closes (|long1 - long0 - 2 pi| < 1e-6)."""
+    try:
+        (lo0, lo1), (la0, la1), (Hh, W) = (float(v) for v in long_range), (float(v) for v in lat_range), (int(v) for v in shape)
+    except (TypeError, ValueError):
+        raise ValueError(f"temporal_affine: long_range and lat_range are pairs of radians and shape is (H, W), got {long_range!r}, "
+                         f"{lat_range!r}, {shape!r}") from None
+    if not (math.isfinite(lo0) and math.isfinite(lo1) and math.isfinite(la0) and math.isfinite(la1) and lo1 > lo0 and la1 > la0):
+        raise ValueError(f"temporal_affine: need finite long0 < long1 and lat0 < lat1, got {(lo0, lo1)}, {(la0, la1)}")
+    if Hh < 1 or W < 1:
+        raise ValueError(f"temporal_affine: shape (H, W) with H, W >= 1, got {(Hh, W)}")
+    # where the equirectangular model is the ray table's inverse: phi = lat + pi / 2 in [0, pi], and theta = lon in [-pi, pi] unless the
+    # longitude closes (then the wrap brings a column home)
+    eps = 1e-6
+    closes = abs(lo1 - lo0 - 2 * math.pi) < eps
+    if la0 < -eps or la1 > math.pi + eps or not (closes or (lo0 >= -math.pi - eps and lo1 <= math.pi + eps)):
+        raise ValueError(f"temporal_affine: the closed-form inverse needs lat_range inside [0, pi] and long_range inside [-pi, pi] or a "
+                         f"full turn, got {(lo0, lo1)}, {(la0, la1)}")
+    return (math.pi * W / (lo1 - lo0), -lo0 * W / (lo1 - lo0), (math.pi / 2) * Hh / (la1 - la0), (math.pi / 2 - la0) * Hh / (la1 - la0),
+            abs(lo1 - lo0 - 2 * math.pi) < 1e-6)
+
+
+def temporal_gate2(gate: float) -> float:
+    """gate^2 in double: the factor of the agreement test, which the call rounds to fp32 once."""
+    gate = float(gate)
+    if not 0.0 < gate < float("inf"):
+        raise ValueError(f"gate: 0 < gate < inf, got {gate}")
+    return gate * gate
+
+
+def _temporal_map(B: int, Hh: int, W: int) -> None:
+    if Hh > 1 << 24 or W > 1 << 24 or Hh * W >= 1 << 32:
+        raise ValueError(f"temporal fusion: map {Hh} x {W}: H, W <= 2^24 and H * W < 2^32 (a key holds the source index in 32 bits)")
+    if B * -(-(Hh * -(-W // 4)) // 256) >= 1 << 31:
+        raise ValueError(f"temporal fusion: B * H * W = {B} * {Hh} * {W} is too large for one launch")
+
+
+def _temporal_state(prev_inv, prev_age, prev_var=None):
+    """The state as the two calls take it: caller-owned [B, H, W] tensors read in place -> (B, H, W, device)"""
+    prev_inv = _arg(prev_inv, "prev_inv", None)
+    if prev_inv.dim() != 3 or not prev_inv.numel():
+        raise AssertionError(f"prev_inv must be a non-empty [B, H, W], got {list(prev_inv.shape)}")
+    shape, dev = tuple(int(v) for v in prev_inv.shape), prev_inv.device
+    _temporal_map(*shape)
+    _arg(prev_age, "prev_age", dev, torch.uint8, shape=shape)
+    if prev_var is not None:
+        _arg(prev_var, "prev_var", dev, shape=shape)
+    return shape + (dev,)
+
+
+def temporal_splat(prev_inv, prev_age, rays, T, bf: float, affine, out=None) -> torch.Tensor:
+    """Stage A of the temporal fusion (include/mvsgi.h, "temporal fusion"): the previous fused inverse distance
+    back-projected, moved by T and splatted into the rig panorama's own cells: zkey [B, H, W] int64, per cell the smallest
+    (bits(r2) << 32 | source index) of the live points that land in it, TEMPORAL_EMPTY in an empty cell.  prev_inv [B, H, W] fp32 and
+    prev_age [B, H, W] uint8 (0: the pixel holds nothing): the state, read in place; rays [3, H, W] fp32; T [B, 4, 4] fp32 ON THE
+    DEVICE (the pose of the previous rig frame in the current one; the launch reads it from memory, so a captured graph sees the value
+    of each replay); affine = temporal_affine(long_range, lat_range, (H, W)); out: the tensor to write.  Two launches on prev_inv's
+    stream (fill, splat); the minimum is an integer atomic, independent of the order of arrival: the same inputs give the same bits.
+    With `out` the call allocates nothing and can be captured.  There is no CPU fallback."""
+    B, Ho, Wo, dev = _temporal_state(prev_inv, prev_age)
+    rays = _dev(rays, "rays")
+    if tuple(rays.shape) != (3, Ho, Wo) or rays.device != dev:
+        raise AssertionError(f"rays must be [3, {Ho}, {Wo}] on {dev}, got {list(rays.shape)} on {rays.device}")
+    _arg(T, "T", dev, shape=(B, 4, 4))
+    try:
+        au, bu, av, bv, wrap = affine
+        au, bu, av, bv = (float(v) for v in (au, bu, av, bv))
+    except (TypeError, ValueError):
+        raise ValueError(f"affine: (au, bu, av, bv, wrap) of temporal_affine(), got {affine!r}") from None
+    if not all(math.isfinite(v) for v in (au, bu, av, bv)):
+        raise ValueError(f"affine: (au, bu, av, bv) must be finite, got {(au, bu, av, bv)}")
+    if out is None:
+        out = torch.empty((B, Ho, Wo), device=dev, dtype=torch.int64)
+    else:
+        _arg(out, "out", dev, torch.int64, shape=(B, Ho, Wo))
+    _call("mvsgi_temporal_splat_f32", prev_inv.data_ptr(), prev_age.data_ptr(), rays.data_ptr(), T.data_ptr(), out.data_ptr(), B, Ho, Wo,
+          float(bf), au, bu, av, bv, 1 if wrap else 0, _stream_ptr(prev_inv))
+    return out
+
+
+def temporal_fuse(zkey, prev_inv, prev_var, prev_age, cur_inv, bf: float, gate: float = TEMPORAL_GATE, q_var: float = 0.0, cur_std=None,
+                  meas_std=None, want=TEMPORAL_OUTPUTS, out=None) -> dict:
+    """Stage B of the temporal fusion: every target pixel resolves its cell of temporal_splat()'s zkey (warped_inv = bf / sqrt(r2), the
+    variance carried along the ray plus q_var), and fuses it with the measurement cur_inv [B, H, W] whose standard deviation is cur_std
+    [B, H, W] or the scalar meas_std > 0: a Kalman update where the two agree within gate standard deviations, the measurement alone
+    where they do not or where there is no prior, the prior alone where there is no measurement.  -> dict of the wanted
+    TEMPORAL_OUTPUTS: fused, var fp32, age uint8 (the new state), warped_inv, warped_var fp32 and src int32 (the prior and its source
+    pixel; 0, +inf and -1 in an empty cell), each [B, H, W].  prev_inv, prev_var, prev_age: the state the splat read, read in place and
+    gathered at the source index, so no output may be one of them; out: a dict with tensors to write in place.  One launch on
+    cur_inv's stream; with `out` the call allocates nothing and can be captured.  There is no CPU fallback."""
+    B, Ho, Wo, dev = _temporal_state(prev_inv, prev_age, prev_var)
+    shape = (B, Ho, Wo)
+    _arg(zkey, "zkey", dev, torch.int64, shape=shape)
+    cur_inv = _dev(cur_inv, "cur_inv")
+    if cur_inv.dim() == 4 and cur_inv.shape[1] == 1:
+        cur_inv = cur_inv.squeeze(1)
+    if tuple(cur_inv.shape) != shape or cur_inv.device != dev:
+        raise AssertionError(f"cur_inv must be {list(shape)} on {dev}, got {list(cur_inv.shape)} on {cur_inv.device}")
+    if cur_std is not None:
+        if meas_std is not None:
+            raise ValueError("temporal_fuse: cur_std or meas_std, not both")
+        cur_std = _dev(cur_std, "cur_std")
+        if cur_std.dim() == 4 and cur_std.shape[1] == 1:
+            cur_std = cur_std.squeeze(1)
+        if tuple(cur_std.shape) != shape or cur_std.device != dev:
+            raise AssertionError(f"cur_std must be {list(shape)} on {dev}, got {list(cur_std.shape)} on {cur_std.device}")
+        sd = 0.0
+    else:
+        if meas_std is None:
+            raise ValueError("temporal_fuse: the measurement's standard deviation, cur_std [B, H, W] or meas_std > 0")
+        sd = float(meas_std)
+        if not 0.0 < sd < float("inf"):
+            raise ValueError(f"meas_std: 0 < meas_std < inf, got {sd}")
+    g2 = temporal_gate2(gate)
+    q_var = float(q_var)
+    if not 0.0 <= q_var < float("inf"):
+        raise ValueError(f"q_var: 0 <= q_var < inf, got {q_var}")
+    want = _wanted(want, TEMPORAL_OUTPUTS)
+    kinds = {"fused": torch.float32, "var": torch.float32, "age": torch.uint8, "warped_inv": torch.float32, "warped_var": torch.float32,
+             "src": torch.int32}
+    res = _outputs(want, out, dev, {k: (shape, d) for k, d in kinds.items()})
+    state = {t.data_ptr() for t in (prev_inv, prev_var, prev_age)}
+    for k, t in res.items():
+        if t.data_ptr() in state:
+            raise AssertionError(f"out['{k}'] is a tensor of the state: the state is gathered at the source index and cannot be written in place")
+    _call("mvsgi_temporal_fuse_f32", zkey.data_ptr(), prev_inv.data_ptr(), prev_var.data_ptr(), prev_age.data_ptr(), cur_inv.data_ptr(),
+          _ptr(cur_std), sd, *(_ptr(res.get(k)) for k in TEMPORAL_OUTPUTS), B, Ho, Wo, float(bf), g2, q_var, _stream_ptr(cur_inv))
+    return res
+
+
 # the packed point cloud (csrc/cloud.hip), restated: tiles of 1024 consecutive pixels, 16 words of 64 bits each; at most 4 gates, 4 colour
 # channels and 16 floats per record
 CLOUD_TILE, CLOUD_WORDS_PER_TILE, CLOUD_MAX_GATES, CLOUD_MAX_CHANNELS, CLOUD_MAX_RECORD, CLOUD_MAX_BATCH = 1024, 16, 4, 4, 16, 65535

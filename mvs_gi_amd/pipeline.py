@@ -356,10 +356,19 @@ class InferencePipeline:
     (csrc/visibility.hip, four launches).  `pipe.visibility` is the dict of dropin.Visibility.OUTPUTS, static tensors made by the first
     call and valid until the next.  A `photo` stage built with this Visibility fuses the cameras that see the point only, and the
     `cloud` packer takes `visible` where it took the back-projection's `valid`: the colour of the lowest camera that sees the point.
-    Without it every launch and every result is what it was."""
+    Without it every launch and every result is what it was.
+
+    With `temporal` (a dropin.TemporalFusion built on this pipeline's `reprojector`) the last stage carries the prediction from frame
+    to frame (csrc/temporal.hip, three launches and three copies), in forward_device and inside the captured graph: the fused map of
+    the previous frame, warped by the pose `pipe.temporal_stage.set_pose(T)` staged (identity before any), is fused with this frame's
+    inv_dist, whose standard deviation is the confidence map "spread" where `confidence` selects it and the stage's meas_std
+    otherwise.  `pipe.temporal` is the dict of fused, var, age, warped_inv, warped_var and src, the stage's own static tensors, valid
+    until the next call.  Every other stage keeps consuming the raw inv_dist, and the returned map is the raw one.  capture() runs
+    the stage on its warm-up frames and then resets it: the first replay starts the sequence.  Without it every launch and every result
+    is what it was."""
 
     def __init__(self, cfg: PathConfig, weights, consts, device="cuda", extractor: str = "simple", samplers=None, raw_masks=None,
-                 reprojector=None, confidence=None, cloud=None, photo=None, visibility=None):
+                 reprojector=None, confidence=None, cloud=None, photo=None, visibility=None, temporal=None):
         """extractor: 'simple' = SimpleFeatExtraction (G16V, config29), 'sphere' = SphereEquirectFeatExtraction with the
         sphere-convolution final layer (G16VV, config103; configs/feature_extractor/sphereconv_featext.yaml).
         samplers / raw_masks: per-camera image samplers and raw-resolution masks; with both, consts["masks"] may be omitted
@@ -386,6 +395,14 @@ class InferencePipeline:
                 raise ValueError("visibility: the photo= stage was built with another Visibility")
         elif photo is not None and getattr(photo, "visibility", None) is not None:
             raise ValueError("photo: the stage was built with a Visibility; pass it as visibility= too")
+        if temporal is not None:
+            if reprojector is None or getattr(temporal, "reprojector", None) is not reprojector:
+                raise ValueError("temporal: the stage needs reprojector=, the Reprojector the TemporalFusion was built on")
+            if temporal.meas_std is None and "spread" not in (_confidence_selection(confidence) or ()):
+                raise ValueError('temporal: the stage has no meas_std and confidence= does not select "spread": the measurement\'s '
+                                 "standard deviation is needed")
+        self.temporal_stage = temporal
+        self.temporal = None
         self.visibility_stage = visibility
         self.visibility = None
         self._vis_out = None
@@ -443,6 +460,7 @@ class InferencePipeline:
             self.cloud = self._static_cloud
             self.photo = self._static_photo
             self.visibility = self._static_vis
+            self.temporal = self._static_temporal
             out = self._static_inv.squeeze(0).squeeze(0).cpu().numpy()
         else:
             out = self.forward_device(t.to(self.hot.device)).squeeze(0).squeeze(0).cpu().numpy()
@@ -481,6 +499,10 @@ class InferencePipeline:
             more = dict(photo=self.photo) if self.photo_stage is not None else {}
             self.cloud = self.cloud_packer.pack(inv, confidence=self.confidence, warped=r["warped"] if colour else None,
                                                 valid=(r["valid"] if seen is None else seen) if colour else None, **more)
+        if self.temporal_stage is not None:
+            # the state, the pose and the outputs are the stage's own, made by its first step at this shape
+            spread = self.confidence.get("spread") if self.confidence is not None else None
+            self.temporal = self.temporal_stage.step(inv, std=spread, want=H.TEMPORAL_OUTPUTS)
         return inv
 
     # ---- hipGraph replay of the whole chain for one frame (the robot's operating point: one frame at a time) ----
@@ -509,6 +531,9 @@ class InferencePipeline:
         self._static_cloud = self.cloud
         self._static_photo = self.photo
         self._static_vis = self.visibility
+        self._static_temporal = self.temporal
+        if self.temporal_stage is not None:
+            self.temporal_stage.reset()                 # the warm-up frames are not part of any sequence
 
     @torch.no_grad()
     def replay(self, imgs_u8: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -525,4 +550,5 @@ class InferencePipeline:
         self.cloud = self._static_cloud
         self.photo = self._static_photo
         self.visibility = self._static_vis
+        self.temporal = self._static_temporal
         return self._static_inv

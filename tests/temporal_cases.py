@@ -1,0 +1,254 @@
+"""Cases and numpy restatement of the temporal fusion (mvs_gi_amd/dropin/temporal.py, csrc/temporal.hip).  TEST INFRASTRUCTURE ONLY.
+
+Definition (include/mvsgi.h, "temporal fusion"), frame b; fp32, one IEEE operation per written operation (every
+array below is float32 and numpy does not contract; the fused multiply-adds of the transform's row are grid_exact_cases.fma_f32):
+  A, source pixel s = i * W + j:
+    1. v = prev_inv, d = bf / v, p = rays * d
+    2. live = prev_age != 0 and 0 < v <= FLT_MAX and d <= FLT_MAX
+    3. q = T_b p (per row fma(t2, z, fma(t1, y, t0 * x)) + t3); r2 = (qx qx + qy qy) + qz qz; rejected unless 0 < r2 <= FLT_MAX
+    4. xz = sqrt(qx qx + qz qz), lon = -1 * atan2(qz, qx), lat = atan2(qy, xz), gx = lon / pi, gy = (2 * lat) / pi;
+       u = gx * au + bu, w = gy * av + bv; cx = floor(u), cy = floor(w); wrap: cx += W when cx < 0, cx -= W when cx >= W;
+       rejected unless 0 <= cx < W and 0 <= cy < H
+    5. zkey[b, cy, cx] = min(zkey, (bits(r2) << 32) | s), from EMPTY = 0x7F800000FFFFFFFF            (np.minimum.at on uint64)
+  B, target pixel t:
+    1. r2 = float(bits(key >> 32)), s = min(key & 0xffffffff, H W - 1)
+    2. warped_inv = bf / sqrt(r2); ratio = warped_inv / prev_inv[b, s]; g = ratio * ratio; var_w = prev_var[b, s] * (g * g) + q_var
+    3. prior = key != EMPTY and 0 <= var_w <= FLT_MAX
+    4. m = cur_inv, sd = cur_std or the scalar, var_m = sd * sd;  5. meas = 0 < m <= FLT_MAX and 0 < var_m <= FLT_MAX
+    6. the table of fuse() below
+The only operation of the whole definition that is not correctly rounded everywhere is atan2 (and, on the device, the root of
+warped_inv, which the tests bound against its correctly rounded value): numpy's and the device's may differ in the last bits, which
+moves a cell only when a coordinate sits within that of a cell's edge.
+"""
+import math
+
+import numpy as np
+
+import grid_exact_cases as GE
+from oracle import grid_oracle as G
+
+F32 = np.float32
+FLT_MAX = F32(np.finfo(np.float32).max)
+PI_F = F32(np.pi)
+EMPTY = np.uint64(0x7F800000FFFFFFFF)
+BAD = (0.0, -1.0, float("nan"), float("inf"))
+GATE, Q_VAR = 3.0, 1e-6
+GATE_MARGIN = 1e-5            # the decision must agree where |e e - gate2 S| > GATE_MARGIN gate2 S in the float64 restatement
+FULL = ((-math.pi, math.pi), (0.0, math.pi))
+PART = ((-math.pi / 2, math.pi / 2), (math.pi / 4, 3 * math.pi / 4))
+
+# name: frames, map, the rig camera's ranges, the seeded fraction of bad values (0, -1, NaN, inf) in prev_inv, cur_inv and cur_std
+CASES = {
+    "tail": dict(B=1, hw=(6, 10), ranges=FULL, bad=0.06, seed=2301),          # row tail; full sphere, so wrap
+    "part": dict(B=1, hw=(8, 16), ranges=PART, bad=0.05, seed=2302),          # no wrap; points leave the map
+    "row": dict(B=1, hw=(1, 7), ranges=FULL, bad=0.0, seed=2303),             # a single row; the one case without bad values
+    "b2": dict(B=2, hw=(5, 12), ranges=FULL, bad=0.05, seed=2304),            # batch of two
+    "waves": dict(B=3, hw=(48, 100), ranges=FULL, bad=0.02, seed=2305),       # batch of three at a larger map: several blocks per frame
+}
+POSES = ("identity", "yaw", "shift", "rigid")
+YAW_COLUMNS = 3
+BFS = (96.0, 1.0)
+
+
+# ---------------------------------------------------------------------------------------------- inputs
+def affine(ranges, hw):
+    """(au, bu, av, bv) as float32, each rounded once from float64, and wrap: include/mvsgi.h's formulas"""
+    (lo0, lo1), (la0, la1) = ranges
+    Hh, W = hw
+    c = (math.pi * W / (lo1 - lo0), -lo0 * W / (lo1 - lo0), (math.pi / 2) * Hh / (la1 - la0), (math.pi / 2 - la0) * Hh / (la1 - la0))
+    return tuple(F32(v) for v in c) + (abs(lo1 - lo0 - 2 * math.pi) < 1e-6,)
+
+
+def rays(name):
+    c = CASES[name]
+    return G.rays_panorama(np.ones(1, np.float32), c["ranges"][0], c["ranges"][1], c["hw"])[:, 0].numpy()
+
+
+def _rot(yaw=0.0, pitch=0.0, roll=0.0):
+    cy, sy, cp, sp, cr, sr = math.cos(yaw), math.sin(yaw), math.cos(pitch), math.sin(pitch), math.cos(roll), math.sin(roll)
+    Ry = np.array([[cy, 0, sy], [0, 1, 0], [-sy, 0, cy]])               # about the vertical: longitude theta -> theta + yaw
+    Rx = np.array([[1, 0, 0], [0, cp, -sp], [0, sp, cp]])
+    Rz = np.array([[cr, -sr, 0], [sr, cr, 0], [0, 0, 1]])
+    return Ry @ Rx @ Rz
+
+
+def pose(kind, name, b=0):
+    """T [4, 4] float32 of frame b: identity; a yaw of exactly YAW_COLUMNS columns of the full sphere (2 pi k / W); a translation; a
+    general rigid motion.  Metres: the surfaces are 2 ... 12 m away."""
+    W = CASES[name]["hw"][1]
+    T = np.eye(4)
+    if kind == "yaw":
+        T[:3, :3] = _rot(yaw=2 * math.pi * (YAW_COLUMNS + b) / W)
+    elif kind == "shift":
+        T[:3, 3] = [0.25 + 0.1 * b, -0.05, 0.4]
+    elif kind == "rigid":
+        T[:3, :3] = _rot(0.11 + 0.05 * b, -0.04, 0.07)
+        T[:3, 3] = [-0.3, 0.08, 0.2 + 0.1 * b]
+    elif kind != "identity":
+        raise KeyError(kind)
+    return T.astype(np.float32)
+
+
+def poses(kind, name):
+    return np.stack([pose(kind, name, b) for b in range(CASES[name]["B"])])
+
+
+def collapse(t=(1.5, -0.5, 2.0)):
+    """A transform whose rotation block is zero: every point goes to q = t."""
+    T = np.zeros((4, 4), np.float32)
+    T[:3, 3] = t
+    T[3, 3] = 1
+    return T
+
+
+def onto_x():
+    """q = (px, 0, 0): every point in front lands in the cell of the +x axis with r2 = px^2, the nearer surface nearer."""
+    T = np.zeros((4, 4), np.float32)
+    T[0, 0] = T[3, 3] = 1
+    return T
+
+
+def _seed_bad(rng, a, frac, keep=None):
+    flat = a.reshape(-1)
+    if frac:
+        pos = rng.permutation(flat.size)[:max(int(round(frac * flat.size)), len(BAD))]
+        flat[pos] = np.asarray(BAD, F32)[np.arange(pos.size) % len(BAD)]
+    if keep is not None and frac:                                     # the same bad values at chosen places
+        for k, at in enumerate(keep):
+            flat[at] = F32(BAD[k % len(BAD)])
+
+
+def make_inputs(name, bf=96.0):
+    """-> dict(prev_inv, prev_var, cur_inv, cur_std [B, H, W] float32, prev_age [B, H, W] uint8): a smooth surface 2 ... 12 m away with
+    depth steps as the state (inverse distance bf / d, standard deviation 3 %), the measurement within a few per cent of it except
+    in a patch where the scene changed by half, ages 1 ... 255 with a patch of 0, and the seeded bad values."""
+    c = CASES[name]
+    rng = np.random.default_rng(c["seed"])
+    B, (Hh, W) = c["B"], c["hw"]
+    i, j = np.meshgrid(np.arange(Hh), np.arange(W), indexing="ij")
+    d = np.empty((B, Hh, W))
+    for b in range(B):
+        d[b] = 6.0 + 2.5 * np.sin(2 * math.pi * (j + 3 * b) / W) * np.cos(math.pi * (i + 0.5) / max(Hh, 2)) + 1.5 * np.sin(0.9 * j + 0.7 * i)
+        d[b][:, W // 3: W // 2] -= 2.5                                  # a nearer object: depth steps at both sides
+        d[b][Hh // 2:, (2 * W) // 3:] += 3.0
+    prev_inv = (F32(bf) / d.astype(F32)).astype(F32)
+    prev_var = np.square(F32(0.03) * prev_inv * rng.uniform(0.5, 1.5, prev_inv.shape).astype(F32)).astype(F32)
+    cur_inv = (prev_inv * (1 + 0.02 * rng.standard_normal(prev_inv.shape)).astype(F32)).astype(F32)
+    cur_inv[:, : max(Hh // 3, 1), W // 2: W // 2 + max(W // 5, 1)] *= F32(1.5)                         # the scene changed: disagreement
+    cur_std = (F32(0.02) * np.abs(cur_inv) * rng.uniform(0.5, 2.0, prev_inv.shape).astype(F32)).astype(F32)
+    age = rng.integers(1, 256, size=prev_inv.shape).astype(np.uint8)
+    age[:, Hh - max(Hh // 3, 1):, : max(W // 4, 2)] = 0                                                # a patch that holds nothing
+    age[:, 0, W - 1] = 255                                                                           # saturates
+    hole = [(b * Hh + Hh - 1) * W + k for b in range(B) for k in range(min(2, W))]                    # bad measurements inside the empty patch
+    _seed_bad(rng, prev_inv, c["bad"])
+    _seed_bad(rng, cur_inv, c["bad"], keep=hole)
+    _seed_bad(rng, cur_std, c["bad"])
+    return dict(prev_inv=prev_inv, prev_var=prev_var, prev_age=age, cur_inv=cur_inv, cur_std=cur_std)
+
+
+# ---------------------------------------------------------------------------------------------- the restatement
+def splat(prev_inv, prev_age, ray_table, T, bf, aff):
+    """Stage A -> dict(zkey uint64 [B, H, W], live bool [B, H, W], r2, cx, cy of every source pixel, splat bool)"""
+    prev_inv, ray_table, T = (np.ascontiguousarray(a, dtype=F32) for a in (prev_inv, ray_table, T))
+    B, Hh, W = prev_inv.shape
+    au, bu, av, bv, wrap = aff
+    with np.errstate(all="ignore"):
+        v = prev_inv
+        d = F32(bf) / v
+        p = (ray_table[None] * d[:, None]).astype(F32)
+        live = (np.asarray(prev_age) != 0) & (v > 0) & (v <= FLT_MAX) & (d <= FLT_MAX)
+        q = GE.transform(T, p.reshape(B, 3, Hh * W)).reshape(B, 3, Hh, W)
+        qx, qy, qz = q[:, 0], q[:, 1], q[:, 2]
+        r2 = (qx * qx + qy * qy) + qz * qz
+        near = (r2 > 0) & (r2 <= FLT_MAX)
+        xz = np.sqrt(qx * qx + qz * qz)
+        lon = F32(-1.0) * np.arctan2(qz, qx)
+        lat = np.arctan2(qy, xz)
+        gx = lon / PI_F
+        gy = (F32(2.0) * lat) / PI_F
+        u = gx * au + bu
+        w = gy * av + bv
+        fx, fy = np.floor(u), np.floor(w)
+        if wrap:
+            fx = np.where(fx < 0, fx + F32(W), np.where(fx >= W, fx - F32(W), fx))
+        inside = (fx >= 0) & (fx < W) & (fy >= 0) & (fy < Hh)
+    assert all(a.dtype == F32 for a in (d, p, q, r2, xz, lon, lat, gx, gy, u, w, fx, fy))
+    ok = live & near & inside
+    cx, cy = np.where(ok, fx, 0).astype(np.int64), np.where(ok, fy, 0).astype(np.int64)
+    s = np.arange(Hh * W, dtype=np.uint64).reshape(1, Hh, W)
+    key = (r2.view(np.uint32).astype(np.uint64) << np.uint64(32)) | s
+    zkey = np.full(B * Hh * W, EMPTY, np.uint64)
+    at = (np.arange(B).reshape(B, 1, 1) * (Hh * W) + cy * W + cx)
+    np.minimum.at(zkey, at[ok], np.broadcast_to(key, ok.shape)[ok])
+    return dict(zkey=zkey.reshape(B, Hh, W), live=live, r2=r2, cx=cx, cy=cy, splat=ok)
+
+
+def src_of(zkey):
+    """-> int64 [B, H, W]: the source index of every cell, -1 where it is empty"""
+    return np.where(zkey != EMPTY, (zkey & np.uint64(0xFFFFFFFF)).astype(np.int64), -1)
+
+
+def exact_warped_inv(zkey, bf):
+    """RN_fp32(bf / sqrt(float64(r2))) of every cell's own r2 bits (53 bits against 24: the double rounding is harmless); 0 where empty"""
+    r2 = (zkey >> np.uint64(32)).astype(np.uint32).view(F32).astype(np.float64)
+    with np.errstate(all="ignore"):
+        return np.where(zkey != EMPTY, (np.float64(F32(bf)) / np.sqrt(r2)).astype(F32), F32(0))
+
+
+ROWS = ("neither", "prior", "meas", "both", "restart")
+
+
+def fuse(zkey, state, cur_inv, cur_std, bf, gate=GATE, q_var=Q_VAR, meas_std=None, warped=None):
+    """Stage B -> dict(fused, var, warped_inv, warped_var float32, age uint8, src int32 [B, H, W], row: the index into ROWS of the
+    table's row every pixel took, margin: float64 |e e - gate2 S| / (gate2 S) where prior and measurement both hold, inf elsewhere).
+    state = (prev_inv, prev_var, prev_age).  warped = (warped_inv, src) replaces steps 1 and the root of step 2 (the device's own)."""
+    p_inv, p_var, p_age = (np.asarray(a) for a in state)
+    B, Hh, W = p_inv.shape
+    last = Hh * W - 1
+    gate2, q = F32(float(gate) * float(gate)), F32(q_var)
+    with np.errstate(all="ignore"):
+        if warped is None:
+            filled = zkey != EMPTY
+            s = np.minimum((zkey & np.uint64(0xFFFFFFFF)).astype(np.int64), last)
+            w_inv = exact_warped_inv(zkey, bf)
+        else:
+            w_inv, src = (np.asarray(a) for a in warped)
+            filled = src >= 0
+            s = np.where(filled, src.astype(np.int64), last)
+        take = lambda a: np.take_along_axis(a.reshape(B, -1), s.reshape(B, -1), axis=1).reshape(B, Hh, W)
+        s_inv, s_var, s_age = take(p_inv), take(p_var), take(p_age).astype(np.int64)
+        ratio = w_inv / s_inv
+        g = ratio * ratio
+        var_w = s_var * (g * g) + q
+        prior = filled & (var_w >= 0) & (var_w <= FLT_MAX)
+        m = np.asarray(cur_inv, dtype=F32)
+        sd = np.asarray(cur_std, dtype=F32) if cur_std is not None else np.full_like(m, F32(meas_std))
+        var_m = sd * sd
+        meas = (m > 0) & (m <= FLT_MAX) & (var_m > 0) & (var_m <= FLT_MAX)
+        e = m - w_inv
+        S = var_w + var_m
+        agree = e * e <= gate2 * S
+        K = var_w / S
+        upd, upd_var = w_inv + K * e, var_w - K * var_w
+        assert all(a.dtype == F32 for a in (ratio, g, var_w, var_m, e, S, K, upd, upd_var))
+        both, only_prior = prior & meas & agree, prior & ~meas
+        restart, only_meas = prior & meas & ~agree, meas & ~prior
+        fused = np.where(both, upd, np.where(only_prior, w_inv, m))
+        var = np.where(both, upd_var, np.where(only_prior, var_w, np.where(meas, var_m, F32(np.inf)))).astype(F32)
+        age = np.where(both, np.minimum(s_age + 1, 255), np.where(only_prior, s_age, np.where(meas, 1, 0))).astype(np.uint8)
+        row = np.where(both, 3, np.where(restart, 4, np.where(only_prior, 1, np.where(only_meas, 2, 0))))
+        e64, S64 = m.astype(np.float64) - w_inv.astype(np.float64), var_w.astype(np.float64) + var_m.astype(np.float64)
+        margin = np.where(prior & meas, np.abs(e64 * e64 - np.float64(gate2) * S64) / (np.float64(gate2) * S64), np.inf)
+    return dict(fused=fused.astype(F32), var=var, age=age, warped_inv=np.where(filled, w_inv, F32(0)).astype(F32),
+                warped_var=np.where(filled, var_w, F32(np.inf)).astype(F32), src=np.where(filled, s, -1).astype(np.int32), row=row,
+                margin=margin)
+
+
+def step(name, kind, bf=96.0, inputs=None, ray_table=None, T=None):
+    """One step of a case on the CPU: the splat and the fuse on the seeded inputs -> dict(inp, aff, A, B)"""
+    c = CASES[name]
+    inp = make_inputs(name, bf) if inputs is None else inputs
+    aff = affine(c["ranges"], c["hw"])
+    A = splat(inp["prev_inv"], inp["prev_age"], rays(name) if ray_table is None else ray_table, poses(kind, name) if T is None else T, bf, aff)
+    Bs = fuse(A["zkey"], (inp["prev_inv"], inp["prev_var"], inp["prev_age"]), inp["cur_inv"], inp["cur_std"], bf)
+    return dict(inp=inp, aff=aff, A=A, B=Bs)

@@ -831,6 +831,54 @@ int mvsgi_temporal_fuse_f32(const unsigned long long* zkey, const float* prev_in
                             float* var, unsigned char* age, float* warped_inv, float* warped_var, int* src, long long B, int H, int W,
                             float bf, float gate2, float q_var, mvsgi_stream_t stream);
 
+/* ---- volumetric fusion (csrc/tsdf.hip) --------------------------------------------------------------------------------------------
+ * The predictions of a sequence integrated into a world-fixed truncated signed distance volume that rolls with the rig, and that
+ * volume ray-cast back into the rig's view.  Not part of the reference's interface; defined as a composition of operations this
+ * library already has.  All arithmetic is fp32, no contraction, one IEEE operation per written operation; the row of a transform,
+ * the equirectangular projection and the affine map into the panorama's cells are the functions mvsgi_temporal_splat_f32 uses.
+ * State, per sequence b: vol [Nz][Ny][Nx][2] fp32, the pair (f, w) of a voxel: the truncated signed distance in units of trunc
+ * (positive in front of the surface) and the accumulated weight.  The store is TOROIDAL: the voxel with world index i = (ix, iy, iz)
+ * (integers of any sign; its centre is (i + 0.5) * vs) lives in slot i mod N per axis, the floored modulus; the volume covers
+ * origin[b][a] <= i_a < origin[b][a] + N_a.  origin, origin_prev [B][3] int32 and the poses are DEVICE pointers, read by the
+ * launches: a captured step follows a moving rig.  |i_a| < 2^23 is the caller's to keep (the origin is device data and not checked;
+ * whatever it holds, no address outside the buffers is formed).
+ * mvsgi_tsdf_integrate_f32, one launch, in place; slot s = (sx, sy, sz) of sequence b:
+ *     1. i_a = origin_a + ((s_a - origin_a) mod N_a); fresh = some axis has i_a < origin_prev_a or i_a >= origin_prev_a + N_a (the
+ *        slot scrolled in since the previous integrate: re-centring costs no pass of its own); (f, w) = fresh ? (1, 0) : vol[b][s]
+ *     2. c_a = (float(i_a) + 0.5f) * vs; q = T_b c (T: world -> rig, rows 0..2, the row rule of mvsgi_transform_points_f32);
+ *        r2 = (qx * qx + qy * qy) + qz * qz, rejected unless 0 < r2 <= FLT_MAX; r = sqrtf(r2), rejected unless r_min <= r <= r_max
+ *     3. (gx, gy) = the equirectangular projection of q; u = gx * au + bu, v = gy * av + bv; floorf, the column wrapped once when
+ *        wrap != 0; rejected outside the map, decided on the floats (step 4 of mvsgi_temporal_splat_f32: the same cell (cx, cy))
+ *     4. m = inv[b][cy][cx]; rejected where mask is given and mask[b][cy][cx] == 0; d = bf / m; rejected unless
+ *        0 < m <= FLT_MAX && d <= FLT_MAX
+ *     5. sdf = d - r; rejected if sdf < -trunc (behind the surface: not observed); obs = fminf(sdf, trunc) / trunc
+ *     6. w_obs = 1 without std; with std: sd = std[b][cy][cx] (in inv's unit), sig = sd * d / m (the standard deviation of the
+ *        distance), w_obs = t2 / (t2 + sig * sig), t2 = fp32(trunc^2); rejected unless 0 < w_obs <= 1 (a NaN compares false)
+ *     7. W = w + w_obs; f' = (f * w + obs * w_obs) / W; w' = fminf(W, w_max)
+ *     8. vol[b][s] = (f', w'); a rejected voxel keeps the (f, w) of step 1, so a fresh rejected one is stored as (1, 0)
+ *        optional: range[b][s] = r (0 where r2 was rejected), for the tests that bound the root
+ *   host: vs > 0, trunc > 0, t2, w_max > 0, 0 <= r_min < r_max <= FLT_MAX, the affine map finite, wrap 0 / 1, every N_a >= 1,
+ *         Nx * Ny * Nz < 2^31 (offsets are 64-bit), H * W < 2^31, B * ceil(Nx * Ny * Nz / 512) < 2^31; 16-byte alignment.
+ * mvsgi_tsdf_raycast_f32, one launch; pixel (i, j) of sequence b, P_b the rig -> world pose:
+ *     1. dir_a = fma(P[a][2], rz, fma(P[a][1], ry, P[a][0] * rx)) of rays[:, i, j] (the row rule without the translation);
+ *        o_a = P[a][3]
+ *     2. for k = 0 .. K - 1: t_k = t0 + float(k) * step; p_a = o_a + dir_a * t_k; g_a = floorf(p_a * inv_vs) (inv_vs = fp32(1 / vs),
+ *        rounded once on the host); inside = every axis has origin_a <= g_a < origin_a + N_a, decided on the floats; (f_k, w_k) =
+ *        the pair of slot g mod N; valid_k = inside && w_k >= w_min
+ *     3. the first k >= 1 with valid_k && valid_{k-1} && f_{k-1} > 0 && f_k <= 0 ends the march: t* = t_{k-1} + step * (f_{k-1} /
+ *        (f_{k-1} - f_k)); inv = bf / t*, weight = w_k, steps = k.  No crossing: inv = 0, weight = 0, steps = K.  A back-face
+ *        crossing (f rising through 0) is ignored.  The fixed step is part of the definition.
+ *   `origin` is the coverage of what the volume holds: origin_prev after an integrate.  inv, weight fp32 and steps int32 [B][H][W]
+ *   may each be NULL, not all.  1 <= K <= 4096, inv_vs > 0, t0 >= 0, step > 0, w_min finite; rays [3][H][W]; 16-byte alignment.
+ * No host synchronisation, no allocation: capturable.  No atomics: every slot and every pixel has one owner. */
+int mvsgi_tsdf_integrate_f32(float* vol, const float* inv, const float* std, const unsigned char* mask, const float* T,
+                             const int* origin, const int* origin_prev, float* range, long long B, int Nx, int Ny, int Nz, int H,
+                             int W, float vs, float trunc, float t2, float w_max, float r_min, float r_max, float bf, float au,
+                             float bu, float av, float bv, int wrap, mvsgi_stream_t stream);
+int mvsgi_tsdf_raycast_f32(const float* vol, const float* rays, const float* P, const int* origin, float* inv, float* weight,
+                           int* steps, long long B, int Nx, int Ny, int Nz, int H, int W, float inv_vs, float t0, float step, int K,
+                           float w_min, float bf, mvsgi_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -148,6 +148,8 @@ SIGNATURES = {
     "mvsgi_visibility_f32": (c_int, [_P] * 5 + [c_float, _P, _P, _P, c_longlong] + [c_int] * 5 + [c_float, _P]),
     "mvsgi_temporal_splat_f32": (c_int, [_P] * 5 + [c_longlong, c_int, c_int] + [c_float] * 5 + [c_int, _P]),
     "mvsgi_temporal_fuse_f32": (c_int, [_P] * 6 + [c_float] + [_P] * 6 + [c_longlong, c_int, c_int] + [c_float] * 3 + [_P]),
+    "mvsgi_tsdf_integrate_f32": (c_int, [_P] * 8 + [c_longlong] + [c_int] * 5 + [c_float] * 11 + [c_int, _P]),
+    "mvsgi_tsdf_raycast_f32": (c_int, [_P] * 7 + [c_longlong] + [c_int] * 5 + [c_float] * 3 + [c_int, c_float, c_float, _P]),
 }
 
 _lib = None

@@ -12,6 +12,7 @@ from .cloud import CloudPacker  # noqa: F401
 from .photo import PhotoConsistency  # noqa: F401
 from .visibility import Visibility  # noqa: F401
 from .temporal import TemporalFusion  # noqa: F401
+from .tsdf import TsdfVolume  # noqa: F401
 from .metrics import (Evaluator, MVSMetric, SSIMMetric, RMSEMetric, MAEMetric, BadPixelRatioMetric,  # noqa: F401
                       InverseMetricWrapper)
 from .losses import (LossEvaluator, VolumeCrossEntropy, MaskedSmoothL1Loss, InBoundsBCEDistanceLoss,  # noqa: F401

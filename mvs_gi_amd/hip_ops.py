@@ -1723,6 +1723,134 @@ def temporal_fuse(zkey, prev_inv, prev_var, prev_age, cur_inv, bf: float, gate: 
     return res
 
 
+# ---- volumetric fusion (csrc/tsdf.hip; include/mvsgi.h, "volumetric fusion") ----
+TSDF_OUTPUTS = ("inv", "weight", "steps")                   # the order of mvsgi_tsdf_raycast_f32's output pointers
+TSDF_MAX_STEPS = 4096
+TSDF_FLT_MAX = 3.4028234663852886e+38
+
+
+def _tsdf_volume(vol):
+    """The volume as the two calls take it: a caller-owned [B, Nz, Ny, Nx, 2] fp32 tensor used in place -> (B, Nx, Ny, Nz, device)"""
+    vol = _arg(vol, "vol", None)
+    if vol.dim() != 5 or vol.shape[4] != 2 or not vol.numel():
+        raise AssertionError(f"vol must be a non-empty [B, Nz, Ny, Nx, 2], got {list(vol.shape)}")
+    B, Nz, Ny, Nx = (int(v) for v in vol.shape[:4])
+    tsdf_dims(B, Nx, Ny, Nz)
+    return B, Nx, Ny, Nz, vol.device
+
+
+def tsdf_dims(B: int, Nx: int, Ny: int, Nz: int) -> None:
+    """What one launch addresses: every N >= 1, Nx * Ny * Nz < 2^31 and B * ceil(Nx * Ny * Nz / 512) < 2^31."""
+    if min(B, Nx, Ny, Nz) < 1:
+        raise ValueError(f"volumetric fusion: B, Nx, Ny, Nz >= 1, got {(B, Nx, Ny, Nz)}")
+    n = Nx * Ny * Nz
+    if n >= 1 << 31 or B * -(-(n // 2 if n % 2 == 0 else n) // 256) >= 1 << 31:
+        raise ValueError(f"volumetric fusion: {B} volumes of {Nx} x {Ny} x {Nz} voxels are too large for one launch")
+
+
+def _tsdf_map(B: int, Hh: int, W: int) -> None:
+    if Hh > 1 << 24 or W > 1 << 24 or Hh * W >= 1 << 31 or B * -(-(Hh * -(-W // 4)) // 256) >= 1 << 31:
+        raise ValueError(f"volumetric fusion: map {B} x {Hh} x {W}: H, W <= 2^24, H * W < 2^31 and one launch's blocks")
+
+
+def _tsdf_scalar(v, name: str, low_ok: bool = False) -> float:
+    v = float(v)
+    if not (0.0 <= v if low_ok else 0.0 < v) or not v <= TSDF_FLT_MAX:
+        raise ValueError(f"{name}: {'0 <=' if low_ok else '0 <'} {name} <= FLT_MAX, got {v}")
+    return v
+
+
+def _tsdf_plane(t, name: str, shape, dev, dtype=torch.float32):
+    """A measurement plane [B, H, W] (or [B, 1, H, W]): an activation, copied when its form is awkward"""
+    if dtype == torch.uint8 and isinstance(t, torch.Tensor) and t.dtype == torch.bool:
+        t = t.view(torch.uint8)
+    t = _dev(t, name, dtype)
+    if t.dim() == 4 and t.shape[1] == 1:
+        t = t.squeeze(1)
+    if (shape is not None and tuple(t.shape) != shape) or t.dim() != 3 or not t.numel() or (dev is not None and t.device != dev):
+        raise AssertionError(f"{name} must be {list(shape) if shape else '[B, H, W]'} on {dev}, got {list(t.shape)} on {t.device}")
+    return t
+
+
+def tsdf_integrate(vol, inv, T, origin, origin_prev, bf: float, affine, voxel: float, trunc: float, w_max: float = 64.0,
+                   r_range=(0.0, TSDF_FLT_MAX), std=None, mask=None, r_out=None) -> torch.Tensor:
+    """One prediction integrated into the rolling truncated signed distance volume, in place (include/mvsgi.h, "volumetric fusion";
+    DESIGN.md section 24).  vol [B, Nz, Ny, Nx, 2] fp32, the pairs (f, w), toroidal: world voxel i lives in slot i mod N; T [B, 4, 4]
+    fp32 (world -> rig), origin and origin_prev [B, 3] int32 (the coverage now and at the previous integrate: what scrolled in is
+    cleared on the way), all ON THE DEVICE and read by the launch, so a captured graph sees the values of each replay.  inv [B, H, W]
+    (or [B, 1, H, W]) fp32: the rig panorama's inverse distance; affine = temporal_affine(long_range, lat_range, (H, W)); std
+    likewise (the standard deviation of inv: the observation's weight is trunc^2 / (trunc^2 + sigma_d^2)) or None (weight 1); mask
+    [B, H, W] uint8 / bool or None (0: the pixel is not integrated); r_out [B, Nz, Ny, Nx] fp32 or None: every voxel centre's range.
+    One launch on inv's stream; nothing is allocated: capturable.  There is no CPU fallback.  -> vol"""
+    B, Nx, Ny, Nz, dev = _tsdf_volume(vol)
+    inv = _tsdf_plane(inv, "inv", None, dev)
+    if inv.shape[0] != B:
+        raise AssertionError(f"inv must be [{B}, H, W], got {list(inv.shape)}")
+    shape = tuple(int(v) for v in inv.shape)
+    _tsdf_map(*shape)
+    if std is not None:
+        std = _tsdf_plane(std, "std", shape, dev)
+    if mask is not None:
+        mask = _tsdf_plane(mask, "mask", shape, dev, torch.uint8)
+    _arg(T, "T", dev, shape=(B, 4, 4))
+    _arg(origin, "origin", dev, torch.int32, shape=(B, 3))
+    _arg(origin_prev, "origin_prev", dev, torch.int32, shape=(B, 3))
+    if r_out is not None:
+        _arg(r_out, "r_out", dev, shape=(B, Nz, Ny, Nx))
+    try:
+        au, bu, av, bv, wrap = affine
+        au, bu, av, bv = (float(v) for v in (au, bu, av, bv))
+    except (TypeError, ValueError):
+        raise ValueError(f"affine: (au, bu, av, bv, wrap) of temporal_affine(), got {affine!r}") from None
+    if not all(math.isfinite(v) for v in (au, bu, av, bv)):
+        raise ValueError(f"affine: (au, bu, av, bv) must be finite, got {(au, bu, av, bv)}")
+    voxel, trunc, w_max = _tsdf_scalar(voxel, "voxel"), _tsdf_scalar(trunc, "trunc"), _tsdf_scalar(w_max, "w_max")
+    t2 = _tsdf_scalar(trunc * trunc, "trunc^2")
+    try:
+        r_min, r_max = (float(v) for v in r_range)
+    except (TypeError, ValueError):
+        raise ValueError(f"r_range: (r_min, r_max), got {r_range!r}") from None
+    r_max = min(r_max, TSDF_FLT_MAX)
+    if not 0.0 <= r_min < r_max:
+        raise ValueError(f"r_range: 0 <= r_min < r_max, got {(r_min, r_max)}")
+    _call("mvsgi_tsdf_integrate_f32", vol.data_ptr(), inv.data_ptr(), _ptr(std), _ptr(mask), T.data_ptr(), origin.data_ptr(),
+          origin_prev.data_ptr(), _ptr(r_out), B, Nx, Ny, Nz, shape[1], shape[2], voxel, trunc, t2, w_max, r_min, r_max, float(bf), au, bu,
+          av, bv, 1 if wrap else 0, _stream_ptr(inv))
+    return vol
+
+
+def tsdf_raycast(vol, rays, P, origin, bf: float, voxel: float, t0: float, step: float, K: int, w_min: float = 1.0, want=TSDF_OUTPUTS,
+                 out=None) -> dict:
+    """The volume ray-cast into the rig's view: every pixel of the panorama marches its ray, moved into the world by P [B, 4, 4] fp32
+    (rig -> world, ON THE DEVICE, read by the launch), in K fixed steps t_k = t0 + k step through the nearest voxels, and stops at
+    the first front-face zero crossing between two valid samples (weight >= w_min), interpolated linearly.  vol [B, Nz, Ny, Nx, 2]
+    and origin [B, 3] int32 (the coverage of what the volume holds): caller-owned, on the device, read in place; rays [3, H, W] fp32.
+    -> dict of the wanted TSDF_OUTPUTS, each [B, H, W]: inv fp32 (bf / t*, 0 without a crossing), weight fp32 (the weight of the
+    sample behind the surface, 0 without), steps int32 (the index of that sample, K without).  out: a dict with tensors to write in
+    place.  One launch on vol's stream; with `out` nothing is allocated: capturable.  There is no CPU fallback."""
+    B, Nx, Ny, Nz, dev = _tsdf_volume(vol)
+    rays = _dev(rays, "rays")
+    if rays.dim() != 3 or rays.shape[0] != 3 or not rays.numel() or rays.device != dev:
+        raise AssertionError(f"rays must be [3, H, W] on {dev}, got {list(rays.shape)} on {rays.device}")
+    Ho, Wo = int(rays.shape[1]), int(rays.shape[2])
+    _tsdf_map(B, Ho, Wo)
+    _arg(P, "P", dev, shape=(B, 4, 4))
+    _arg(origin, "origin", dev, torch.int32, shape=(B, 3))
+    voxel, step, t0 = _tsdf_scalar(voxel, "voxel"), _tsdf_scalar(step, "step"), _tsdf_scalar(t0, "t0", low_ok=True)
+    inv_vs = _tsdf_scalar(1.0 / voxel, "1 / voxel")
+    w_min = float(w_min)
+    if not math.isfinite(w_min):
+        raise ValueError(f"w_min must be finite, got {w_min}")
+    if int(K) != K or not 1 <= int(K) <= TSDF_MAX_STEPS:
+        raise ValueError(f"K: 1 <= K <= {TSDF_MAX_STEPS} march steps, got {K!r}")
+    want = _wanted(want, TSDF_OUTPUTS)
+    shape = (B, Ho, Wo)
+    res = _outputs(want, out, dev, {"inv": (shape, torch.float32), "weight": (shape, torch.float32), "steps": (shape, torch.int32)})
+    _call("mvsgi_tsdf_raycast_f32", vol.data_ptr(), rays.data_ptr(), P.data_ptr(), origin.data_ptr(),
+          *(_ptr(res.get(k)) for k in TSDF_OUTPUTS), B, Nx, Ny, Nz, Ho, Wo, inv_vs, t0, step, int(K), w_min, float(bf), _stream_ptr(vol))
+    return res
+
+
 # the packed point cloud (csrc/cloud.hip), restated: tiles of 1024 consecutive pixels, 16 words of 64 bits each; at most 4 gates, 4 colour
 # channels and 16 floats per record
 CLOUD_TILE, CLOUD_WORDS_PER_TILE, CLOUD_MAX_GATES, CLOUD_MAX_CHANNELS, CLOUD_MAX_RECORD, CLOUD_MAX_BATCH = 1024, 16, 4, 4, 16, 65535

@@ -365,10 +365,18 @@ class InferencePipeline:
     otherwise.  `pipe.temporal` is the dict of fused, var, age, warped_inv, warped_var and src, the stage's own static tensors, valid
     until the next call.  Every other stage keeps consuming the raw inv_dist, and the returned map is the raw one.  capture() runs
     the stage on its warm-up frames and then resets it: the first replay starts the sequence.  Without it every launch and every result
-    is what it was."""
+    is what it was.
+
+    With `tsdf` (a dropin.TsdfVolume built on this pipeline's `reprojector`) the prediction is integrated into the stage's rolling
+    truncated signed distance volume and the volume is ray-cast back into the rig's view (csrc/tsdf.hip, two launches and one small
+    copy), behind the soft-argmin, in forward_device and inside the captured graph, at the pose `pipe.tsdf_stage.set_pose(P)` staged
+    (identity before any).  The observation's weight comes from the confidence map "spread" where `confidence` selects it and is 1
+    otherwise.  `pipe.tsdf` is the dict of inv, weight and steps, the stage's own static tensors, valid until the next call.  Every
+    other stage keeps consuming the raw inv_dist.  capture() resets the stage after its warm-up frames.  Without it every launch and
+    every result is what it was."""
 
     def __init__(self, cfg: PathConfig, weights, consts, device="cuda", extractor: str = "simple", samplers=None, raw_masks=None,
-                 reprojector=None, confidence=None, cloud=None, photo=None, visibility=None, temporal=None):
+                 reprojector=None, confidence=None, cloud=None, photo=None, visibility=None, temporal=None, tsdf=None):
         """extractor: 'simple' = SimpleFeatExtraction (G16V, config29), 'sphere' = SphereEquirectFeatExtraction with the
         sphere-convolution final layer (G16VV, config103; configs/feature_extractor/sphereconv_featext.yaml).
         samplers / raw_masks: per-camera image samplers and raw-resolution masks; with both, consts["masks"] may be omitted
@@ -403,6 +411,10 @@ class InferencePipeline:
                                  "standard deviation is needed")
         self.temporal_stage = temporal
         self.temporal = None
+        if tsdf is not None and (reprojector is None or getattr(tsdf, "reprojector", None) is not reprojector):
+            raise ValueError("tsdf: the stage needs reprojector=, the Reprojector the TsdfVolume was built on")
+        self.tsdf_stage = tsdf
+        self.tsdf = None
         self.visibility_stage = visibility
         self.visibility = None
         self._vis_out = None
@@ -461,6 +473,7 @@ class InferencePipeline:
             self.photo = self._static_photo
             self.visibility = self._static_vis
             self.temporal = self._static_temporal
+            self.tsdf = self._static_tsdf
             out = self._static_inv.squeeze(0).squeeze(0).cpu().numpy()
         else:
             out = self.forward_device(t.to(self.hot.device)).squeeze(0).squeeze(0).cpu().numpy()
@@ -503,6 +516,11 @@ class InferencePipeline:
             # the state, the pose and the outputs are the stage's own, made by its first step at this shape
             spread = self.confidence.get("spread") if self.confidence is not None else None
             self.temporal = self.temporal_stage.step(inv, std=spread, want=H.TEMPORAL_OUTPUTS)
+        if self.tsdf_stage is not None:
+            # the volume, the poses, the origins and the outputs are the stage's own, made by its first call at this batch size
+            spread = self.confidence.get("spread") if self.confidence is not None else None
+            self.tsdf_stage.integrate(inv, std=spread)
+            self.tsdf = self.tsdf_stage.raycast(B=int(inv.shape[0]))
         return inv
 
     # ---- hipGraph replay of the whole chain for one frame (the robot's operating point: one frame at a time) ----
@@ -534,6 +552,9 @@ class InferencePipeline:
         self._static_temporal = self.temporal
         if self.temporal_stage is not None:
             self.temporal_stage.reset()                 # the warm-up frames are not part of any sequence
+        self._static_tsdf = self.tsdf
+        if self.tsdf_stage is not None:
+            self.tsdf_stage.reset()
 
     @torch.no_grad()
     def replay(self, imgs_u8: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -551,4 +572,5 @@ class InferencePipeline:
         self.photo = self._static_photo
         self.visibility = self._static_vis
         self.temporal = self._static_temporal
+        self.tsdf = self._static_tsdf
         return self._static_inv

@@ -2,7 +2,9 @@
 // pixel) and fused with the new measurement (a gated per-pixel Kalman update).  The definition is in include/mvsgi.h (section
 // "temporal fusion") and DESIGN.md 23.  Steps 1-3 of the splat are reproject.hip's and visibility.hip's (the same functions of
 // view_rig.hpp and camera_models.hpp: the thread's quad and its points, the row of a transform, the equirectangular projection), so p,
-// q, r2 and the grid are their bits.  This file is compiled with contraction off.
+// q, r2 and the grid are their bits.  Step 4, the cell of the panorama, is panorama_map.hpp's pano_cell, which tsdf.hip calls for a
+// voxel centre; the thread's frame and quad (frame_quad), the pose's rows (load_pose_rows) and the host checks of the map are that
+// header's too, the per-quad stores view_rig.hpp's.  This file is compiled with contraction off.
 //
 //   1. temporal_fill_kernel     zkey = EMPTY (+inf over the largest index), 16 bytes per thread with an element-wise tail.
 //   2. temporal_splat_kernel    range_splat_kernel's thread shape: a thread owns four consecutive pixels of a row, 16-byte loads of
@@ -13,11 +15,11 @@
 //
 // Two things no other file of the library does.  The transform is READ FROM DEVICE MEMORY (it changes every step, and a captured
 // launch must see the value of the replay): a block never straddles frames (the grid is B * blocks-per-frame, the frame is
-// blockIdx.x / blocks-per-frame), so the address of T[b] is uniform over the block and the twelve floats arrive by scalar loads.  And
-// the minimum is atomicMin on unsigned long long, result unused: the key's upper word is the bit pattern of a positive finite r2, which
-// orders like an unsigned integer, the lower word the source index, so the nearest source wins and the lower index among equals, in
-// whatever order they arrive.  Every cell index is checked before it addresses the buffer; every source index read back from a key is
-// clamped before the gather.
+// blockIdx.x / blocks-per-frame: frame_quad), so the address of T[b] is uniform over the block and the twelve floats arrive by scalar
+// loads.  And the minimum is atomicMin on unsigned long long, result unused: the key's upper word is the bit pattern of a positive
+// finite r2, which orders like an unsigned integer, the lower word the source index, so the nearest source wins and the lower index
+// among equals, in whatever order they arrive.  Every cell index is checked before it addresses the buffer; every source index read
+// back from a key is clamped before the gather.
 #include "common.hpp"
 
 #include <cfloat>
@@ -25,19 +27,13 @@
 namespace {
 
 #include "device_prims.hpp"
-#include "view_rig.hpp"
+#include "panorama_map.hpp"
 
 using mvsgi::aligned;
 typedef unsigned long long u64;
 typedef u64 u64x2 __attribute__((ext_vector_type(2)));
 constexpr u64 kEmpty = 0x7F800000FFFFFFFFull;
 constexpr float kInf = __builtin_inff();
-
-struct TempDims {
-    int H, W;
-    int Wq;                               // threads per map row: ceil(W / 4)
-    unsigned per_frame;                   // blocks per frame: ceil(H * Wq / 256)
-};
 
 __global__ __launch_bounds__(256) void temporal_fill_kernel(u64* __restrict__ zkey, long long count) {
     const long long i = ((long long)blockIdx.x * 256 + threadIdx.x) * 2;
@@ -48,42 +44,26 @@ __global__ __launch_bounds__(256) void temporal_fill_kernel(u64* __restrict__ zk
     }
 }
 
-// a thread's place: the frame of its block and view_rig.hpp's split of the quad index inside the frame
-struct TempQuad {
-    long long b, pix;
-    int n;
-};
-template <bool VEC>
-__device__ __forceinline__ bool quad_of_thread(const TempDims& s, TempQuad& q) {
-    const unsigned blk = blockIdx.x % s.per_frame;
-    const long long idx = (long long)blk * 256 + threadIdx.x;
-    if (idx >= (long long)s.H * s.Wq) return false;
-    const Quad t = quad_at<VEC>(idx, s.H, s.W, s.Wq);
-    q.b = blockIdx.x / s.per_frame, q.n = t.n, q.pix = t.pix(s.W);
-    return true;
-}
-
 template <bool VEC>
 __global__ __launch_bounds__(256) void temporal_splat_kernel(const float* __restrict__ prev_inv, const unsigned char* __restrict__ prev_age,
                                                              const float* __restrict__ rays, const float* __restrict__ T,
-                                                             u64* __restrict__ zkey, TempDims s, float bf, float au, float bu, float av,
+                                                             u64* __restrict__ zkey, FrameMap s, float bf, float au, float bu, float av,
                                                              float bv, int wrap, float pi_f) {
 #pragma clang fp contract(off)
-    TempQuad t;
-    if (!quad_of_thread<VEC>(s, t)) return;
+    Quad t;
+    if (!frame_quad<VEC>(s, t)) return;
+    const long long pix = t.pix(s.W);
     const long long HW = (long long)s.H * s.W;
     // steps 1, 2: visibility.hip's live rule through view_rig.hpp's quad, and the age
-    const unsigned aw = load_byte_quad<VEC>(prev_age + t.b * HW + t.pix, t.n);
+    const unsigned aw = load_byte_quad<VEC>(prev_age + t.b * HW + pix, t.n);
     bool live[4];
     float px[4], py[4], pz[4];
-    quad_points<VEC>(prev_inv + t.b * HW, rays, HW, t.pix, t.n, bf, px, py, pz, [&](int k, float v, float d) {
+    quad_points<VEC>(prev_inv + t.b * HW, rays, HW, pix, t.n, bf, px, py, pz, [&](int k, float v, float d) {
         live[k] = k < t.n && ((aw >> (8 * k)) & 0xffu) != 0u && v > 0.0f && v <= FLT_MAX && d <= FLT_MAX;
     });
-    float tr[12];                                                         // uniform over the block: scalar loads
-    const float* Tb = T + t.b * 16;
-#pragma unroll
-    for (int k = 0; k < 12; ++k) tr[k] = Tb[k];
-    const float Wf = (float)s.W, Hf = (float)s.H;
+    float tr[12];
+    load_pose_rows(T, t.b, tr);
+    const PanoMap map{s.H, s.W, au, bu, av, bv, wrap};
     u64* plane = zkey + t.b * HW;
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
@@ -93,18 +73,10 @@ __global__ __launch_bounds__(256) void temporal_splat_kernel(const float* __rest
         const float qz = transform_row(tr + 8, px[k], py[k], pz[k]);
         const float r2 = (qx * qx + qy * qy) + qz * qz;
         if (!(r2 > 0.0f && r2 <= FLT_MAX)) continue;
-        float gx, gy;                                                     // step 4
-        project_equirect(qx, qy, qz, pi_f, gx, gy);
-        const float u = gx * au + bu, w = gy * av + bv;
-        float fx = floorf(u);
-        const float fy = floorf(w);
-        if (wrap) {
-            if (fx < 0.0f) fx += Wf;
-            else if (fx >= Wf) fx -= Wf;
-        }
-        if (!(fx >= 0.0f && fx < Wf && fy >= 0.0f && fy < Hf)) continue;  // a NaN compares false; inside, the conversions are exact
-        const u64 key = ((u64)__float_as_uint(r2) << 32) | (u64)(unsigned)(t.pix + k);    // step 5
-        atomicMin(plane + (long long)(int)fy * s.W + (int)fx, key);
+        int row, col;                                                     // step 4
+        if (!pano_cell(map, qx, qy, qz, pi_f, row, col)) continue;
+        const u64 key = ((u64)__float_as_uint(r2) << 32) | (u64)(unsigned)(pix + k);    // step 5
+        atomicMin(plane + (long long)row * s.W + col, key);
     }
 }
 
@@ -114,13 +86,14 @@ __global__ __launch_bounds__(256) void temporal_fuse_kernel(const u64* __restric
                                                             const float* __restrict__ cur_inv, const float* __restrict__ cur_std,
                                                             float* __restrict__ fused, float* __restrict__ var, unsigned char* __restrict__ age,
                                                             float* __restrict__ warped_inv, float* __restrict__ warped_var,
-                                                            int* __restrict__ src, TempDims s, float bf, float gate2, float q_var,
+                                                            int* __restrict__ src, FrameMap s, float bf, float gate2, float q_var,
                                                             float meas_std) {
 #pragma clang fp contract(off)
-    TempQuad t;
-    if (!quad_of_thread<VEC>(s, t)) return;
+    Quad t;
+    if (!frame_quad<VEC>(s, t)) return;
+    const long long pix = t.pix(s.W);
     const long long HW = (long long)s.H * s.W;
-    const long long at = t.b * HW + t.pix;
+    const long long at = t.b * HW + pix;
     const unsigned last = (unsigned)(HW - 1);
     u64 key[4];
     float m[4], sd[4];
@@ -181,40 +154,18 @@ __global__ __launch_bounds__(256) void temporal_fuse_kernel(const u64* __restric
         of[k] = f, ov[k] = v, oa |= a << (8 * k);
         wi[k] = filled ? w_inv : 0.0f, wv[k] = filled ? var_w : kInf, os[k] = filled ? (int)sk : -1;     // step 7
     }
-    auto store4 = [&](float* p, const float (&r)[4]) {
-        if (!p) return;
-        if (VEC) {
-            *reinterpret_cast<f32x4*>(p + at) = f32x4{r[0], r[1], r[2], r[3]};
-        } else {
-#pragma unroll
-            for (int k = 0; k < 4; ++k)
-                if (k < t.n) p[at + k] = r[k];
-        }
-    };
-    store4(fused, of), store4(var, ov), store4(warped_inv, wi), store4(warped_var, wv);
+    store_f32_quad<VEC>(fused, at, t.n, of);
+    store_f32_quad<VEC>(var, at, t.n, ov);
+    store_f32_quad<VEC>(warped_inv, at, t.n, wi);
+    store_f32_quad<VEC>(warped_var, at, t.n, wv);
     if (age) store_byte_quad<VEC>(age + at, t.n, oa);
-    if (src) {
-        if (VEC) {
-            *reinterpret_cast<u32x4*>(src + at) = u32x4{(unsigned)os[0], (unsigned)os[1], (unsigned)os[2], (unsigned)os[3]};
-        } else {
-#pragma unroll
-            for (int k = 0; k < 4; ++k)
-                if (k < t.n) src[at + k] = os[k];
-        }
-    }
+    store_u32_quad<VEC>(src, at, t.n, os);
 }
 
 // the checks both entry points share; 0 on success
-int temporal_dims(const char* what, long long B, int H, int W, TempDims& s, long long& blocks) {
+int temporal_dims(const char* what, long long B, int H, int W, FrameMap& s, long long& blocks) {
     MVSGI_REQUIRE(B >= 1 && H >= 1 && W >= 1, "%s: non-positive dimension (B = %lld, H = %d, W = %d)", what, B, H, W);
-    MVSGI_REQUIRE(H <= (1 << 24) && W <= (1 << 24), "%s: map %d x %d: a side above 2^24 is no exact float", what, H, W);
-    MVSGI_REQUIRE((long long)H * W < (1ll << 32), "%s: map %d x %d: H * W must be below 2^32 (a key holds the source index in 32 bits)", what, H, W);
-    const int Wq = (W + 3) / 4;
-    const long long per_frame = mvsgi::cdiv((long long)H * Wq, 256);
-    MVSGI_REQUIRE(B <= ((1ll << 31) - 1) / per_frame, "%s: B * H * W too large for one launch (%lld frames of %lld blocks)", what, B, per_frame);
-    s = TempDims{H, W, Wq, (unsigned)per_frame};
-    blocks = B * per_frame;
-    return 0;
+    return check_pano_sides(what, H, W, 32, " (a key holds the source index in 32 bits)") || check_frame_launch(what, B, H, W, s, blocks);
 }
 
 }  // namespace
@@ -224,12 +175,10 @@ extern "C" int mvsgi_temporal_splat_f32(const float* prev_inv, const unsigned ch
                                         float bv, int wrap, mvsgi_stream_t stream) {
     const char* what = "mvsgi_temporal_splat_f32";
     MVSGI_REQUIRE(prev_inv && prev_age && rays && T && zkey, "%s: null pointer (prev_inv, prev_age, rays, T and zkey are required)", what);
-    TempDims s;
+    FrameMap s;
     long long blocks = 0;
     if (temporal_dims(what, B, H, W, s, blocks)) return 1;
-    MVSGI_REQUIRE(wrap == 0 || wrap == 1, "%s: wrap = %d (0: the map's longitude ends at its edges, 1: it closes)", what, wrap);
-    MVSGI_REQUIRE(au - au == 0.0f && bu - bu == 0.0f && av - av == 0.0f && bv - bv == 0.0f,
-                  "%s: the affine map (au, bu, av, bv) = (%g, %g, %g, %g) must be finite", what, (double)au, (double)bu, (double)av, (double)bv);
+    if (check_pano_affine(what, au, bu, av, bv, wrap)) return 1;
     MVSGI_REQUIRE(aligned(prev_inv, 16) && aligned(prev_age, 16) && aligned(rays, 16) && aligned(T, 16) && aligned(zkey, 16),
                   "%s: prev_inv, prev_age, rays, T and zkey must be 16-byte aligned", what);
     const long long cells = B * H * (long long)W;
@@ -254,7 +203,7 @@ extern "C" int mvsgi_temporal_fuse_f32(const unsigned long long* zkey, const flo
     MVSGI_REQUIRE(zkey && prev_inv && prev_var && prev_age && cur_inv,
                   "%s: null pointer (zkey, prev_inv, prev_var, prev_age and cur_inv are required)", what);
     MVSGI_REQUIRE(fused || var || age || warped_inv || warped_var || src, "%s: null pointer (every output is NULL)", what);
-    TempDims s;
+    FrameMap s;
     long long blocks = 0;
     if (temporal_dims(what, B, H, W, s, blocks)) return 1;
     MVSGI_REQUIRE(gate2 > 0.0f && gate2 <= FLT_MAX, "%s: gate2 = %g (need 0 < gate^2 < inf)", what, (double)gate2);

@@ -1,8 +1,10 @@
 // Volumetric fusion: the predicted inverse distance integrated into a world-fixed, rolling truncated signed distance volume around the
 // rig, and that volume ray-cast back into the rig's view.  The definition is in include/mvsgi.h (section "volumetric fusion") and
-// DESIGN.md 24.  The row of a transform and the equirectangular projection are camera_models.hpp's functions, the affine map and the
-// floor-and-wrap are temporal.hip's step 4 as written, so a voxel centre lands in the cell a splatted point at the same place lands
-// in.  This file is compiled with contraction off.
+// DESIGN.md 24.  The row of a transform is camera_models.hpp's function, and the cell of the panorama (the equirectangular projection,
+// the affine map, floor and wrap, the test) is panorama_map.hpp's pano_cell, the function temporal.hip's splat calls in its step 4, so
+// a voxel centre lands in the cell a splatted point at the same place lands in.  The ray-cast's thread placement (frame_quad), the
+// pose's rows (load_pose_rows) and the host checks of the map are that header's too, the per-quad stores view_rig.hpp's.  This file
+// is compiled with contraction off.
 //
 //   1. tsdf_integrate_kernel    a thread owns two consecutive slots of a sequence's store (16 bytes: f, w, f, w), one where the
 //                               sequence's slot count is odd (8-byte accesses).  Slot -> world index (floored modulus around the
@@ -23,7 +25,7 @@
 namespace {
 
 #include "device_prims.hpp"
-#include "view_rig.hpp"
+#include "panorama_map.hpp"
 
 using mvsgi::aligned;
 typedef float f32x2 __attribute__((ext_vector_type(2)));
@@ -44,9 +46,8 @@ struct TsdfMeasure {
     const float* inv;
     const float* std;
     const unsigned char* mask;
-    int H, W;
-    float bf, au, bu, av, bv;
-    int wrap;
+    PanoMap map;
+    float bf;
 };
 struct TsdfParams {
     float vs, trunc, t2, w_max, r_min, r_max;
@@ -71,18 +72,9 @@ __device__ __forceinline__ float integrate_voxel(int e, const TsdfGrid& g, const
     if (!(r2 > 0.0f && r2 <= FLT_MAX)) return 0.0f;
     const float r = sqrtf(r2);
     if (!(r >= p.r_min && r <= p.r_max)) return r;
-    float gx, gy;                                                          // step 3
-    project_equirect(qx, qy, qz, pi_f, gx, gy);
-    const float u = gx * m.au + m.bu, v = gy * m.av + m.bv;
-    const float Wf = (float)m.W, Hf = (float)m.H;
-    float fx = floorf(u);
-    const float fy = floorf(v);
-    if (m.wrap) {
-        if (fx < 0.0f) fx += Wf;
-        else if (fx >= Wf) fx -= Wf;
-    }
-    if (!(fx >= 0.0f && fx < Wf && fy >= 0.0f && fy < Hf)) return r;      // a NaN compares false; inside, the conversions are exact
-    const long long cell = (long long)(int)fy * m.W + (int)fx;
+    int row, col;                                                          // step 3
+    if (!pano_cell(m.map, qx, qy, qz, pi_f, row, col)) return r;
+    const long long cell = (long long)row * m.map.W + col;
     const float mv = m.inv[cell];                                          // step 4
     if (m.mask && m.mask[cell] == 0) return r;
     const float d = m.bf / mv;
@@ -116,9 +108,8 @@ __global__ __launch_bounds__(256) void tsdf_integrate_kernel(float* __restrict__
     float tr[12];
 #pragma unroll
     for (int k = 0; k < 3; ++k) org[k] = origin[b * 3 + k], prev[k] = origin_prev[b * 3 + k];
-#pragma unroll
-    for (int k = 0; k < 12; ++k) tr[k] = T[b * 16 + k];
-    const long long HW = (long long)m.H * m.W;
+    load_pose_rows(T, b, tr);
+    const long long HW = (long long)m.map.H * m.map.W;
     m.inv += b * HW;
     if (m.std) m.std += b * HW;
     if (m.mask) m.mask += b * HW;
@@ -139,11 +130,6 @@ __global__ __launch_bounds__(256) void tsdf_integrate_kernel(float* __restrict__
     }
 }
 
-struct RayDims {
-    int H, W;
-    int Wq;                               // threads per map row: ceil(W / 4)
-    unsigned per_frame;                   // blocks per frame: ceil(H * Wq / 256)
-};
 struct RayMarch {
     float t0, step, inv_vs, w_min, bf;
     int K;
@@ -153,20 +139,17 @@ template <bool VEC>
 __global__ __launch_bounds__(256) void tsdf_raycast_kernel(const float* __restrict__ vol, const float* __restrict__ rays,
                                                            const float* __restrict__ P, const int* __restrict__ origin,
                                                            float* __restrict__ inv, float* __restrict__ weight, int* __restrict__ steps,
-                                                           TsdfGrid g, RayDims s, RayMarch mr) {
+                                                           TsdfGrid g, FrameMap s, RayMarch mr) {
 #pragma clang fp contract(off)
-    const unsigned blk = blockIdx.x % s.per_frame;
-    const long long idx = (long long)blk * 256 + threadIdx.x;
-    if (idx >= (long long)s.H * s.Wq) return;
-    const Quad t = quad_at<VEC>(idx, s.H, s.W, s.Wq);
-    const long long b = blockIdx.x / s.per_frame;
+    Quad t;
+    if (!frame_quad<VEC>(s, t)) return;
+    const long long b = t.b;
     const long long HW = (long long)s.H * s.W;
     const long long pix = t.pix(s.W);
     const long long at = b * HW + pix;
     float pr[12];                                                          // uniform over the block
     int org[3];
-#pragma unroll
-    for (int k = 0; k < 12; ++k) pr[k] = P[b * 16 + k];
+    load_pose_rows(P, b, pr);
 #pragma unroll
     for (int k = 0; k < 3; ++k) org[k] = origin[b * 3 + k];
     const float lo[3] = {(float)org[0], (float)org[1], (float)org[2]};
@@ -227,26 +210,9 @@ __global__ __launch_bounds__(256) void tsdf_raycast_kernel(const float* __restri
             pf[k] = f, pv[k] = valid;
         }
     }
-    auto store4 = [&](float* p, const float (&r)[4]) {
-        if (!p) return;
-        if (VEC) {
-            *reinterpret_cast<f32x4*>(p + at) = f32x4{r[0], r[1], r[2], r[3]};
-        } else {
-#pragma unroll
-            for (int k = 0; k < 4; ++k)
-                if (k < t.n) p[at + k] = r[k];
-        }
-    };
-    store4(inv, oi), store4(weight, ow);
-    if (steps) {
-        if (VEC) {
-            *reinterpret_cast<u32x4*>(steps + at) = u32x4{(unsigned)os[0], (unsigned)os[1], (unsigned)os[2], (unsigned)os[3]};
-        } else {
-#pragma unroll
-            for (int k = 0; k < 4; ++k)
-                if (k < t.n) steps[at + k] = os[k];
-        }
-    }
+    store_f32_quad<VEC>(inv, at, t.n, oi);
+    store_f32_quad<VEC>(weight, at, t.n, ow);
+    store_u32_quad<VEC>(steps, at, t.n, os);
 }
 
 // the volume's checks both entry points share; 0 on success
@@ -260,9 +226,7 @@ int tsdf_grid(const char* what, long long B, int Nx, int Ny, int Nz, TsdfGrid& g
 
 int tsdf_map(const char* what, int H, int W) {
     MVSGI_REQUIRE(H >= 1 && W >= 1, "%s: non-positive dimension (H = %d, W = %d)", what, H, W);
-    MVSGI_REQUIRE(H <= (1 << 24) && W <= (1 << 24), "%s: map %d x %d: a side above 2^24 is no exact float", what, H, W);
-    MVSGI_REQUIRE((long long)H * W < (1ll << 31), "%s: map %d x %d: H * W must be below 2^31", what, H, W);
-    return 0;
+    return check_pano_sides(what, H, W, 31, "");
 }
 
 }  // namespace
@@ -281,9 +245,7 @@ extern "C" int mvsgi_tsdf_integrate_f32(float* vol, const float* inv, const floa
     MVSGI_REQUIRE(w_max > 0.0f && w_max <= FLT_MAX, "%s: w_max = %g (need 0 < w_max < inf)", what, (double)w_max);
     MVSGI_REQUIRE(r_min >= 0.0f && r_min < r_max && r_max <= FLT_MAX, "%s: r_min = %g, r_max = %g (need 0 <= r_min < r_max <= FLT_MAX)", what,
                   (double)r_min, (double)r_max);
-    MVSGI_REQUIRE(wrap == 0 || wrap == 1, "%s: wrap = %d (0: the map's longitude ends at its edges, 1: it closes)", what, wrap);
-    MVSGI_REQUIRE(au - au == 0.0f && bu - bu == 0.0f && av - av == 0.0f && bv - bv == 0.0f,
-                  "%s: the affine map (au, bu, av, bv) = (%g, %g, %g, %g) must be finite", what, (double)au, (double)bu, (double)av, (double)bv);
+    if (check_pano_affine(what, au, bu, av, bv, wrap)) return 1;
     MVSGI_REQUIRE(aligned(vol, 16) && aligned(inv, 16) && aligned(std, 16) && aligned(mask, 16) && aligned(T, 16) && aligned(origin, 16) &&
                       aligned(origin_prev, 16) && aligned(range, 16),
                   "%s: vol, inv, std, mask, T, origin, origin_prev and range must be 16-byte aligned", what);
@@ -291,7 +253,7 @@ extern "C" int mvsgi_tsdf_integrate_f32(float* vol, const float* inv, const floa
     const long long per_seq = mvsgi::cdiv(vec ? (long long)g.n / 2 : (long long)g.n, 256);
     MVSGI_REQUIRE(B <= ((1ll << 31) - 1) / per_seq, "%s: B * Nx * Ny * Nz too large for one launch (%lld sequences of %lld blocks)", what, B, per_seq);
     g.per_seq = (unsigned)per_seq;
-    const TsdfMeasure m{inv, std, mask, H, W, bf, au, bu, av, bv, wrap};
+    const TsdfMeasure m{inv, std, mask, PanoMap{H, W, au, bu, av, bv, wrap}, bf};
     const TsdfParams p{vs, trunc, t2, w_max, r_min, r_max};
     hipStream_t st = mvsgi::as_stream(stream);
     if (vec)
@@ -318,15 +280,14 @@ extern "C" int mvsgi_tsdf_raycast_f32(const float* vol, const float* rays, const
     MVSGI_REQUIRE(aligned(vol, 16) && aligned(rays, 16) && aligned(P, 16) && aligned(origin, 16) && aligned(inv, 16) && aligned(weight, 16) &&
                       aligned(steps, 16),
                   "%s: vol, rays, P, origin and the outputs must be 16-byte aligned", what);
-    const int Wq = (W + 3) / 4;
-    const long long per_frame = mvsgi::cdiv((long long)H * Wq, 256);
-    MVSGI_REQUIRE(B <= ((1ll << 31) - 1) / per_frame, "%s: B * H * W too large for one launch (%lld frames of %lld blocks)", what, B, per_frame);
-    const RayDims s{H, W, Wq, (unsigned)per_frame};
+    FrameMap s;
+    long long blocks = 0;
+    if (check_frame_launch(what, B, H, W, s, blocks)) return 1;
     const RayMarch mr{t0, step, inv_vs, w_min, bf, K};
     hipStream_t st = mvsgi::as_stream(stream);
     if (W % 4 == 0)
-        hipLaunchKernelGGL(tsdf_raycast_kernel<true>, dim3((unsigned)(B * per_frame)), dim3(256), 0, st, vol, rays, P, origin, inv, weight, steps, g, s, mr);
+        hipLaunchKernelGGL(tsdf_raycast_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, st, vol, rays, P, origin, inv, weight, steps, g, s, mr);
     else
-        hipLaunchKernelGGL(tsdf_raycast_kernel<false>, dim3((unsigned)(B * per_frame)), dim3(256), 0, st, vol, rays, P, origin, inv, weight, steps, g, s, mr);
+        hipLaunchKernelGGL(tsdf_raycast_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, st, vol, rays, P, origin, inv, weight, steps, g, s, mr);
     return mvsgi::check_launch(what);
 }

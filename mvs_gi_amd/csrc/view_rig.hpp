@@ -1,7 +1,7 @@
 // What every kernel that looks at the prediction through the rig shares, once: the rig as a kernel argument and the host loop that
 // fills it from the camera table, the thread that owns four consecutive pixels of a row (its place, its 16-byte loads of inv and the
-// ray planes with their element-wise tail, its back-projected points), one point's way into one camera, and the four bytes a thread
-// reads or writes as one word.  The fused back-projection (reproject.hip), photometric consistency (photo.hip / photo_reduce.inc) and
+// ray planes with their element-wise tail, its back-projected points), one point's way into one camera, the four bytes a thread
+// reads or writes as one word, and the four floats or integers it stores as sixteen bytes.  The fused back-projection (reproject.hip), photometric consistency (photo.hip / photo_reduce.inc) and
 // the camera range images and visibility (visibility.hip) call these, so q, the grid and valid_n of the latter two are the bits of
 // mvsgi_reproject_f32 by construction, not by three texts that agree.  One exception: photo_reduce.inc keeps the text of quad_points
 // and of its n_views store inline (as calls its row-tail instances became other, slower code).  fp32 with contraction
@@ -144,5 +144,30 @@ __device__ __forceinline__ void store_byte_quad(unsigned char* __restrict__ p, i
 #pragma unroll
         for (int k = 0; k < 4; ++k)
             if (k < n) p[k] = (unsigned char)(w >> (8 * k));
+    }
+}
+
+// four floats, or four 32-bit integers, of a row at p + at (p == nullptr: an output nobody wants, nothing is stored): a 16-byte
+// store, or the first n elements one by one
+template <bool VEC>
+__device__ __forceinline__ void store_f32_quad(float* p, long long at, int n, const float (&r)[4]) {
+    if (!p) return;
+    if (VEC) {
+        *reinterpret_cast<f32x4*>(p + at) = f32x4{r[0], r[1], r[2], r[3]};
+    } else {
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+            if (k < n) p[at + k] = r[k];
+    }
+}
+template <bool VEC>
+__device__ __forceinline__ void store_u32_quad(int* p, long long at, int n, const int (&r)[4]) {
+    if (!p) return;
+    if (VEC) {
+        *reinterpret_cast<u32x4*>(p + at) = u32x4{(unsigned)r[0], (unsigned)r[1], (unsigned)r[2], (unsigned)r[3]};
+    } else {
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+            if (k < n) p[at + k] = r[k];
     }
 }

@@ -69,6 +69,35 @@ def camera_table(grid_makers) -> torch.Tensor:
     return torch.tensor(rows, dtype=torch.float64).to(torch.float32).contiguous()
 
 
+def pose_arg(T, B=None, name: str = "T") -> torch.Tensor:
+    """A pose argument of the stages that read it from device memory: [B, 4, 4] fp32, or [4, 4] for every one of B (default 1)
+    sequences; name: the argument's letter in the messages"""
+    T = torch.as_tensor(T)
+    if T.dim() == 2 and tuple(T.shape) == (4, 4):
+        T = T.unsqueeze(0).expand(1 if B is None else int(B), 4, 4)
+    if T.dim() != 3 or tuple(T.shape[1:]) != (4, 4) or (B is not None and T.shape[0] != B):
+        raise AssertionError(f"{name} must be [{'B' if B is None else B}, 4, 4] (or [4, 4]), got {list(T.shape)}")
+    if T.dtype != torch.float32:
+        raise TypeError(f"{name}: expected torch.float32, got {T.dtype}")
+    return T
+
+
+def panorama_cell(g: torch.Tensor, affine, hw) -> tuple:
+    """The cell of the rig panorama (H, W) = hw an equirectangular grid coordinate g [..., 2] lands in (include/mvsgi.h, "temporal
+    fusion", step A4; csrc/panorama_map.hpp), one operation per line: the affine map of hip_ops.temporal_affine(), floor, the column
+    wrapped once where the longitude closes, the test.  -> fx, fy (whole floats; column, row), inside"""
+    Ho, Wo = hw
+    au, bu, av, bv = (torch.full((), c, device=g.device, dtype=torch.float32) for c in affine[:4])   # each rounded to fp32 once
+    u = g[..., 0] * au + bu
+    v = g[..., 1] * av + bv
+    fx = torch.floor(u)
+    fy = torch.floor(v)
+    if affine[4]:
+        fx = torch.where(fx < 0, fx + float(Wo), torch.where(fx >= float(Wo), fx - float(Wo), fx))
+    inside = (fx >= 0) & (fx < float(Wo)) & (fy >= 0) & (fy < float(Ho))
+    return fx, fy, inside
+
+
 class Reprojector:
     """reprojector(inv, imgs, invalid_pixel_value=0.0) -> (xyz [B, 3, H, W], warped [B, N, C, H, W], valid [B, N, H, W] bool);
     reprojector.point_cloud(inv) -> xyz.

@@ -26,6 +26,7 @@ import numpy as np
 import torch
 
 from .. import hip_ops as H
+from .reproject import panorama_cell, pose_arg
 
 _FLT_MAX = float(torch.finfo(torch.float32).max)
 _LOW32 = 0xFFFFFFFF
@@ -68,7 +69,7 @@ class TemporalFusion:
             if not 0.0 < meas_std < float("inf"):
                 raise ValueError(f"TemporalFusion: meas_std: 0 < meas_std < inf, got {meas_std!r}")
         self.meas_std = meas_std
-        H._temporal_map(1, *self.out_shape)
+        H._pano_map("temporal fusion", 32, 1, *self.out_shape)
         self._bufs = {}          # (B, H, W, device) -> dict: made at first use, NEVER replaced (a captured graph holds them)
 
     # ---- what the evaluator owns ----
@@ -102,24 +103,11 @@ class TemporalFusion:
         """Stage the pose of the previous rig frame in the current one for the next step(T=None) -- the step a captured graph replays.
         T: [B, 4, 4], or [4, 4] for every sequence (then B, default 1, names the buffers), on the host or the device; written into the
         evaluator's own device tensor with copy_."""
-        T = self._pose(T, B)
+        T = pose_arg(T, B)
         self.buffers(T.shape[0])["T"].copy_(T, non_blocking=True)
 
-    def _pose(self, T, B=None) -> torch.Tensor:
-        T = torch.as_tensor(T)
-        if T.dim() == 2 and tuple(T.shape) == (4, 4):
-            T = T.unsqueeze(0).expand(1 if B is None else int(B), 4, 4)
-        if T.dim() != 3 or tuple(T.shape[1:]) != (4, 4) or (B is not None and T.shape[0] != B):
-            raise AssertionError(f"T must be [{'B' if B is None else B}, 4, 4] (or [4, 4]), got {list(T.shape)}")
-        if T.dtype != torch.float32:
-            raise TypeError(f"T: expected torch.float32, got {T.dtype}")
-        return T
-
     def _want(self, want) -> tuple:
-        want = tuple(want)
-        if not want or set(want) - set(self.OUTPUTS) or len(set(want)) != len(want):
-            raise ValueError(f"want: a non-empty selection of {', '.join(repr(k) for k in self.OUTPUTS)}, got {want}")
-        return want
+        return H._wanted(want, self.OUTPUTS)
 
     def _measurement(self, inv, std):
         rp = self.reprojector
@@ -144,7 +132,7 @@ class TemporalFusion:
         B = int(inv.shape[0])
         bufs = self.buffers(B, inv.device)
         if T is not None:
-            bufs["T"].copy_(self._pose(T, B), non_blocking=True)
+            bufs["T"].copy_(pose_arg(T, B), non_blocking=True)
         rp = self.reprojector
         H.temporal_splat(bufs["inv"], bufs["age"], rp.rays, bufs["T"], rp.bf, self.affine, out=bufs["zkey"])
         sel = tuple(k for k in H.TEMPORAL_OUTPUTS if k in want or k in self.STATE)
@@ -159,7 +147,7 @@ class TemporalFusion:
     # ---- the definition, executed ----
     def splat_chain(self, state_inv, state_age, T) -> torch.Tensor:
         """Stage A of the definition, executed: Reprojector.reproject()'s xyz of the state, the transform kernel with T, the
-        equirectangular grid kernel, then torch, one operation per line: the squared range, the affine map, floor and wrap, the keys
+        equirectangular grid kernel, then torch, one operation per line: the squared range, panorama_cell(), the keys
         and scatter_reduce(amin) into a buffer of EMPTY (a pixel that is not splatted contributes EMPTY, which changes nothing; on a
         build whose scatter_reduce refuses int64 the minimum is numpy's minimum.at on the host).  -> zkey [B, H, W] int64, the bits
         temporal_splat() returns."""
@@ -168,8 +156,7 @@ class TemporalFusion:
         v = H._dev(rp._inv(state_inv), "state_inv")
         dev = v.device
         B, (Ho, Wo) = int(v.shape[0]), self.out_shape
-        T = self._pose(T, B).to(dev).contiguous()
-        au, bu, av, bv = (torch.full((), c, device=dev, dtype=torch.float32) for c in self.affine[:4])   # each rounded to fp32 once
+        T = pose_arg(T, B).to(dev).contiguous()
         xyz = rp.reproject(v, want=("xyz",))["xyz"]
         q = transform_3D_points_torch(T, xyz.unsqueeze(2))
         g = EquirectangularSampleGridMaker().make_grid(q)[:, 0]
@@ -178,13 +165,7 @@ class TemporalFusion:
         live = (state_age != 0) & (v > 0) & (v <= _FLT_MAX) & (d <= _FLT_MAX)
         r2 = (qx * qx + qy * qy) + qz * qz
         near = (r2 > 0) & (r2 <= _FLT_MAX)
-        u = g[..., 0] * au + bu
-        w = g[..., 1] * av + bv
-        fx = torch.floor(u)
-        fy = torch.floor(w)
-        if self.affine[4]:
-            fx = torch.where(fx < 0, fx + float(Wo), torch.where(fx >= float(Wo), fx - float(Wo), fx))
-        inside = (fx >= 0) & (fx < float(Wo)) & (fy >= 0) & (fy < float(Ho))
+        fx, fy, inside = panorama_cell(g, self.affine, self.out_shape)
         splat = live & near & inside
         zero = torch.zeros_like(fx)
         cell = torch.where(splat, fy, zero).to(torch.int64) * Wo + torch.where(splat, fx, zero).to(torch.int64)

@@ -25,6 +25,7 @@ import math
 import torch
 
 from .. import hip_ops as H
+from .reproject import panorama_cell, pose_arg
 
 _FLT_MAX = H.TSDF_FLT_MAX
 
@@ -65,7 +66,7 @@ class TsdfVolume:
         except (TypeError, ValueError):
             raise ValueError(f"TsdfVolume: dims = (Nx, Ny, Nz), whole numbers, got {dims!r}") from None
         H.tsdf_dims(1, *self.dims)
-        H._tsdf_map(1, *self.out_shape)
+        H._pano_map("volumetric fusion", 31, 1, *self.out_shape)
         self.voxel = H._tsdf_scalar(voxel, "voxel")
         self.trunc = H._tsdf_scalar(4.0 * self.voxel if trunc is None else trunc, "trunc")
         H._tsdf_scalar(self.trunc * self.trunc, "trunc^2")
@@ -141,7 +142,7 @@ class TsdfVolume:
         """Stage the rig's pose in the world for the next integrate(P=None) / raycast(P=None) -- the calls a captured graph replays.
         P: [B, 4, 4], or [4, 4] for every sequence (then B, default 1, names the buffers), on the host or the device.  Writes P, its
         rigid inverse T (R^T, -R^T t) and origin = floor(t / voxel) - N // 2 with torch operations on the device only."""
-        P = self._pose(P, B)
+        P = pose_arg(P, B, "P")
         bufs = self.buffers(P.shape[0])
         Pd = bufs["P"]
         Pd.copy_(P, non_blocking=True)
@@ -151,27 +152,17 @@ class TsdfVolume:
         bufs["T"][:, :3, 3] = -(Rt * t.unsqueeze(1)).sum(-1)
         bufs["origin"].copy_(self.origin_of(t, self.voxel, bufs["half"]))
 
-    def _pose(self, P, B=None) -> torch.Tensor:
-        P = torch.as_tensor(P)
-        if P.dim() == 2 and tuple(P.shape) == (4, 4):
-            P = P.unsqueeze(0).expand(1 if B is None else int(B), 4, 4)
-        if P.dim() != 3 or tuple(P.shape[1:]) != (4, 4) or (B is not None and P.shape[0] != B):
-            raise AssertionError(f"P must be [{'B' if B is None else B}, 4, 4] (or [4, 4]), got {list(P.shape)}")
-        if P.dtype != torch.float32:
-            raise TypeError(f"P: expected torch.float32, got {P.dtype}")
-        return P
-
     def _want(self, want) -> tuple:
         return H._wanted(want, self.OUTPUTS)
 
     def _measurement(self, inv, std, mask):
         rp = self.reprojector
-        inv = H._tsdf_plane(rp._inv(inv), "inv", None, None)
+        inv = H._pano_plane(rp._inv(inv), "inv", None, None)
         shape = tuple(int(v) for v in inv.shape)
         if std is not None:
-            std = H._tsdf_plane(std, "std", shape, inv.device)
+            std = H._pano_plane(std, "std", shape, inv.device)
         if mask is not None:
-            mask = H._tsdf_plane(mask, "mask", shape, inv.device, torch.uint8)
+            mask = H._pano_plane(mask, "mask", shape, inv.device, torch.uint8)
         return inv, std, mask
 
     # ---- the stage ----
@@ -184,7 +175,7 @@ class TsdfVolume:
         B = int(inv.shape[0])
         bufs = self.buffers(B, inv.device)
         if P is not None:
-            self.set_pose(self._pose(P, B))
+            self.set_pose(pose_arg(P, B, "P"))
         H.tsdf_integrate(bufs["vol"], inv, bufs["T"], bufs["origin"], bufs["origin_prev"], self.reprojector.bf, self.affine, self.voxel,
                          self.trunc, self.w_max, self.r_range, std=std, mask=mask, r_out=r_out)
         bufs["origin_prev"].copy_(bufs["origin"])
@@ -196,7 +187,7 @@ class TsdfVolume:
         volume's own tensors, valid until the next raycast at this batch size."""
         want = self._want(want)
         if P is not None:
-            P = self._pose(P, None if torch.as_tensor(P).dim() == 3 else B)
+            P = pose_arg(P, None if torch.as_tensor(P).dim() == 3 else B, "P")
             B = int(P.shape[0])
             self.set_pose(P)
         bufs = self.buffers(B)
@@ -214,11 +205,10 @@ class TsdfVolume:
         dev = inv.device
         B, (Ho, Wo), (Nx, Ny, Nz) = int(inv.shape[0]), self.out_shape, self.dims
         bufs = self.buffers(B, dev)
-        T = bufs["T"] if T is None else self._pose(T, B).to(dev).contiguous()
+        T = bufs["T"] if T is None else pose_arg(T, B, "P").to(dev).contiguous()
         origin = (bufs["origin"] if origin is None else origin).to(dev)
         origin_prev = (bufs["origin_prev"] if origin_prev is None else origin_prev).to(dev)
         c32 = lambda c: torch.full((), c, device=dev, dtype=torch.float32)              # each rounded to fp32 once
-        au, bu, av, bv = (c32(c) for c in self.affine[:4])
         vs, trunc, t2, w_max, bf = c32(self.voxel), c32(self.trunc), c32(self.trunc * self.trunc), c32(self.w_max), c32(self.reprojector.bf)
         r_min, r_max = c32(self.r_range[0]), c32(self.r_range[1])
         full = (B, Nz, Ny, Nx)
@@ -244,13 +234,8 @@ class TsdfVolume:
         ok = (r2 > 0) & (r2 <= _FLT_MAX)
         rr = torch.sqrt(r2) if r is None else r
         ok = ok & (rr >= r_min) & (rr <= r_max)
-        u = g[..., 0] * au + bu                                                         # step 3
-        v = g[..., 1] * av + bv
-        fx = torch.floor(u)
-        fy = torch.floor(v)
-        if self.affine[4]:
-            fx = torch.where(fx < 0, fx + float(Wo), torch.where(fx >= float(Wo), fx - float(Wo), fx))
-        ok = ok & (fx >= 0) & (fx < float(Wo)) & (fy >= 0) & (fy < float(Ho))
+        fx, fy, inside = panorama_cell(g, self.affine, self.out_shape)                  # step 3
+        ok = ok & inside
         zero = torch.zeros_like(fx)
         cell = (torch.where(ok, fy, zero).to(torch.int64) * Wo + torch.where(ok, fx, zero).to(torch.int64)).view(B, -1)
         m = torch.gather(inv.reshape(B, -1), 1, cell).view(full)                        # step 4
@@ -281,7 +266,7 @@ class TsdfVolume:
         dev = vol.device
         B, (Ho, Wo), (Nx, Ny, Nz) = int(vol.shape[0]), self.out_shape, self.dims
         bufs = self.buffers(B, dev)
-        P = bufs["P"] if P is None else self._pose(P, B).to(dev).contiguous()
+        P = bufs["P"] if P is None else pose_arg(P, B, "P").to(dev).contiguous()
         origin = (bufs["origin_prev"] if origin is None else origin).to(dev)
         c32 = lambda c: torch.full((), c, device=dev, dtype=torch.float32)
         t0, step, inv_vs, w_min, bf = c32(self.t0), c32(self.step), c32(1.0 / self.voxel), c32(self.w_min), c32(self.reprojector.bf)

@@ -1623,11 +1623,35 @@ def temporal_gate2(gate: float) -> float:
     return gate * gate
 
 
-def _temporal_map(B: int, Hh: int, W: int) -> None:
-    if Hh > 1 << 24 or W > 1 << 24 or Hh * W >= 1 << 32:
-        raise ValueError(f"temporal fusion: map {Hh} x {W}: H, W <= 2^24 and H * W < 2^32 (a key holds the source index in 32 bits)")
-    if B * -(-(Hh * -(-W // 4)) // 256) >= 1 << 31:
-        raise ValueError(f"temporal fusion: B * H * W = {B} * {Hh} * {W} is too large for one launch")
+def _pano_map(stage: str, index_bits: int, B: int, Hh: int, W: int) -> None:
+    """What one launch of a stage over the rig panorama addresses: sides that are exact floats, a cell index of index_bits bits, and
+    B frames of ceil(H * ceil(W / 4) / 256) blocks"""
+    if Hh > 1 << 24 or W > 1 << 24 or Hh * W >= 1 << index_bits or B * -(-(Hh * -(-W // 4)) // 256) >= 1 << 31:
+        raise ValueError(f"{stage}: map {B} x {Hh} x {W}: H, W <= 2^24, H * W < 2^{index_bits} and one launch's blocks")
+
+
+def _affine_args(affine) -> tuple:
+    """affine = temporal_affine(...) as the calls pass it -> (au, bu, av, bv, wrap01)"""
+    try:
+        au, bu, av, bv, wrap = affine
+        au, bu, av, bv = (float(v) for v in (au, bu, av, bv))
+    except (TypeError, ValueError):
+        raise ValueError(f"affine: (au, bu, av, bv, wrap) of temporal_affine(), got {affine!r}") from None
+    if not all(math.isfinite(v) for v in (au, bu, av, bv)):
+        raise ValueError(f"affine: (au, bu, av, bv) must be finite, got {(au, bu, av, bv)}")
+    return au, bu, av, bv, 1 if wrap else 0
+
+
+def _pano_plane(t, name: str, shape, dev, dtype=torch.float32):
+    """A map [B, H, W] (or [B, 1, H, W]) of the rig panorama: an activation, copied when its form is awkward; bool as uint8"""
+    if dtype == torch.uint8 and isinstance(t, torch.Tensor) and t.dtype == torch.bool:
+        t = t.view(torch.uint8)
+    t = _dev(t, name, dtype)
+    if t.dim() == 4 and t.shape[1] == 1:
+        t = t.squeeze(1)
+    if (shape is not None and tuple(t.shape) != shape) or t.dim() != 3 or not t.numel() or (dev is not None and t.device != dev):
+        raise AssertionError(f"{name} must be {list(shape) if shape else '[B, H, W]'} on {dev}, got {list(t.shape)} on {t.device}")
+    return t
 
 
 def _temporal_state(prev_inv, prev_age, prev_var=None):
@@ -1636,7 +1660,7 @@ def _temporal_state(prev_inv, prev_age, prev_var=None):
     if prev_inv.dim() != 3 or not prev_inv.numel():
         raise AssertionError(f"prev_inv must be a non-empty [B, H, W], got {list(prev_inv.shape)}")
     shape, dev = tuple(int(v) for v in prev_inv.shape), prev_inv.device
-    _temporal_map(*shape)
+    _pano_map("temporal fusion", 32, *shape)
     _arg(prev_age, "prev_age", dev, torch.uint8, shape=shape)
     if prev_var is not None:
         _arg(prev_var, "prev_var", dev, shape=shape)
@@ -1657,19 +1681,13 @@ def temporal_splat(prev_inv, prev_age, rays, T, bf: float, affine, out=None) -> 
     if tuple(rays.shape) != (3, Ho, Wo) or rays.device != dev:
         raise AssertionError(f"rays must be [3, {Ho}, {Wo}] on {dev}, got {list(rays.shape)} on {rays.device}")
     _arg(T, "T", dev, shape=(B, 4, 4))
-    try:
-        au, bu, av, bv, wrap = affine
-        au, bu, av, bv = (float(v) for v in (au, bu, av, bv))
-    except (TypeError, ValueError):
-        raise ValueError(f"affine: (au, bu, av, bv, wrap) of temporal_affine(), got {affine!r}") from None
-    if not all(math.isfinite(v) for v in (au, bu, av, bv)):
-        raise ValueError(f"affine: (au, bu, av, bv) must be finite, got {(au, bu, av, bv)}")
+    affine = _affine_args(affine)
     if out is None:
         out = torch.empty((B, Ho, Wo), device=dev, dtype=torch.int64)
     else:
         _arg(out, "out", dev, torch.int64, shape=(B, Ho, Wo))
     _call("mvsgi_temporal_splat_f32", prev_inv.data_ptr(), prev_age.data_ptr(), rays.data_ptr(), T.data_ptr(), out.data_ptr(), B, Ho, Wo,
-          float(bf), au, bu, av, bv, 1 if wrap else 0, _stream_ptr(prev_inv))
+          float(bf), *affine, _stream_ptr(prev_inv))
     return out
 
 
@@ -1686,19 +1704,11 @@ def temporal_fuse(zkey, prev_inv, prev_var, prev_age, cur_inv, bf: float, gate: 
     B, Ho, Wo, dev = _temporal_state(prev_inv, prev_age, prev_var)
     shape = (B, Ho, Wo)
     _arg(zkey, "zkey", dev, torch.int64, shape=shape)
-    cur_inv = _dev(cur_inv, "cur_inv")
-    if cur_inv.dim() == 4 and cur_inv.shape[1] == 1:
-        cur_inv = cur_inv.squeeze(1)
-    if tuple(cur_inv.shape) != shape or cur_inv.device != dev:
-        raise AssertionError(f"cur_inv must be {list(shape)} on {dev}, got {list(cur_inv.shape)} on {cur_inv.device}")
+    cur_inv = _pano_plane(cur_inv, "cur_inv", shape, dev)
     if cur_std is not None:
         if meas_std is not None:
             raise ValueError("temporal_fuse: cur_std or meas_std, not both")
-        cur_std = _dev(cur_std, "cur_std")
-        if cur_std.dim() == 4 and cur_std.shape[1] == 1:
-            cur_std = cur_std.squeeze(1)
-        if tuple(cur_std.shape) != shape or cur_std.device != dev:
-            raise AssertionError(f"cur_std must be {list(shape)} on {dev}, got {list(cur_std.shape)} on {cur_std.device}")
+        cur_std = _pano_plane(cur_std, "cur_std", shape, dev)
         sd = 0.0
     else:
         if meas_std is None:
@@ -1748,28 +1758,11 @@ def tsdf_dims(B: int, Nx: int, Ny: int, Nz: int) -> None:
         raise ValueError(f"volumetric fusion: {B} volumes of {Nx} x {Ny} x {Nz} voxels are too large for one launch")
 
 
-def _tsdf_map(B: int, Hh: int, W: int) -> None:
-    if Hh > 1 << 24 or W > 1 << 24 or Hh * W >= 1 << 31 or B * -(-(Hh * -(-W // 4)) // 256) >= 1 << 31:
-        raise ValueError(f"volumetric fusion: map {B} x {Hh} x {W}: H, W <= 2^24, H * W < 2^31 and one launch's blocks")
-
-
 def _tsdf_scalar(v, name: str, low_ok: bool = False) -> float:
     v = float(v)
     if not (0.0 <= v if low_ok else 0.0 < v) or not v <= TSDF_FLT_MAX:
         raise ValueError(f"{name}: {'0 <=' if low_ok else '0 <'} {name} <= FLT_MAX, got {v}")
     return v
-
-
-def _tsdf_plane(t, name: str, shape, dev, dtype=torch.float32):
-    """A measurement plane [B, H, W] (or [B, 1, H, W]): an activation, copied when its form is awkward"""
-    if dtype == torch.uint8 and isinstance(t, torch.Tensor) and t.dtype == torch.bool:
-        t = t.view(torch.uint8)
-    t = _dev(t, name, dtype)
-    if t.dim() == 4 and t.shape[1] == 1:
-        t = t.squeeze(1)
-    if (shape is not None and tuple(t.shape) != shape) or t.dim() != 3 or not t.numel() or (dev is not None and t.device != dev):
-        raise AssertionError(f"{name} must be {list(shape) if shape else '[B, H, W]'} on {dev}, got {list(t.shape)} on {t.device}")
-    return t
 
 
 def tsdf_integrate(vol, inv, T, origin, origin_prev, bf: float, affine, voxel: float, trunc: float, w_max: float = 64.0,
@@ -1783,27 +1776,21 @@ def tsdf_integrate(vol, inv, T, origin, origin_prev, bf: float, affine, voxel: f
     [B, H, W] uint8 / bool or None (0: the pixel is not integrated); r_out [B, Nz, Ny, Nx] fp32 or None: every voxel centre's range.
     One launch on inv's stream; nothing is allocated: capturable.  There is no CPU fallback.  -> vol"""
     B, Nx, Ny, Nz, dev = _tsdf_volume(vol)
-    inv = _tsdf_plane(inv, "inv", None, dev)
+    inv = _pano_plane(inv, "inv", None, dev)
     if inv.shape[0] != B:
         raise AssertionError(f"inv must be [{B}, H, W], got {list(inv.shape)}")
     shape = tuple(int(v) for v in inv.shape)
-    _tsdf_map(*shape)
+    _pano_map("volumetric fusion", 31, *shape)
     if std is not None:
-        std = _tsdf_plane(std, "std", shape, dev)
+        std = _pano_plane(std, "std", shape, dev)
     if mask is not None:
-        mask = _tsdf_plane(mask, "mask", shape, dev, torch.uint8)
+        mask = _pano_plane(mask, "mask", shape, dev, torch.uint8)
     _arg(T, "T", dev, shape=(B, 4, 4))
     _arg(origin, "origin", dev, torch.int32, shape=(B, 3))
     _arg(origin_prev, "origin_prev", dev, torch.int32, shape=(B, 3))
     if r_out is not None:
         _arg(r_out, "r_out", dev, shape=(B, Nz, Ny, Nx))
-    try:
-        au, bu, av, bv, wrap = affine
-        au, bu, av, bv = (float(v) for v in (au, bu, av, bv))
-    except (TypeError, ValueError):
-        raise ValueError(f"affine: (au, bu, av, bv, wrap) of temporal_affine(), got {affine!r}") from None
-    if not all(math.isfinite(v) for v in (au, bu, av, bv)):
-        raise ValueError(f"affine: (au, bu, av, bv) must be finite, got {(au, bu, av, bv)}")
+    affine = _affine_args(affine)
     voxel, trunc, w_max = _tsdf_scalar(voxel, "voxel"), _tsdf_scalar(trunc, "trunc"), _tsdf_scalar(w_max, "w_max")
     t2 = _tsdf_scalar(trunc * trunc, "trunc^2")
     try:
@@ -1814,8 +1801,8 @@ def tsdf_integrate(vol, inv, T, origin, origin_prev, bf: float, affine, voxel: f
     if not 0.0 <= r_min < r_max:
         raise ValueError(f"r_range: 0 <= r_min < r_max, got {(r_min, r_max)}")
     _call("mvsgi_tsdf_integrate_f32", vol.data_ptr(), inv.data_ptr(), _ptr(std), _ptr(mask), T.data_ptr(), origin.data_ptr(),
-          origin_prev.data_ptr(), _ptr(r_out), B, Nx, Ny, Nz, shape[1], shape[2], voxel, trunc, t2, w_max, r_min, r_max, float(bf), au, bu,
-          av, bv, 1 if wrap else 0, _stream_ptr(inv))
+          origin_prev.data_ptr(), _ptr(r_out), B, Nx, Ny, Nz, shape[1], shape[2], voxel, trunc, t2, w_max, r_min, r_max, float(bf), *affine,
+          _stream_ptr(inv))
     return vol
 
 
@@ -1833,7 +1820,7 @@ def tsdf_raycast(vol, rays, P, origin, bf: float, voxel: float, t0: float, step:
     if rays.dim() != 3 or rays.shape[0] != 3 or not rays.numel() or rays.device != dev:
         raise AssertionError(f"rays must be [3, H, W] on {dev}, got {list(rays.shape)} on {rays.device}")
     Ho, Wo = int(rays.shape[1]), int(rays.shape[2])
-    _tsdf_map(B, Ho, Wo)
+    _pano_map("volumetric fusion", 31, B, Ho, Wo)
     _arg(P, "P", dev, shape=(B, 4, 4))
     _arg(origin, "origin", dev, torch.int32, shape=(B, 3))
     voxel, step, t0 = _tsdf_scalar(voxel, "voxel"), _tsdf_scalar(step, "step"), _tsdf_scalar(t0, "t0", low_ok=True)

@@ -6,9 +6,8 @@ array below is float32 and numpy does not contract; the fused multiply-adds of t
     1. v = prev_inv, d = bf / v, p = rays * d
     2. live = prev_age != 0 and 0 < v <= FLT_MAX and d <= FLT_MAX
     3. q = T_b p (per row fma(t2, z, fma(t1, y, t0 * x)) + t3); r2 = (qx qx + qy qy) + qz qz; rejected unless 0 < r2 <= FLT_MAX
-    4. xz = sqrt(qx qx + qz qz), lon = -1 * atan2(qz, qx), lat = atan2(qy, xz), gx = lon / pi, gy = (2 * lat) / pi;
-       u = gx * au + bu, w = gy * av + bv; cx = floor(u), cy = floor(w); wrap: cx += W when cx < 0, cx -= W when cx >= W;
-       rejected unless 0 <= cx < W and 0 <= cy < H
+    4. the panorama cell (cx, cy) of q (panorama_cases.cell: the projection, the affine map, floor, the column wrapped once); rejected
+       unless 0 <= cx < W and 0 <= cy < H
     5. zkey[b, cy, cx] = min(zkey, (bits(r2) << 32) | s), from EMPTY = 0x7F800000FFFFFFFF            (np.minimum.at on uint64)
   B, target pixel t:
     1. r2 = float(bits(key >> 32)), s = min(key & 0xffffffff, H W - 1)
@@ -25,17 +24,12 @@ import math
 import numpy as np
 
 import grid_exact_cases as GE
-from oracle import grid_oracle as G
+import panorama_cases as PC
+from panorama_cases import BAD, F32, FLT_MAX, FULL, PART, PI_F, _rot, _seed_bad, affine  # noqa: F401  (this module's public names)
 
-F32 = np.float32
-FLT_MAX = F32(np.finfo(np.float32).max)
-PI_F = F32(np.pi)
 EMPTY = np.uint64(0x7F800000FFFFFFFF)
-BAD = (0.0, -1.0, float("nan"), float("inf"))
 GATE, Q_VAR = 3.0, 1e-6
 GATE_MARGIN = 1e-5            # the decision must agree where |e e - gate2 S| > GATE_MARGIN gate2 S in the float64 restatement
-FULL = ((-math.pi, math.pi), (0.0, math.pi))
-PART = ((-math.pi / 2, math.pi / 2), (math.pi / 4, 3 * math.pi / 4))
 
 # name: frames, map, the rig camera's ranges, the seeded fraction of bad values (0, -1, NaN, inf) in prev_inv, cur_inv and cur_std
 CASES = {
@@ -51,25 +45,9 @@ BFS = (96.0, 1.0)
 
 
 # ---------------------------------------------------------------------------------------------- inputs
-def affine(ranges, hw):
-    """(au, bu, av, bv) as float32, each rounded once from float64, and wrap: include/mvsgi.h's formulas"""
-    (lo0, lo1), (la0, la1) = ranges
-    Hh, W = hw
-    c = (math.pi * W / (lo1 - lo0), -lo0 * W / (lo1 - lo0), (math.pi / 2) * Hh / (la1 - la0), (math.pi / 2 - la0) * Hh / (la1 - la0))
-    return tuple(F32(v) for v in c) + (abs(lo1 - lo0 - 2 * math.pi) < 1e-6,)
-
-
 def rays(name):
     c = CASES[name]
-    return G.rays_panorama(np.ones(1, np.float32), c["ranges"][0], c["ranges"][1], c["hw"])[:, 0].numpy()
-
-
-def _rot(yaw=0.0, pitch=0.0, roll=0.0):
-    cy, sy, cp, sp, cr, sr = math.cos(yaw), math.sin(yaw), math.cos(pitch), math.sin(pitch), math.cos(roll), math.sin(roll)
-    Ry = np.array([[cy, 0, sy], [0, 1, 0], [-sy, 0, cy]])               # about the vertical: longitude theta -> theta + yaw
-    Rx = np.array([[1, 0, 0], [0, cp, -sp], [0, sp, cp]])
-    Rz = np.array([[cr, -sr, 0], [sr, cr, 0], [0, 0, 1]])
-    return Ry @ Rx @ Rz
+    return PC.rays(c["ranges"], c["hw"])
 
 
 def pose(kind, name, b=0):
@@ -108,16 +86,6 @@ def onto_x():
     return T
 
 
-def _seed_bad(rng, a, frac, keep=None):
-    flat = a.reshape(-1)
-    if frac:
-        pos = rng.permutation(flat.size)[:max(int(round(frac * flat.size)), len(BAD))]
-        flat[pos] = np.asarray(BAD, F32)[np.arange(pos.size) % len(BAD)]
-    if keep is not None and frac:                                     # the same bad values at chosen places
-        for k, at in enumerate(keep):
-            flat[at] = F32(BAD[k % len(BAD)])
-
-
 def make_inputs(name, bf=96.0):
     """-> dict(prev_inv, prev_var, cur_inv, cur_std [B, H, W] float32, prev_age [B, H, W] uint8): a smooth surface 2 ... 12 m away with
     depth steps as the state (inverse distance bf / d, standard deviation 3 %), the measurement within a few per cent of it except
@@ -151,7 +119,6 @@ def splat(prev_inv, prev_age, ray_table, T, bf, aff):
     """Stage A -> dict(zkey uint64 [B, H, W], live bool [B, H, W], r2, cx, cy of every source pixel, splat bool)"""
     prev_inv, ray_table, T = (np.ascontiguousarray(a, dtype=F32) for a in (prev_inv, ray_table, T))
     B, Hh, W = prev_inv.shape
-    au, bu, av, bv, wrap = aff
     with np.errstate(all="ignore"):
         v = prev_inv
         d = F32(bf) / v
@@ -161,18 +128,8 @@ def splat(prev_inv, prev_age, ray_table, T, bf, aff):
         qx, qy, qz = q[:, 0], q[:, 1], q[:, 2]
         r2 = (qx * qx + qy * qy) + qz * qz
         near = (r2 > 0) & (r2 <= FLT_MAX)
-        xz = np.sqrt(qx * qx + qz * qz)
-        lon = F32(-1.0) * np.arctan2(qz, qx)
-        lat = np.arctan2(qy, xz)
-        gx = lon / PI_F
-        gy = (F32(2.0) * lat) / PI_F
-        u = gx * au + bu
-        w = gy * av + bv
-        fx, fy = np.floor(u), np.floor(w)
-        if wrap:
-            fx = np.where(fx < 0, fx + F32(W), np.where(fx >= W, fx - F32(W), fx))
-        inside = (fx >= 0) & (fx < W) & (fy >= 0) & (fy < Hh)
-    assert all(a.dtype == F32 for a in (d, p, q, r2, xz, lon, lat, gx, gy, u, w, fx, fy))
+        fx, fy, inside, _, _ = PC.cell(qx, qy, qz, aff, (Hh, W))
+    assert all(a.dtype == F32 for a in (d, p, q, r2, fx, fy))
     ok = live & near & inside
     cx, cy = np.where(ok, fx, 0).astype(np.int64), np.where(ok, fy, 0).astype(np.int64)
     s = np.arange(Hh * W, dtype=np.uint64).reshape(1, Hh, W)

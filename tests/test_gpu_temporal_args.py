@@ -114,10 +114,10 @@ def test_maps_whose_index_does_not_fit_a_key_are_refused(recorder):  # noqa: F81
     library, called with addresses it never reads)."""
     for shape in ((1, 1 << 16, 1 << 16), (1, 1 << 25, 4), (1, 4, 1 << 25)):
         with pytest.raises(ValueError):
-            H._temporal_map(*shape)
-    H._temporal_map(1, 1 << 16, (1 << 16) - 1)
+            H._pano_map("temporal fusion", 32, *shape)
+    H._pano_map("temporal fusion", 32, 1, 1 << 16, (1 << 16) - 1)
     with pytest.raises(ValueError):
-        H._temporal_map(1 << 20, 1 << 12, 1 << 12)                       # too many blocks for one launch
+        H._pano_map("temporal fusion", 32, 1 << 20, 1 << 12, 1 << 12)      # too many blocks for one launch
     lib = recorder._real
     fake = 1 << 20                                                       # 16-byte aligned, never dereferenced: the dimensions are checked first
     st = torch.cuda.current_stream().cuda_stream

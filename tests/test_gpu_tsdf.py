@@ -174,6 +174,30 @@ def test_hand_made_planes_cross_exactly(arena):
         assert np.array_equal(_np(got["inv"])[1], np.full(hw, np.float32(bf) / np.float32(0.5625)))
 
 
+def test_hand_made_planes_on_two_frames_of_two_blocks(arena):
+    """The same planes on maps of 270 and 300 quads (two blocks per frame, the second partly empty; the 16-byte form and a row tail)
+    for two sequences: the thread's frame and quad come from csrc/panorama_map.hpp's frame_quad.  Every third ray is half as long,
+    so neighbours in a quad stop at different steps; every pixel of both frames crosses."""
+    dims, voxel, bf, K = (8, 4, 4), 0.25, 96.0, 24
+    for hw in ((30, 36), (30, 38)):
+        i, j = np.meshgrid(np.arange(hw[0]), np.arange(hw[1]), indexing="ij")
+        half = (i * hw[1] + j) % 3 == 0
+        rays = np.zeros((3,) + hw, np.float32)
+        rays[0] = np.where(half, np.float32(0.5), np.float32(1))
+        P = np.tile(np.eye(4, dtype=np.float32), (2, 1, 1))
+        P[0, :3, 3], P[1, :3, 3] = [0.125, 0.5, 0.5], [0.375, 0.25, 0.75]
+        vol = TC.plane_volume(dims, B=2)
+        org = np.zeros((2, 3), np.int32)
+        dv = {k: arena.guarded(torch.from_numpy(a).to(DEV)) for k, a in dict(vol=vol, rays=rays, P=P, org=org).items()}
+        got = H.tsdf_raycast(dv["vol"], dv["rays"], dv["P"], dv["org"], bf, voxel, 0.25, 0.125, K, w_min=1.0)
+        rest = TC.raycast(vol, rays, P, org, voxel, 0.25, 0.125, K, 1.0, bf)
+        for k in H.TSDF_OUTPUTS:
+            assert _same(got[k], rest[k]), (hw, k)
+        steps = _np(got["steps"])
+        assert np.array_equal(steps[0], np.where(half, 12, 5)) and np.array_equal(steps[1], np.where(half, 8, 3)), hw
+        assert (_np(got["weight"]) == 2).all(), hw
+
+
 # ------------------------------------------------------------------------------ 2. structure
 def test_every_subset_of_the_outputs_and_poisoned_tensors(arena):
     name = "b2"

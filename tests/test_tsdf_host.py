@@ -213,7 +213,7 @@ def test_the_wrappers_refuse_host_tensors_and_bad_scalars(no_launch):
     assert H._tsdf_scalar(0.0, "t0", low_ok=True) == 0.0
     for shape in ((1, 1 << 25, 4), (1, 1 << 16, 1 << 15), (1 << 22, 1 << 12, 1 << 12)):
         with pytest.raises(ValueError):
-            H._tsdf_map(*shape)
+            H._pano_map("volumetric fusion", 31, *shape)
 
 
 def test_the_origin_of_a_negative_position_is_floored():

@@ -7,8 +7,8 @@ Definition (include/mvsgi.h, "volumetric fusion"), sequenc
        (f, w) = fresh ? (1, 0) : vol[s]
     2. c = (float(i) + 0.5) * vs; q = T c (per row fma(t2, z, fma(t1, y, t0 * x)) + t3); r2 = (qx qx + qy qy) + qz qz, rejected unless
        0 < r2 <= FLT_MAX; r = sqrt(r2), rejected unless r_min <= r <= r_max
-    3. the temporal splat's step 4: xz = sqrt(qx qx + qz qz), lon = -1 * atan2(qz, qx), lat = atan2(qy, xz), gx = lon / pi,
-       gy = (2 * lat) / pi; u = gx * au + bu, v = gy * av + bv; floor; the column wrapped once; rejected outside the map
+    3. the panorama cell of q (panorama_cases.cell, the temporal splat's step 4: the projection, the affine map, floor, the column
+       wrapped once); rejected outside the map
     4. m = inv[cell]; rejected where mask[cell] == 0; d = bf / m; rejected unless 0 < m <= FLT_MAX and d <= FLT_MAX
     5. sdf = d - r; rejected if sdf < -trunc; obs = min(sdf, trunc) / trunc
     6. w_obs = 1, or with std: sig = std[cell] * d / m, w_obs = t2 / (t2 + sig * sig), rejected unless 0 < w_obs <= 1
@@ -45,14 +45,9 @@ import math
 import numpy as np
 
 import grid_exact_cases as GE
-from oracle import grid_oracle as G
+import panorama_cases as PC
+from panorama_cases import BAD, F32, FLT_MAX, FULL, PART, PI_F, _rot, _seed_bad, affine  # noqa: F401  (this module's public names)
 
-F32 = np.float32
-FLT_MAX = F32(np.finfo(np.float32).max)
-PI_F = F32(np.pi)
-BAD = (0.0, -1.0, float("nan"), float("inf"))
-FULL = ((-math.pi, math.pi), (0.0, math.pi))
-PART = ((-math.pi / 2, math.pi / 2), (math.pi / 4, 3 * math.pi / 4))
 VOXEL = 0.25
 
 # name: sequences, voxels (Nx, Ny, Nz), the panorama and its ranges
@@ -75,24 +70,9 @@ def params(bf):
     return dict(PARAMS, vs=VOXEL, bf=bf)
 
 
-def affine(ranges, hw):
-    (lo0, lo1), (la0, la1) = ranges
-    Hh, W = hw
-    c = (math.pi * W / (lo1 - lo0), -lo0 * W / (lo1 - lo0), (math.pi / 2) * Hh / (la1 - la0), (math.pi / 2 - la0) * Hh / (la1 - la0))
-    return tuple(F32(v) for v in c) + (abs(lo1 - lo0 - 2 * math.pi) < 1e-6,)
-
-
 def rays(name):
     c = CASES[name]
-    return G.rays_panorama(np.ones(1, np.float32), c["ranges"][0], c["ranges"][1], c["hw"])[:, 0].numpy()
-
-
-def _rot(yaw=0.0, pitch=0.0, roll=0.0):
-    cy, sy, cp, sp, cr, sr = math.cos(yaw), math.sin(yaw), math.cos(pitch), math.sin(pitch), math.cos(roll), math.sin(roll)
-    Ry = np.array([[cy, 0, sy], [0, 1, 0], [-sy, 0, cy]])
-    Rx = np.array([[1, 0, 0], [0, cp, -sp], [0, sp, cp]])
-    Rz = np.array([[cr, -sr, 0], [sr, cr, 0], [0, 0, 1]])
-    return Ry @ Rx @ Rz
+    return PC.rays(c["ranges"], c["hw"])
 
 
 def pose(kind, name, b=0):
@@ -144,12 +124,6 @@ def shifted(origin, kind, dims):
     return (np.asarray(origin, np.int32) - d).astype(np.int32)
 
 
-def _seed_bad(rng, a, frac):
-    flat = a.reshape(-1)
-    pos = rng.permutation(flat.size)[:max(int(round(frac * flat.size)), len(BAD))]
-    flat[pos] = np.asarray(BAD, F32)[np.arange(pos.size) % len(BAD)]
-
-
 def make_inputs(name, bf=96.0):
     """-> dict(vol [B, Nz, Ny, Nx, 2], inv, std [B, H, W] float32, mask [B, H, W] uint8): a surface that crosses the volume (a smooth
     one with depth steps), its standard deviation a third of it, a mask with holes, the seeded bad values in inv and std, and a
@@ -197,7 +171,6 @@ def integrate(vol, inv, std, mask, T, origin, origin_prev, par, aff, r=None):
     B, Nz, Ny, Nx, _ = vol.shape
     dims = (Nx, Ny, Nz)
     Hh, W = inv.shape[1:]
-    au, bu, av, bv, wrap = aff
     vs, trunc, w_max, bf = F32(par["vs"]), F32(par["trunc"]), F32(par["w_max"]), F32(par["bf"])
     t2 = F32(float(par["trunc"]) * float(par["trunc"]))
     r_min, r_max = F32(par["r_range"][0]), F32(min(par["r_range"][1], float(FLT_MAX)))
@@ -217,17 +190,8 @@ def integrate(vol, inv, std, mask, T, origin, origin_prev, par, aff, r=None):
         near = (r2 > 0) & (r2 <= FLT_MAX)
         rr = np.sqrt(r2) if r is None else np.asarray(r, dtype=F32)
         ok = near & (rr >= r_min) & (rr <= r_max)
-        xz = np.sqrt(qx * qx + qz * qz)
-        lon = F32(-1.0) * np.arctan2(qz, qx)
-        lat = np.arctan2(qy, xz)
-        gx = lon / PI_F
-        gy = (F32(2.0) * lat) / PI_F
-        u = gx * au + bu
-        v = gy * av + bv
-        fx, fy = np.floor(u), np.floor(v)
-        if wrap:
-            fx = np.where(fx < 0, fx + F32(W), np.where(fx >= W, fx - F32(W), fx))
-        ok = ok & (fx >= 0) & (fx < W) & (fy >= 0) & (fy < Hh)
+        fx, fy, inside, u, v = PC.cell(qx, qy, qz, aff, (Hh, W))
+        ok = ok & inside
         cell = (np.where(ok, fy, 0).astype(np.int64) * W + np.where(ok, fx, 0).astype(np.int64)).reshape(B, -1)
         take = lambda a: np.take_along_axis(np.asarray(a).reshape(B, -1), cell, axis=1).reshape(full)
         m = take(inv)
@@ -330,7 +294,7 @@ def sphere_bar():
 
 
 def sphere_rays():
-    return G.rays_panorama(np.ones(1, np.float32), FULL[0], FULL[1], SPHERE["hw"])[:, 0].numpy()
+    return PC.rays(FULL, SPHERE["hw"])
 
 
 def sphere_distance(a, ray_table):

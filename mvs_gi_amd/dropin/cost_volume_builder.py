@@ -42,6 +42,30 @@ class _SweepBase(nn.Module):
                                          activation=self.relu_type(), norm_layer=self.norm_type(feat_chs))
 
 
+def _check_call(self, feats, grids, cat: bool) -> None:
+    """What a forward refuses, BEFORE anything is launched and with a message that names the argument (INTEGRATION.md lists
+    these): a post_vol kernel other than 3, a norm layer left in training mode, feats that are not [B, N, C, Hi, Wi] with the
+    channels `feat_chs` promised, more cameras than the masked sweep takes, grids for another number of cameras."""
+    conv = self.post_vol.conv_layer
+    if tuple(conv.kernel_size) != (3, 3, 3):
+        raise NotImplementedError(f"post_k_sz = {conv.kernel_size[0]}: the HIP post_vol is a 3 x 3 x 3 conv (post_k_sz = 3) only")
+    norm = self.post_vol.norm_layer
+    if norm.training and (isinstance(norm, cm._BN) or (isinstance(norm, cm._IN) and norm.track_running_stats)):
+        raise RuntimeError(f"HIP path implements eval-mode {type(norm).__name__} only: the module is in training mode, "
+                           "call model.eval()")
+    if feats.dim() != 5:
+        raise AssertionError(f"feats must be [B, N, C, Hi, Wi], got {tuple(feats.shape)}")
+    B, N, C = feats.shape[:3]
+    if (N * C if cat else C) != conv.in_channels:
+        raise ValueError(f"feats {tuple(feats.shape)} carry {N * C if cat else C} volume channels"
+                         f"{' (num_cams x channels)' if cat else ''}, the module was built with feat_chs = {conv.in_channels}")
+    if not cat and not 1 <= N <= H.sweep_max_cams():
+        raise ValueError(f"num_cams = {N} (feats {tuple(feats.shape)}): the masked-variance sweep takes 1 to "
+                         f"{H.sweep_max_cams()} cameras")
+    if grids.dim() != 6 or tuple(grids.shape[:2]) != (B, N) or grids.shape[5] != 2:
+        raise AssertionError(f"grids {tuple(grids.shape)} must be [{B}, {N}, D, Ho, Wo, 2] for feats {tuple(feats.shape)}")
+
+
 def _rig_hit(entry, tensors) -> bool:
     """A cache entry holds STRONG references to the three rig tensors it was computed from and their in-place
     version counters: identity (`is`) + version decide a hit.  Holding the references also keeps the caching
@@ -152,6 +176,7 @@ def _std_front(self, feats: Tensor, grids: Tensor, grid_masks: Tensor, masks: Te
 
 
 def std_forward(self, feats: Tensor, grids: Tensor, grid_masks: Tensor, masks: Tensor) -> Tensor:
+    _check_call(self, feats, grids, cat=False)
     y = _std_front(self, feats, grids, grid_masks, masks, False)
     if y is not None:
         return cm._to_ncdhw_view(y)
@@ -164,13 +189,15 @@ def std_forward_split(self, feats: Tensor, grids: Tensor, grid_masks: Tensor, ma
     """forward() with the cost volume handed over as a split-padded H.SplitAct (module-owned, valid until the next call) instead
     of an fp32 tensor, for a regulator that takes it (cost_volume_regulator.regulator_takes_split); None when this builder
     configuration does not produce it -- the caller then uses forward()."""
+    _check_call(self, feats, grids, cat=False)
     return _std_front(self, feats, grids, grid_masks, masks, True)
 
 
 def cat_forward(self, feats: Tensor, grids: Tensor, grid_masks: Tensor, masks: Tensor) -> Tensor:
     # grid_masks / masks are accepted and ignored, as in the reference (spherical_sweep.py:80)
-    vol_raw = cat_sweep_ndhwc(feats, grids)
-    return cm._to_ncdhw_view(cm.lower_conv_block(self.post_vol).run(vol_raw))
+    _check_call(self, feats, grids, cat=True)
+    L = cm.lower_conv_block(self.post_vol)       # before the sweep: whatever the lowering refuses is refused before a launch
+    return cm._to_ncdhw_view(L.run(cat_sweep_ndhwc(feats, grids)))
 
 
 class SphericalSweepStdMasked(_SweepBase):

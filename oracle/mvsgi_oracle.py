@@ -78,10 +78,22 @@ def bilinear_sample_zeros(im: Tensor, grid: Tensor) -> Tensor:
 # ----------------------------------------------------------------------------
 # sweeps
 # ----------------------------------------------------------------------------
-def sweep_std_masked(feats: Tensor, grids: Tensor, grid_masks: Tensor, masks: Tensor) -> Tensor:
+def _camera_sum(t: Tensor, in_order: bool) -> Tensor:
+    """sum over dim 1, keepdim.  in_order: ((t0 + t1) + t2) + ... as the HIP kernels add the cameras; else ATen's own sum, which
+    gives the same bits up to four addends and associates differently from five on."""
+    if not in_order:
+        return t.sum(dim=1, keepdim=True)
+    acc = t[:, 0]
+    for i in range(1, t.shape[1]):
+        acc = acc + t[:, i]
+    return acc.unsqueeze(1)
+
+
+def sweep_std_masked(feats: Tensor, grids: Tensor, grid_masks: Tensor, masks: Tensor, camera_order: bool = False) -> Tensor:
     """feats [B,N,C,Hi,Wi], grids [B,N,D,Ho,Wo,2], grid_masks [B,N,D,Ho,Wo,1] (bool or
     float), masks [B,N,1,Hm,Wm] -> vol_raw [B,C,D,Ho,Wo]
-    (spherical_sweep_avg.py:38-136)."""
+    (spherical_sweep_avg.py:38-136).  camera_order: the two sums over the cameras taken
+    camera by camera (_camera_sum) -- the same operations, another association."""
     B, N, C = feats.shape[:3]
     D, Ho, Wo = grids.shape[2:5]
     f = feats.flatten(0, 1)
@@ -98,9 +110,9 @@ def sweep_std_masked(feats: Tensor, grids: Tensor, grid_masks: Tensor, masks: Te
         n = vf.sum(dim=1, keepdim=True)                           # :106
         ok = n > 1.0                                              # :108
         cnt = torch.where(ok, n, torch.ones_like(n))              # :111
-        mean = (sf * vf).sum(dim=1, keepdim=True) / cnt           # :114
+        mean = _camera_sum(sf * vf, camera_order) / cnt           # :114
         sf2 = torch.where(valid, sf, mean)                        # :119
-        var = ((sf2 - mean) ** 2).sum(dim=1, keepdim=True) / cnt  # :122
+        var = _camera_sum((sf2 - mean) ** 2, camera_order) / cnt  # :122
         var = torch.where(ok.expand_as(var), var, torch.zeros_like(var))
         planes.append(var[:, 0].unsqueeze(2))
     return torch.cat(planes, dim=2)

@@ -16,13 +16,14 @@ GOLDEN_C = {5: 16, 6: 8, 7: 8, 8: 16}          # channels of the golden case per
 B, HI, WI, D, HO, WO, HM, WM = 2, 12, 20, 4, 6, 70, 24, 40      # Wo 70: two w-tiles, the second 6 voxels wide
 
 
-def small_case(N: int, C: int = None, shape=None) -> dict:
+def small_case(N: int, C: int = None, shape=None, seed: int = None) -> dict:
     """feats [B, N, C, Hi, Wi] standard normal, grids [B, N, D, Ho, Wo, 2] uniform in [-1.15, 1.15] (taps outside the image on
     every side), grid_masks [B, N, D, Ho, Wo, 1] bool with a uniformly drawn count of true cameras per voxel, masks
-    [B, N, 1, Hm, Wm] Bernoulli(0.9) as fp32.  shape = (B, Hi, Wi, D, Ho, Wo, Hm, Wm) overrides the small shape."""
+    [B, N, 1, Hm, Wm] Bernoulli(0.9) as fp32.  shape = (B, Hi, Wi, D, Ho, Wo, Hm, Wm) overrides the small shape, `seed` the
+    generator's (100 + N)."""
     C = GOLDEN_C[N] if C is None else C
     b, hi, wi, d, ho, wo, hm, wm = shape or (B, HI, WI, D, HO, WO, HM, WM)
-    rng = np.random.default_rng(100 + N)
+    rng = np.random.default_rng(100 + N if seed is None else seed)
     feats = rng.standard_normal((b, N, C, hi, wi)).astype(np.float32)
     grids = rng.uniform(-1.15, 1.15, (b, N, d, ho, wo, 2)).astype(np.float32)
     masks = (rng.random((b, N, 1, hm, wm)) < 0.9).astype(np.float32)
